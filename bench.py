@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — attack-samples/s of the Bayesian attack hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5                  # the headline run alone
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full           # + the sub-records and the CPU baseline listed below
+    python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs D # + what the last timed step returned, as D/<name>.npy
     python bench.py --gpus N ...           # N > 1 without a torchrun environment: spawns the N ranks itself (child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -24,7 +26,7 @@ SVI too (one launch draws the six tensors, the conv2 weight images are rebuilt b
 N GPUs: one process per GPU.  With no --workload, `--gpus 1` runs C2 (BASELINE.json configs[1]) and `--gpus N` (N > 1) runs **C4**
 (configs[3]: n_samples = 2000 sharded 8-way = 250 samples per GPU, expected_loss_gradients + FGSM, the posterior SAMPLE-sharded, each
 step all-reducing sum_s p_s [N,16] and the summed gradients [N,784] over RCCL/xGMI — north star; weak scaling: per-GPU
-work fixed, at N = 8 exactly the config) as the headline, and attaches C2 POINT-sharded (`c2_point_sharded`: n_samples = 100 kept on every
+work fixed, at N = 8 exactly the config) as the headline, and with --full attaches C2 POINT-sharded (`c2_point_sharded`: n_samples = 100 kept on every
 rank, the config's 10 000 points split over the ranks, no data-path collective, strong scaling) as a sub-record.  An explicit
 --workload / --shard runs that one record only.  `--shard points` replicates the samples and splits the workload's points over the ranks.
 
@@ -33,8 +35,8 @@ differ in the matrix pipe used.  "exact": both GEMMs on v_mfma_f32_16x16x4_f32. 
 workloads c2 / c3 / c4): every fp32 operand carried at FULL width as three fp16 pieces (exact, bit for bit), six exact product
 terms per fp32 product on v_mfma_f32_16x16x32_f16, fp32 accumulation — nothing is narrower than fp32, the only rounding is the
 accumulation as on the fp32 MFMA (tests/test_hip_triple.py: error vs fp64 below the fp32-MFMA kernels').  "split" (opt-in): two
-fp16 pieces, 3 products — operands 22-23 bits, narrower than fp32.  The modes that are not on top are timed afterwards at N=1
-and reported as sub-records (`exact_fp32_mode`, `triple_f16x6_mode`, `split_f16x3_mode`).
+fp16 pieces, 3 products — operands 22-23 bits, narrower than fp32.  With --full the modes that are not on top are timed afterwards
+at N=1 and reported as sub-records (`exact_fp32_mode`, `triple_f16x6_mode`, `split_f16x3_mode`).
 
 `--workload eval` times adversarialAttacks.attack_evaluation at C2's size (clean + adversarial batched forward + rbnn_eval_metrics: forward only).
 Beside the mean `ms_per_step` the line carries `ms_per_step_min / _median / _max` from one HIP-event pair per step (per group of steps when a step is
@@ -43,9 +45,15 @@ library reports it, the ranks an all-reduce of ones summed, RCCL's version, all-
 stood waiting for an exchange.
 
 The JSON line carries `roofline` for the dominant kernel (the other GEMM kernel is listed beside it under roofline.kernels),
-timed with HIP events on the launch stream inside the timed region, and `cpu_baseline`: the loop-structured oracle port
+timed with HIP events on the launch stream inside the timed region, and with --full `cpu_baseline`: the loop-structured oracle port
 (oracle/bnn_oracle.py::loop_attack — the reference's batch-1 autograd nest) timed on this host's cores on a bounded sample
 of the same workload.
+
+--full is off by default: a plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line.  What --full adds
+runs after the timed steps of the headline and does not change its numbers: the other kind of posterior (`stored_posterior_mode` /
+`svi_posterior_mode`), the other precision modes, c4's two-call step (`separate_calls_mode`), `cpu_baseline`, and at N > 1 with no
+--workload `c2_point_sharded`.  --dump-outputs DIR: the arrays the last timed step returned to its caller (adversarial inputs `x_adv`,
+`loss_gradients`; eval: `accuracy`, `robustness`, `clean_probs`, `adversarial_probs`), rank 0's, with inputs fixed by their seeds.
 """
 import argparse
 import json
@@ -171,6 +179,45 @@ def make_guide(w, rank):
 
 
 SVI_NAMED = {"c1", "c2", "c5", "conv", "conv1024"}      # BASELINE.json configs that say "SVI" (conv / c5: the in-place draw does not cover conv)
+
+DUMP_BYTES = 64 * 10 ** 6                                # --dump-outputs: cap on the bytes written in all (.npy headers included)
+
+
+def step_outputs(w, eps_list, res, separate_calls):
+    """name -> array of what one step's calls returned to their caller (`res`: their return values in call order, see run().step)."""
+    tag = (lambda i: "") if len(eps_list) == 1 else (lambda i: "_eps%d" % i)
+    if w["method"] == "eval":                          # evaluate(): (clean acc %, adversarial acc %, rob [N], clean probs [N, C], adversarial probs [N, C])
+        acc_clean, acc_adv, rob, probs, probs_adv = res[0]
+        return {"accuracy": torch.tensor([acc_clean, acc_adv], dtype=torch.float64), "robustness": rob, "clean_probs": probs,
+                "adversarial_probs": probs_adv}
+    out = {}
+    if w["method"] == "lossgrad+fgsm" and not separate_calls:
+        for i, (grads, x_adv) in enumerate(res):
+            out["loss_gradients" + tag(i)], out["x_adv" + tag(i)] = grads, x_adv
+        return out
+    if "lossgrad" in w["method"]:
+        out["loss_gradients"], res = res[0], res[1:]
+    for i, x_adv in enumerate(res):                    # fgsm / pgd: the adversarial inputs, one array per epsilon
+        out["x_adv" + tag(i)] = x_adv
+    return out
+
+
+def dump_outputs(path, outputs, n_points):
+    """Write `outputs` as path/<name>.npy (float64 stays float64, everything else float32).  Above DUMP_BYTES in all, every array whose leading
+    dimension is the points keeps the same fixed, seeded sample of points (sorted), so that two runs dump the same rows."""
+    import numpy as np
+    arrs = {k: (v if v.dtype == torch.float64 else v.float()).detach().cpu().numpy() for k, v in outputs.items()}
+    per_point = lambda a: a.ndim > 0 and a.shape[0] == n_points
+    budget = DUMP_BYTES - 4096 * len(arrs)                            # room for the .npy headers
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        row_bytes = sum(a.nbytes // n_points for a in arrs.values() if per_point(a))
+        keep = max(1, (budget - (total - row_bytes * n_points)) // row_bytes)
+        rows = torch.randperm(n_points, generator=torch.Generator().manual_seed(0))[:keep].sort().values.numpy()
+        arrs = {k: (a[rows] if per_point(a) else a) for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(w, x, y, post, budget_s):
@@ -301,6 +348,14 @@ def main():
     ap.add_argument("--posterior", default="config", choices=["config", "svi", "stored"],
                     help="svi: a variational guide, all S samples redrawn in place every step inside the timed region; stored: S stored samples "
                          "(HMC-style); config (default): what BASELINE.json names for the workload (c1, c2, c5, conv: svi; c3, c4: stored)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other kind of posterior, the other precision modes, c4's two-call "
+                         "step, the CPU baseline and, with --gpus N > 1 and no --workload, the c2_point_sharded sub-record.  Off: the line is the "
+                         "headline run alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32, accuracies "
+                         "float64; rank 0's arrays); above %d MB in all, the same fixed seeded sample of points of every per-point array"
+                         % (DUMP_BYTES // 10 ** 6))
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -325,7 +380,7 @@ def main():
     # what the line measures.  One GPU: C2, the config BASELINE.json's metric is quoted on (and what the driver's BENCH record holds).  N > 1: the
     # BASELINE configs that ARE multi-GPU jobs — C4 as the headline (sample-sharded, the north star's all-reduce of the summed gradients; at
     # N = 8 exactly configs[3]) and C2 with its n_samples = 100 kept, point-sharded ("strictly faster when weights fit"), beside it
-    default_pair = args.workload is None and args.shard is None and world > 1
+    default_pair = args.workload is None and args.shard is None and world > 1 and args.full
     name = args.workload or ("c4" if world > 1 else "c2")
     out = bench_one(args, name, args.shard or "samples", rt, rank, world, device, group)
     if default_pair:
@@ -393,14 +448,20 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
     x, y, post = make_problem(w, rank if shard == "samples" else 0, device)
     D = x[0].numel()
     from robustbnns_amd.factory import make_engine, posterior_from_stacked
-    sp = posterior_from_stacked(w["arch"], w["act"], w["shape"], w["C"], w["H"], post, device)
+    stored = []
+
+    def stored_posterior():
+        """the stored-sample stack, uploaded when a run first uses it (an SVI line without --full never does)"""
+        if not stored:
+            stored.append(posterior_from_stacked(w["arch"], w["act"], w["shape"], w["C"], w["H"], post, device))
+        return stored[0]
     posterior_kind = args.posterior
     if posterior_kind == "config":
         posterior_kind = "svi" if name in SVI_NAMED else "stored"
     sp_svi = None
-    # the redrawable SVI stack (a second full posterior + its images) is built only when a run will use it: the line's own kind, or the
+    # the redrawable SVI stack (a second full posterior + its images) is built only when a run will use it: the line's own kind, or (--full) the
     # "other kind of posterior" sub-record of a single-GPU fc / fc2 line
-    if posterior_kind == "svi" or (world == 1 and w["arch"] != "conv" and not args.no_other_mode):
+    if posterior_kind == "svi" or (args.full and world == 1 and w["arch"] != "conv" and not args.no_other_mode):
         loc, scale = make_guide(w, rank if shard == "samples" else 0)
         if w["arch"] == "conv":
             from robustbnns_amd.conv import ConvStackedPosterior, ConvSviGuide
@@ -486,12 +547,13 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
 
     t_start = time.perf_counter()
 
-    def run(precision, kind=None, separate_calls=os.environ.get("RBNN_C4_SEPARATE") == "1"):
+    def run(precision, kind=None, separate_calls=os.environ.get("RBNN_C4_SEPARATE") == "1", dump=None):
         """warmup, then EXACTLY --steps timed steps between barrier + synchronize; returns (engine precision, seconds, kernel events).
-        kind "svi": every step first redraws all S samples of the resident stack in place (PGD: before every iteration)."""
+        kind "svi": every step first redraws all S samples of the resident stack in place (PGD: before every iteration).
+        dump: a directory — rank 0 writes there what the last timed step returned (dump_outputs)."""
         kind = kind or posterior_kind
         kern = TimedKernels()
-        post_ = sp_svi if kind == "svi" else sp
+        post_ = sp_svi if kind == "svi" else stored_posterior()
         if shard == "samples":
             eng = make_engine(post_, kernels=kern, group=group, total_samples=S_job, precision=precision)
             eng._S_total = S_job
@@ -548,29 +610,32 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
                 post_.redraw(key, draws[0], **lazy_kw)
 
         def step():
+            """one step; returns what its calls returned, in call order (step_outputs names them)"""
+            res = []
             if kind == "svi":
                 redraw()
             if w["method"] == "eval":
                 # adversarialAttacks.attack_evaluation's arithmetic (:173-196): forward of the clean set, forward of the adversarial set, eval_metrics,
                 # the two accuracy counters read back to the host (the reference returns them as floats)
-                eng.evaluate(xs, x_adv, labels, w["S"])
-                return
+                res.append(eng.evaluate(xs, x_adv, labels, w["S"]))
+                return res
             if w["method"] == "lossgrad+fgsm" and not separate_calls:
                 # C4: expected_loss_gradients + FGSM on the same inputs and samples — one forward, the tail + backward GEMM twice
                 # (AttackEngine.loss_gradients_and_fgsm; both results bit-identical to the two calls: tests/test_hip_round5.py)
                 for e in eps_list:
-                    eng.loss_gradients_and_fgsm(xs, labels, w["S"], e)
-                return
+                    res.append(eng.loss_gradients_and_fgsm(xs, labels, w["S"], e))
+                return res
             if "lossgrad" in w["method"]:
-                eng.loss_gradients(xs, labels, w["S"])
+                res.append(eng.loss_gradients(xs, labels, w["S"]))
             if "fgsm" in w["method"]:
                 for e in eps_list:
-                    eng.fgsm(xs, labels, w["S"], e)
+                    res.append(eng.fgsm(xs, labels, w["S"], e))
             if w["method"] == "pgd":
                 for e in eps_list:
-                    eng.pgd(xs, labels, w["S"], e, alpha=None, iters=w["iters"], before_step=redraw if kind == "svi" else None)
+                    res.append(eng.pgd(xs, labels, w["S"], e, alpha=None, iters=w["iters"], before_step=redraw if kind == "svi" else None))
                     if rank == 0 and w["iters"] * w["N"] >= 200000:        # a step of minutes (c5 at its full definition): a heartbeat on stderr
                         print(f"[bench] {name}: eps={e:.5f} attack enqueued, t={time.perf_counter() - t_start:.0f} s", file=sys.stderr, flush=True)
+            return res
 
         t_w = time.perf_counter()
         for _ in range(args.warmup):
@@ -594,12 +659,16 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
         # (+-5 % on the power-limited f16 kernels) shows up in the record itself.  A launch-bound step (C1: 31 us, one launch)
         # would pay for the two event records themselves (+10 us): steps shorter than ~1 ms are bracketed in groups of `grp` consecutive steps
         grp = 1 if (args.warmup == 0 or warm_ms >= 1.0) else max(1, min(args.steps, int(round(2.0 / max(warm_ms, 1e-3)))))
+        last = None
         t0 = time.perf_counter()
         for i in range(args.steps):
             if i % grp == 0:
                 e0 = rt.event()
                 e0.record()
-            step()
+            if i + 1 < args.steps:
+                step()
+            else:
+                last = step()                                              # what the last timed step computed: --dump-outputs
             if (i + 1) % grp == 0 or i + 1 == args.steps:
                 e1 = rt.event()
                 e1.record()
@@ -619,6 +688,9 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if dump and rank == 0 and last is not None:
+            dump_outputs(dump, step_outputs(w, eps_list, last, separate_calls), w["N"])
+        last = None
         svi = None
         if kind == "svi":
             ms = sum(a.elapsed_time(b) for a, b in draw_ev) / max(1, len(draw_ev))
@@ -789,16 +861,17 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
               "triple": "f32 (full-width operands as three f16 pieces: 6 exact f16 MFMA product terms per fp32 product, f32 accumulate)",
               "split": "f32 carried as f16 hi+lo pairs: 3 f16 MFMA products per fp32 product, f32 accumulate (2^-22 per product)"}
     SUBKEY = {"exact": "exact_fp32_mode", "triple": "triple_f16x6_mode", "split": "split_f16x3_mode"}
-    mode, dt, evs, svi_rec, extra = run(args.precision)
+    mode, dt, evs, svi_rec, extra = run(args.precision, dump=None if sub_record else args.dump_outputs)
     other_kind = None
-    if world == 1 and not args.no_other_mode and not sub_record and sp_svi is not None and name != "c5":      # the same workload on the other kind of posterior (c5: a step is minutes)
+    if args.full and world == 1 and not args.no_other_mode and not sub_record and sp_svi is not None and name != "c5":      # the same workload on the other kind of posterior (c5: a step is minutes)
         other_kind = run(args.precision, "stored" if posterior_kind == "svi" else "svi")
     separate = None
     # (always beside the shared-forward number — at N > 1 too —, so that a c4 line stays comparable with the two-call definition of earlier records)
-    if w["method"] == "lossgrad+fgsm" and not sub_record and os.environ.get("RBNN_C4_SEPARATE") != "1" and not (world == 1 and args.no_other_mode):
+    if (args.full and w["method"] == "lossgrad+fgsm" and not sub_record and os.environ.get("RBNN_C4_SEPARATE") != "1"
+            and not (world == 1 and args.no_other_mode)):
         separate = run(args.precision, separate_calls=True)           # the same step as loss_gradients() then fgsm(): four GEMMs (rounds 1-4)
     others = []
-    if world == 1 and not args.no_other_mode and not sub_record:
+    if args.full and world == 1 and not args.no_other_mode and not sub_record:
         for want in ("exact", "triple", "split"):                         # the other precision modes on the same workload
             if want == mode or (mode == "lowdim" and want != "exact"):
                 continue
@@ -867,7 +940,7 @@ def bench_one(args, name, shard, rt, rank, world, device, group, sub_record=Fals
             o_ms = 1e3 * other[1] / args.steps
             out[SUBKEY[other[0]]] = {"value": units / other[1], "ms_per_step": o_ms, "dtype": DTYPES[other[0]],
                                      "roofline": roofline(other[0], other[2], o_ms, posterior_kind == "svi")}
-        if world == 1 and args.cpu_seconds > 0 and not sub_record:
+        if args.full and world == 1 and args.cpu_seconds > 0 and not sub_record:
             out["cpu_baseline"] = cpu_baseline(w, x, y, post, args.cpu_seconds)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         return out

@@ -748,14 +748,14 @@ def _bench_world(world, argv):
 
 
 def test_bench_default_multi_gpu_line_is_baseline_config_4_with_c2_point_sharded():
-    """`bench.py --gpus 2` (what the driver's scaling run issues, no --workload): the headline is BASELINE config 4 — n_samples = 2000 split
+    """`bench.py --gpus 2 --full` (no --workload): the headline is BASELINE config 4 — n_samples = 2000 split
     8-way, this run holding shards 0 and 1 (250 samples each), sample-sharded with the two all-reduces, `loss_gradients` + FGSM = 2 passes
     per step, weak scaling — and C2 with its n_samples = 100 KEPT, point-sharded (strong scaling), is the sub-record.  Two gloo ranks on the
     CPU with the test double (points and hidden size cut down by the debug overrides, which the line reports)."""
     import json
     bench, root = _load_bench()
     configs = json.load(open(os.path.join(root, "BASELINE.json")))["configs"]
-    out = _bench_world(2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--points", "24", "--hidden", "32", "--posterior", "stored"])
+    out = _bench_world(2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--points", "24", "--hidden", "32", "--posterior", "stored", "--full"])
     c = out["config"]
     assert c["workload"] == configs[3] and c["name"] == "c4" and out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert (c["n_samples_config"], c["n_samples_config_ranks"], c["samples_per_rank"], c["samples_total"]) == (2000, 8, [250, 250], 500)
@@ -822,6 +822,63 @@ def test_bench_line_carries_the_counter_traffic_of_its_workload(tmp_path, monkey
     assert r["traffic"] == {"fc_forward": 1000.0, "fc_input_grad": 3000.0}[dom] and r["traffic_source"] == ["a test record"]
     assert r["hbm"]["counter_bytes_by_call"] == {"fc_forward": 1000.0, "fc_input_grad": 3000.0}
     assert r["hbm"]["counter_bytes_per_pass"] == 4000.0 + 50.0 + 7.0 and r["hbm"]["counter_small_kernels_bytes"] == 57.0
+
+
+SUB_RECORDS = {"stored_posterior_mode", "svi_posterior_mode", "exact_fp32_mode", "triple_f16x6_mode", "split_f16x3_mode", "separate_calls_mode",
+               "c2_point_sharded", "cpu_baseline", "gpu_over_cpu"}
+
+
+def test_bench_plain_line_is_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """Without --full a line carries the headline run only, whatever --cpu-seconds / --no-other-mode say; --full adds the CPU baseline (and
+    the other sub-records, asserted on two ranks above).  --steps is the number of timed steps: value and ms_per_step say the same."""
+    small = ["--gpus", "1", "--warmup", "1", "--points", "16", "--hidden", "32", "--samples", "3", "--posterior", "stored"]
+    out = _bench_world(1, small + ["--steps", "4"])
+    assert not SUB_RECORDS & set(out) and out["steps"] == 4
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert abs(out["value"] - 16 * 3 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    c4 = _bench_world(1, small + ["--steps", "1", "--workload", "c4"])
+    assert not SUB_RECORDS & set(c4)
+    full = _bench_world(1, small + ["--steps", "2", "--full", "--no-other-mode", "--cpu-seconds", "0.2"])
+    assert full["cpu_baseline"]["kind"] == "port" and full["gpu_over_cpu"] > 0
+
+
+def test_bench_dump_outputs_writes_what_the_last_timed_step_returned(tmp_path):
+    """--dump-outputs DIR: the arrays the timed path's caller receives (FGSM: the adversarial inputs; c4: the expected loss gradients and the
+    adversarial inputs; eval: accuracies, robustness and both probability sets), float32 / float64, identical from run to run."""
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--points", "16", "--hidden", "32", "--samples", "3", "--posterior", "stored"]
+    for d in ("a", "b"):
+        _bench_world(1, small + ["--dump-outputs", str(tmp_path / d)])
+    a, b = (np.load(tmp_path / d / "x_adv.npy") for d in "ab")
+    assert sorted(os.listdir(tmp_path / "a")) == ["x_adv.npy"] and a.dtype == np.float32 and a.shape == (16, 1, 28, 28)
+    assert np.array_equal(a, b)
+    g = torch.Generator().manual_seed(1234)                      # bench.make_problem's inputs: an FGSM image stays within eps of them, in [0, 1]
+    x = torch.rand((16, 1, 28, 28), generator=g).numpy()
+    assert np.abs(a - x).max() <= 0.3 + 1e-6 and a.min() >= 0 and a.max() <= 1 and np.abs(a - x).max() > 0
+    _bench_world(1, small + ["--workload", "c4", "--dump-outputs", str(tmp_path / "c4")])
+    assert sorted(os.listdir(tmp_path / "c4")) == ["loss_gradients.npy", "x_adv.npy"]
+    assert np.load(tmp_path / "c4" / "loss_gradients.npy").shape == (16, 1, 28, 28)
+    _bench_world(1, small + ["--workload", "eval", "--dump-outputs", str(tmp_path / "eval")])
+    ev = {f[:-4]: np.load(tmp_path / "eval" / f) for f in os.listdir(tmp_path / "eval")}
+    assert set(ev) == {"accuracy", "robustness", "clean_probs", "adversarial_probs"} and ev["accuracy"].dtype == np.float64
+    assert ev["clean_probs"].shape == (16, 10) and ev["robustness"].shape == (16,) and ev["clean_probs"].dtype == np.float32
+    assert np.allclose(ev["clean_probs"].sum(1), 1, atol=1e-5)
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_of_points_under_the_cap(tmp_path, monkeypatch):
+    """Above the cap every per-point array keeps the SAME seeded rows, so that two builds' dumps compare row for row."""
+    bench, _ = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 1024)
+    x = torch.arange(100 * 200, dtype=torch.float32).reshape(100, 200)             # 80 kB + 40 kB per-point, over the 64 kB cap
+    outs = {"x_adv": x, "loss_gradients": -x[:, :100], "accuracy": torch.tensor([50.0, 25.0], dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, 100)
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) <= 64 * 1024
+    rows = got["x_adv.npy"][:, 0] / 200
+    assert 0 < len(rows) < 100 and np.array_equal(rows, np.sort(rows)) and np.array_equal(got["loss_gradients.npy"], -got["x_adv.npy"][:, :100])
+    assert got["accuracy.npy"].dtype == np.float64 and got["accuracy.npy"].tolist() == [50.0, 25.0]
+    assert all(np.array_equal(got[f], np.load(tmp_path / "b" / f)) for f in got)
 
 
 # ----------------------------------------------------------------------------- files WRITTEN BY THE REFERENCE (SURVEY 8f2)
@@ -899,9 +956,13 @@ def test_reads_result_pickles_written_by_the_reference(monkeypatch, tmp_path):
     save_to_pickle(data=mine, path=str(tmp_path) + "/", filename="a.pkl")
     b = open(os.path.join(REF_FILES, "TESTS", "attacks", f"{name}_fgsm_attackSamp={S}_attack.pkl"), "rb").read()
     # a pickled torch tensor names its storage by the storage's ADDRESS in the writing process (torch/_tensor.py __reduce_ex__ ->
-    # torch.save's persistent id): mask that decimal key, everything else — protocol, classes, flags, strides, payload — is byte-equal
+    # torch.save's persistent id): mask that decimal key, everything else — protocol, classes, flags, strides, payload — is byte-equal.
+    # The address's number of digits depends on where the process's heap lies, and the sizes that enclose the key (its string, the nested
+    # torch.save blob, the pickle frame) follow it: compare opcode by opcode with the key masked inside the blob and the frame sizes dropped
+    import pickletools
     key = lambda raw: re.sub(rb"X.\x00\x00\x00\d{8,20}", b"<storage key>", raw)
-    assert key(open(tmp_path / "a.pkl", "rb").read()) == key(b) and key(b) != b
+    ops = lambda raw: [(op.name, key(arg) if isinstance(arg, bytes) else arg) for op, arg, _ in pickletools.genops(raw) if op.name != "FRAME"]
+    assert ops(open(tmp_path / "a.pkl", "rb").read()) == ops(b) and key(b) != b
 
 
 def test_reference_trained_posteriors_are_far_inside_the_dynamic_range_guard(golden):

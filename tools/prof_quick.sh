@@ -6,7 +6,7 @@ tag=$1; wl=$2; shift 2
 OUT=$R/gpurun_out/$tag/$wl
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $R/bench.py --workload $wl --cpu-seconds 0 --steps 5 --warmup 2 "$@" > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $R/bench.py --full --workload $wl --cpu-seconds 0 --steps 5 --warmup 2 "$@" > $OUT/trace.log 2>&1
 rc=$?
 cd $R && python tools/summarize_profile.py $OUT $wl > $OUT/summary.txt 2>&1
 rm -rf $OUT/trace
