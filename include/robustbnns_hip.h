@@ -238,7 +238,8 @@ int rbnn_conv_workspace_query(const rbnn_conv_posterior *net, int32_t n_points, 
                               rbnn_conv_workspace_sizes *out);
 
 /* Stacked per-sample forward of the conv net: P[s] = softmax(NN_s(X)) (or logits) + the two pooling stashes.
- * Replaces the sample loop of BNN.forward (model_bnn.py:251-255) with NN.forward = model_nn.py:98-106,126-141. */
+ * Replaces the sample loop of BNN.forward (model_bnn.py:251-255) with NN.forward = model_nn.py:98-106,126-141.
+ * X: [N, ldx], 16-byte aligned (RBNN_ERR_ALIGN otherwise), ldx >= Cin*W*W, multiple of 4 (RBNN_ERR_SHAPE otherwise). */
 int rbnn_conv_forward(const rbnn_conv_posterior *net, const float *X, int32_t ldx, int32_t n_points,
                       const int32_t *sample_idx, int32_t n_samples, int32_t out_kind,
                       const rbnn_conv_workspace *ws, void *stream);
@@ -254,7 +255,7 @@ int rbnn_conv_input_grad(const rbnn_conv_posterior *net, const int32_t *sample_i
  * the pooled conv1 activations are carried as value * 2^p1_exp = hi + lo (the caller bounds them: |P1| <= max_c(sum|K1w_c| *
  * max|x| + |K1b_c|)).  ws->P1 holds the 24 KiB split image per (sample, point) (rbnn_conv_workspace_query sizes it);
  * same outputs as rbnn_conv_forward, and rbnn_conv_input_grad follows it unchanged.  p1_dev_scale != NULL: record [1] of
- * rbnn_input_scales, read on the device instead of p1_exp. */
+ * rbnn_input_scales, read on the device instead of p1_exp.  X: as for rbnn_conv_forward (16-byte aligned, ldx a multiple of 4). */
 int rbnn_conv_forward_split(const rbnn_conv_posterior *net, const void *K2_rows, int32_t k2_exp, int32_t p1_exp,
                             const rbnn_dev_scale *p1_dev_scale, const float *X, int32_t ldx,
                             int32_t n_points, const int32_t *sample_idx, int32_t n_samples, int32_t out_kind,
@@ -264,7 +265,8 @@ int rbnn_conv_forward_split(const rbnn_conv_posterior *net, const void *K2_rows,
  * fp16 pieces, six exact product terms per product on the f16 matrix pipe, fp32 accumulation (see the triple-split section below).
  * K2_triple = rbnn_triple_rows image of model.3.weight regrouped [S_total*Hc, 25 taps * 32 ci] (K tap-major) holding W * 2^k2_exp;
  * the pooled conv1 activations (computed in fp32 by the exact conv1 kernel into ws->P1) are split on the fly, scaled by 2^p1_exp or
- * by record [1] of rbnn_input_scales (p1_dev_scale != NULL).  Same outputs as rbnn_conv_forward; rbnn_conv_input_grad follows it unchanged. */
+ * by record [1] of rbnn_input_scales (p1_dev_scale != NULL).  Same outputs as rbnn_conv_forward; rbnn_conv_input_grad follows it unchanged.
+ * X: as for rbnn_conv_forward (16-byte aligned, ldx >= Cin*W*W and a multiple of 4: its conv1 reads each image row as float4). */
 int rbnn_conv_forward_triple(const rbnn_conv_posterior *net, const void *K2_triple, int32_t k2_exp, int32_t p1_exp,
                              const rbnn_dev_scale *p1_dev_scale, const float *X, int32_t ldx, int32_t n_points,
                              const int32_t *sample_idx, int32_t n_samples, int32_t out_kind,

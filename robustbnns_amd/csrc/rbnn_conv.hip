@@ -535,9 +535,9 @@ int rbnn_conv_forward(const rbnn_conv_posterior* net, const float* X, int32_t ld
     int rc = validate_conv(net);
     if (rc) return rc;
     if (!X || !ws || !ws->P || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || ldx < net->in_channels * net->in_width * net->in_width) return RBNN_ERR_SHAPE;
+    if (N < 1 || S < 1 || ldx < net->in_channels * net->in_width * net->in_width || (ldx & 3)) return RBNN_ERR_SHAPE;
     if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
+    if (!aligned16(X) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     ConvArgs a = {};
     a.X = X; a.ldx = ldx; a.N = N;
@@ -558,9 +558,9 @@ int rbnn_conv_forward_split(const rbnn_conv_posterior* net, const void* K2_rows,
     int rc = validate_conv_split(net);
     if (rc) return rc;
     if (!K2_rows || !X || !ws || !ws->P || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || ldx < 784 || k2_exp < -100 || k2_exp > 100 || p1_exp < -100 || p1_exp > 100) return RBNN_ERR_SHAPE;
+    if (N < 1 || S < 1 || ldx < 784 || (ldx & 3) || k2_exp < -100 || k2_exp > 100 || p1_exp < -100 || p1_exp > 100) return RBNN_ERR_SHAPE;
     if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(K2_rows) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
+    if (!aligned16(K2_rows) || !aligned16(X) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     ConvArgs a = {};
     a.X = X; a.ldx = ldx; a.N = N;

@@ -206,7 +206,9 @@ class AttackEngine:
         if xf.shape[1] != p.D:
             raise ValueError(f"inputs flatten to {xf.shape[1]} features, posterior expects {p.D}")
         if p.Dp == p.D:
-            return xf.clone() if clone else xf.contiguous()
+            xf = xf.contiguous()
+            # the kernels read X rows as 16-byte vectors (RBNN_ERR_ALIGN otherwise): a view at an unaligned offset costs one copy
+            return xf.clone() if (clone or xf.data_ptr() % 16) else xf
         out = torch.zeros(x.shape[0], p.Dp, dtype=torch.float32, device=self.device)
         out[:, :p.D] = xf
         return out

@@ -484,20 +484,23 @@ MEDIAN_BAR = 3e-6   # per-point median of the conv gradients' error (a third of 
 KINK_CONV = 2e-6    # a conv2 pre-activation is an 800-term fp32 sum of magnitude ~1: its rounding noise is ~sqrt(800) * 6e-8 ~ 2e-6
 
 
-def conv_pinned_oracle(x, lab, post, act, S, st1, st2, mode="mean_prob"):
+def conv_pinned_oracle(x, lab, post, act, S, st1, st2, mode="mean_prob", gup=None):
     """fp64 input gradient of the conv net (model_nn.py:98-106) with every pooling-argmax and relu / leaky sign decision taken from
     the HIP stashes st1 [S,N,32,P1W,P1W], st2 [S,N,Hc,P2W,P2W] (bits 0-1: argmax dy*2+dx of the window, bit 2: pre-activation > 0;
     include/robustbnns_hip.h).  A conv net has ~10^5 such decisions per (point, sample); a pre-activation (or the gap between a
     window's two largest) within fp32 rounding of zero legitimately goes either way, and then moves the gradient by that element's
     worth.  With the decisions pinned EVERY point is comparable to 1e-5; `worst` returns how far from a tie the decisions that
-    differ from fp64's own were (must be within fp32 noise)."""
+    differ from fp64's own were (must be within fp32 noise).
+    mode: "mean_prob" (CE on the mean probabilities), "per_sample" (CE per sample, averaged), "mean_logit" (CE on the mean logits:
+    a deterministic net / an ensemble), "upstream" / "upstream_logit" (the vector-Jacobian product with `gup` [N, C] of the mean
+    probabilities / the mean logits: the autograd hook)."""
     import torch.nn.functional as F
     smooth = act in ("sigm", "tanh")
     xr = x.double().clone().requires_grad_(True)
     N = len(x)
     worst = 0.0
     n_diff = torch.zeros(N, dtype=torch.long)
-    probs = []
+    probs, logits = [], []
     for s in range(S):
         h = xr
         for (wk, bk, stash, stride) in (("model.0.weight", "model.0.bias", st1[s], 2), ("model.3.weight", "model.3.bias", st2[s], 1)):
@@ -520,11 +523,18 @@ def conv_pinned_oracle(x, lab, post, act, S, st1, st2, mode="mean_prob"):
             h = chosen if smooth else chosen * torch.where(bit, 1.0, 0.0 if act == "relu" else O.LEAKY_SLOPE).double()
         z = F.linear(h.flatten(1), post["model.7.weight"][s].double(), post["model.7.bias"][s].double())
         probs.append(torch.softmax(z, -1))
+        logits.append(z)
     p = torch.stack(probs)
     if mode == "mean_prob":
         loss = F.cross_entropy(p.mean(0), lab, reduction="sum")
-    else:
+    elif mode == "per_sample":
         loss = F.cross_entropy(p.reshape(S * N, -1), lab.repeat(S), reduction="sum") / S
+    elif mode == "mean_logit":
+        loss = F.cross_entropy(torch.stack(logits).mean(0), lab, reduction="sum")
+    elif mode in ("upstream", "upstream_logit"):
+        loss = ((p if mode == "upstream" else torch.stack(logits)).mean(0) * gup.double()).sum()
+    else:
+        raise ValueError(mode)
     loss.backward()
     return xr.grad.detach(), worst, n_diff
 

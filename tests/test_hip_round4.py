@@ -161,24 +161,25 @@ def test_lazy_svi_draw_inside_the_lowdim_launch_equals_draw_then_run(shape, H, C
     assert float(a["W1"].abs().max()) > 0 and rel_err(a["exact"], a["seeded"]) < TOL
 
 
-@pytest.mark.parametrize("arch", ["fc", "fc2"])
-def test_images_only_svi_draw_for_triple_engines(arch):
+@pytest.mark.parametrize("arch,shape", [pytest.param(a, s, id=a if s == (1, 28, 28) else f"{a}-D{int(np.prod(s))}")
+                                        for s in ((1, 28, 28), (1, 10, 10), (3, 32, 32)) for a in ("fc", "fc2")])
+def test_images_only_svi_draw_for_triple_engines(arch, shape):
     """redraw(lazy=True) on a posterior with triple images = rbnn_svi_draw_images: the images, biases and W2 of a full draw — bit for bit —
     while the fp32 W1 / Wm stack and its pack_rows4 copy (read by no triple kernel) stay untouched until somebody reads them; forward, gradients
     and a PGD attack equal the full draw's; an fp32-MFMA engine on the same posterior (which DOES read the stack) sees the materialised weights."""
     from robustbnns_amd import AttackEngine, StackedPosterior
     from robustbnns_amd.posterior import SviGuide
-    D, H, C, S, N = 784, 128, 10, 5, 200
+    D, H, C, S, N = int(np.prod(shape)), 128, 10, 5, 200
     g = torch.Generator().manual_seed(9)
     names = {"model.1.weight": (H, D), "model.1.bias": (H,)}
     names.update({"model.3.weight": (H, H), "model.3.bias": (H,), "model.5.weight": (C, H), "model.5.bias": (C,)} if arch == "fc2"
                  else {"model.3.weight": (C, H), "model.3.bias": (C,)})
     loc = {k: torch.randn(*v, generator=g) * 0.05 for k, v in names.items()}
     scl = {k: torch.full(v, -3.0) for k, v in names.items()}
-    x, y = O.synthetic_inputs(N, (1, 28, 28), C, seed=1)
+    x, y = O.synthetic_inputs(N, shape, C, seed=1)
 
     def run(lazy):
-        post = StackedPosterior.for_guide(SviGuide(loc, scl, arch, DEV), "leaky", (1, 28, 28), C, S)
+        post = StackedPosterior.for_guide(SviGuide(loc, scl, arch, DEV), "leaky", shape, C, S)
         eng = AttackEngine(post)
         assert eng.precision == "triple"
         post.triple_images()

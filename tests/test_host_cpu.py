@@ -189,6 +189,32 @@ def test_triple_abi_rejects_bad_arguments():
     assert lib.rbnn_conv_input_grad_dense(C.byref(cnet), None, 0, 1.0, None, 1, 4, None, None) != 0
 
 
+@pytest.mark.parametrize("cin,w", [(1, 28), (3, 32)])
+def test_conv_forwards_reject_unaligned_or_ragged_inputs(cin, w):
+    """rbnn_conv_forward{,_split,_triple} read X rows as 16-byte vectors: an ldx that is not a multiple of 4 floats is RBNN_ERR_SHAPE,
+    an X that is not 16-byte aligned RBNN_ERR_ALIGN — both before any launch (fake pointers: a call that got past them would fault)."""
+    import ctypes as C
+    lib = _hip.load()
+    net = _hip.ConvPosterior()
+    net.activation, net.hidden, net.n_classes, net.n_stored, net.in_channels, net.in_width = 1, 16, 10, 2, cin, w
+    for k in ("K1w", "K1b", "K2w", "K2b", "Fw", "Fb", "K2w_ci"):
+        setattr(net, k, 16)
+    ws = _hip.ConvWorkspace(*[16] * len(_hip.CONV_WS_KEYS))
+    din = cin * w * w
+    fwd = lambda X, ldx: lib.rbnn_conv_forward(C.byref(net), X, ldx, 4, None, 2, 0, C.byref(ws), None)
+    tri = lambda X, ldx: lib.rbnn_conv_forward_triple(C.byref(net), C.c_void_p(16), 0, 0, None, X, ldx, 4, None, 2, 0, C.byref(ws), None)
+    calls = [fwd, tri]
+    if cin == 1:
+        calls.append(lambda X, ldx: lib.rbnn_conv_forward_split(C.byref(net), C.c_void_p(16), 0, 0, None, X, ldx, 4, None, 2, 0, C.byref(ws), None))
+    for f in calls:
+        assert f(C.c_void_p(16), din - 4) == -2                   # ldx < Cin*W*W (unchanged)
+        assert f(C.c_void_p(16), din + 1) == -2                   # ldx % 4
+        assert f(C.c_void_p(16), din + 2) == -2
+        assert f(C.c_void_p(20), din) == -5                       # X 4 bytes past a 16-byte boundary
+        assert f(C.c_void_p(24), din + 4) == -5
+        assert f(None, din) == -1
+
+
 def test_lowdim_fc2_scratch_holds_the_sign_bit_stash():
     """rbnn_lowdim_scratch_bytes (host arithmetic only): fc = the per-sample outputs; fc2 = outputs + gradient slabs + the sum over samples
     + 16 bytes per thread of every low2_kernel block for the sign bits the forward launch leaves to the backward launch (round 4)."""
