@@ -19,9 +19,10 @@
  *
  * Padding contract (lets every kernel run whole 16-wide MFMA tiles, no tail code in the
  * K loops): D_pad = round_up(D,16) is the row stride of X, W1 and of gradient buffers;
- * columns [D, D_pad) are ZERO.  hidden is a multiple of 32 (the reference only allows
- * powers of two >= 16, model_nn.py:39-40; 16 is zero-padded to 32 by the host, which is
- * exact: a padded unit has zero outgoing weights).  n_classes <= 16.
+ * columns [D, D_pad) are ZERO.  hidden is 32, 64 or a multiple of 128 for the fc / fc2
+ * kernels (the reference only allows powers of two >= 16, model_nn.py:39-40; 16 is
+ * zero-padded to 32 by the host, which is exact: a padded unit has zero outgoing weights;
+ * the fp32 kernels take every hidden size the triple kernels take).  n_classes <= 16.
  */
 #ifndef ROBUSTBNNS_HIP_H
 #define ROBUSTBNNS_HIP_H
@@ -70,7 +71,7 @@ typedef struct rbnn_posterior {
     int32_t activation;            /* rbnn_activation                                            */
     int32_t in_features;           /* D  (784 MNIST, 2 half-moons)                               */
     int32_t in_stride;             /* D_pad, multiple of 16: row stride of W1                    */
-    int32_t hidden;                /* H, multiple of 32                                          */
+    int32_t hidden;                /* H: 32, 64 or a multiple of 128                             */
     int32_t n_classes;             /* C <= 16                                                    */
     int32_t n_stored;              /* S_total                                                    */
     int32_t reserved;

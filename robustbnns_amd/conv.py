@@ -14,7 +14,7 @@ import torch
 
 from . import _hip
 from .engine import AttackEngine, to_labels
-from .posterior import scale_exp
+from .posterior import narrow_range, scale_exp, slice_ratio, slices_in_range
 from ._hip import OUT_LOGITS, OUT_PROBS
 
 CONV_KEYS = ("model.0", "model.3", "model.7")
@@ -26,6 +26,13 @@ def conv_geometry(input_shape):
     """(pooled conv1 width, pooled conv2 width) of model_nn.py:98-106 on a Cin x W x W input: 5x5 convs, pool 2, pool 2 stride 1."""
     p1 = (int(input_shape[1]) - 4) // 2
     return p1, p1 - 4 - 1
+
+
+def range_slices(k2, k1):
+    """slice_ratio of the slices that share an image scale: model.3.weight k2 [S, Hc, 32, 25] per (sample, output channel) and per
+    (sample, input channel) against its one scale; model.0.weight k1 [S, 32, Cin*25] per (sample, channel) against its sample's (conv1's
+    triple kernel scales each sample by its own max)."""
+    return [slice_ratio(k2, (2, 3)), slice_ratio(k2, (1, 3)), slice_ratio(k1, 2, per_sample=True)]
 
 
 class ConvSviGuide:
@@ -43,10 +50,11 @@ class ConvSviGuide:
         k2 = bnd["model.3.weight"]
         typ = (self.loc["model.3.weight"].abs() + 0.8 * self.sigma["model.3.weight"]).double().mean().float()
         Cn = self.loc["model.7.bias"].numel()
+        slices = range_slices(k2.reshape(1, k2.shape[0], 32, 25), bnd["model.0.weight"].reshape(1, 32, -1))
         rec = torch.stack([k2.max(), typ, bnd["model.0.weight"].reshape(32, -1).sum(-1).max(), bnd["model.0.bias"].max(),
-                           bnd["model.7.weight"].reshape(Cn, -1).sum(0).max()]).cpu().tolist()           # the one sync, at load
+                           bnd["model.7.weight"].reshape(Cn, -1).sum(0).max(), torch.stack(slices).max()]).cpu().tolist()   # the one sync, at load
         self.k2_max, self.p1_bound, self.fw_l1 = rec[0], (rec[2], rec[3]), rec[4]
-        self.range_ok = 0.0 < rec[0] <= 4096.0 * rec[1] and rec[0] != float("inf")
+        self.range_ok = 0.0 < rec[0] <= 4096.0 * rec[1] and rec[0] != float("inf") and rec[5] <= 4096.0
 
 
 class ConvStackedPosterior:
@@ -200,13 +208,21 @@ class ConvStackedPosterior:
 
     # ------------------------------------------------------------------ triple-split ("f16x6") mode: full-width operands on the f16 pipe
     def triple_supported(self):
-        """The triple conv2 kernels cover both geometries and all four activations, for posteriors whose conv2 weights have an ordinary
-        dynamic range (posterior.narrow_range)."""
+        """The triple conv kernels cover both geometries and all four activations, for posteriors whose conv weights have an ordinary
+        dynamic range (range_ok)."""
         if self.device.type != "cuda":
             return False
+        return self.range_ok()
+
+    def range_ok(self):
+        """posterior.narrow_range of model.3.weight and posterior.slices_in_range of the slices that share the images' scales
+        (range_slices; a redrawable SVI stack: the guide's verdict on its bounds).  Decided once, at load."""
         if getattr(self, "_range_ok", None) is None:
-            from .posterior import narrow_range
-            self._range_ok = self._guide.range_ok if self._guide is not None else narrow_range(self.K2w)
+            if self._guide is not None:
+                self._range_ok = self._guide.range_ok
+            else:
+                S = self.S
+                self._range_ok = narrow_range(self.K2w) and slices_in_range(range_slices(self.K2w.abs().view(S, self.H, 32, 25), self.K1w.abs()))
         return self._range_ok
 
     def triple_images(self):
@@ -228,8 +244,9 @@ class ConvStackedPosterior:
 
     # ------------------------------------------------------------------ split-half precision mode (forward conv2)
     def split_supported(self):
-        """The split-half conv kernels are built for 1x28x28 inputs with relu / leaky (the reference's saved conv models)."""
-        return self.device.type == "cuda" and self.input_shape == (1, 28, 28) and self.activation in ("relu", "leaky")
+        """The split-half conv kernels are built for 1x28x28 inputs with relu / leaky (the reference's saved conv models), for posteriors
+        whose conv weights have an ordinary dynamic range (range_ok)."""
+        return self.device.type == "cuda" and self.input_shape == (1, 28, 28) and self.activation in ("relu", "leaky") and self.range_ok()
 
     def split_images(self):
         """(K2 split-rows image of model.3.weight regrouped tap-major [S*Hc, 25*32], its exponent, per-unit bound of the pooled

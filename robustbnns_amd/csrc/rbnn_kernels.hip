@@ -678,7 +678,7 @@ int validate_net(const rbnn_posterior* net) {
     if (net->in_features < 1 || net->in_stride < net->in_features || (net->in_stride & 15)) return RBNN_ERR_SHAPE;
     const int H = net->hidden;
     if (H < 32 || (H & 31)) return RBNN_ERR_SHAPE;
-    if (H < 512 ? (H & (H - 1)) != 0 : (H % 512) != 0) return RBNN_ERR_SHAPE;   // 32..256 powers of two, or k*512
+    if (H != 32 && H != 64 && (H % 128) != 0) return RBNN_ERR_SHAPE;             // 32, 64, or k*128 (every size the triple mode takes)
     if (net->n_classes < 1 || net->n_classes > RBNN_CPAD || net->n_stored < 1) return RBNN_ERR_SHAPE;
     if (!aligned16(net->W1) || !aligned16(net->b1) || !aligned16(net->W2)) return RBNN_ERR_ALIGN;
     if (net->arch == RBNN_ARCH_FC2 && (!aligned16(net->Wm) || !aligned16(net->bm))) return RBNN_ERR_ALIGN;
@@ -734,7 +734,7 @@ int launch_forward_act(const FwdArgs& a, bool layer2, hipStream_t st) {
     // lost their round-1 A/Bs too: HISTORY.md)
     if (H % 512 == 0) return launch_forward_cfg<ACT, 2, 8, 2, 4>(a, layer2, st);
     if (H == 256)     return launch_forward_cfg<ACT, 2, 8, 2, 4>(a, layer2, st);   // 256 h x 128 n
-    if (H == 128)     return launch_forward_cfg<ACT, 1, 8, 4, 4>(a, layer2, st);   // 128 h x 256 n
+    if (H % 128 == 0) return launch_forward_cfg<ACT, 1, 8, 4, 4>(a, layer2, st);   // 128 h x 256 n, H/128 chunks per item (384, 640, ...)
     if (H == 64)      return launch_forward_cfg<ACT, 1, 4, 4, 4>(a, layer2, st);   //  64 h x 256 n
     if (H == 32)      return launch_forward_cfg<ACT, 1, 2, 4, 4>(a, layer2, st);   //  32 h x 256 n
     return RBNN_ERR_SHAPE;
@@ -817,7 +817,7 @@ const char* rbnn_strerror(int status) {
     switch (status) {
         case RBNN_OK: return "ok";
         case RBNN_ERR_NULL: return "required pointer is NULL";
-        case RBNN_ERR_SHAPE: return "shape violates the padding contract (D_pad %16, hidden %32 and 2^k or k*512, classes <= 16)";
+        case RBNN_ERR_SHAPE: return "shape violates the padding contract (D_pad %16, hidden 32, 64 or k*128, classes <= 16)";
         case RBNN_ERR_UNSUPPORTED: return "unsupported architecture / activation / mode";
         case RBNN_ERR_LAUNCH: return "HIP kernel launch failed";
         case RBNN_ERR_ALIGN: return "pointer is not 16-byte aligned";

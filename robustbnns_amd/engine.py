@@ -146,13 +146,14 @@ class AttackEngine:
         tri = bool(getattr(self.post, "triple_supported", lambda: False)()) and isinstance(self.k, _hip.HipKernels)
         if want == "triple" and not tri:
             raise _hip.HipError("precision='triple' covers fc / fc2 posteriors with hidden % 128 == 0 and classes <= 10 and the conv "
-                                "architecture, on the GPU, for weight tensors of ordinary dynamic range (posterior.narrow_range)")
+                                "architecture, on the GPU, for weight tensors of ordinary dynamic range (range_ok: posterior.narrow_range and "
+                                "posterior.slices_in_range)")
         if want == "triple" or (want == "auto" and tri):
             return "triple"
         ok = bool(getattr(self.post, "split_supported", lambda: False)()) and isinstance(self.k, _hip.HipKernels)
         if want == "split" and not ok:
             raise _hip.HipError("precision='split' covers fc / fc2 posteriors with hidden % 128 == 0 and classes <= 10, and the conv "
-                                "architecture, on the GPU")
+                                "architecture, on the GPU, for weight tensors of ordinary dynamic range (range_ok)")
         return "split" if (want in ("split", "fast") and ok) else "exact"
 
     # ------------------------------------------------------------------ plumbing

@@ -46,6 +46,24 @@ def narrow_range(*tensors, ratio=4096.0):
     return True
 
 
+def slice_ratio(mag, dims, per_sample=False):
+    """Largest (max of the scale) / (max of a slice) over the non-zero slices of `mag` (>= 0), a slice being what is left after reducing over
+    `dims`; the scale's max is the whole tensor's, or each sample's (dim 0) with per_sample.  A 0-d device tensor: no sync.  NaN / inf -> inf."""
+    m = mag.amax(dim=dims)
+    top = mag.flatten(1).amax(1).reshape((-1,) + (1,) * (m.dim() - 1)) if per_sample else mag.amax()
+    r = torch.where(m > 0, top / m.clamp_min(torch.finfo(m.dtype).tiny), torch.zeros_like(m)).amax()
+    return torch.where(torch.isfinite(top).all() & ~torch.isnan(r), r, torch.full_like(r, math.inf))
+
+
+def slices_in_range(ratios, ratio=4096.0):
+    """The guard of the images that share ONE power-of-two scale among many rows / columns / samples (triple_rows, split_rows, the conv
+    images; conv1's per-sample scale): every non-zero slice that shares a scale holds its max within `ratio` (2^12) of that scale's max.
+    narrow_range alone compares the max with the MEAN, and a whole block of large slices (one sample's hidden units scaled by 2^a and the next
+    layer's weights by 2^-a: the same function) moves the mean with it; every other slice then sits 2^a below the scale and its pieces 2 and 3
+    fall into fp16 subnormals.  `ratios`: slice_ratio values, evaluated with one sync."""
+    return bool(float(torch.stack([r.float() for r in ratios]).max()) <= ratio)
+
+
 def scale_exp(max_abs, target=14):
     """e with max_abs * 2^e <= 2^target: the power-of-two scale of a split-half image (rbnn_split_rows & co)."""
     if not (max_abs > 0.0) or math.isinf(max_abs):
@@ -60,7 +78,8 @@ class SviGuide:
 
       bound[k] = max(|loc| + RBNN_SVI_EPS_MAX * softplus(scale))   of W1, W2, Wm: the images' power-of-two scales
       h1       = (max_h sum_d bound(W1[h,d]), max bound(b1))       the fc2 hidden-activation bound (StackedPosterior.scale_bounds)
-      range_ok = narrow_range on the bound against mean|loc| + 0.8 softplus(scale)  (the guard of the triple mode)
+      range_ok = narrow_range on the bound against mean|loc| + 0.8 softplus(scale), and slices_in_range on the bound's rows / columns
+                 (the guard of the triple and split modes)
 
     Box-Muller on a 32-bit uniform cannot exceed 6.764 standard deviations, so these are bounds, not estimates."""
 
@@ -84,12 +103,15 @@ class SviGuide:
         bnd = {n: self.loc[n].abs() + _hip.SVI_EPS_MAX * self.sigma[n] for n in self.loc}
         typ = {n: self.loc[n].abs() + 0.8 * self.sigma[n] for n in self.loc}                         # ~ E|w|
         mats = [n for n in ("W1", "W2", "Wm") if n in bnd]
+        # the slices that share an image scale (slices_in_range): W1 rows, W2 columns, Wm rows and columns — of the bounds
+        slices = [slice_ratio(bnd["W1"], -1), slice_ratio(bnd["W2"], 0)] + ([slice_ratio(bnd["Wm"], -1), slice_ratio(bnd["Wm"], 0)] if "Wm" in bnd else [])
         rec = torch.stack([bnd[n].max() for n in mats] + [typ[n].double().mean().float() for n in mats] +
-                          [bnd["W1"].sum(-1).max(), bnd["b1"].max()]).cpu().tolist()                   # the one sync, at load
+                          [bnd["W1"].sum(-1).max(), bnd["b1"].max(), torch.stack(slices).max()]).cpu().tolist()   # the one sync, at load
         k = len(mats)
         self.bound = dict(zip(mats, rec[:k]))
         self.h1_bound = (rec[2 * k], rec[2 * k + 1])
-        self.range_ok = all(0.0 < m <= 4096.0 * t and m != float("inf") for m, t in zip(rec[:k], rec[k:2 * k]))
+        self.range_ok = (all(0.0 < m <= 4096.0 * t and m != float("inf") for m, t in zip(rec[:k], rec[k:2 * k]))
+                         and rec[2 * k + 2] <= 4096.0)
         self._desc = None
 
     def descriptor(self):
@@ -161,8 +183,10 @@ class StackedPosterior:
 
     # ------------------------------------------------------------------ split-half ("f16x3") precision mode
     def split_supported(self):
-        """The split kernels cover fc and fc2 (all four activations) with hidden % 128 == 0 and <= 10 classes."""
-        return self.arch in ("fc", "fc2") and self.Hp % 128 == 0 and self.C <= 10 and self.device.type == "cuda"
+        """The split kernels cover fc and fc2 (all four activations) with hidden % 128 == 0 and <= 10 classes — for posteriors whose images
+        carry every weight to fp32's resolution (range_ok)."""
+        return (self.arch in ("fc", "fc2") and self.Hp % 128 == 0 and self.C <= 10 and self.device.type == "cuda"
+                and self.range_ok())
 
     def split_images(self):
         """rbnn_split_images of this posterior (built once, resident): W1 as split rows (forward A operand), W1 as
@@ -197,11 +221,23 @@ class StackedPosterior:
     # ------------------------------------------------------------------ triple-split ("f16x6") mode: full-width operands
     def triple_supported(self):
         """The triple kernels cover fc and fc2 (all four activations) with hidden % 128 == 0 and <= 10 classes — and posteriors whose
-        weight tensors have an ordinary dynamic range (narrow_range): anything else stays on the fp32 MFMA."""
+        weight tensors have an ordinary dynamic range (range_ok): anything else stays on the fp32 MFMA."""
         if not (self.arch in ("fc", "fc2") and self.Hp % 128 == 0 and self.C <= 10 and self.device.type == "cuda"):
             return False
+        return self.range_ok()
+
+    def range_ok(self):
+        """The images' one scale per tensor carries every weight to fp32's resolution: narrow_range of W1, W2, Wm and slices_in_range of
+        the slices that share those scales — W1 rows, W2 columns, Wm rows and columns, per sample (a redrawable SVI stack: the guide's
+        a-priori verdict).  Decided once, at load."""
         if self._range_ok is None:
-            self._range_ok = self._guide.range_ok if self._guide is not None else narrow_range(self.W1, self.W2, self.Wm)
+            if self._guide is not None:
+                self._range_ok = self._guide.range_ok
+            else:
+                sl = [slice_ratio(self.W1.abs(), -1), slice_ratio(self.W2.abs(), 1)]
+                if self.Wm is not None:
+                    sl += [slice_ratio(self.Wm.abs(), -1), slice_ratio(self.Wm.abs(), 1)]
+                self._range_ok = narrow_range(self.W1, self.W2, self.Wm) and slices_in_range(sl)
         return self._range_ok
 
     def triple_images(self):
@@ -438,7 +474,7 @@ class StackedPosterior:
             t = getattr(self, name)
             setattr(out, name, None if t is None else t[lo:hi].contiguous())
         # the dynamic-range guard is decided ONCE, on the full posterior: every rank (and the single-process run) picks the same mode
-        out.S, out._desc, out._split, out._triple, out._range_ok = hi - lo, None, None, None, self.triple_supported() and self._range_ok
+        out.S, out._desc, out._split, out._triple, out._range_ok = hi - lo, None, None, None, self.range_ok()
         out._guide, out._back = None, None
         out._pack()
         return out

@@ -265,11 +265,17 @@ def test_autograd_hook_against_fp64_vjp(arch, act, shape, H, C, S, N, std, preci
     """forward(x.requires_grad_()) -> backward(gup) (the caller's surface: BNN.forward for probabilities, the engine's forward with
     logits=True as NN / Ensemble_NN call it) and eng.gradient(LOSS_UPSTREAM[_LOGIT], G_up) against fp64 autograd of <gup, forward>;
     gup has mixed signs and a one-hot row; NaN in G_up's padding classes C..15 leaves the result bit-identical."""
+    D = int(np.prod(shape))
+    post = _conv_post(shape, H, C, S, std) if arch == "conv" else O.synthetic_posterior(arch, D, H, C, S, std)
+    hook_checks(arch, act, shape, H, C, S, N, post, precision)
+
+
+def hook_checks(arch, act, shape, H, C, S, N, post, precision):
+    """The checks of test_autograd_hook_against_fp64_vjp on a given posterior (also run by test_hip_rescale at 13 and 16 classes)."""
     import test_hip_round2 as R2
     from robustbnns_amd import _hip
     from robustbnns_amd.model_bnn import BNN
     D = int(np.prod(shape))
-    post = _conv_post(shape, H, C, S, std) if arch == "conv" else O.synthetic_posterior(arch, D, H, C, S, std)
     x, y = O.synthetic_inputs(N, shape, C, seed=D + H + 3)
     # conv's default is triple: the exact conv kernels are asked for by name (fc at H = 64 resolves to exact by itself)
     eng = _engine(arch, act, shape, H, C, post, precision="exact" if (arch == "conv" and precision == "exact") else None)

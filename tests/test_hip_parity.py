@@ -38,7 +38,7 @@ def split_covers(arch, act, H, C):
 
 def exact_covers(H):
     H = max(32, H)
-    return (H % 512 == 0) or (H <= 256 and H & (H - 1) == 0)          # include/robustbnns_hip.h: 32..256 powers of two, or k*512
+    return H in (32, 64) or H % 128 == 0                               # include/robustbnns_hip.h: 32, 64 or k*128
 
 
 def modes_for(arch, act, H, C):
@@ -268,7 +268,10 @@ ORACLE_CASES += [("fc2", "leaky", (1, 28, 28), 10, 256, 5, 300, 0.05), ("fc2", "
 ORACLE_CASES += [("fc2", "leaky", (1, 28, 28), 10, 1024, 2, 70, 0.03)]       # the reference's saved model_3 / model_7 shape
 ORACLE_CASES += [("fc", "sigm", (1, 28, 28), 10, 256, 3, 140, 0.05), ("fc", "tanh", (1, 14, 14), 5, 128, 4, 90, 0.1),
                  ("fc2", "tanh", (1, 28, 28), 10, 256, 3, 130, 0.05), ("fc2", "sigm", (1, 8, 8), 3, 128, 2, 50, 0.2)]
-ORACLE_MODES = [c + (m,) for c in ORACLE_CASES for m in modes_for(c[0], c[1], c[4], c[3])]
+ORACLE_MODES = [c + (m,) for c in ORACLE_CASES for m in modes_for(c[0], c[1], c[4], c[3])
+                if m != "exact" or max(32, c[4]) % 512 == 0 or max(32, c[4]) & (max(32, c[4]) - 1) == 0]
+# exact at the hidden sizes k*128 that are neither a power of two nor k*512 (640): appended, so that every case above keeps its id
+ORACLE_MODES += [c + ("exact",) for c in ORACLE_CASES if "exact" in modes_for(c[0], c[1], c[4], c[3]) and c + ("exact",) not in ORACLE_MODES]
 
 
 @pytest.mark.parametrize("arch,act,shape,C,H,S,N,std,precision", ORACLE_MODES)
