@@ -552,6 +552,56 @@ int rbnn_lowdim_run_svi(const rbnn_posterior *net, const rbnn_svi_guide *guide, 
                         const float *alpha, float alpha_scalar, int32_t alpha_per_image, int32_t project, int32_t iters, float *P_scratch,
                         float *out, int32_t ldo, float *linf, float *l2, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * SVI training of fc / fc2 guides (csrc/rbnn_train.hip).  One training step of model_bnn.py:303-365 (SVI with TraceMeanField_ELBO and
+ * pyro.optim.Adam) on a batch of B points: draw ONE weight sample, loss L = sum_b CE(z_b, y_b) + sum KL(N(loc, sigma) || N(0, 1)), its
+ * gradients, one torch.optim.Adam step on every loc and raw scale.  Issued in this order on one stream:
+ *   draw -> train_forward -> weight_grads -> adam_step -> [accuracy forward] -> train_finalize.
+ * Parameters live in FLAT buffers of n_params floats: the state_dict tensors in order (model.1.weight [H, D], model.1.bias [H],
+ * (fc2: model.3.weight [H, H], model.3.bias [H],) output weight [C, H], output bias [C]), unpadded, row-major.  eps is rbnn_svi_draw's
+ * generator at sample 0 (counter (quad, tensor id, 0, draw_id), quad = r * ceil(cols/4) + c/4): the same (key, draw_id) gives the same
+ * weights as rbnn_svi_draw's sample 0, and the update regenerates eps instead of storing it.  No atomics: two runs are bit-identical.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_svi_train_net {
+    int32_t arch;                  /* rbnn_arch                                                                    */
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_features, hidden, n_classes;    /* D (any), H (the net's own, unpadded), C <= 16                    */
+    int32_t reserved;
+    float *loc, *raw, *sigma;      /* [n_params] variational mean, raw scale, sigma = softplus(raw) (written by the update)   */
+    float *m_loc, *v_loc, *m_raw, *v_raw;      /* [n_params] Adam moments (zero before the first step)             */
+    float *W;                      /* [n_params] the drawn weight sample                                           */
+    float *grad;                   /* [n_params] dCE/dW of the step                                                */
+} rbnn_svi_train_net;
+
+typedef struct rbnn_svi_train_ws { /* caller-owned, for up to B points                                              */
+    float *hid1, *dact1, *dA1;     /* [B, H] layer-1 activations, act'(pre-activation), dL/d(pre-activation)      */
+    float *hid2, *dact2, *dA2;     /* [B, H] fc2 only: the same for the second hidden layer                       */
+    float *dZ;                     /* [B, 16] dL/dlogits                                                           */
+    float *ce;                     /* [B] cross-entropy per point                                                  */
+} rbnn_svi_train_ws;
+
+/* [host] n_params (the flat buffers' length); *n_partials (nullable) = the KL partial sums rbnn_svi_adam_step writes.  < 0: rbnn_status. */
+int64_t rbnn_svi_train_sizes(const rbnn_svi_train_net *net, int64_t *n_partials);
+/* W = loc + sigma * eps(key, draw_id): one launch. */
+int rbnn_svi_train_draw(const rbnn_svi_train_net *net, uint64_t key, uint32_t draw_id, void *stream);
+/* The training forward on W: hidden activations, act', logits, ce[b] = CE(z_b, labels[b]), dZ = softmax(z) - e_y (summed CE: no 1/B), and
+ * the backward to dA1 (fc2: dA2, then dA1) — fc 2 launches, fc2 4.  X [B, ldx] fp32 (ldx >= D), labels int32[B] in [0, C). */
+int rbnn_svi_train_forward(const rbnn_svi_train_net *net, const float *X, int32_t ldx, int32_t n_points, const int32_t *labels,
+                           const rbnn_svi_train_ws *ws, void *stream);
+/* grad = dCE/dW of every tensor (dW1 = dA1^T X, dWm = dA2^T H1, dW2 = dZ^T H, the biases as column sums): one launch, fp32 MFMA. */
+int rbnn_svi_weight_grads(const rbnn_svi_train_net *net, const float *X, int32_t ldx, int32_t n_points, const rbnn_svi_train_ws *ws,
+                          void *stream);
+/* One torch.optim.Adam step (single-tensor formula, no weight decay) on loc and raw with g_loc = grad + loc,
+ * g_raw = (grad * eps + sigma - 1/sigma) * sigmoid(raw), eps regenerated from (key, draw_id); `step` = the step number t >= 1 of the
+ * bias corrections.  Writes loc, raw, sigma = softplus(raw), the moments, and kl_partials[i] = the KL of the PRE-update parameters
+ * summed over block i (n_partials of rbnn_svi_train_sizes). */
+int rbnn_svi_adam_step(const rbnn_svi_train_net *net, uint64_t key, uint32_t draw_id, int64_t step, float lr, float beta1, float beta2,
+                       float adam_eps, float *kl_partials, void *stream);
+/* One block, fixed order, fp64: stats[0] = sum kl_partials + sum_b ce[b] (the step's loss), stats[1] += stats[0]; Psum [B, ldp] (nullable:
+ * sum over samples of the accuracy forward's probabilities): stats[2] += #{b : first argmax_c Psum[b, c] == labels[b]}. */
+int rbnn_svi_train_finalize(const float *kl_partials, int64_t n_partials, const float *ce, int32_t n_points, const float *Psum, int32_t ldp,
+                            const int32_t *labels, int32_t n_classes, double *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

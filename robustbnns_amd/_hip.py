@@ -78,6 +78,18 @@ class SviFlatTensor(C.Structure):
                 ("tensor_id", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SviTrainNet(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("arch", "activation", "in_features", "hidden", "n_classes", "reserved")] + \
+               [(k, _fp) for k in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "W", "grad")]
+
+
+SVI_TRAIN_WS_KEYS = ("hid1", "dact1", "dA1", "hid2", "dact2", "dA2", "dZ", "ce")
+
+
+class SviTrainWs(C.Structure):
+    _fields_ = [(k, _fp) for k in SVI_TRAIN_WS_KEYS]
+
+
 SVI_EPS_MAX = 6.77                                                     # RBNN_SVI_EPS_MAX: Box-Muller on a 32-bit uniform cannot exceed it
 
 TRIPLE_WS_KEYS = ("X_triple", "dZ_gen", "g_scale", "hid_triple")
@@ -163,6 +175,12 @@ SIGNATURES = {
     "rbnn_svi_draw": (_i32, [_PP, C.POINTER(TripleImages), C.POINTER(SviGuide), _i32, _fp, C.c_uint64, C.c_uint32, _fp]),
     "rbnn_svi_draw_supported": (_i32, [_PP, _i32]),
     "rbnn_svi_draw_images": (_i32, [_PP, C.POINTER(TripleImages), C.POINTER(SviGuide), _i32, _fp, C.c_uint64, C.c_uint32, _fp]),
+    "rbnn_svi_train_sizes": (_i64, [C.POINTER(SviTrainNet), C.POINTER(_i64)]),
+    "rbnn_svi_train_draw": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _fp]),
+    "rbnn_svi_train_forward": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, _fp, C.POINTER(SviTrainWs), _fp]),
+    "rbnn_svi_weight_grads": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, C.POINTER(SviTrainWs), _fp]),
+    "rbnn_svi_adam_step": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _i64, _f32, _f32, _f32, _f32, _fp, _fp]),
+    "rbnn_svi_train_finalize": (_i32, [_fp, _i64, _fp, _i32, _fp, _i32, _fp, _i32, _fp, _fp]),
 }
 
 _lib = None

@@ -12,7 +12,9 @@ model_bnn.py:198-258, computed for the whole batch and all samples by the HIP ke
        PARITY UNPINNED for the draw itself (pyro-ppl 1.3.0 is not available to check RNG order against); everything
        downstream of explicit weights is pinned.
 
-Inference (SVI/HMC training, model_bnn.py:260-365) is out of scope: posteriors are inputs here.
+Training: `train(train_loader, device, rel_path, filename)` runs the reference's SVI training (model_bnn.py:303-365) for fc / fc2 on the GPU
+(svi_train.SviTrainer: one weight draw, the training forward, the weight gradients and one Adam step per batch — csrc/rbnn_train.hip) and
+saves the param store.  HMC, conv SVI and CPU devices raise NotImplementedError: those posteriors are inputs here.
 """
 import os
 import random
@@ -330,10 +332,53 @@ class BNN(nn.Module):
         return eng.forward(inputs.to(self.device), S, seeds=sd, logits=logits)
 
     def train(self, *args, **kwargs):
+        """model_bnn.py:350-365 (SVI, fc / fc2, on the GPU); train(mode) is nn.Module's pass-through (:333-334)."""
         if args and isinstance(args[0], bool) or "mode" in kwargs:
             return super().train(*args, **kwargs)
-        raise NotImplementedError("SVI/HMC inference is outside the accelerated hot path (SURVEY.md section 2, row 8): "
-                                  "run it with the reference and load the posterior here")
+        return self._train_svi(*args, **kwargs)
+
+    def _train_svi(self, train_loader, device, rel_path=TESTS, filename=None):
+        """model_bnn.py:303-348 + :350-360: seed, epochs of SviTrainer steps, the per-epoch line, save().  The guide's parameters are
+        initialised at the first step (after the loader's iterator has made its first batch: a shuffled loader draws its permutation seed
+        from the CPU generator first, as the reference's does — RandomSampler's order of draws recalled, not checked) unless the net
+        already holds some (load() or an earlier train(): pyro's param store persists), which are then trained further."""
+        if self.inference == "hmc":
+            raise NotImplementedError("HMC inference is outside the accelerated path: run it with the reference and load the chain here")
+        if self.basenet.architecture not in ("fc", "fc2"):
+            raise NotImplementedError(f"SVI training covers fc and fc2, not {self.basenet.architecture!r} (conv needs conv weight gradients)")
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        from .svi_train import SviTrainer, draw_key, initial_params
+        self.device = device
+        self.basenet.device = device
+        random.seed(0)
+        set_rng_seed(0)
+        print("\n == SVI training ==")
+        b, trainer = self.basenet, None
+        loss_list, accuracy_list = [], []
+        n = len(train_loader.dataset)
+        for epoch in range(self.epochs):
+            for x_batch, y_batch in train_loader:
+                if trainer is None:
+                    if self.svi_loc is None:
+                        loc, raw = initial_params([(k, tuple(v.shape)) for k, v in b.state_dict().items()])
+                    else:
+                        loc, raw = self.svi_loc, self.svi_scale
+                    trainer = SviTrainer(b.architecture, b.activation, b.input_shape, b.output_size, loc, raw, self.lr, device,
+                                         draw_key(), batch_size=int(x_batch.shape[0]))
+                trainer.step(x_batch.to(device), y_batch.to(device).argmax(-1))
+            loss, correct = trainer.epoch_totals() if trainer is not None else (0.0, 0.0)
+            if trainer is not None:
+                trainer.begin_epoch()
+            total_loss, accuracy = loss / n, 100 * correct / n
+            print(f"\n[Epoch {epoch + 1}]\t loss: {total_loss:.2f} \t accuracy: {accuracy:.2f}", end="\t")
+            loss_list.append(loss)                        # the reference's loss_list holds the epoch's sum (model_bnn.py:342)
+            accuracy_list.append(accuracy)
+        self.training_history = {"loss": loss_list, "accuracy": accuracy_list}
+        if trainer is not None:
+            loc, raw = trainer.params()
+            self.set_variational_params(loc, raw, device)   # drops the guide, slots and seeded draws of the previous parameters
+        self.save(rel_path=rel_path, filename=filename)
 
     def evaluate(self, test_loader, device, n_samples=10, seeds_list=None):
         """model_bnn.py:367-391"""
