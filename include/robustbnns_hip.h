@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RBNN_ABI_VERSION 9
+#define RBNN_ABI_VERSION 10
 #define RBNN_CPAD 16               /* class axis of P / dZ buffers is padded to 16 floats */
 
 typedef enum rbnn_status {
@@ -594,9 +594,11 @@ int rbnn_svi_weight_grads(const rbnn_svi_train_net *net, const float *X, int32_t
 /* One torch.optim.Adam step (single-tensor formula, no weight decay) on loc and raw with g_loc = grad + loc,
  * g_raw = (grad * eps + sigma - 1/sigma) * sigmoid(raw), eps regenerated from (key, draw_id); `step` = the step number t >= 1 of the
  * bias corrections.  Writes loc, raw, sigma = softplus(raw), the moments, and kl_partials[i] = the KL of the PRE-update parameters
- * summed over block i (n_partials of rbnn_svi_train_sizes). */
-int rbnn_svi_adam_step(const rbnn_svi_train_net *net, uint64_t key, uint32_t draw_id, int64_t step, float lr, float beta1, float beta2,
-                       float adam_eps, float *kl_partials, void *stream);
+ * summed over block i (n_partials of rbnn_svi_train_sizes).  lr, the betas and eps are doubles (ABI 10), as torch's Python floats: the
+ * step size lr / (1 - beta1^t), sqrt(1 - beta2^t) and the weights 1 - beta1, 1 - beta2 are formed in double and rounded to fp32 ONCE, as
+ * torch's scalar arguments are (1 - 0.999f in fp32 is 1.3e-5 off 0.001). */
+int rbnn_svi_adam_step(const rbnn_svi_train_net *net, uint64_t key, uint32_t draw_id, int64_t step, double lr, double beta1, double beta2,
+                       double adam_eps, float *kl_partials, void *stream);
 /* One block, fixed order, fp64: stats[0] = sum kl_partials + sum_b ce[b] (the step's loss), stats[1] += stats[0]; Psum [B, ldp] (nullable:
  * sum over samples of the accuracy forward's probabilities): stats[2] += #{b : first argmax_c Psum[b, c] == labels[b]}. */
 int rbnn_svi_train_finalize(const float *kl_partials, int64_t n_partials, const float *ce, int32_t n_points, const float *Psum, int32_t ldp,

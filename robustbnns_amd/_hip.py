@@ -179,12 +179,12 @@ SIGNATURES = {
     "rbnn_svi_train_draw": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _fp]),
     "rbnn_svi_train_forward": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, _fp, C.POINTER(SviTrainWs), _fp]),
     "rbnn_svi_weight_grads": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, C.POINTER(SviTrainWs), _fp]),
-    "rbnn_svi_adam_step": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _i64, _f32, _f32, _f32, _f32, _fp, _fp]),
+    "rbnn_svi_adam_step": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp, _fp]),
     "rbnn_svi_train_finalize": (_i32, [_fp, _i64, _fp, _i32, _fp, _i32, _fp, _i32, _fp, _fp]),
 }
 
 _lib = None
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class HipError(RuntimeError):

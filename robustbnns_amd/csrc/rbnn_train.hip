@@ -230,12 +230,12 @@ struct AdamArgs {
     float* kl_part;
     unsigned long long key;
     uint32_t draw_id;
-    float beta1, beta2, adam_eps, step_size, bc2_sqrt;
+    float w1, beta2, w2, adam_eps, step_size, bc2_sqrt;      // w1 = 1 - beta1, w2 = 1 - beta2: formed in double on the host
 };
 
 __device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, const AdamArgs& a) {
-    m = fmaf(1.f - a.beta1, g - m, m);                       // exp_avg.lerp_(grad, 1 - beta1)
-    v = fmaf(1.f - a.beta2, g * g, v * a.beta2);             // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    m = fmaf(a.w1, g - m, m);                                // exp_avg.lerp_(grad, 1 - beta1)
+    v = fmaf(a.w2, g * g, v * a.beta2);                      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
     const float denom = sqrtf(v) / a.bc2_sqrt + a.adam_eps;
     p = p + (-a.step_size * m) / denom;                      // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
@@ -434,8 +434,8 @@ int rbnn_svi_weight_grads(const rbnn_svi_train_net* net, const float* X, int32_t
     return gemm_launch(g, (hipStream_t)stream);
 }
 
-int rbnn_svi_adam_step(const rbnn_svi_train_net* net, uint64_t key, uint32_t draw_id, int64_t step, float lr, float beta1, float beta2,
-                       float adam_eps, float* kl_partials, void* stream) {
+int rbnn_svi_adam_step(const rbnn_svi_train_net* net, uint64_t key, uint32_t draw_id, int64_t step, double lr, double beta1, double beta2,
+                       double adam_eps, float* kl_partials, void* stream) {
     int rc = check_net(net);
     if (rc) return rc;
     if (!net->loc || !net->raw || !net->sigma || !net->m_loc || !net->v_loc || !net->m_raw || !net->v_raw || !net->grad || !kl_partials)
@@ -445,10 +445,11 @@ int rbnn_svi_adam_step(const rbnn_svi_train_net* net, uint64_t key, uint32_t dra
     a.L = layout_of(*net);
     a.loc = net->loc; a.raw = net->raw; a.sigma = net->sigma; a.m_loc = net->m_loc; a.v_loc = net->v_loc; a.m_raw = net->m_raw; a.v_raw = net->v_raw;
     a.grad = net->grad; a.kl_part = kl_partials; a.key = key; a.draw_id = draw_id;
-    a.beta1 = beta1; a.beta2 = beta2; a.adam_eps = adam_eps;
-    // torch's single-tensor Adam takes the bias corrections in Python floats (double) and hands them to fp32 tensor ops
-    a.step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    // torch's single-tensor Adam takes its scalars (the bias corrections, 1 - beta1, 1 - beta2) in Python floats (double) and hands them to
+    // fp32 tensor ops: each is rounded to fp32 once.  (1.f - 0.999f is 1.3e-5 off 0.001: with v << (1 - beta2) g^2 that is 6e-6 of the update.)
+    a.w1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.w2 = (float)(1.0 - beta2); a.adam_eps = (float)adam_eps;
+    a.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
+    a.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((a.L.n_quads + ELT_THREADS - 1) / ELT_THREADS)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
     return launch_status();
 }

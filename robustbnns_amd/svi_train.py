@@ -108,6 +108,10 @@ class SviTrainer:
         self.acc_post = StackedPosterior.for_guide(self.guide, activation, self.input_shape, self.C, ACC_SAMPLES)
         if not self.k.svi_draw_supported(self.acc_post, False):
             raise NotImplementedError(f"{arch} hidden {self.H}, {self.C} classes: outside what rbnn_svi_draw covers (the accuracy forward's draw)")
+        # rbnn_fc_forward (the accuracy forward) takes a padded hidden size of 32, 64 or k * 128 only; the training kernels take any.  A trainer
+        # of another size (96, 160, ...) computes gradients and steps without the accuracy; step(accuracy=True) refuses it up front (BNN's hidden sizes, powers of two >= 16, are all covered)
+        Hp = self.acc_post.Hp
+        self.accuracy_supported = Hp in (32, 64) or Hp % 128 == 0
         self.Bmax = 0
         self._ensure(int(batch_size))
 
@@ -163,6 +167,8 @@ class SviTrainer:
     def step(self, x, labels, accuracy=True):
         """One SVI step on the device batch (x [B, ...], labels int [B]); accuracy: the 10-sample forward of the updated guide is scored too.
         No device->host synchronisation."""
+        if accuracy and not self.accuracy_supported:          # before anything is launched: no half-applied step
+            raise NotImplementedError(f"hidden {self.H}: outside what rbnn_fc_forward covers (32, 64 or a multiple of 128): no accuracy forward")
         B = self.gradients(x, labels)
         lib, st = self.k.lib, _hip.stream_of(self.X)
         _hip.check(lib.rbnn_svi_adam_step(C.byref(self.net), C.c_uint64(self.key), C.c_uint32(self.t & 0xFFFFFFFF), self.t + 1, self.lr,

@@ -8,6 +8,8 @@ import torch.nn.functional as F
 from oracle import bnn_oracle as O
 
 BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
+ACC_SAMPLES = 10                        # model_bnn.py:327: the per-step training accuracy is forward(x_batch, n_samples=10)
+ACC_KEY = 0x9E3779B97F4A7C15            # xor-ed into the training key: the accuracy forward's draws (robustbnns_amd.svi_train.ACC_KEY)
 
 
 def layer_keys(arch):
@@ -89,7 +91,8 @@ def adam_update(p, g, m, v, t, lr):
 class Restatement:
     """SviTrainer.step on the CPU: same init, same (key, draw id = step) eps, in `dtype`."""
 
-    def __init__(self, loc, raw, arch, act, lr, key, dtype=torch.float64):
+    def __init__(self, loc, raw, arch, act, lr, key, dtype=torch.float64, record=False):
+        self.losses = [] if record else None              # record=True: the loss of every step, in order (epoch sums are formed from it)
         self.arch, self.act, self.lr, self.key, self.dtype = arch, act, lr, key, dtype
         self.loc = {k: loc[k].detach().cpu().to(dtype).clone() for k in state_keys(arch)}
         self.raw = {k: raw[k].detach().cpu().to(dtype).clone() for k in state_keys(arch)}
@@ -110,7 +113,40 @@ class Restatement:
         for k in self.loc:
             adam_update(self.loc[k], gl[k], self.m_loc[k], self.v_loc[k], self.t, self.lr)
             adam_update(self.raw[k], gr[k], self.m_raw[k], self.v_raw[k], self.t, self.lr)
+        if self.losses is not None:
+            self.losses.append(float(loss))
         return float(loss)
+
+
+def first_argmax(p):
+    """Index of the FIRST maximum of every row (finalize_kernel's rule: a later class wins only if strictly larger)."""
+    best = torch.zeros(p.shape[0], dtype=torch.long)
+    top = p[:, 0].clone()
+    for c in range(1, p.shape[1]):
+        better = p[:, c] > top
+        best[better] = c
+        top = torch.where(better, p[:, c], top)
+    return best
+
+
+def top2_gap(p):
+    """Per row: the gap between the two largest entries (inf for a single class)."""
+    if p.shape[1] < 2:
+        return torch.full((p.shape[0],), float("inf"), dtype=p.dtype)
+    t = p.topk(2, dim=-1)[0]
+    return t[:, 0] - t[:, 1]
+
+
+def accuracy_forward(loc, raw, arch, act, x, key, t, n_samples=ACC_SAMPLES):
+    """The per-step training accuracy of SviTrainer.step(accuracy=True) in fp64, at the guide (loc, raw) as it stands AFTER the update of
+    step t (t = 0 for the first step): n_samples weights loc + softplus(raw) eps with eps of the draw (key ^ ACC_KEY, draw id t, sample s),
+    Psum = sum over the samples of softmax(logits) (rbnn_reduce_samples at scale 1.0), the first-maximum argmax of Psum and, per point, the gap
+    between the two largest MEAN probabilities.  Returns (Psum [B, C], prediction [B], gap [B])."""
+    shapes = {k: tuple(v.shape) for k, v in loc.items()}
+    eps = draw_eps(shapes, arch, (int(key) ^ ACC_KEY) & 0xFFFFFFFFFFFFFFFF, t, n_samples)
+    post = {k: loc[k].detach().cpu().double()[None] + F.softplus(raw[k].detach().cpu().double())[None] * eps[k] for k in shapes}
+    psum = torch.softmax(O.nn_logits(x.detach().cpu().double(), post, arch, act), -1).sum(0)
+    return psum, first_argmax(psum), top2_gap(psum / n_samples)
 
 
 def predict(loc, raw, x, arch, act, seeds):

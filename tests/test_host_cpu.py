@@ -30,7 +30,7 @@ def test_library_exports_every_declared_symbol():
     lib = _hip.load()
     for name in declared:
         assert getattr(lib, name) is not None
-    assert lib.rbnn_abi_version() == _hip.ABI_VERSION == 9
+    assert lib.rbnn_abi_version() == _hip.ABI_VERSION == 10
     assert lib.rbnn_build_flags() == 0                       # a product build: no timing-only ablation switch in any translation unit
     assert lib.rbnn_strerror(0) == b"ok" and b"NULL" in lib.rbnn_strerror(-1)
 

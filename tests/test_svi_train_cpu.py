@@ -1,6 +1,7 @@
 """CPU tests of SVI training (model_bnn.py:105-136, :303-365): the restatement in tests/svi_restate.py is the reference's semantics (the loss
 torch.distributions computes, the gradients autograd gives, torch.optim.Adam's update), the guide's initialisation order, and the argument
-checks of the training entry points of the C-ABI (no GPU touched)."""
+checks of the training entry points of the C-ABI (no GPU touched); the restated accuracy forward against a plain loop over samples, and —
+with the reference alone — that every case of the GPU module's gradient and epoch tests keeps its exclusions under its cap."""
 import ctypes as C
 
 import pytest
@@ -70,6 +71,114 @@ def test_guide_init_draws_loc_then_scale_per_key_in_state_dict_order():
     for k, s in shapes:
         assert torch.equal(loc[k], torch.randn(s)) and torch.equal(raw[k], torch.randn(s)), k
     assert list(loc) == state_keys("fc2") == [k for k, _ in shapes]
+
+
+def test_accuracy_forward_is_a_plain_loop_over_the_ten_samples():
+    from robustbnns_amd import svi_train
+    assert (R.ACC_KEY, R.ACC_SAMPLES) == (svi_train.ACC_KEY, svi_train.ACC_SAMPLES)
+    for arch, act in (("fc", "tanh"), ("fc2", "leaky")):
+        shapes, loc, raw, x, y = _guide(arch, 6, 8, 3, seed=11)
+        key, t = 0xABCDEF0123456789, 4
+        psum, pred, gap = R.accuracy_forward(loc, raw, arch, act, x.reshape(13, 1, 6, 1), key, t)
+        eps = R.draw_eps(shapes, arch, key ^ R.ACC_KEY, t, n_samples=10)
+        acts = {"leaky": torch.nn.functional.leaky_relu, "tanh": torch.tanh}
+        total = torch.zeros(13, 3, dtype=torch.float64)
+        for s in range(10):
+            W = {k: loc[k] + torch.nn.functional.softplus(raw[k]) * eps[k][s] for k in shapes}
+            h, ks = x, R.layer_keys(arch)
+            for i, k in enumerate(ks):
+                h = h @ W[k + ".weight"].T + W[k + ".bias"]
+                if i + 1 < len(ks):
+                    h = acts[act](h)
+            total += torch.softmax(h, -1)
+        assert torch.allclose(psum, total, rtol=1e-13, atol=0)
+        assert torch.equal(pred, torch.argmax(total, -1))
+        top = (total / 10).sort(-1, descending=True)[0]
+        assert torch.allclose(gap, top[:, 0] - top[:, 1], rtol=0, atol=1e-15)
+        # another step, another key: other draws
+        assert not torch.equal(R.accuracy_forward(loc, raw, arch, act, x.reshape(13, 1, 6, 1), key, t + 1)[0], psum)
+        assert not torch.equal(R.accuracy_forward(loc, raw, arch, act, x.reshape(13, 1, 6, 1), key + 1, t)[0], psum)
+
+
+def test_first_maximum_wins_an_exact_tie():
+    p = torch.tensor([[0.25, 0.5, 0.5], [0.5, 0.5, 0.25], [0.125, 0.25, 0.75], [1.0, 1.0, 1.0], [0.3, 0.2, 0.3]], dtype=torch.float64)
+    assert R.first_argmax(p).tolist() == [1, 0, 2, 0, 0]
+    assert R.top2_gap(p).tolist() == [0.0, 0.0, 0.5, 0.0, 0.0]
+    assert R.first_argmax(p[:, :1]).tolist() == [0] * 5 and bool(torch.isinf(R.top2_gap(p[:, :1])).all())       # one class: never marginal
+
+
+def test_restatement_records_the_loss_of_every_step():
+    shapes, loc, raw, x, y = _guide("fc", 6, 8, 3, seed=2)
+    r, plain = R.Restatement(loc, raw, "fc", "leaky", 0.01, 7, record=True), R.Restatement(loc, raw, "fc", "leaky", 0.01, 7)
+    got = [r.step(x, y) for _ in range(4)]
+    assert r.losses == got and len(set(got)) == 4 and plain.losses is None
+    assert [plain.step(x, y) for _ in range(4)] == got
+    # the recorded loss of step t is the ELBO of the guide BEFORE that step's update, at the draw of step t
+    again = R.Restatement(loc, raw, "fc", "leaky", 0.01, 7)
+    for t in range(3):
+        again.step(x, y)
+    assert got[3] == float(R.step_gradients(again.loc, again.raw, again.eps(3), x, y, "fc", "leaky")[0])
+
+
+def _gpu_cases():
+    import test_hip_svi_train as T
+    return T
+
+
+@pytest.mark.parametrize("case", _gpu_cases().GRAD_CASES, ids=lambda c: f"{c[0]}-{c[1]}-{c[2][0] * c[2][1] * c[2][2]}-{c[3]}-{c[4]}-{c[5]}")
+def test_gradient_cases_keep_their_exclusions_under_the_cap(case):
+    """With the oracle alone: at most 1 % of a case's points lie within the kink margin (none at B <= 3), a case with C > 1 and B >= 65 has
+    points on both branches of the head kernel's CE, and the confident case has at least a quarter of its points at CE < 1e-3."""
+    T = _gpu_cases()
+    c, B = T.grad_case(*case), case[5]
+    n = int(c["ok"].sum())
+    assert B - n <= 0.01 * B
+    if case[4] > 1 and B >= 65:
+        assert 0 < int(c["log1p"].sum()) < n
+    if c["confident"]:
+        assert int((c["log1p"] & (c["ce"] < T.CONFIDENT)).sum()) >= n // 4
+
+
+def test_gradient_cases_cover_the_edges():
+    T = _gpu_cases()
+    D = lambda c: c[2][0] * c[2][1] * c[2][2]
+    cases = T.GRAD_CASES
+    assert {96, 160, 1024} <= {c[3] for c in cases} and {1, 16} <= {c[4] for c in cases} and {1, 3, 65, 300} <= {c[5] for c in cases}
+    for arch in ("fc", "fc2"):
+        assert {10, 17, 3072} <= {D(c) for c in cases if c[0] == arch}
+    assert ("fc2", "relu") in {c[:2] for c in cases} and ("fc", "sigm") in {c[:2] for c in cases}
+    assert any(c[3] % 64 and D(c) % 16 and c[5] % 64 for c in cases)
+    assert len(set(cases)) == len(cases) and sum(1 for c in cases if T.grad_case(*c)["confident"]) == 1
+
+
+@pytest.mark.parametrize("name", _gpu_cases().EPOCH_CASES)
+def test_epoch_cases_keep_the_marginal_points_under_the_cap(name):
+    """The fp64 restatement's own trajectory of every epoch set-up: points whose two largest mean probabilities are closer than the margin are
+    at most 1 % of each epoch's points (expected: none), and every epoch ends on a short batch."""
+    T = _gpu_cases()
+    c = T.epoch_case(name)
+    n, bs = c["n"], c["batch"]
+    assert 0 < n % bs < bs
+    r = R.Restatement(c["loc"], c["raw"], c["arch"], c["act"], c["lr"], c["key"], torch.float64)
+    for epoch in range(c["epochs"]):
+        marginal = 0
+        for i in range(0, n, bs):
+            x, lab = c["x"][i:i + bs], c["lab"][i:i + bs]
+            t = r.t
+            r.step(x, lab)
+            psum, pred, gap = R.accuracy_forward(r.loc, r.raw, c["arch"], c["act"], x, c["key"], t)
+            marginal += T.accuracy_bounds(psum, pred, gap, lab)[1]
+        assert marginal <= 0.01 * n, (epoch, marginal)
+        assert marginal == 0, (epoch, marginal)
+
+
+def test_history_case_spread_is_the_measured_one():
+    """The bar of the GPU module's history test is 10 x the relative fp32-vs-fp64 spread of the restatement's own epoch losses: measured here."""
+    T = _gpu_cases()
+    out = T.history_restatements([torch.float32, torch.float64])
+    spread = max(abs(a - b) / abs(b) for a, b in zip(out[torch.float32], out[torch.float64]))
+    print(f"epoch losses fp32 {out[torch.float32]}  fp64 {out[torch.float64]}  relative spread {spread:.3e} (recorded {T.HISTORY_CASE['spread']:.3e})")
+    assert T.HISTORY_CASE["spread"] / 4 <= spread <= 4 * T.HISTORY_CASE["spread"]
 
 
 @pytest.mark.usefixtures("built_library")
