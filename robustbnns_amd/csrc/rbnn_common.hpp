@@ -102,12 +102,9 @@ template <int CM> __device__ __forceinline__ void ce_softmax_grad(const float (&
 // per backward call, 4 TB/s under a 3.9-ms kernel).  a_from_memory: the order is blocked 2-D — TB point tiles x all column groups, column
 // group fastest — so that the ~56 blocks an XCD holds at a time read 8 A tiles and 7 W1 slices per stage between them.  Same work per item:
 // results bit-identical.  fc2-512 backward 6.61 -> 6.17 ms, fc2-1024 17.74 -> 16.73 (same box, profiles/r05s).
-#ifndef RBNN_GRAD_STEP2_TB
-#define RBNN_GRAD_STEP2_TB 8
-#endif
 __device__ __forceinline__ void grad_item(int id, int NT, int ND, bool a_from_memory, int& ntile, int& dg, int& ch) {
-    if (a_from_memory && RBNN_GRAD_STEP2_TB > 0) {
-        constexpr int TB = RBNN_GRAD_STEP2_TB > 0 ? RBNN_GRAD_STEP2_TB : 1;
+    if (a_from_memory) {
+        constexpr int TB = 8;                                  // point tiles per block of the 2-D order (see above: 8 A tiles x 7 W1 slices per XCD)
         const int per = NT * ND, blk = TB * ND, full = NT / TB;
         ch = id / per;
         const int il = id - ch * per;

@@ -17,10 +17,6 @@
 // activation, and then the first one wins); their backward takes act' from the stored activation value, no sign bit.
 #include "rbnn_conv_common.hpp"
 
-#ifndef RBNN_FCBWD_NT
-#define RBNN_FCBWD_NT 1                                                    // conv_fc_bwd writes dQ2 (5 GB per C5 pass, re-read from HBM by the dense kernel in any case) with non-temporal stores:
-#endif                                                                     // they no longer push the sample's Fw out of the L2 — 1.54 -> 1.25 ms (same box, alternating: backward call 16.3 -> 16.0 ms)
-
 using namespace rbnn_conv_shared;
 
 namespace {
@@ -35,14 +31,8 @@ namespace {
 // the FMA loop (0.52 -> see profiles/r03a/conv_small_kernels.txt).  Each output is still produced by one thread in the same order.
 // (3x32x32: 196 positions fill a 256-thread block well enough, and the two-halves form measured slower there: 2.45 -> 2.66 ms at c5)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef RBNN_CONV1_W128
-#define RBNN_CONV1_W128 1
-#endif
-#ifndef RBNN_CONV1_WAVES
-#define RBNN_CONV1_WAVES 1
-#endif
 template <int ACT, class G>
-__global__ void __launch_bounds__(conv1_threads<G>(), RBNN_CONV1_WAVES) conv1_pool_kernel(const ConvArgs a) {
+__global__ void __launch_bounds__(conv1_threads<G>(), 1) conv1_pool_kernel(const ConvArgs a) {
     constexpr int NPP = G::P1W * G::P1W, IW = G::IW, NTH = conv1_threads<G>();
     // Weights in LDS as CHANNEL PAIRS: [c / 2][ci][tap][2] (52 floats per (pair, ci): thirteen aligned float4).  The FMA loop then runs on
     // v_pk_fma_f32 — one instruction = the same tap of two output channels against one broadcast patch value — i.e. at the packed fp32 rate
@@ -90,12 +80,9 @@ __global__ void __launch_bounds__(conv1_threads<G>(), RBNN_CONV1_WAVES) conv1_po
 #pragma unroll
                 for (int kx = 0; kx < 5; ++kx) {
                     const int tap = ky * 5 + kx;
-#if RBNN_CONV1_W128
+                    // one 16-byte read per tap pair (it keeps 52 more registers live than 8-byte reads: 252 VGPRs, hence one wave per SIMD in the launch bounds)
                     const f32x4 w4 = *(const f32x4*)(wrow + 4 * (tap >> 1));
                     const f32x2 wv = (tap & 1) ? (f32x2){w4[2], w4[3]} : (f32x2){w4[0], w4[1]};
-#else
-                    const f32x2 wv = *(const f32x2*)(wrow + 2 * tap);     // (a 16-byte read per tap pair keeps 52 more registers live: 252 VGPRs, two waves per SIMD)
-#endif
 #pragma unroll
                     for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -658,11 +645,9 @@ __global__ void __launch_bounds__(256) conv_fc_bwd_kernel(const ConvBwdArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] *= act_grad_from_value<ACT>(h[r]);
             }
-#if RBNN_FCBWD_NT
+            // dQ2 (5 GB per C5 pass, re-read from HBM by the dense kernel in any case) leaves by non-temporal stores: they no longer push the
+            // sample's Fw out of the L2 — 1.54 -> 1.25 ms (same box, alternating: backward call 16.3 -> 16.0 ms)
             __builtin_nontemporal_store(v, (f32x4*)dst);
-#else
-            *(f32x4*)dst = v;
-#endif
         }
     }
 }
@@ -713,11 +698,7 @@ __global__ void __launch_bounds__(256, 2) conv_bwd_kernel(const ConvBwdArgs a) {
     // all K = 25*Hc products (12 800 at Hc = 512) carries ~sqrt(K) roundings of the running sum; blocks of 800 carry
     // ~sqrt(800) + sqrt(K/800) — measured against fp64 the per-point median error of the whole path drops accordingly.
     // (The second register set fits two blocks per CU only while 2 * 2 * NPT tiles do: 1x28x28.  3x32x32 keeps one chain.)
-#ifndef RBNN_CONV_BWD_UNBLOCKED
     constexpr bool BLOCKED = NPT <= 9;
-#else
-    constexpr bool BLOCKED = false;
-#endif
     constexpr int FLUSH = 2, NTOT = BLOCKED ? NPT : 1;
     f32x4 acc[2][NPT], tot[2][NTOT];
 #pragma unroll

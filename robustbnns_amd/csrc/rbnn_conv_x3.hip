@@ -10,14 +10,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#ifndef RBNN_X3FWD_NT
-#define RBNN_X3FWD_NT 0                                                    // non-temporal Q2 / stash stores of conv2_pool_x3_kernel: measured equal / slower
-#endif
-#ifndef RBNN_CONV1_BWD_X3_MINCIN
-#define RBNN_CONV1_BWD_X3_MINCIN 2                                        // input channels from which conv1^T runs on the f16 pipe (1x28x28 keeps the fp32 kernel)
-#endif
-
 using namespace rbnn_conv_shared;
+
+constexpr int CONV1_BWD_X3_MINCIN = 2;                                     // input channels from which conv1^T runs on the f16 pipe (1x28x28 keeps the fp32 kernel)
 
 namespace {
 
@@ -124,15 +119,12 @@ __global__ void __launch_bounds__(512, 2) conv2_pool_x3_kernel(const ConvArgs a,
     const int prow = lane >> 2;
     const unsigned src_off = (unsigned)(prow * 64 + ((lane & 3) ^ swz(prow)) * 16);   // inside a 1-KiB piece: row prow, logical chunk (lane & 3) ^ swz(row)
     const int foff = li * 64 + ((lg ^ swz(li)) * 16);
-    // RBNN_X3FWD_PAIR13 (round 5; geometries whose NPOS is not a multiple of 16, i.e. 3x32x32): the two points of a block are tiled TOGETHER —
+    // PAIR (round 5; geometries whose NPOS is not a multiple of 16, i.e. 3x32x32): the two points of a block are tiled TOGETHER —
     // combined position c = 100 * point + position, 200 positions = 13 tiles of 16 instead of 2 x 7 (7.1 % fewer MFMAs: eight idle columns per
     // pair instead of twenty-four).  The wave of the pair's first point takes tiles 0 .. 6 (its last tile: 4 positions of point 0, 12 of point 1,
     // which it writes into its partner's pooling tile), the other wave tiles 7 .. 12; the two waves of a channel group share a SIMD (wave & 3),
     // so every SIMD issues 13 tiles per tap instead of 14.  Same-box: 14.37 -> 13.97 ms per C5 forward call (profiles/r05w).
-#ifndef RBNN_X3FWD_PAIR13
-#define RBNN_X3FWD_PAIR13 1
-#endif
-    constexpr bool PAIR = RBNN_X3FWD_PAIR13 && (NPOS_ % 16 != 0);
+    constexpr bool PAIR = NPOS_ % 16 != 0;
     static_assert(!PAIR || (2 * NPOS_ + 15) / 16 == 2 * NPT - 1, "13 = 7 + 6 tiles");
     const char* const img = imgs + wp * L::IMGB;
     constexpr int CPITCH = NPOS_ + 4, EIT = (16 * NP2_ / 4 + 63) / 64;
@@ -296,13 +288,8 @@ __global__ void __launch_bounds__(512, 2) conv2_pool_x3_kernel(const ConvArgs a,
                         stw |= (unsigned)(arg | (best > 0.f ? 4 : 0)) << (8 * j);
                     }
                     const long long o = sn * F + (long long)hcb * NP2_ + 4 * i4;       // a multiple of 4
-#if RBNN_X3FWD_NT
-                    __builtin_nontemporal_store(q, (f32x4*)(a.Q2 + o));
-                    __builtin_nontemporal_store(stw, (unsigned*)(a.st2 + o));
-#else
-                    *(f32x4*)(a.Q2 + o) = q;
+                    *(f32x4*)(a.Q2 + o) = q;                                       // (plain stores: non-temporal ones measured equal / slower)
                     *(unsigned*)(a.st2 + o) = stw;
-#endif
                 }
             }
             if (PAIR && ht + 1 < HTW) __syncthreads();                     // the tiles are rewritten by the next channel tile (the partner's wave writes into this one's)
@@ -850,17 +837,11 @@ __global__ void __launch_bounds__(512, 2) conv_bwd_dense_x3_kernel(const ConvBwd
     const long long sn = (long long)s * a.N + n;
     const int F = a.Hc * NP2_, KS = (a.Hc + 31) / 32;
     const float slope = ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE;
-#ifndef RBNN_DENSE_PRIO
-#define RBNN_DENSE_PRIO 1
-#endif
     // A SIMD issues from its OLDEST ready wave: of the two waves that share one, the lower-numbered ran ahead every K step and its partner did the
     // rest of its taps alone, its stalls uncovered (stamps: a 7-tap wave 47k of 189k K-loop cycles at the barrier, its partner 15k).  The wave of a
     // SIMD that must not be the one left alone — the 7-tap waves (0, 5), the staging waves (2, 7) — takes the higher issue priority.
-    // (RBNN_DENSE_PRIO: 1 = those four waves, always — the default; 2 = the 7-tap waves only; 3 = the four, but only through tap 3 of every K step;
-    //  4 = the OTHER four waves; measured in profiles/r05q/dense_prio.txt)
-    const bool prio_wave = RBNN_DENSE_PRIO == 4 ? !(wave == 0 || wave == 5 || wave == 2 || wave == 7)
-                         : (wave == 0 || wave == 5 || (RBNN_DENSE_PRIO != 2 && (wave == 2 || wave == 7)));
-    if (RBNN_DENSE_PRIO && prio_wave) __builtin_amdgcn_s_setprio(1);
+    // (the 7-tap waves only, the four only through tap 3 of every K step, and the OTHER four waves all measured worse: profiles/r05q/dense_prio.txt)
+    if (wave == 0 || wave == 5 || wave == 2 || wave == 7) __builtin_amdgcn_s_setprio(1);
 #ifdef RBNN_DENSE_STAMPS
     unsigned long long tprev = __builtin_amdgcn_s_memtime();
     const unsigned long long tstart = tprev;
@@ -1087,10 +1068,6 @@ __global__ void __launch_bounds__(512, 2) conv_bwd_dense_x3_kernel(const ConvBwd
             ATile& cur = ic == 0 ? A0 : (ic == 1 ? A1 : A2);
             ATile& nxt = in == 0 ? A0 : (in == 1 ? A1 : A2);
             // a later tap's tile into a free register set (the compiler places the counted wait in front of the first MFMA that reads `cur`)
-            if constexpr (RBNN_DENSE_PRIO == 3) {                          // (wave-uniform scalar branches: two per K step)
-                if (t == 0 && prio_wave) __builtin_amdgcn_s_setprio(1);
-                if (t == 4 && prio_wave) __builtin_amdgcn_s_setprio(0);
-            }
             tile_load((t + LA) / NT ? ksn : ks, (t + LA) % NT, nxt);
             // (the staging role is a compile-time fact here, so that the counted waits of the other waves know of no staging piece)
             if constexpr (t == 0 && STGR != 0) stage_issue(min(ks + 2, KS - 1), ks & 1, WHOLEC, STGC);   // behind tap 2's request: first covered by the wait of tap 3
@@ -1226,7 +1203,7 @@ __global__ void __launch_bounds__(512, 2) conv_bwd_dense_x3_kernel(const ConvBwd
             }
         }
     }
-    if (G::CIN >= RBNN_CONV1_BWD_X3_MINCIN) {                              // max |dP1| of this (sample, point) -> G[sn][0]: the scale of conv1_bwd_x3_kernel (which reads it before it writes G)
+    if (G::CIN >= CONV1_BWD_X3_MINCIN) {                              // max |dP1| of this (sample, point) -> G[sn][0]: the scale of conv1_bwd_x3_kernel (which reads it before it writes G)
         // (the butterfly's lane indices from a fresh lane id: those of set_scales() at the top of the block, kept for reuse here, were five registers
         // spilled over the K loops)
         int lane_e;
@@ -1353,7 +1330,7 @@ extern "C" int rbnn_conv_input_grad_dense(const rbnn_conv_posterior* net, const 
             if ((rc2 = launch_status())) return rc2;
             // conv1^T: on the f16 pipe for more than one input channel (scaled by the max |dP1| the dense kernel left in G[sn][0]); one input
             // channel (1x28x28): two row tiles either way, and the fp32 kernel runs three waves per SIMD — measured 0.73 against 0.79 ms
-            if (G::CIN >= RBNN_CONV1_BWD_X3_MINCIN) {
+            if (G::CIN >= CONV1_BWD_X3_MINCIN) {
                 hipLaunchKernelGGL((conv1_bwd_x3_kernel<ACT, G>), dim3(grid_for_items((long long)((a.N + 3) / 4) * a.S)), dim3(256), 0, st, a);
                 return launch_status();
             }

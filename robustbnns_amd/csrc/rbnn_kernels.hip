@@ -22,9 +22,6 @@
 // The k <-> memory-index map of a K step is free as long as A and B agree; both kernels use
 // "step r of a 16-wide k block: k = lg  <->  index 4*lg + r", so one 16-byte load feeds four K steps.
 #include "rbnn_common.hpp"
-#ifndef RBNN_FWD_SB
-#define RBNN_FWD_SB 8                                          // forward: samples per XCD-resident panel of blocks
-#endif
 #include <stdlib.h>
 
 namespace {
@@ -53,21 +50,12 @@ __global__ void __launch_bounds__(64 * WH * WN, (HTW * NTW > 16 ? 2 : (WH * WN) 
     static_assert(NW == 4 || NW == 8, "4 or 8 waves per block");
     static_assert(HTW % 2 == 0 && HTW <= 8, "a wave's h range is whole 32-bit mask words, at most 4");
     static_assert(WH * BN * 16 <= 2 * TILE, "the Z^T reduction scratch aliases the tile buffers");
-    // K tiles go through a ring of LDS buffers filled by LDS-DMA.  When every wave issues the same number of DMA
-    // pieces per tile (OPS) the ring is 3 deep and tile kt+2 is in flight while tile kt is multiplied: the wait
-    // before the barrier is a COUNTED vmcnt(OPS) (tile kt+1 landed, kt+2 may still fly) and the barrier is a raw
-    // s_barrier — __syncthreads() would drain vmcnt(0) and expose one full L2/HBM latency per tile.
-    // (Measured at C2: the 3-deep ring is NOT faster than the 2-deep one — 6.34 vs 6.23 ms — the forward kernel is
-    // bound by the CU's memory-pipe throughput for the DMA pieces, not by their latency.  Kept behind RBNN_RING3.)
-#ifdef RBNN_RING3
-    constexpr bool RING3 = (BH / 16) % NW == 0 && (BN / 16) % NW == 0;
-#else
-    constexpr bool RING3 = false;
-#endif
-    constexpr int NBUF = RING3 ? 3 : 2, OPS = BH / 16 / NW + BN / 16 / NW;
-    // ONE LDS array (tile ring; the softmax scratch aliases it after the K loop): global_load_lds
+    // K tiles go through two LDS buffers filled by LDS-DMA: tile kt+1 is in flight while tile kt is multiplied.
+    // (A 3-deep ring with counted vmcnt waits measured no faster at C2 — 6.34 vs 6.23 ms: the forward kernel is bound
+    // by the CU's memory-pipe throughput for the DMA pieces, not by their latency.)
+    // ONE LDS array (both tile buffers; the softmax scratch aliases it after the K loop): global_load_lds
     // staging beside a second __shared__ object makes hipcc drain vmcnt before every ds_read.
-    __shared__ __attribute__((aligned(16))) float lds[NBUF * TILE];
+    __shared__ __attribute__((aligned(16))) float lds[2 * TILE];
     float* const zred = lds;
 
     int id;
@@ -75,17 +63,13 @@ __global__ void __launch_bounds__(64 * WH * WN, (HTW * NTW > 16 ? 2 : (WH * WN) 
     // item -> (point tile, sample), 2-D blocked: panels of 8 samples, inside a panel the sample index runs fastest, so
     // the ~64 blocks resident on an XCD are 8 point tiles x 8 samples: each X tile and each W1 slice is fetched into that
     // XCD's L2 once per 8 users instead of once per user.
-#ifndef RBNN_FWD_ITEM_1D
     int ntile, s;
     {
-        constexpr int SB = RBNN_FWD_SB;
+        constexpr int SB = 8;                                  // samples per XCD-resident panel of blocks
         const int full = a.S / SB, per = SB * a.NT;
         if (id < full * per) { ntile = (id % per) / SB; s = (id / per) * SB + id % SB; }
         else { const int rem = id - full * per, cnt = a.S - full * SB; ntile = rem / cnt; s = full * SB + rem % cnt; }
     }
-#else
-    const int ntile = id % a.NT, s = id / a.NT;
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
     const int wave_h = wave % WH, wave_n = wave / WH;
     const int sw = a.sidx ? a.sidx[s] : s;
@@ -122,13 +106,11 @@ __global__ void __launch_bounds__(64 * WH * WN, (HTW * NTW > 16 ? 2 : (WH * WN) 
             }
         };
         stage(0, 0);
-        if (RING3 && a.KT > 1) stage(1, 1);
-        if (RING3 && a.KT > 1) ring_wait_barrier<OPS>(); else ring_wait_barrier<0>();   // tile 0 landed for every wave
+        ring_wait_barrier<0>();                                // tile 0 landed for every wave
         f32x4 bf[NTW], a_cur, a_nxt;
-        int buf = 0, nbuf = RING3 ? 2 : 1;                     // buffer of tile kt / of the tile staged in this iteration
+        int buf = 0, nbuf = 1;                                 // buffer of tile kt / of the tile staged in this iteration
         for (int kt = 0; kt < a.KT; ++kt) {
-            const bool more = kt + (RING3 ? 2 : 1) < a.KT;
-            if (!(RBNN_ABL & 1) && more) stage(kt + (RING3 ? 2 : 1), nbuf);   // lands while this (and the next) tile is multiplied
+            if (!(RBNN_ABL & 1) && kt + 1 < a.KT) stage(kt + 1, nbuf);   // lands while this tile is multiplied
             const float* const Wt = lds + buf * TILE;
             const float* const Xt = Wt + BH * 16;
             // Fragment reads are software-pipelined one h-tile ahead of the MFMAs that consume them, and the
@@ -161,10 +143,10 @@ __global__ void __launch_bounds__(64 * WH * WN, (HTW * NTW > 16 ? 2 : (WH * WN) 
             }
             if (!(RBNN_ABL & 2)) {
                 // tile kt+1 landed (this wave's share; the barrier covers the others); everyone is done with tile kt
-                if (RING3 && more) ring_wait_barrier<OPS>(); else ring_wait_barrier<0>();
+                ring_wait_barrier<0>();
             }
-            buf = (buf + 1 == NBUF) ? 0 : buf + 1;
-            nbuf = (nbuf + 1 == NBUF) ? 0 : nbuf + 1;
+            buf = (buf + 1 == 2) ? 0 : buf + 1;                // (ring arithmetic as the compiler has always seen it: an xor schedules the loop differently)
+            nbuf = (nbuf + 1 == 2) ? 0 : nbuf + 1;
         }
         if (RBNN_ABL & 2) __syncthreads();
         if (RBNN_ABL & 8) {                                    // diagnostic: keep the accumulators live, skip the epilogue
@@ -287,9 +269,10 @@ struct GradArgs {
     const uint32_t* omask;  const float* odact;  int OHW;                              // PER_SAMPLE epilogue: derivative of the layer below
 };
 
-template <int ACT, int TD, int CQ, bool A_MEM, bool PER_SAMPLE, int HSTG>
+template <int ACT, int TD, int CQ, bool A_MEM, bool PER_SAMPLE>
 __global__ void __launch_bounds__(256, 2) fc_grad_kernel(const GradArgs a) {
-    constexpr int NTW = 4, BM = 256;                           // 4 waves x 64 points; HSTG (32 or 64) hidden units per LDS stage
+    constexpr int NTW = 4, BM = 256;                           // 4 waves x 64 points
+    constexpr int HSTG = 32;                                   // hidden units per LDS stage (64 spills: 256 VGPR + 124 B scratch, 7.31 vs 6.79 ms at C2)
     constexpr int LD = TD * 16;                                // W1 stage tile: [HSTG/4 h-quads][TD*16 d][4], linear LDS-DMA image
     constexpr int W2RPP = 256 / HSTG;                          // W2 tile rows (classes) per 1-KiB piece
     constexpr int W2ROWS = (4 * CQ + W2RPP - 1) / W2RPP * W2RPP;   // W2 stage tile: [classes, whole pieces][HSTG h]
@@ -441,9 +424,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_kernel(const GradArgs a) {
                     for (int nt = 0; nt < NTW; ++nt)
                         acc[nt][dt] = MFMA16(da[(RBNN_ABL & 20) ? 0 : (t2 & 1)][nt][r], b4[dt][r], acc[nt][dt]);
                 if (!(RBNN_ABL & 4) && t2 + 1 < NT2) read_b(t2 + 1, dt);
-#ifndef RBNN_NO_PIN
                 __builtin_amdgcn_sched_barrier(0);             // keep the re-read HERE: hipcc would sink it to its consumer
-#endif
             }
         });
         if (!(RBNN_ABL & 2)) __syncthreads();                  // vmcnt(0): next tiles landed; everyone is done with these
@@ -758,19 +739,11 @@ template <int ACT, int TD, bool A_MEM, bool PER_SAMPLE>
 int launch_grad_c(const GradArgs& a, hipStream_t st) {
     const int grid = grid_for_items((long long)a.NT * a.ND * a.nchunks);
     if constexpr (A_MEM) {
-        hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 1, true, PER_SAMPLE, 32>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 1, true, PER_SAMPLE>), dim3(grid), dim3(256), 0, st, a);
     } else {                          // CQ = MFMA K steps (4 classes each) of the dA product
-        // (64-unit stages — template parameter HSTG — halve the per-stage overhead but spill: 256 VGPR + 124 B scratch,
-        //  7.31 ms vs 6.79 ms at C2, so only the 32-unit stage is dispatched.)
-#ifdef RBNN_GRAD_STAGE64
-        if (!PER_SAMPLE && TD == 7 && a.C > 4 && a.C <= 12 && a.H % 64 == 0) {
-            hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 3, false, PER_SAMPLE, 64>), dim3(grid), dim3(256), 0, st, a);
-            return launch_status();
-        }
-#endif
-        if (a.C <= 4)       hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 1, false, PER_SAMPLE, 32>), dim3(grid), dim3(256), 0, st, a);
-        else if (a.C <= 12) hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 3, false, PER_SAMPLE, 32>), dim3(grid), dim3(256), 0, st, a);
-        else                hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 4, false, PER_SAMPLE, 32>), dim3(grid), dim3(256), 0, st, a);
+        if (a.C <= 4)       hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 1, false, PER_SAMPLE>), dim3(grid), dim3(256), 0, st, a);
+        else if (a.C <= 12) hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 3, false, PER_SAMPLE>), dim3(grid), dim3(256), 0, st, a);
+        else                hipLaunchKernelGGL((fc_grad_kernel<ACT, TD, 4, false, PER_SAMPLE>), dim3(grid), dim3(256), 0, st, a);
     }
     return launch_status();
 }

@@ -399,9 +399,6 @@ template <int ACT> int launch_low_act(const LowArgs& a, hipStream_t st) {
 //   low2_finish_kernel         sum of the S slabs in a fixed order, then the gradient + its norms, or the sign / project / clamp step
 // — three (two kernels) for the per-sample loss of lossGradients.py:29-40.  Every sum has a fixed order: results are deterministic.
 // =====================================================================================================
-#ifndef RBNN_LOW2_STASH
-#define RBNN_LOW2_STASH 1                                                  // 0: the backward launch always recomputes the forward (the form until round 4's second half)
-#endif
 struct Low2Args {
     rbnn_posterior net;
     const float* X;                // current iterate [N, ldx]
@@ -878,7 +875,7 @@ int run_low2(const rbnn_posterior* net, int op, int loss, int out_kind, const fl
     }
     a.probs = loss != RBNN_LOSS_MEAN_LOGIT;
     // relu / leaky with a forward launch in the pass: the forward leaves the sign bits of both hidden layers, the backward starts at dZ
-    a.mask = (RBNN_LOW2_STASH && loss != RBNN_LOSS_PER_SAMPLE && (net->activation == RBNN_ACT_RELU || net->activation == RBNN_ACT_LEAKY)) ? mask : nullptr;
+    a.mask = (loss != RBNN_LOSS_PER_SAMPLE && (net->activation == RBNN_ACT_RELU || net->activation == RBNN_ACT_LEAKY)) ? mask : nullptr;
     const int T = op == OP_ATTACK ? iters : 1;
     for (int it = 0; it < T; ++it) {
         a.X = (it == 0) ? X : out;                                         // the iterate lives in `out` from the first step on,

@@ -542,8 +542,9 @@ struct GradSplitArgs {
 };
 enum { GRAD_FC = 0, GRAD_FC2_STEP1 = 1, GRAD_FC2_STEP2 = 2 };
 
-template <int ACT, int TD, int NTW, int NW, int MODE>
-__global__ void __launch_bounds__(64 * NW, (TD * NTW > 32 ? 1 : 2)) fc_grad_split_kernel(const GradSplitArgs a) {   // wide column groups: one wave per SIMD, up to 512 registers
+template <int ACT, int TD, int MODE>
+__global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradSplitArgs a) {
+    constexpr int NW = 4, NTW = 4;                             // 4 waves x 4 point tiles, two blocks per CU (8-wave and 1-block shapes lost: see launch_grad_split)
     constexpr bool GEN = MODE != GRAD_FC2_STEP2;               // dA generated from dZ, or read from memory
     constexpr bool BITMASK = (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY);   // act' from the 1-bit stash, or an fp32 stream
     constexpr bool STREAM = !GEN || !BITMASK;                  // a per-lane fp32 operand (A itself, or act') is prefetched from memory
@@ -726,16 +727,16 @@ __global__ void __launch_bounds__(64 * NW, (TD * NTW > 32 ? 1 : 2)) fc_grad_spli
         }
 }
 
-template <int ACT, int TD, int NTW, int NW, int MODE>
+template <int ACT, int TD, int MODE>
 int launch_grad_split_cfg(GradSplitArgs a, hipStream_t st) {
     constexpr int LDSB = 2 * (8 * TD * 16 * 16 + 3072) + 2 * 256 * 64;
     a.NT = (a.N + 255) / 256;
     a.ND = (a.Dt + TD - 1) / TD;
-    auto kern = fc_grad_split_kernel<ACT, TD, NTW, NW, MODE>;
+    auto kern = fc_grad_split_kernel<ACT, TD, MODE>;
     static unsigned long long attr_done = 0;
     if (!ensure_dynamic_lds((const void*)kern, LDSB, attr_done)) return RBNN_ERR_LAUNCH;
     const int grid = grid_for_items((long long)a.NT * a.ND * a.nchunks);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), LDSB, st, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDSB, st, a);
     return launch_status();
 }
 
@@ -746,20 +747,13 @@ int launch_grad_split_cfg(GradSplitArgs a, hipStream_t st) {
 // Building stage st+1's dA tiles inside stage st's MFMA stream (in-wave software pipelining, dA registers double-buffered,
 // slices fenced between groups of 12 MFMAs) was also slower, 2.73 vs 2.49 ms: a wave issues in order, and the dependent
 // VALU chains stall the independent MFMAs queued behind them.  (profiles/r01f/ablation_split.txt)
-// RBNN_GRAD_SPLIT_TD14 keeps the first of those selectable for experiments.
 template <int ACT, int MODE>
 int launch_grad_split(const GradSplitArgs& a, hipStream_t st) {
-#ifdef RBNN_GRAD_SPLIT_TD14
-    if (MODE == GRAD_FC && a.Dt > 7) return launch_grad_split_cfg<ACT, 14, 2, 8, MODE>(a, st);
-#endif
-#ifdef RBNN_GRAD_SPLIT_TDW                                      // experiment: 4 waves x 4 point tiles x TDW column tiles, one block per CU
-    if (MODE == GRAD_FC && a.Dt > 7) return launch_grad_split_cfg<ACT, RBNN_GRAD_SPLIT_TDW, 4, 4, MODE>(a, st);
-#endif
     // 7 or 4 column tiles per block.  A partial last group skips its missing tiles' MFMAs, so padding costs little; every
     // group pays the dA generator (or the A-operand reads) again, so FEWER groups win: 7 wherever that saves a group
     // (fc2 step 1 at H = 512: 32 tiles = 5 groups of 7 instead of 8 of 4 — 2.72 -> see profiles)
-    if ((a.Dt + 6) / 7 < (a.Dt + 3) / 4) return launch_grad_split_cfg<ACT, 7, 4, 4, MODE>(a, st);
-    return launch_grad_split_cfg<ACT, 4, 4, 4, MODE>(a, st);
+    if ((a.Dt + 6) / 7 < (a.Dt + 3) / 4) return launch_grad_split_cfg<ACT, 7, MODE>(a, st);
+    return launch_grad_split_cfg<ACT, 4, MODE>(a, st);
 }
 
 template <int MODE>

@@ -26,13 +26,6 @@
 #include <algorithm>
 #include <cstdlib>
 
-#ifndef RBNN_X3_FWD_SB
-#define RBNN_X3_FWD_SB 4                                      // forward: samples per XCD-resident group of blocks
-#endif
-#ifndef RBNN_X3_BARRIER_END
-#define RBNN_X3_BARRIER_END 0
-#endif
-
 namespace {
 
 __device__ __forceinline__ void split3(float v, _Float16& p0, _Float16& p1, _Float16& p2) {
@@ -189,7 +182,7 @@ __global__ void __launch_bounds__(64 * WH * WN, WH * WN / 4) fc_forward_x3_kerne
     // sample's W1 image (H * ldw * 6 B) and its X tile (BN * ldx * 6 B), both shared through that XCD's L2 with the co-resident blocks
     // of the same sample / tile: bytes from beyond the L2 per 32 blocks ~ SB * |W1| + (32 / SB) * |X tile|, minimal at SB = 2..4 here
     // (2.46 MB vs 0.61 MB); the exact kernel's SB = 8 cost 33 % more (profiles/r02t: FETCH_SIZE)
-    constexpr int SB = RBNN_X3_FWD_SB;
+    constexpr int SB = 4;                                      // samples per XCD-resident group of blocks
     int ntile, s;
     {
         const int full = a.S / SB, per = SB * a.NT;
@@ -344,7 +337,6 @@ __global__ void __launch_bounds__(64 * WH * WN, WH * WN / 4) fc_forward_x3_kerne
                 __builtin_amdgcn_sched_group_barrier(0x008, 3 * NTW, 0);
             }
         }
-        if (RBNN_X3_BARRIER_END) __builtin_amdgcn_sched_barrier(0);   // keep the hand-off behind the stage's last MFMA
         if (!(RBNN_ABL & 2)) ring_wait_barrier<0>();           // stage g+1 landed; everyone is done with stage g
         const int hc0 = ch * BH;
         kt = wrap ? 0 : kt + 1;
@@ -479,13 +471,9 @@ int launch_forward_x3_cfg(FwdX3Args a, hipStream_t st) {
     return launch_status();
 }
 
-#ifndef RBNN_X3_FWD_CFG
-#define RBNN_X3_FWD_CFG 4, 4, 2, 4                              // 256 h x 128 n, 8 waves of 64 h x 64 n, 144 KB of LDS
-#endif
-
 template <int ACT, bool LAYER2, bool XF32>
 int launch_forward_x3_act(const FwdX3Args& a, hipStream_t st) {
-    if (a.H % 256 == 0) return launch_forward_x3_cfg<ACT, RBNN_X3_FWD_CFG, LAYER2, XF32>(a, st);
+    if (a.H % 256 == 0) return launch_forward_x3_cfg<ACT, 4, 4, 2, 4, LAYER2, XF32>(a, st);   // 256 h x 128 n, 8 waves of 64 h x 64 n, 144 KB of LDS
     if (a.H % 128 == 0) return launch_forward_x3_cfg<ACT, 2, 4, 2, 4, LAYER2, XF32>(a, st);   // 128 h x 128 n, 4 waves
     return RBNN_ERR_UNSUPPORTED;
 }
@@ -1032,73 +1020,43 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) 
         return;
     }
     // ---- epilogue: acc[nt][dt][r] = D[n = nb + nt*16 + 4*lg + r][d = dc0 + dt*16 + li], un-scaled per point ----
-#ifndef RBNN_X3_GRAD_EPI_LDS
-#define RBNN_X3_GRAD_EPI_LDS 1
-#endif
-    if constexpr (RBNN_X3_GRAD_EPI_LDS) {
-        // (round 5) Straight from the registers a store instruction covered four point rows x 64 BYTES — 128 of them per wave, half-line writes
-        // (and, fc2 step 1, a mask-word load per element).  The timing ablation without epilogues priced them at 1.1 of the fc2 backward's
-        // 6.2 ms (profiles/r05s).  Now each 16-point tile of a wave goes through a wave-private LDS tile [16 points][LD + 4] (row pitch = 4 mod 16
-        // floats: the four row groups of a ds_write_b32 land 16 banks apart) and leaves as 16-BYTE stores of whole rows: a store instruction is
-        // 64 x 16 B of at most 2 rows' contiguous runs; the stash word of the layer below is loaded once per 16 bytes.  The loop buffers are free:
-        // every wave has passed the last stage's barrier.  Same values, same order of operations per element: bit-identical results.
-        constexpr int LDW = LD + 4, C4 = LD / 4, E4 = 16 * C4;
-        static_assert(NW * 16 * LDW * 4 <= 2 * BUFB + DZB, "the waves' transposition tiles fit the loop buffers");
-        float* const tw = (float*)ldsb + wave * (16 * LDW);
+    // (round 5) Straight from the registers a store instruction covered four point rows x 64 BYTES — 128 of them per wave, half-line writes
+    // (and, fc2 step 1, a mask-word load per element).  The timing ablation without epilogues priced them at 1.1 of the fc2 backward's
+    // 6.2 ms (profiles/r05s).  Now each 16-point tile of a wave goes through a wave-private LDS tile [16 points][LD + 4] (row pitch = 4 mod 16
+    // floats: the four row groups of a ds_write_b32 land 16 banks apart) and leaves as 16-BYTE stores of whole rows: a store instruction is
+    // 64 x 16 B of at most 2 rows' contiguous runs; the stash word of the layer below is loaded once per 16 bytes.  The loop buffers are free:
+    // every wave has passed the last stage's barrier.  Same values, same order of operations per element: bit-identical results.
+    constexpr int LDW = LD + 4, C4 = LD / 4, E4 = 16 * C4;
+    static_assert(NW * 16 * LDW * 4 <= 2 * BUFB + DZB, "the waves' transposition tiles fit the loop buffers");
+    float* const tw = (float*)ldsb + wave * (16 * LDW);
 #pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = nb + nt * 16 + 4 * lg + r;
-                const float gs = (MODE == X3_FC2_STEP1) ? a.out_scale : (n < a.N ? a.gscale[n] : 0.f) * a.out_scale;
-#pragma unroll
-                for (int dt = 0; dt < TD; ++dt) tw[(4 * lg + r) * LDW + dt * 16 + li] = acc[nt][dt][r] * gs;
-            }
-#pragma unroll
-            for (int i = 0; i < (E4 + 63) / 64; ++i) {
-                const int e4 = i * 64 + lane, row = e4 / C4, c4 = e4 - row * C4;
-                const int n = nb + nt * 16 + row, d = dc0 + 4 * c4;
-                if (e4 < E4 && n < a.N && d < Dp) {                       // (Dp is a multiple of 16: a quad is in or out as a whole)
-                    f32x4 v = *(const f32x4*)(tw + row * LDW + 4 * c4);
-                    if (MODE == X3_FC2_STEP1) {                           // derivative of the layer below: units d .. d + 3 of point n, sample ch
-                        if (BITMASK) {
-                            const unsigned w = a.omask[((long long)ch * a.OHW + (d >> 5)) * a.n_pad + n] >> (d & 31);
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) v[k] = ((w >> k) & 1u) ? v[k] : (ACT == RBNN_ACT_RELU ? 0.f : v[k] * LEAKY_SLOPE);
-                        } else {
-                            v *= *(const f32x4*)(a.odact + ((long long)ch * a.N + n) * a.ldo + d);
-                        }
-                    }
-                    *(f32x4*)(a.out + ((long long)ch * a.N + n) * a.ldo + d) = v;
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt)
+    for (int nt = 0; nt < NTW; ++nt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = nb + nt * 16 + 4 * lg + r;
-            if (n >= a.N) continue;
-            const float gs = (MODE == X3_FC2_STEP1) ? a.out_scale : a.gscale[n] * a.out_scale;
-            float* const dst = a.out + ((long long)ch * a.N + n) * a.ldo;
+            const float gs = (MODE == X3_FC2_STEP1) ? a.out_scale : (n < a.N ? a.gscale[n] : 0.f) * a.out_scale;
 #pragma unroll
-            for (int dt = 0; dt < TD; ++dt) {
-                const int d = dc0 + dt * 16 + li;
-                if (d >= Dp) continue;
-                float v = acc[nt][dt][r] * gs;
-                if (MODE == X3_FC2_STEP1) {                     // derivative of the layer below: unit d of point n, sample ch
+            for (int dt = 0; dt < TD; ++dt) tw[(4 * lg + r) * LDW + dt * 16 + li] = acc[nt][dt][r] * gs;
+        }
+#pragma unroll
+        for (int i = 0; i < (E4 + 63) / 64; ++i) {
+            const int e4 = i * 64 + lane, row = e4 / C4, c4 = e4 - row * C4;
+            const int n = nb + nt * 16 + row, d = dc0 + 4 * c4;
+            if (e4 < E4 && n < a.N && d < Dp) {                       // (Dp is a multiple of 16: a quad is in or out as a whole)
+                f32x4 v = *(const f32x4*)(tw + row * LDW + 4 * c4);
+                if (MODE == X3_FC2_STEP1) {                           // derivative of the layer below: units d .. d + 3 of point n, sample ch
                     if (BITMASK) {
-                        const unsigned w = a.omask[((long long)ch * a.OHW + (d >> 5)) * a.n_pad + n];
-                        v = ((w >> (d & 31)) & 1u) ? v : (ACT == RBNN_ACT_RELU ? 0.f : v * LEAKY_SLOPE);
+                        const unsigned w = a.omask[((long long)ch * a.OHW + (d >> 5)) * a.n_pad + n] >> (d & 31);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) v[k] = ((w >> k) & 1u) ? v[k] : (ACT == RBNN_ACT_RELU ? 0.f : v[k] * LEAKY_SLOPE);
                     } else {
-                        v *= a.odact[((long long)ch * a.N + n) * a.ldo + d];
+                        v *= *(const f32x4*)(a.odact + ((long long)ch * a.N + n) * a.ldo + d);
                     }
                 }
-                dst[d] = v;
+                *(f32x4*)(a.out + ((long long)ch * a.N + n) * a.ldo + d) = v;
             }
         }
+    }
 }
 
 template <int ACT, int TD, int MODE>
@@ -1114,13 +1072,6 @@ int launch_grad_x3_cfg(GradX3Args a, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDSB, st, a);
     return launch_status();
 }
-
-#ifndef RBNN_X3_GRAD_TD9
-#define RBNN_X3_GRAD_TD9 1
-#endif
-#ifndef RBNN_X3_GRAD_TD8
-#define RBNN_X3_GRAD_TD8 1
-#endif
 
 inline bool x3_grad_td9() {
     static const bool on = [] { const char* e = getenv("RBNN_X3_GRAD_TD9"); return !e || e[0] != '0'; }();
@@ -1150,20 +1101,16 @@ bool x3_grad_two_blocks() {
 // that saves a group (a partial last group skips its missing tiles' MFMAs)
 template <int ACT, int MODE>
 int launch_grad_x3(const GradX3Args& a, hipStream_t st) {
-#if RBNN_X3_GRAD_TD9
     // 9 column tiles per block (two blocks' LDS = exactly 160 KB): 6 column groups instead of 7 at D = 784, i.e. one generator + split
     // pass in seven less: 3.71 / 3.68 -> 3.59 / 3.59 ms at C2 (alternating builds, same box).  Environment RBNN_X3_GRAD_TD9=0 switches
     // back.  (Re-planning the slab size for the 6-group grid — 6 samples per slab instead of 5 — measured slower, 3.75 ms: kept as planned.)
     if constexpr (MODE == X3_FC && (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY)) {   // (fc2 step 2 spills at 9 tiles)
         if (x3_grad_td9() && (a.Dt + 8) / 9 < (a.Dt + 6) / 7 && x3_grad_two_blocks<ACT, 9, MODE>()) return launch_grad_x3_cfg<ACT, 9, MODE>(a, st);
     }
-#endif
-#if RBNN_X3_GRAD_TD8
     // 8 column tiles per block where that saves a group over 7 (hidden = 512: fc2 step 1 runs 4 groups instead of 5)
     if constexpr (MODE != X3_FC2_STEP2 && (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY)) {   // (the streamed-operand forms spill at 8 tiles)
         if (x3_grad_td9() && (a.Dt + 7) / 8 < (a.Dt + 6) / 7 && x3_grad_two_blocks<ACT, 8, MODE>()) return launch_grad_x3_cfg<ACT, 8, MODE>(a, st);
     }
-#endif
     if ((a.Dt + 6) / 7 < (a.Dt + 3) / 4) return launch_grad_x3_cfg<ACT, 7, MODE>(a, st);
     return launch_grad_x3_cfg<ACT, 4, MODE>(a, st);
 }

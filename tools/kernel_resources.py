@@ -3,7 +3,9 @@
 
 The library carries one clang offload bundle per translation unit (magic __CLANG_OFFLOAD_BUNDLE__: entry table of offset / size / target
 triple); the gfx950 entry of each is an ELF code object whose NT_AMDGPU_METADATA note `llvm-readelf --notes` prints as YAML.
-usage: python tools/kernel_resources.py [library] [name filter]      (tests/test_host_cpu.py asserts on kernel_resources())"""
+usage: python tools/kernel_resources.py [library] [name filter]      (tests/test_host_cpu.py asserts on kernel_resources())
+       python tools/kernel_resources.py --hazards                    (the two MFMA wait-state scans over the built library)
+       python tools/kernel_resources.py --isa-hashes [library | object file]   (one `sha256  kernel` line per function: diff two builds' listings)"""
 import os
 import re
 import struct
@@ -178,7 +180,34 @@ def mfma_result_hazards(lib=LIB):
     return [(n,) + b[1:] for n, b in zip(names, bad)]
 
 
+def isa_hashes(lib=LIB):
+    """-> [(sha256 hex, demangled kernel name)], sorted by name: one hash per gfx950 function of the library (or of one object file), over its
+    instructions as `llvm-objdump -d` prints them without addresses, encodings and the trailing comments (branch offsets are relative, so a
+    function hashes the same wherever it lies in its code object).  Two builds with equal listings run the same device code."""
+    import hashlib
+    out = []
+    for co in code_objects(lib):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            txt = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "--no-leading-addr", f.name], capture_output=True, text=True, check=True).stdout
+        syms, bodies = [], []
+        for line in txt.split("\n"):
+            m = re.match(r"^(?:[0-9a-f]+ )?<(.+)>:$", line)
+            if m:
+                syms.append(m.group(1))
+                bodies.append([])
+            elif syms and line.split("//")[0].strip():
+                bodies[-1].append(line.split("//")[0].strip())
+        out += [(hashlib.sha256("\n".join(b).encode()).hexdigest(), n) for b, n in zip(bodies, demangle(syms))]
+    return sorted(out, key=lambda e: e[1])
+
+
 if __name__ == "__main__":
+    if "--isa-hashes" in sys.argv:                               # usage: --isa-hashes [library or object file]
+        for h, n in isa_hashes(sys.argv[-1] if os.path.exists(sys.argv[-1]) and sys.argv[-1] != sys.argv[0] else LIB):
+            print(f"{h}  {n}")
+        sys.exit(0)
     if "--hazards" in sys.argv:
         hz = mfma_operand_hazards()
         for h in hz:
