@@ -604,6 +604,50 @@ int rbnn_svi_adam_step(const rbnn_svi_train_net *net, uint64_t key, uint32_t dra
 int rbnn_svi_train_finalize(const float *kl_partials, int64_t n_partials, const float *ce, int32_t n_points, const float *Psum, int32_t ldp,
                             const int32_t *labels, int32_t n_classes, double *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic training of fc / fc2 nets (csrc/rbnn_nn_train.hip): torch.optim.Adam on nn.CrossEntropyLoss() (model_nn.py:175-219), for
+ * n_members independent nets of the same shape in LOCKSTEP (the deep ensemble of model_ensemble.py:69-83): every launch covers all members.
+ * Issued in this order on one stream:  train_forward -> weight_grads -> adam_step -> train_finalize.
+ * Parameters, Adam moments and gradients are flat per-member buffers in the layout of the SVI trainer above (state_dict order, unpadded,
+ * row-major); member m sits at m * member_stride floats.  The batch of member m is rows[m, 0..B) of a RESIDENT data matrix X [n_rows, ldx]
+ * (int32 indices; labels go through the same indices); rows == NULL: rows 0..B-1 of X for every member (a staged batch).  An index outside
+ * [0, n_rows) is clamped into it.  Workspaces are packed [n_members, B, .] for the call's B.  No atomics, no sum across members: member m
+ * of a lockstep run is bit-identical to that member run alone, and two runs are bit-identical.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_nn_train_net {
+    int32_t arch;                  /* rbnn_arch                                                                    */
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_features, hidden, n_classes;    /* D (any), H (any), C <= 16                                        */
+    int32_t n_members;             /* M, 1 .. 65535                                                                */
+    float *P;                      /* [M, member_stride] parameters                                                */
+    float *m, *v;                  /* [M, member_stride] Adam moments (zero before the first step)                 */
+    float *grad;                   /* [M, member_stride] dL/dP of the step (L = mean CE of the member's batch)     */
+    int64_t member_stride;         /* floats between members, >= n_params                                          */
+} rbnn_nn_train_net;
+
+typedef struct rbnn_nn_train_ws {  /* caller-owned, for M members x up to B points                                  */
+    float *hid1, *dact1, *dA1;     /* [M, B, H] layer-1 activations, act'(pre-activation), dL/d(pre-activation)   */
+    float *hid2, *dact2, *dA2;     /* [M, B, H] fc2 only: the same for the second hidden layer                    */
+    float *dZ;                     /* [M, B, 16] dL/dlogits = (softmax - e_y) / B                                  */
+    float *ce;                     /* [M, B] cross-entropy per point                                               */
+    int32_t *correct;              /* [M, B] 1 where the first maximum of the training forward's logits is the label */
+} rbnn_nn_train_ws;
+
+/* [host] n_params of one member (the least member_stride).  < 0: rbnn_status. */
+int64_t rbnn_nn_train_sizes(const rbnn_nn_train_net *net);
+/* The training forward of every member on its batch: hidden activations, act', logits, ce, dZ, correct, and the backward to dA1
+ * (fc2: dA2, then dA1): fc 2 launches, fc2 4.  labels: int32 [n_rows] in [0, C), indexed like X. */
+int rbnn_nn_train_forward(const rbnn_nn_train_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *labels, const int32_t *rows,
+                          int32_t n_points, const rbnn_nn_train_ws *ws, void *stream);
+/* grad = dL/dP of every tensor of every member (the biases as column sums): one launch, fp32 MFMA. */
+int rbnn_nn_weight_grads(const rbnn_nn_train_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *rows, int32_t n_points,
+                         const rbnn_nn_train_ws *ws, void *stream);
+/* One torch.optim.Adam step (single-tensor formula, no weight decay) on P of every member; `step` = the step number t >= 1 of the bias
+ * corrections.  The scalars are doubles and each derived one is rounded to fp32 once, as in the SVI update above. */
+int rbnn_nn_adam_step(const rbnn_nn_train_net *net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void *stream);
+/* One block per member, fixed order, fp64: stats[m] = [the fp32-rounded mean of ce[m, :] (the step's loss), += it, += sum correct[m, :]]. */
+int rbnn_nn_train_finalize(const rbnn_nn_train_net *net, const rbnn_nn_train_ws *ws, int32_t n_points, double *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,7 +90,19 @@ class SviTrainWs(C.Structure):
     _fields_ = [(k, _fp) for k in SVI_TRAIN_WS_KEYS]
 
 
-SVI_EPS_MAX = 6.77                                                     # RBNN_SVI_EPS_MAX: Box-Muller on a 32-bit uniform cannot exceed it
+class NnTrainNet(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("arch", "activation", "in_features", "hidden", "n_classes", "n_members")] + \
+               [(k, _fp) for k in ("P", "m", "v", "grad")] + [("member_stride", C.c_int64)]
+
+
+NN_TRAIN_WS_KEYS = ("hid1", "dact1", "dA1", "hid2", "dact2", "dA2", "dZ", "ce", "correct")
+
+
+class NnTrainWs(C.Structure):
+    _fields_ = [(k, _fp) for k in NN_TRAIN_WS_KEYS]
+
+
+SVI_EPS_MAX = 6.77                                                    # RBNN_SVI_EPS_MAX: Box-Muller on a 32-bit uniform cannot exceed it
 
 TRIPLE_WS_KEYS = ("X_triple", "dZ_gen", "g_scale", "hid_triple")
 
@@ -181,6 +193,11 @@ SIGNATURES = {
     "rbnn_svi_weight_grads": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, C.POINTER(SviTrainWs), _fp]),
     "rbnn_svi_adam_step": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp, _fp]),
     "rbnn_svi_train_finalize": (_i32, [_fp, _i64, _fp, _i32, _fp, _i32, _fp, _i32, _fp, _fp]),
+    "rbnn_nn_train_sizes": (_i64, [C.POINTER(NnTrainNet)]),
+    "rbnn_nn_train_forward": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
+    "rbnn_nn_weight_grads": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
+    "rbnn_nn_adam_step": (_i32, [C.POINTER(NnTrainNet), _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
+    "rbnn_nn_train_finalize": (_i32, [C.POINTER(NnTrainNet), C.POINTER(NnTrainWs), _i32, _fp, _fp]),
 }
 
 _lib = None

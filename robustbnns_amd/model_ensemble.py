@@ -21,6 +21,23 @@ class Ensemble_NN(NN):
         return str(self.dataset_name) + "_ensemble_hid=" + str(self.hidden_size) + "_act=" + str(self.activation) + \
                "_arch=" + str(self.architecture) + "_size=" + str(ensemble_size)
 
+    def save(self, seed=None, *args, **kwargs):
+        """model_ensemble.py:33-42 (seed 0 is falsy there and saves every member: the same files)"""
+        savedir = self.name + "/weights"
+        if seed:
+            self.ensemble_models[str(seed)].save(savedir=savedir, seed=seed)
+        else:
+            for idx, net in self.ensemble_models.items():
+                net.save(savedir=savedir, seed=idx)
+
+    def train(self, *args, **kwargs):
+        """model_ensemble.py:69-83 — train(x_train, y_train, device): every member on its own shuffled batches of 100, all members in
+        lockstep on the GPU (robustbnns_amd.nn_train.train_ensemble), saved to <name>/weights/.  train(mode) is nn.Module's."""
+        if args and isinstance(args[0], bool) or "mode" in kwargs:
+            return super().train(*args, **kwargs)
+        from .nn_train import train_ensemble
+        train_ensemble(self, *args, **kwargs)
+
     def load(self, device, rel_path=TESTS):
         """model_ensemble.py:44-55"""
         self.device = device

@@ -3,7 +3,8 @@
 The module keeps the reference's `nn.Sequential` layout so `state_dict()` keys (`model.1.weight`, ...)
 and the on-disk `<name>_weights[_<seed>].pt` files are interchangeable.  `forward` does not run the
 Sequential: it stacks the parameters as a one-sample posterior and calls the HIP path (logits out),
-so NN, Ensemble_NN and BNN share the same kernels.  Training (model_nn.py:175-219) is out of scope.
+so NN, Ensemble_NN and BNN share the same kernels.  `train` (model_nn.py:175-219) runs on the GPU for fc and fc2
+(robustbnns_amd/nn_train.py, csrc/rbnn_nn_train.hip); conv nets and CPU devices raise NotImplementedError.
 """
 import math
 import os
@@ -116,10 +117,12 @@ class NN(nn.Module):
         self._engine = None
 
     def train(self, *args, **kwargs):
+        """model_nn.py:175-219 — train(train_loader, device, seed=0, save=True): Adam on the mean cross-entropy, from the module's current
+        parameters, on the GPU (robustbnns_amd.nn_train; fc and fc2).  train(mode) is nn.Module's."""
         if args and isinstance(args[0], bool) or "mode" in kwargs:          # nn.Module.train(mode)
             return super().train(*args, **kwargs)
-        raise NotImplementedError("training is outside the accelerated hot path (SURVEY.md section 2, row 8): "
-                                  "train with the reference and load the weights here")
+        from .nn_train import train_nn
+        train_nn(self, *args, **kwargs)
 
     def evaluate(self, test_loader, device, *args, **kwargs):
         """model_nn.py:221-240"""
