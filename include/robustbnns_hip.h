@@ -648,6 +648,61 @@ int rbnn_nn_adam_step(const rbnn_nn_train_net *net, int64_t step, double lr, dou
 /* One block per member, fixed order, fp64: stats[m] = [the fp32-rounded mean of ce[m, :] (the step's loss), += it, += sum correct[m, :]]. */
 int rbnn_nn_train_finalize(const rbnn_nn_train_net *net, const rbnn_nn_train_ws *ws, int32_t n_points, double *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * HMC over the weights of an fc / fc2 net (csrc/rbnn_hmc.hip): pyro's HMC(model, step_size, num_steps) under MCMC as model_bnn.py:260-301
+ * calls it.  Position q = the flat parameter buffer of the SVI trainer above; U(q) = sum_b CE(z_b(q), y_b) + 1/2 sum q^2, grad U = dCE/dW + q.
+ * dCE/dW is rbnn_svi_train_forward + rbnn_svi_weight_grads on an rbnn_svi_train_net whose W is the trajectory's position and whose grad
+ * receives dCE/dW (the other pointers of that struct are not read).  One transition, issued in this order on one stream:
+ *   momentum -> leapfrog_update(OPEN) -> { train_forward -> weight_grads -> leapfrog_update(MID, or CLOSE after the last step) } x L
+ *            -> decide -> commit        (a leapfrog step: fc 2 + 1 + 1 launches, fc2 4 + 1 + 1)
+ * The chain's scalars live in a device-side block of RBNN_HMC_STATE doubles (indices RBNN_HMC_ST_*); every element-wise kernel reads the
+ * step size from it.  Acceptance uniform of transition i: component 0 of the Philox4x32-10 block with counter (i, 0, 0, 0) under
+ * key ^ RBNN_HMC_UNIF_KEY, times 2^-32.  Momentum: rbnn_svi_draw's counter layout at sample 0 with draw id = the caller's draw_id.
+ * No atomics: two runs with the same key are bit-identical.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_HMC_STATE 16
+#define RBNN_HMC_LOG 8            /* doubles per log row: eps used, dH, accept_prob, accepted, u, U', K', K */
+#define RBNN_HMC_UNIF_KEY 0xE7037ED1A0B428DBull
+#define RBNN_HMC_SEARCH_KEY 0xA0761D6478BD642Full   /* xor-ed into the key by the CALLER for the step-size search's momenta */
+enum { RBNN_HMC_ST_EPS = 0, RBNN_HMC_ST_U = 1, RBNN_HMC_ST_T = 2, RBNN_HMC_ST_GBAR = 3, RBNN_HMC_ST_XBAR = 4, RBNN_HMC_ST_MU = 5,
+       RBNN_HMC_ST_DH = 6, RBNN_HMC_ST_ACC_PROB = 7, RBNN_HMC_ST_ACCEPTED = 8, RBNN_HMC_ST_UNIF = 9, RBNN_HMC_ST_U_NEW = 10,
+       RBNN_HMC_ST_K_NEW = 11, RBNN_HMC_ST_K_OLD = 12 };
+enum { RBNN_HMC_OPEN = 0, RBNN_HMC_MID = 1, RBNN_HMC_CLOSE = 2, RBNN_HMC_KICK = 3, RBNN_HMC_DRIFT = 4, RBNN_HMC_ENERGY = 5 };
+enum { RBNN_HMC_DECIDE_INIT = 0, RBNN_HMC_DECIDE_PROBE = 1, RBNN_HMC_DECIDE_TRANSITION = 2 };
+
+typedef struct rbnn_hmc_chain {
+    float *q_cur, *g_cur;          /* [n_params] the chain's position and dCE/dW there (U is state[RBNN_HMC_ST_U])  */
+    float *r;                      /* [n_params] momentum                                                          */
+    float *m_inv;                  /* [n_params] diagonal inverse mass                                             */
+    float *w_mean, *w_m2;          /* [n_params] Welford mean and M2 of the position (zero at a window's start)    */
+    float *k0_part;                /* [n_quad_partials] partial sums of K at the trajectory's start               */
+    float *k1_part, *p_part;       /* [n_elem_partials] partial sums of K' and of 1/2 sum q'^2                     */
+    double *state;                 /* [RBNN_HMC_STATE]                                                             */
+    double *log;                   /* [log_rows, RBNN_HMC_LOG], nullable                                           */
+    float *samples;                /* [sample_rows, n_params], nullable                                            */
+    int64_t log_rows, sample_rows;
+} rbnn_hmc_chain;
+
+/* [host] n_params; the lengths of k0_part and of k1_part / p_part (nullable).  < 0: rbnn_status. */
+int64_t rbnn_hmc_sizes(const rbnn_svi_train_net *net, int64_t *n_quad_partials, int64_t *n_elem_partials);
+/* r = eps_n(key, draw_id) * rsqrt(m_inv), k0_part: one launch. */
+int rbnn_hmc_momentum(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, uint64_t key, uint32_t draw_id, void *stream);
+/* One element-wise launch on net->W / net->grad / chain->r with eps = state[RBNN_HMC_ST_EPS].  OPEN: r -= eps/2 (g_cur + q_cur),
+ * W = q_cur + eps m_inv r.  MID: r -= eps/2 (grad + W) twice, W += eps m_inv r.  CLOSE: r -= eps/2 (grad + W), then k1_part / p_part.
+ * KICK: CLOSE's half kick alone.  DRIFT: W += eps m_inv r.  ENERGY: k1_part / p_part of (W, r) as they stand. */
+int rbnn_hmc_leapfrog_update(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t phase, void *stream);
+/* One block, fp64, fixed order: U' = sum ce + sum p_part, K' = sum k1_part, K = sum k0_part.  INIT: state U = U'.  PROBE: state dH only
+ * (dH = (U' + K') - (U + K), NaN -> +inf).  TRANSITION: accept_prob = min(1, exp(-dH)), u, accepted = u < accept_prob (then U = U'), the
+ * log row `transition`, and, if adapt, one dual-averaging update that writes the next step size (exp(x), at a window's end exp(xbar)). */
+int rbnn_hmc_decide(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, const float *ce, int32_t n_points, uint64_t key,
+                    int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void *stream);
+/* One launch: if accepted (or force) q_cur = W, g_cur = grad — a rejection writes neither; welford_n > 0: the Welford update number
+ * welford_n of the window with the position after the decision; sample_row >= 0: that row of samples = the position after the decision. */
+int rbnn_hmc_commit(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t force, int32_t welford_n, int64_t sample_row,
+                    void *stream);
+/* One launch: m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5) for a window of n_window >= 2 positions, then mean = M2 = 0. */
+int rbnn_hmc_window_end(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t n_window, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,19 @@ class NnTrainWs(C.Structure):
     _fields_ = [(k, _fp) for k in NN_TRAIN_WS_KEYS]
 
 
+class HmcChain(C.Structure):
+    _fields_ = [(k, _fp) for k in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state", "log", "samples")] + \
+               [("log_rows", C.c_int64), ("sample_rows", C.c_int64)]
+
+
+# rbnn_hmc.hip: the state block's indices, the log's columns, the update phases and the decide modes (include/robustbnns_hip.h)
+HMC_STATE, HMC_LOG = 16, 8
+HMC_ST = {"eps": 0, "U": 1, "t": 2, "gbar": 3, "xbar": 4, "mu": 5, "dH": 6, "accept_prob": 7, "accepted": 8, "u": 9, "U_new": 10, "K_new": 11,
+          "K_old": 12}
+HMC_OPEN, HMC_MID, HMC_CLOSE, HMC_KICK, HMC_DRIFT, HMC_ENERGY = range(6)
+HMC_DECIDE_INIT, HMC_DECIDE_PROBE, HMC_DECIDE_TRANSITION = range(3)
+HMC_UNIF_KEY, HMC_SEARCH_KEY = 0xE7037ED1A0B428DB, 0xA0761D6478BD642F
+
 SVI_EPS_MAX = 6.77                                                    # RBNN_SVI_EPS_MAX: Box-Muller on a 32-bit uniform cannot exceed it
 
 TRIPLE_WS_KEYS = ("X_triple", "dZ_gen", "g_scale", "hid_triple")
@@ -198,6 +211,12 @@ SIGNATURES = {
     "rbnn_nn_weight_grads": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
     "rbnn_nn_adam_step": (_i32, [C.POINTER(NnTrainNet), _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
     "rbnn_nn_train_finalize": (_i32, [C.POINTER(NnTrainNet), C.POINTER(NnTrainWs), _i32, _fp, _fp]),
+    "rbnn_hmc_sizes": (_i64, [C.POINTER(SviTrainNet), C.POINTER(_i64), C.POINTER(_i64)]),
+    "rbnn_hmc_momentum": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), C.c_uint64, C.c_uint32, _fp]),
+    "rbnn_hmc_leapfrog_update": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _fp]),
+    "rbnn_hmc_decide": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _fp, _i32, C.c_uint64, _i64, _i32, _i32, _i32, _fp]),
+    "rbnn_hmc_commit": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _i32, _i64, _fp]),
+    "rbnn_hmc_window_end": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _fp]),
 }
 
 _lib = None

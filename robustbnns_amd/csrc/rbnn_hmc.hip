@@ -1,0 +1,328 @@
+// rbnn_hmc.hip — Hamiltonian Monte Carlo over the weights of an fc / fc2 net (model_bnn.py:260-301: pyro's HMC(model, step_size, num_steps) under
+// MCMC(num_samples, warmup_steps)), everything around the potential's gradient.  The position q is the flat parameter buffer of rbnn_train.hip
+// (state_dict order, unpadded, row-major), U(q) = sum_b CE(z_b(q), y_b) + 1/2 sum q^2, grad U = dCE/dW + q: dCE/dW is rbnn_svi_train_forward +
+// rbnn_svi_weight_grads, called unchanged on an rbnn_svi_train_net whose W is the trajectory's position and whose grad receives dCE/dW.
+//
+//      rbnn_hmc_momentum        r = eps_n rsqrt(m_inv), per-block partial sums of K = 1/2 sum m_inv r^2
+//      rbnn_hmc_leapfrog_update one element-wise launch: OPEN (half kick + drift from the cached position), MID (the closing half kick of step k,
+//                               the opening half kick and the drift of step k + 1), CLOSE (the last half kick, partial sums of K' and 1/2 sum q^2),
+//                               and the plain KICK / DRIFT / ENERGY pieces the fused ones are tested against
+//      rbnn_hmc_decide          one block, fp64, fixed order: U', K', dH, accept_prob, u, the decision, dual averaging, the next step size, the log row
+//      rbnn_hmc_commit          keeps or replaces the cached position / gradient by the decision, Welford mean / M2, the sample stack's row
+//      rbnn_hmc_window_end      m_inv from Welford's M2, then the Welford reset
+//
+// Randomness.  Momentum: the SVI draw's counter layout (rbnn_common.hpp: Philox4x32-10 counter (quad, tensor id, 0, draw id), quad =
+// r * ceil(cols/4) + c/4, components (0,1) and (2,3) Box-Muller pairs of u = (x + 0.5) 2^-32) under the caller's key, draw id = the transition —
+// with libm's logf / sincospif instead of the hardware approximations (one launch per transition: accuracy is free here).  The step-size search
+// passes key ^ RBNN_HMC_SEARCH_KEY and a draw id counting its tries.  The acceptance uniform of transition i: component 0 of the Philox block
+// with counter (i, 0, 0, 0) under key ^ RBNN_HMC_UNIF_KEY, u = x0 2^-32 in [0, 1), exact in fp64.
+// No atomics anywhere: every sum has one fixed order, two runs with the same key are bit-identical.
+#include "rbnn_common.hpp"
+
+namespace {
+
+// Parameter layout of the flat buffers, as rbnn_train.hip's (that unit's code is left as it is): the state_dict tensors in order.
+struct Seg { long long off, first_quad; int rows, cols, tensor_id; };
+struct Layout { Seg s[6]; int n; long long n_params, n_quads; };
+
+Layout layout_of(const rbnn_svi_train_net& n) {
+    Layout L = {};
+    const int D = n.in_features, H = n.hidden, C = n.n_classes;
+    const bool fc2 = n.arch == RBNN_ARCH_FC2;
+    const int rows[6] = {H, 1, fc2 ? H : C, 1, C, 1}, cols[6] = {D, H, H, fc2 ? H : C, H, C};
+    const int ids[6] = {T_W1, T_B1, fc2 ? T_WM : T_W2, fc2 ? T_BM : T_B2, T_W2, T_B2};
+    L.n = fc2 ? 6 : 4;
+    long long off = 0, q = 0;
+    for (int i = 0; i < L.n; ++i) {
+        L.s[i] = {off, q, rows[i], cols[i], ids[i]};
+        off += (long long)rows[i] * cols[i];
+        q += (long long)rows[i] * ((cols[i] + 3) / 4);
+    }
+    L.n_params = off; L.n_quads = q;
+    return L;
+}
+
+constexpr int ELT_THREADS = 256;
+
+__device__ __forceinline__ int seg_of(const Layout& L, long long q) {
+    int i = 0;
+#pragma unroll
+    for (int j = 1; j < 6; ++j) if (j < L.n && q >= L.s[j].first_quad) i = j;
+    return i;
+}
+
+// the block's sum of v in one fixed tree order -> out[blockIdx.x]
+__device__ __forceinline__ void block_sum_to(float v, float* red, float* out) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = ELT_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    __syncthreads();
+}
+
+// four standard normals from one Philox block, normal4's pairing on libm's logf / sincospif
+__device__ __forceinline__ void normal4_libm(const uint32_t x[4], float n[4]) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const float u1 = fminf(((float)x[2 * p] + 0.5f) * 2.3283064365386963e-10f, 0.99999994f);
+        const float u2 = ((float)x[2 * p + 1] + 0.5f) * 2.3283064365386963e-10f;
+        const float r = sqrtf(-2.f * logf(u1));
+        float sn, cs;
+        sincospif(2.f * u2, &sn, &cs);
+        n[2 * p] = r * cs; n[2 * p + 1] = r * sn;
+    }
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) hmc_momentum_kernel(const Layout L, const rbnn_hmc_chain c, unsigned long long key, uint32_t draw_id) {
+    __shared__ float red[ELT_THREADS];
+    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    float k = 0.f;
+    if (q < L.n_quads) {
+        const Seg sg = L.s[seg_of(L, q)];
+        const int Q = (sg.cols + 3) >> 2;
+        const long long ql = q - sg.first_quad;
+        const int r = (int)(ql / Q), c4 = (int)(ql % Q);
+        uint32_t x[4];
+        philox4x32_10((uint32_t)(r * Q + c4), (uint32_t)sg.tensor_id, 0u, draw_id, (uint32_t)key, (uint32_t)(key >> 32), x);
+        float eps[4];
+        normal4_libm(x, eps);
+        const long long base = sg.off + (long long)r * sg.cols + 4 * c4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (4 * c4 + j >= sg.cols) continue;
+            const float mi = c.m_inv[base + j], rv = eps[j] * rsqrtf(mi);
+            c.r[base + j] = rv;
+            k += 0.5f * mi * rv * rv;
+        }
+    }
+    block_sum_to(k, red, c.k0_part);
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) hmc_update_kernel(long long n, float* __restrict__ W, const float* __restrict__ grad,
+                                                                 const rbnn_hmc_chain c, int phase) {
+    __shared__ float red[ELT_THREADS];
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    const float e = (float)c.state[RBNN_HMC_ST_EPS], he = 0.5f * e;
+    float kin = 0.f, pot = 0.f;
+    if (i < n) {
+        const float mi = c.m_inv[i];
+        float r = c.r[i];
+        if (phase == RBNN_HMC_OPEN) {
+            float q = c.q_cur[i];
+            r = fmaf(-he, c.g_cur[i] + q, r);
+            q = fmaf(e * mi, r, q);
+            W[i] = q; c.r[i] = r;
+        } else if (phase == RBNN_HMC_MID) {
+            float q = W[i];
+            const float gu = grad[i] + q;
+            r = fmaf(-he, gu, r);                       // the closing half kick of step k
+            r = fmaf(-he, gu, r);                       // the opening half kick of step k + 1: the same two roundings as the plain sequence
+            q = fmaf(e * mi, r, q);
+            W[i] = q; c.r[i] = r;
+        } else if (phase == RBNN_HMC_KICK || phase == RBNN_HMC_CLOSE) {
+            const float q = W[i];
+            r = fmaf(-he, grad[i] + q, r);
+            c.r[i] = r;
+            kin = 0.5f * mi * r * r; pot = 0.5f * q * q;
+        } else if (phase == RBNN_HMC_DRIFT) {
+            W[i] = fmaf(e * mi, r, W[i]);
+        } else {                                        // RBNN_HMC_ENERGY
+            const float q = W[i];
+            kin = 0.5f * mi * r * r; pot = 0.5f * q * q;
+        }
+    }
+    if (phase == RBNN_HMC_CLOSE || phase == RBNN_HMC_ENERGY) {
+        block_sum_to(kin, red, c.k1_part);
+        block_sum_to(pot, red, c.p_part);
+    }
+}
+
+// the sum of a[0..n) + b[0..m) in fp64: thread t takes elements t, t + 256, ..., then one tree
+__device__ __forceinline__ double block_sum64(const float* a, long long n, const float* b, long long m, double* red) {
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (long long i = t; i < n; i += 256) s += (double)a[i];
+    for (long long i = t; i < m; i += 256) s += (double)b[i];
+    red[t] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) red[t] += red[t + w];
+        __syncthreads();
+    }
+    const double out = red[0];
+    __syncthreads();
+    return out;
+}
+
+struct DecideArgs {
+    rbnn_hmc_chain c;
+    const float* ce;
+    long long n_points, n_qpart, n_epart, transition;
+    unsigned long long key;
+    int mode, adapt, window_end;
+};
+
+__global__ void __launch_bounds__(256) hmc_decide_kernel(const DecideArgs a) {
+    __shared__ double red[256];
+    const double U1 = block_sum64(a.ce, a.n_points, a.c.p_part, a.n_epart, red);
+    const double K1 = block_sum64(a.c.k1_part, a.n_epart, nullptr, 0, red);
+    const double K0 = block_sum64(a.c.k0_part, a.n_qpart, nullptr, 0, red);
+    if (threadIdx.x != 0) return;
+    double* const st = a.c.state;
+    st[RBNN_HMC_ST_U_NEW] = U1; st[RBNN_HMC_ST_K_NEW] = K1; st[RBNN_HMC_ST_K_OLD] = K0;
+    if (a.mode == RBNN_HMC_DECIDE_INIT) { st[RBNN_HMC_ST_U] = U1; return; }
+    double dH = (U1 + K1) - (st[RBNN_HMC_ST_U] + K0);
+    if (dH != dH) dH = INFINITY;                                     // NaN counts as +inf
+    st[RBNN_HMC_ST_DH] = dH;
+    if (a.mode == RBNN_HMC_DECIDE_PROBE) return;
+    const double ap = fmin(1.0, exp(-dH));
+    const unsigned long long ukey = a.key ^ RBNN_HMC_UNIF_KEY;
+    uint32_t x[4];
+    philox4x32_10((uint32_t)a.transition, 0u, 0u, 0u, (uint32_t)ukey, (uint32_t)(ukey >> 32), x);
+    const double u = (double)x[0] * 2.3283064365386963e-10;         // x0 2^-32, exact
+    const bool acc = u < ap;
+    const double eps_used = st[RBNN_HMC_ST_EPS];
+    if (acc) st[RBNN_HMC_ST_U] = U1;
+    st[RBNN_HMC_ST_ACC_PROB] = ap; st[RBNN_HMC_ST_ACCEPTED] = acc ? 1.0 : 0.0; st[RBNN_HMC_ST_UNIF] = u;
+    if (a.adapt) {
+        // dual averaging (target 0.8, t0 = 10, kappa = 0.75, gamma = 0.05) on log eps
+        const double t = st[RBNN_HMC_ST_T] + 1.0, g = 0.8 - ap;
+        const double gbar = (1.0 - 1.0 / (t + 10.0)) * st[RBNN_HMC_ST_GBAR] + g / (t + 10.0);
+        const double xx = st[RBNN_HMC_ST_MU] - (sqrt(t) / 0.05) * gbar;
+        const double eta = pow(t, -0.75);
+        const double xbar = (1.0 - eta) * st[RBNN_HMC_ST_XBAR] + eta * xx;
+        st[RBNN_HMC_ST_T] = t; st[RBNN_HMC_ST_GBAR] = gbar; st[RBNN_HMC_ST_XBAR] = xbar;
+        st[RBNN_HMC_ST_EPS] = exp(a.window_end ? xbar : xx);
+    }
+    if (a.c.log && a.transition < a.c.log_rows) {
+        double* const row = a.c.log + a.transition * RBNN_HMC_LOG;
+        row[0] = eps_used; row[1] = dH; row[2] = ap; row[3] = acc ? 1.0 : 0.0; row[4] = u; row[5] = U1; row[6] = K1; row[7] = K0;
+    }
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) hmc_commit_kernel(long long n, const float* __restrict__ W, const float* __restrict__ grad,
+                                                                 const rbnn_hmc_chain c, int force, float welford_n, float* __restrict__ row) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const bool acc = force || c.state[RBNN_HMC_ST_ACCEPTED] != 0.0;
+    float q = c.q_cur[i];
+    if (acc) {                                                       // a rejection writes nothing: position and gradient stay bit for bit
+        q = W[i];
+        c.q_cur[i] = q; c.g_cur[i] = grad[i];
+    }
+    if (welford_n > 0.f) {
+        float mean = c.w_mean[i];
+        const float d = q - mean;
+        mean += d / welford_n;
+        c.w_mean[i] = mean;
+        c.w_m2[i] = fmaf(d, q - mean, c.w_m2[i]);
+    }
+    if (row) row[i] = q;
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) hmc_window_end_kernel(long long n, const rbnn_hmc_chain c, float scale, float shift) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= n) return;
+    c.m_inv[i] = fmaf(scale, c.w_m2[i], shift);
+    c.w_mean[i] = 0.f; c.w_m2[i] = 0.f;
+}
+
+int check_net(const rbnn_svi_train_net* n) {
+    if (!n) return RBNN_ERR_NULL;
+    if (n->arch != RBNN_ARCH_FC && n->arch != RBNN_ARCH_FC2) return RBNN_ERR_UNSUPPORTED;
+    if (n->in_features < 1 || n->hidden < 1 || n->n_classes < 1 || n->n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
+    if ((long long)n->hidden * n->in_features > (1LL << 30) || (long long)n->hidden * n->hidden > (1LL << 30)) return RBNN_ERR_SHAPE;
+    return RBNN_OK;
+}
+
+int check_chain(const rbnn_hmc_chain* c) {
+    if (!c) return RBNN_ERR_NULL;
+    if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state)
+        return RBNN_ERR_NULL;
+    return RBNN_OK;
+}
+
+inline unsigned blocks_for(long long n) { return (unsigned)((n + ELT_THREADS - 1) / ELT_THREADS); }
+
+}  // namespace
+
+extern "C" {
+
+int64_t rbnn_hmc_sizes(const rbnn_svi_train_net* net, int64_t* n_quad_partials, int64_t* n_elem_partials) {
+    const int rc = check_net(net);
+    if (rc) return rc;
+    const Layout L = layout_of(*net);
+    if (n_quad_partials) *n_quad_partials = blocks_for(L.n_quads);
+    if (n_elem_partials) *n_elem_partials = blocks_for(L.n_params);
+    return L.n_params;
+}
+
+int rbnn_hmc_momentum(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, uint64_t key, uint32_t draw_id, void* stream) {
+    int rc = check_net(net);
+    if (rc || (rc = check_chain(chain))) return rc;
+    const Layout L = layout_of(*net);
+    hipLaunchKernelGGL(hmc_momentum_kernel, dim3(blocks_for(L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, *chain,
+                       (unsigned long long)key, draw_id);
+    return launch_status();
+}
+
+int rbnn_hmc_leapfrog_update(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t phase, void* stream) {
+    int rc = check_net(net);
+    if (rc || (rc = check_chain(chain))) return rc;
+    if (!net->W || !net->grad) return RBNN_ERR_NULL;
+    if (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY) return RBNN_ERR_UNSUPPORTED;
+    const long long n = layout_of(*net).n_params;
+    hipLaunchKernelGGL(hmc_update_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, net->W, net->grad, *chain, (int)phase);
+    return launch_status();
+}
+
+int rbnn_hmc_decide(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, const float* ce, int32_t n_points, uint64_t key,
+                    int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    int rc = check_net(net);
+    if (rc || (rc = check_chain(chain))) return rc;
+    if (!ce) return RBNN_ERR_NULL;
+    if (n_points < 1 || transition < 0) return RBNN_ERR_SHAPE;
+    if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
+    const Layout L = layout_of(*net);
+    DecideArgs a = {};
+    a.c = *chain; a.ce = ce; a.n_points = n_points; a.n_qpart = blocks_for(L.n_quads); a.n_epart = blocks_for(L.n_params);
+    a.transition = transition; a.key = key; a.mode = mode; a.adapt = adapt; a.window_end = window_end;
+    hipLaunchKernelGGL(hmc_decide_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+int rbnn_hmc_commit(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t force, int32_t welford_n, int64_t sample_row,
+                    void* stream) {
+    int rc = check_net(net);
+    if (rc || (rc = check_chain(chain))) return rc;
+    if (!net->W || !net->grad) return RBNN_ERR_NULL;
+    const long long n = layout_of(*net).n_params;
+    float* row = nullptr;
+    if (sample_row >= 0) {
+        if (!chain->samples) return RBNN_ERR_NULL;
+        if (sample_row >= chain->sample_rows) return RBNN_ERR_SHAPE;
+        row = chain->samples + sample_row * n;
+    }
+    if (welford_n < 0) return RBNN_ERR_SHAPE;
+    hipLaunchKernelGGL(hmc_commit_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, net->W, net->grad, *chain, (int)force,
+                       (float)welford_n, row);
+    return launch_status();
+}
+
+int rbnn_hmc_window_end(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t n_window, void* stream) {
+    int rc = check_net(net);
+    if (rc || (rc = check_chain(chain))) return rc;
+    if (n_window < 2) return RBNN_ERR_SHAPE;
+    const long long n = layout_of(*net).n_params;
+    // m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5): the two scalars are formed in double and rounded to fp32 once
+    const double w = (double)n_window;
+    hipLaunchKernelGGL(hmc_window_end_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, *chain,
+                       (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
+    return launch_status();
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 """Half-moons model grid: expected loss gradients and attacks for every stored BNN of a hyper-parameter grid — the call
-surface of the reference's grid_search_halfMoons.py (MoonsBNN :18-25, serial_compute_grads :94-102, grid_attack :133-153).
+surface of the reference's grid_search_halfMoons.py (MoonsBNN :18-25, _train / serial_train :30-50, serial_compute_grads :94-102,
+grid_attack :133-153).
 
-The reference trains the grid (`_train`, out of scope here: DESIGN.md section 7), then for every combination loads the HMC
-posterior from disk and runs `loss_gradients` / `attack` — on CPU through 10 joblib processes (:58-59, :91-92, :129-131).
+The reference trains the grid (`_train`: here HMC through BNN.train_hmc and SVI through BNN.train, fc / fc2 on the GPU; conv training is
+out of scope: DESIGN.md section 7), then for every combination loads the HMC posterior from disk and runs `loss_gradients` / `attack` — on CPU through 10 joblib processes (:58-59, :91-92, :129-131).
 Here every model is one resident posterior on the GPU and every (model, n_samples) cell one batched run over all test
 points; the grid itself is a plain loop (the work per cell is milliseconds).  Dataset loading is out of scope as well,
 so the caller passes the test tensors (`x_test [N,1,2,1]`, `y_test [N,2]` one-hot, as utils.load_dataset returns them).
@@ -29,6 +30,41 @@ class MoonsBNN(BNN):
 
 def _combinations(*axes):
     return list(itertools.product(*axes))
+
+
+def moons_loader(x_train, y_train, batch_size):
+    """The reference's half-moons train loader (data_loaders(..., shuffle=False)) over tensors the caller passes."""
+    return DataLoader(dataset=list(zip(x_train, y_train)), batch_size=batch_size, shuffle=False)
+
+
+def _train(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples, rel_path, device,
+           x_train=None, y_train=None, train_loader=None):
+    """:30-41: one model of the grid.  Batch 64 for svi (BNN.train), 1024 for hmc (BNN.train_hmc); the data are x_train / y_train (the first
+    n_inputs points) or a ready train_loader.  Returns the trained net."""
+    if architecture not in ("fc", "fc2"):
+        raise NotImplementedError(f"grid training covers fc and fc2, not {architecture!r} (conv needs conv weight gradients)")
+    batch_size = 64 if inference == "svi" else 1024
+    if train_loader is None:
+        if x_train is None or y_train is None:
+            raise ValueError("_train needs x_train / y_train or a train_loader: dataset loading is out of scope")
+        train_loader = moons_loader(x_train[:n_inputs], y_train[:n_inputs], batch_size)
+    x0, y0 = train_loader.dataset[0]
+    bnn = MoonsBNN(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, tuple(x0.shape), int(y0.shape[-1]))
+    if inference == "hmc":
+        bnn.train_hmc(train_loader=train_loader, device=device, rel_path=rel_path)
+    else:
+        bnn.train(train_loader=train_loader, device=device, rel_path=rel_path)
+    return bnn
+
+
+def serial_train(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples, rel_path,
+                 x_train=None, y_train=None, train_loader=None, device="cuda"):
+    """:43-50: _train over the grid, one model after the other.  Returns {bnn.name: bnn}."""
+    out = {}
+    for init in _combinations(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples):
+        bnn = _train(*init, rel_path, device, x_train=x_train, y_train=y_train, train_loader=train_loader)
+        out[bnn.name] = bnn
+    return out
 
 
 def serial_compute_grads(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs,

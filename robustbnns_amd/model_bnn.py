@@ -14,7 +14,9 @@ model_bnn.py:198-258, computed for the whole batch and all samples by the HIP ke
 
 Training: `train(train_loader, device, rel_path, filename)` runs the reference's SVI training (model_bnn.py:303-365) for fc / fc2 on the GPU
 (svi_train.SviTrainer: one weight draw, the training forward, the weight gradients and one Adam step per batch — csrc/rbnn_train.hip) and
-saves the param store.  HMC, conv SVI and CPU devices raise NotImplementedError: those posteriors are inputs here.
+saves the param store.  conv SVI and CPU devices raise NotImplementedError: those posteriors are inputs here.  `train()` refuses an HMC net
+too and names `train_hmc(train_loader, device, rel_path, filename)`, which samples the chain of an fc / fc2 net on the GPU (hmc.HmcSampler,
+csrc/rbnn_hmc.hip) and writes the per-sample files `load()` reads.
 """
 import os
 import random
@@ -343,7 +345,8 @@ class BNN(nn.Module):
         from the CPU generator first, as the reference's does — RandomSampler's order of draws recalled, not checked) unless the net
         already holds some (load() or an earlier train(): pyro's param store persists), which are then trained further."""
         if self.inference == "hmc":
-            raise NotImplementedError("HMC inference is outside the accelerated path: run it with the reference and load the chain here")
+            raise NotImplementedError("train() runs SVI only: sample an HMC posterior (fc / fc2) with BNN.train_hmc(train_loader, device), "
+                                      "or run it with the reference and load the chain here")
         if self.basenet.architecture not in ("fc", "fc2"):
             raise NotImplementedError(f"SVI training covers fc and fc2, not {self.basenet.architecture!r} (conv needs conv weight gradients)")
         if torch.device(device).type != "cuda":
@@ -378,6 +381,48 @@ class BNN(nn.Module):
         if trainer is not None:
             loc, raw = trainer.params()
             self.set_variational_params(loc, raw, device)   # drops the guide, slots and seeded draws of the previous parameters
+        self.save(rel_path=rel_path, filename=filename)
+
+    def train_hmc(self, train_loader, device, rel_path=TESTS, filename=None):
+        """The hmc half of model_bnn.py:350-365 + _train_hmc (:260-301), fc / fc2 on the GPU: seed, the chain (hmc.HmcSampler with self.step_size,
+        self.num_steps, self.warmup), the resampling of get_samples(n_samples), save().
+
+        The reference calls mcmc.run once per batch; every call is a FRESH chain (warmup + batch_samples = int(n_samples / num_batches) + 1 samples)
+        that replaces the samples of the one before, and get_samples(n_samples) then draws n_samples indices with replacement from the last run.
+        The earlier runs reach the result only through pyro's RNG stream, which is unpinned.  So the loader is iterated (its shuffle draws
+        happen), the chain runs on the LAST batch only, and the stack is resampled with torch.randint(0, batch_samples, (n_samples,)) from the
+        CPU generator.  A dataset smaller than one batch (num_batches = 0, where the reference divides by zero) counts as one batch.
+        self.hmc_history keeps the chain's logs."""
+        if self.inference != "hmc":
+            raise ValueError(f"train_hmc() samples an HMC posterior; this net's inference is {self.inference!r} (use train())")
+        if self.basenet.architecture not in ("fc", "fc2"):
+            raise NotImplementedError(f"HMC covers fc and fc2, not {self.basenet.architecture!r} (conv needs conv weight gradients)")
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        from .hmc import HmcSampler, initial_position
+        from .svi_train import draw_key
+        self.device = device
+        self.basenet.device = device
+        random.seed(0)
+        set_rng_seed(0)
+        print("\n == HMC training ==")
+        b = self.basenet
+        num_batches = int(len(train_loader.dataset) / train_loader.batch_size)
+        batch_samples = int(self.n_samples / max(1, num_batches)) + 1
+        print("\nn_batches=", num_batches, "\tbatch_samples =", batch_samples)
+        x_batch = y_batch = None
+        for x_batch, y_batch in train_loader:            # every batch but the last reaches the result through the RNG stream only
+            pass
+        if x_batch is None:
+            raise ValueError("train_hmc() needs a loader with at least one batch")
+        q0 = initial_position([(k, tuple(v.shape)) for k, v in b.state_dict().items()])
+        sampler = HmcSampler(b.architecture, b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, draw_key(),
+                             batch_size=int(x_batch.shape[0]))
+        stack = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
+        idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
+        self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
+                            "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
+        self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
         self.save(rel_path=rel_path, filename=filename)
 
     def evaluate(self, test_loader, device, n_samples=10, seeds_list=None):
