@@ -658,7 +658,8 @@ int rbnn_nn_train_finalize(const rbnn_nn_train_net *net, const rbnn_nn_train_ws 
  * The chain's scalars live in a device-side block of RBNN_HMC_STATE doubles (indices RBNN_HMC_ST_*); every element-wise kernel reads the
  * step size from it.  Acceptance uniform of transition i: component 0 of the Philox4x32-10 block with counter (i, 0, 0, 0) under
  * key ^ RBNN_HMC_UNIF_KEY, times 2^-32.  Momentum: rbnn_svi_draw's counter layout at sample 0 with draw id = the caller's draw_id.
- * No atomics: two runs with the same key are bit-identical.
+ * No atomics: two runs with the same key are bit-identical.  Every rbnn_hmc_* entry point checks the net as rbnn_svi_train_forward does
+ * (RBNN_ERR_UNSUPPORTED for an arch or activation outside it).
  * ------------------------------------------------------------------------------------------------------------ */
 #define RBNN_HMC_STATE 16
 #define RBNN_HMC_LOG 8            /* doubles per log row: eps used, dH, accept_prob, accepted, u, U', K', K */

@@ -1,7 +1,7 @@
 // rbnn_hmc.hip — Hamiltonian Monte Carlo over the weights of an fc / fc2 net (model_bnn.py:260-301: pyro's HMC(model, step_size, num_steps) under
 // MCMC(num_samples, warmup_steps)), everything around the potential's gradient.  The position q is the flat parameter buffer of rbnn_train.hip
 // (state_dict order, unpadded, row-major), U(q) = sum_b CE(z_b(q), y_b) + 1/2 sum q^2, grad U = dCE/dW + q: dCE/dW is rbnn_svi_train_forward +
-// rbnn_svi_weight_grads, called unchanged on an rbnn_svi_train_net whose W is the trajectory's position and whose grad receives dCE/dW.
+// rbnn_svi_weight_grads, called on an rbnn_svi_train_net whose W is the trajectory's position and whose grad receives dCE/dW.
 //
 //      rbnn_hmc_momentum        r = eps_n rsqrt(m_inv), per-block partial sums of K = 1/2 sum m_inv r^2
 //      rbnn_hmc_leapfrog_update one element-wise launch: OPEN (half kick + drift from the cached position), MID (the closing half kick of step k,
@@ -17,52 +17,11 @@
 // passes key ^ RBNN_HMC_SEARCH_KEY and a draw id counting its tries.  The acceptance uniform of transition i: component 0 of the Philox block
 // with counter (i, 0, 0, 0) under key ^ RBNN_HMC_UNIF_KEY, u = x0 2^-32 in [0, 1), exact in fp64.
 // No atomics anywhere: every sum has one fixed order, two runs with the same key are bit-identical.
-#include "rbnn_common.hpp"
+// The parameter layout, its checks and the block reductions are rbnn_train_core.hpp's.  Every entry point refuses what the forward it depends on
+// refuses, an out-of-range activation included (RBNN_ERR_UNSUPPORTED).
+#include "rbnn_train_core.hpp"
 
 namespace {
-
-// Parameter layout of the flat buffers, as rbnn_train.hip's (that unit's code is left as it is): the state_dict tensors in order.
-struct Seg { long long off, first_quad; int rows, cols, tensor_id; };
-struct Layout { Seg s[6]; int n; long long n_params, n_quads; };
-
-Layout layout_of(const rbnn_svi_train_net& n) {
-    Layout L = {};
-    const int D = n.in_features, H = n.hidden, C = n.n_classes;
-    const bool fc2 = n.arch == RBNN_ARCH_FC2;
-    const int rows[6] = {H, 1, fc2 ? H : C, 1, C, 1}, cols[6] = {D, H, H, fc2 ? H : C, H, C};
-    const int ids[6] = {T_W1, T_B1, fc2 ? T_WM : T_W2, fc2 ? T_BM : T_B2, T_W2, T_B2};
-    L.n = fc2 ? 6 : 4;
-    long long off = 0, q = 0;
-    for (int i = 0; i < L.n; ++i) {
-        L.s[i] = {off, q, rows[i], cols[i], ids[i]};
-        off += (long long)rows[i] * cols[i];
-        q += (long long)rows[i] * ((cols[i] + 3) / 4);
-    }
-    L.n_params = off; L.n_quads = q;
-    return L;
-}
-
-constexpr int ELT_THREADS = 256;
-
-__device__ __forceinline__ int seg_of(const Layout& L, long long q) {
-    int i = 0;
-#pragma unroll
-    for (int j = 1; j < 6; ++j) if (j < L.n && q >= L.s[j].first_quad) i = j;
-    return i;
-}
-
-// the block's sum of v in one fixed tree order -> out[blockIdx.x]
-__device__ __forceinline__ void block_sum_to(float v, float* red, float* out) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = ELT_THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-    __syncthreads();
-}
 
 // four standard normals from one Philox block, normal4's pairing on libm's logf / sincospif
 __device__ __forceinline__ void normal4_libm(const uint32_t x[4], float n[4]) {
@@ -148,11 +107,7 @@ __device__ __forceinline__ double block_sum64(const float* a, long long n, const
     for (long long i = t; i < n; i += 256) s += (double)a[i];
     for (long long i = t; i < m; i += 256) s += (double)b[i];
     red[t] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
+    block_tree64(red);
     const double out = red[0];
     __syncthreads();
     return out;
@@ -231,22 +186,12 @@ __global__ void __launch_bounds__(ELT_THREADS) hmc_window_end_kernel(long long n
     c.w_mean[i] = 0.f; c.w_m2[i] = 0.f;
 }
 
-int check_net(const rbnn_svi_train_net* n) {
-    if (!n) return RBNN_ERR_NULL;
-    if (n->arch != RBNN_ARCH_FC && n->arch != RBNN_ARCH_FC2) return RBNN_ERR_UNSUPPORTED;
-    if (n->in_features < 1 || n->hidden < 1 || n->n_classes < 1 || n->n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
-    if ((long long)n->hidden * n->in_features > (1LL << 30) || (long long)n->hidden * n->hidden > (1LL << 30)) return RBNN_ERR_SHAPE;
-    return RBNN_OK;
-}
-
 int check_chain(const rbnn_hmc_chain* c) {
     if (!c) return RBNN_ERR_NULL;
     if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state)
         return RBNN_ERR_NULL;
     return RBNN_OK;
 }
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + ELT_THREADS - 1) / ELT_THREADS); }
 
 }  // namespace
 

@@ -1,0 +1,208 @@
+// rbnn_train_gemm.hpp — the forward / backward of an fc / fc2 net on the fp32 MFMA, shared by the units that launch it (rbnn_train.hip,
+// rbnn_nn_train.hip): one strided GEMM kernel and one output-layer + loss kernel, for M independent members in lockstep (grid dimension y).
+// Both bodies are templates on LOCKSTEP.  false is a single net: member 0, no index arrays — the member strides, a_idx / b_idx / rows and the
+// clamp are compiled out (measured: with them the SVI step was 5 % and an HMC transition 5 - 7 % slower than the kernels it had before).
+#pragma once
+#include "rbnn_train_core.hpp"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------
+// Strided fp32-MFMA GEMM  C(m, n) = sum_k A(m, k) B(n, k)  of member blockIdx.y over 64 x 64 output tiles, K in stages of 16 staged through LDS
+// (zero outside [M, N, K]: any shape, nothing read out of bounds).  Every operand carries a member stride, and the rows of A (a_idx) or the k
+// index of B (b_idx) may go through a per-member index array (the batch gathered from the resident data).  Each output element is one lane's
+// accumulator over k in increasing order: no atomics, reproducible.  Up to 3 independent problems per launch (the weight gradients of all
+// layers).
+// ---------------------------------------------------------------------------------------------------
+enum { EPI_STORE = 0, EPI_FWD = 1, EPI_MUL = 2 };
+
+struct GemmProb {
+    const float* A; long long a_m, a_k, a_mem;      // A(m, k) = A[mem a_mem + row(m) a_m + k a_k], row(m) = a_idx ? a_idx[mem idx_mem + m] : m
+    const float* B; long long b_n, b_k, b_mem;      // B(n, k) = B[mem b_mem + n b_n + row(k) b_k], row(k) = b_idx ? b_idx[mem idx_mem + k] : k
+    const int32_t *a_idx, *b_idx;
+    long long idx_mem;
+    int idx_max;                                    // gathered indices are clamped to [0, idx_max]: a bad index reads a wrong row, never outside X
+    int M, N, K;
+    int ones_n;                                     // >= 0: B(ones_n, k) = 1, so column ones_n is sum_k A(m, k) (a bias gradient) -> bias_out[m]
+    float* Cout; long long ldc, c_mem;              // C(m, n) -> Cout[mem c_mem + m ldc + n]; Dout and Dmul share the layout
+    float* bias_out;
+    const float* bias;                              // EPI_FWD: pre = C + bias[n]; Cout = act(pre), Dout = act'(pre)
+    long long bias_mem;                             // member stride of bias / bias_out
+    float* Dout;
+    const float* Dmul;                              // EPI_MUL: Cout = C * Dmul
+    int epi, act, tiles_n, first_tile;
+};
+struct GemmArgs { GemmProb p[3]; int n_prob; };
+
+constexpr int GT = 64, GK = 16, GLD = GT + 4;
+
+template <bool LOCKSTEP> __device__ __forceinline__ int gathered(const int32_t* idx, long long at, int i, int idx_max) {
+    return (LOCKSTEP && idx) ? min(max(idx[at + i], 0), idx_max) : i;
+}
+
+template <bool LOCKSTEP> __global__ void __launch_bounds__(256) train_gemm_kernel(const GemmArgs g) {
+    __shared__ float As[GK][GLD], Bs[GK][GLD];
+    int pi = 0;
+#pragma unroll
+    for (int j = 1; j < 3; ++j) if (j < g.n_prob && (int)blockIdx.x >= g.p[j].first_tile) pi = j;
+    const GemmProb& p = g.p[pi];
+    const long long mem = LOCKSTEP ? blockIdx.y : 0;
+    const int tile = blockIdx.x - p.first_tile, m0 = GT * (tile / p.tiles_n), n0 = GT * (tile % p.tiles_n);
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 15, lg = lane >> 4;
+    const int n_real = p.ones_n >= 0 ? p.ones_n : p.N;
+    const float* const A = p.A + mem * p.a_mem;
+    const float* const Bm = p.B + mem * p.b_mem;
+    const long long idx_at = mem * p.idx_mem;
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < p.K; k0 += GK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = t + 256 * i;
+            int mm, kk;
+            if (p.a_k == 1) { mm = idx >> 4; kk = idx & 15; } else { mm = idx & 63; kk = idx >> 6; }     // coalesced along the unit stride
+            const int m = m0 + mm, k = k0 + kk;
+            float av = 0.f;
+            if (m < p.M && k < p.K) av = A[(long long)gathered<LOCKSTEP>(p.a_idx, idx_at, m, p.idx_max) * p.a_m + k * p.a_k];
+            As[kk][mm] = av;
+            int nn, kb;
+            if (p.b_k == 1) { nn = idx >> 4; kb = idx & 15; } else { nn = idx & 63; kb = idx >> 6; }
+            const int n = n0 + nn, kq = k0 + kb;
+            float bv = 0.f;
+            if (kq < p.K) {
+                if (n < n_real) bv = Bm[n * p.b_n + (long long)gathered<LOCKSTEP>(p.b_idx, idx_at, kq, p.idx_max) * p.b_k];
+                else if (n == p.ones_n) bv = 1.f;
+            }
+            Bs[kb][nn] = bv;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < GK / 4; ++ks) {
+            const float a = As[4 * ks + lg][16 * wave + li];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = MFMA16(a, Bs[4 * ks + lg][16 * nt + li], acc[nt]);
+        }
+        __syncthreads();
+    }
+    // lane holds C(m0 + 16 wave + 4 lg + r, n0 + 16 nt + li)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int n = n0 + 16 * nt + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + 16 * wave + 4 * lg + r;
+            if (m >= p.M || n >= p.N) continue;
+            const float v = acc[nt][r];
+            if (n == p.ones_n) { p.bias_out[mem * p.bias_mem + m] = v; continue; }
+            const long long o = mem * p.c_mem + (long long)m * p.ldc + n;
+            if (p.epi == EPI_FWD) {
+                const float pre = v + p.bias[mem * p.bias_mem + n], h = act_value(p.act, pre);
+                p.Cout[o] = h;
+                p.Dout[o] = act_deriv(p.act, pre, h);
+            } else if (p.epi == EPI_MUL) {
+                p.Cout[o] = v * p.Dmul[o];
+            } else {
+                p.Cout[o] = v;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Output layer + loss: one wave per (member, point).  z = H W2^T + b2, CE = logsumexp(z) - z_y (Categorical(logits=log_softmax(z)) /
+// nn.CrossEntropyLoss per point), dZ = (softmax(z) - e_y) inv_S (ce_softmax_grad: inv_S = 1 for a summed loss, 1 / B for a mean),
+// correct = (first argmax z == y) as torch.argmax, dA = (dZ W2) * act'.
+// ---------------------------------------------------------------------------------------------------
+struct HeadArgs {
+    const float *Hl, *Dl, *W2, *b2;           // Hl / Dl [M, B, H]; W2 / b2 of member 0, member stride p_mem
+    long long p_mem;
+    const int32_t *labels, *rows;             // labels of the resident data, rows [M, B] or NULL (point b is row b)
+    int idx_max;
+    float *dZ, *ce, *dA;
+    int32_t* correct;                         // nullable
+    int B, H, C;
+    float inv_S;
+};
+
+template <bool LOCKSTEP> __global__ void __launch_bounds__(256) train_head_kernel(const HeadArgs a) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= a.B) return;
+    const long long mem = LOCKSTEP ? blockIdx.y : 0, pt = mem * a.B + b;
+    const float* const W2 = a.W2 + mem * a.p_mem;
+    float z[RBNN_CPAD];
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c) z[c] = 0.f;
+    const float* hrow = a.Hl + pt * a.H;
+    for (int h = lane; h < a.H; h += 64) {
+        const float hv = hrow[h];
+#pragma unroll
+        for (int c = 0; c < RBNN_CPAD; ++c) if (c < a.C) z[c] = fmaf(hv, W2[(long long)c * a.H + h], z[c]);
+    }
+    const float* const b2 = a.b2 + mem * a.p_mem;
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) z[c] += __shfl_xor(z[c], off, 64);
+        if (c < a.C) z[c] += b2[c];
+    }
+    const int y = a.labels[gathered<LOCKSTEP>(a.rows, mem * a.B, b, a.idx_max)];
+    float g[RBNN_CPAD];
+    ce_softmax_grad<RBNN_CPAD>(z, a.C, y, a.inv_S, g);
+    if (lane == 0) {
+        float m = -INFINITY, zy = 0.f;
+        int best = 0;
+        for (int c = 0; c < a.C; ++c) {
+            if (z[c] > m) { m = z[c]; best = c; }                     // strictly greater: the first maximum, as torch.argmax
+            if (c == y) zy = z[c];
+        }
+        float den = 0.f, rest = 0.f;
+        for (int c = 0; c < a.C; ++c) { const float e = expf(z[c] - m); den += e; if (c != y) rest += e; }
+        // label = argmax: CE = log(1 + sum_{c != y} e^(z_c - z_y)) without the cancellation of log(den) - 0
+        a.ce[pt] = (zy == m) ? log1pf(rest) : logf(den) - (zy - m);
+        if (a.correct) a.correct[pt] = best == y ? 1 : 0;
+#pragma unroll
+        for (int c = 0; c < RBNN_CPAD; ++c) a.dZ[pt * RBNN_CPAD + c] = g[c];
+    }
+    const float* drow = a.Dl + pt * a.H;
+    float* arow = a.dA + pt * a.H;
+    for (int h = lane; h < a.H; h += 64) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < RBNN_CPAD; ++c) if (c < a.C) s = fmaf(g[c], W2[(long long)c * a.H + h], s);
+        arow[h] = s * drow[h];
+    }
+}
+
+template <bool LOCKSTEP> int gemm_launch(GemmArgs& g, int members, hipStream_t st) {
+    int tiles = 0;
+    for (int i = 0; i < g.n_prob; ++i) {
+        GemmProb& p = g.p[i];
+        p.tiles_n = (p.N + GT - 1) / GT;
+        p.first_tile = tiles;
+        tiles += p.tiles_n * ((p.M + GT - 1) / GT);
+    }
+    hipLaunchKernelGGL(train_gemm_kernel<LOCKSTEP>, dim3(tiles, LOCKSTEP ? members : 1), dim3(256), 0, st, g);
+    return launch_status();
+}
+
+// H[mem, b, n] = act(sum_k A[mem, row(b), k] W[mem, n, k] + bias[mem, n]), D = act'
+inline GemmProb fwd_prob(const float* A, long long lda, long long a_mem, const float* W, const float* b, long long p_mem, int M, int N, int K,
+                         float* H, float* D, int act) {
+    GemmProb p = {};
+    p.A = A; p.a_m = lda; p.a_k = 1; p.a_mem = a_mem; p.B = W; p.b_n = K; p.b_k = 1; p.b_mem = p_mem; p.M = M; p.N = N; p.K = K; p.ones_n = -1;
+    p.Cout = H; p.ldc = N; p.c_mem = (long long)M * N; p.bias = b; p.bias_mem = p_mem; p.Dout = D; p.epi = EPI_FWD; p.act = act;
+    return p;
+}
+
+// dW[mem, m, n] = sum_b dA[mem, b, m] src[mem, row(b), n] (n < N), db[mem, m] = sum_b dA[mem, b, m]
+inline GemmProb wgrad_prob(const float* dA, long long ld_da, const float* src, long long ld_src, long long src_mem, int M, int N, int B,
+                           float* dW, float* db, long long p_mem) {
+    GemmProb p = {};
+    p.A = dA; p.a_m = 1; p.a_k = ld_da; p.a_mem = (long long)B * ld_da; p.B = src; p.b_n = 1; p.b_k = ld_src; p.b_mem = src_mem;
+    p.M = M; p.N = N + 1; p.K = B; p.ones_n = N;
+    p.Cout = dW; p.ldc = N; p.c_mem = p_mem; p.bias_out = db; p.bias_mem = p_mem; p.epi = EPI_STORE;
+    return p;
+}
+
+}  // namespace

@@ -3,8 +3,8 @@ HMC(model, step_size, num_steps) under MCMC(num_samples, warmup_steps, num_chain
 there are [recalled]; seed-for-seed parity with pyro's RNG stream is unpinned, as for the SVI draw).
 
 Position q = the flat parameter buffer of svi_train.SviTrainer (state_dict order, unpadded, row-major);
-U(q) = sum_b CE(z_b(q), y_b) + 1/2 sum q^2, grad U = dCE/dW + q.  dCE/dW is rbnn_svi_train_forward + rbnn_svi_weight_grads (csrc/rbnn_train.hip,
-unchanged); the momentum draw, the fused leapfrog updates, the one-block decision with dual averaging, the commit with Welford and the sample
+U(q) = sum_b CE(z_b(q), y_b) + 1/2 sum q^2, grad U = dCE/dW + q.  dCE/dW is rbnn_svi_train_forward + rbnn_svi_weight_grads
+(csrc/rbnn_train.hip); the momentum draw, the fused leapfrog updates, the one-block decision with dual averaging, the commit with Welford and the sample
 stack, and the window end are csrc/rbnn_hmc.hip.  Launches of one leapfrog step: fc 2 + 1 + 1, fc2 4 + 1 + 1 (forward, weight gradients,
 one fused update); of one transition with L steps: 1 (momentum) + 1 (opening update) + L x (step) + 1 (decision) + 1 (commit).
 
@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _hip
+from .flat_params import flatten, train_workspace, unflat, ws_struct
 from .posterior import LAYER_KEYS
 from .svi_train import state_keys
 
@@ -92,7 +93,7 @@ class HmcSampler:
         self.W, self.grad = z(), z()
         net.W, net.grad = self.W.data_ptr(), self.grad.data_ptr()
         self.net = net
-        self.q_cur = torch.cat([q0[k].detach().reshape(-1).to("cpu", torch.float32) for k in self.keys]).to(dev)
+        self.q_cur = flatten(q0, self.keys).to(dev)
         assert self.q_cur.numel() == n, (self.q_cur.numel(), n)
         self.g_cur, self.r, self.w_mean, self.w_m2 = z(), z(), z(), z()
         self.m_inv = torch.ones(n, dtype=torch.float32, device=dev)
@@ -129,29 +130,15 @@ class HmcSampler:
     def _ensure(self, B):
         if B <= self.Bmax:
             return
-        dev, H = self.device, self.H
-        e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        self.ws_t = {k: e(B, H) for k in ("hid1", "dact1", "dA1")}
-        if self.arch == "fc2":
-            self.ws_t.update({k: e(B, H) for k in ("hid2", "dact2", "dA2")})
-        self.ws_t["dZ"], self.ws_t["ce"] = e(B, _hip.CPAD), e(B)
-        ws = _hip.SviTrainWs()
-        for k in _hip.SVI_TRAIN_WS_KEYS:
-            setattr(ws, k, _hip.ptr(self.ws_t.get(k)))
-        self.ws = ws
-        self.X = e(B, self.D)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.ws_t = train_workspace(self.arch, B, self.H, self.device)
+        self.ws = ws_struct(_hip.SviTrainWs, _hip.SVI_TRAIN_WS_KEYS, self.ws_t)
+        self.X = torch.zeros(B, self.D, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.Bmax = B
 
     def unflat(self, buf):
         """state_dict key -> view of `buf` ([n_params] or [S, n_params]) in that tensor's shape."""
-        out, off = {}, 0
-        lead = tuple(buf.shape[:-1])
-        for k in self.keys:
-            m = int(np.prod(self.shapes[k]))
-            out[k] = buf[..., off:off + m].reshape(lead + self.shapes[k])
-            off += m
-        return out
+        return unflat(buf, self.keys, self.shapes)
 
     def _set_state(self, **kv):
         """Host -> device writes of state-block entries (warmup / set-up only)."""

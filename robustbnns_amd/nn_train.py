@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _hip
+from .flat_params import flatten, train_workspace, unflat, ws_struct
 from .posterior import LAYER_KEYS, round_up
 from .svi_train import ADAM_EPS, BETAS, state_keys
 
@@ -30,11 +31,8 @@ class NnTrainer:
     workspaces [M, B, .] and a device-side accumulator stats [M, 3] = [step loss, sum of step losses, correct predictions]."""
 
     def __init__(self, arch, activation, input_shape, n_classes, params, lr, device, batch_size=ENSEMBLE_BATCH):
+        check_trainable(arch, device)
         dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NotImplementedError(f"deterministic training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-        if arch not in LAYER_KEYS:
-            raise NotImplementedError(f"deterministic training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
         if isinstance(params, dict):
             params = [params]
         self.k = _hip.HipKernels()
@@ -52,8 +50,7 @@ class NnTrainer:
         n = int(self.k.lib.rbnn_nn_train_sizes(C.byref(net)))
         _hip.check(min(n, 0), "rbnn_nn_train_sizes")
         self.n_params = n
-        flat = lambda d: torch.cat([d[k].detach().reshape(-1).to("cpu", torch.float32) for k in self.keys])
-        self.P = torch.stack([flat(d) for d in params]).to(dev)
+        self.P = torch.stack([flatten(d, self.keys) for d in params]).to(dev)
         assert tuple(self.P.shape) == (self.M, n), (tuple(self.P.shape), self.M, n)
         z = lambda: torch.zeros(self.M, n, dtype=torch.float32, device=dev)
         self.m, self.v, self.grad = z(), z(), z()
@@ -70,29 +67,17 @@ class NnTrainer:
 
     def unflat(self, buf, member=0):
         """state_dict key -> view of member `member` of `buf` (one of the flat buffers) in that tensor's shape."""
-        out, off = {}, 0
-        for k in self.keys:
-            m = int(np.prod(self.shapes[k]))
-            out[k] = buf[member, off:off + m].view(self.shapes[k])
-            off += m
-        return out
+        return unflat(buf[member], self.keys, self.shapes)
 
     def _ensure(self, B):
         """Workspaces for batches of up to B points per member (grown, never shrunk; a call packs them [M, its own B, .])."""
         if B <= self.Bmax:
             return
-        dev, H, M = self.device, self.H, self.M
-        e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        self.ws_t = {k: e(M * B * H) for k in ("hid1", "dact1", "dA1")}
-        if self.arch == "fc2":
-            self.ws_t.update({k: e(M * B * H) for k in ("hid2", "dact2", "dA2")})
-        self.ws_t["dZ"], self.ws_t["ce"] = e(M * B * _hip.CPAD), e(M * B)
+        dev, M = self.device, self.M
+        self.ws_t = {k: v.reshape(-1) for k, v in train_workspace(self.arch, M * B, self.H, dev).items()}
         self.ws_t["correct"] = torch.zeros(M * B, dtype=torch.int32, device=dev)
-        ws = _hip.NnTrainWs()
-        for k in _hip.NN_TRAIN_WS_KEYS:
-            setattr(ws, k, _hip.ptr(self.ws_t.get(k)))
-        self.ws = ws
-        self.X = e(B, self.Dp)                                  # the staged batch (step(x, labels))
+        self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
+        self.X = torch.zeros(B, self.Dp, dtype=torch.float32, device=dev)         # the staged batch (step(x, labels))
         self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
         self.Bmax = B
 
@@ -151,7 +136,7 @@ class NnTrainer:
 
 
 def check_trainable(arch, device):
-    """The guards of NnTrainer, for callers that have host work to do before they construct one."""
+    """The guards of NnTrainer, also for callers that have host work to do before they construct one."""
     if torch.device(device).type != "cuda":
         raise NotImplementedError(f"deterministic training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
     if arch not in LAYER_KEYS:

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip
+from .flat_params import flatten, train_workspace, unflat, ws_struct
 from .posterior import LAYER_KEYS, StackedPosterior, SviGuide, round_up
 
 BETAS = (0.9, 0.999)                    # torch.optim.Adam defaults, what pyro.optim.Adam({"lr": lr}) wraps
@@ -87,8 +88,7 @@ class SviTrainer:
         n = int(self.k.lib.rbnn_svi_train_sizes(C.byref(net), C.byref(n_part)))
         _hip.check(min(n, 0), "rbnn_svi_train_sizes")
         self.n_params, self.n_partials = n, int(n_part.value)
-        flat = lambda d: torch.cat([d[k].detach().reshape(-1).to("cpu", torch.float32) for k in self.keys]).to(dev)
-        self.loc, self.raw = flat(loc), flat(raw)
+        self.loc, self.raw = flatten(loc, self.keys).to(dev), flatten(raw, self.keys).to(dev)
         assert self.loc.numel() == n, (self.loc.numel(), n)
         self.sigma = F.softplus(self.raw)
         z = lambda: torch.zeros(n, dtype=torch.float32, device=dev)
@@ -117,27 +117,16 @@ class SviTrainer:
 
     def unflat(self, buf):
         """state_dict key -> view of `buf` (one of the flat buffers) in that tensor's shape."""
-        out, off = {}, 0
-        for k in self.keys:
-            m = int(np.prod(self.shapes[k]))
-            out[k] = buf[off:off + m].view(self.shapes[k])
-            off += m
-        return out
+        return unflat(buf, self.keys, self.shapes)
 
     def _ensure(self, B):
         """Workspaces for batches of up to B points (grown, never shrunk: a short last batch reuses them)."""
         if B <= self.Bmax:
             return
-        dev, H = self.device, self.H
+        dev = self.device
         e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        self.ws_t = {k: e(B, H) for k in ("hid1", "dact1", "dA1")}
-        if self.arch == "fc2":
-            self.ws_t.update({k: e(B, H) for k in ("hid2", "dact2", "dA2")})
-        self.ws_t["dZ"], self.ws_t["ce"] = e(B, _hip.CPAD), e(B)
-        ws = _hip.SviTrainWs()
-        for k in _hip.SVI_TRAIN_WS_KEYS:
-            setattr(ws, k, _hip.ptr(self.ws_t.get(k)))
-        self.ws = ws
+        self.ws_t = train_workspace(self.arch, B, self.H, dev)
+        self.ws = ws_struct(_hip.SviTrainWs, _hip.SVI_TRAIN_WS_KEYS, self.ws_t)
         self.X = e(B, self.Dp)                                  # rows of Dp floats, zero columns [D, Dp): what rbnn_fc_forward reads
         self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
         self.Psum = e(B, _hip.CPAD)

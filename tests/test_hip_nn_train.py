@@ -130,6 +130,93 @@ def test_adam_step_kernel_matches_torch_optim_adam(t):
     print(f"[nn-train adam t={t}] worst error {worst:.3f} x (2e-6 x scale) over P, m, v of {M} members; excluded: nothing")
 
 
+class _SviGradients:
+    """SviTrainer's draw + training forward + weight gradients for a hidden size its constructor refuses: it sets up the accuracy forward, whose
+    draw takes 16 or a multiple of 32 hidden units, and gradients() never runs that forward.  The same three entry points, in SviTrainer's order,
+    on buffers laid out as its own (its attribute names)."""
+
+    def __init__(self, arch, act, shape, Cn, loc, raw, key, B):
+        from robustbnns_amd import _hip
+        from robustbnns_amd.svi_train import state_keys
+        self.hip, self.key, self.keys = _hip, key, state_keys(arch)
+        self.shapes = {k: tuple(loc[k].shape) for k in self.keys}
+        D, H = shape[0] * shape[1] * shape[2], self.shapes[self.keys[1]][0]
+        z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=DEV)
+        flat = lambda d: torch.cat([d[k].reshape(-1).float() for k in self.keys]).to(DEV)
+        self.loc, self.sigma = flat(loc), torch.nn.functional.softplus(flat(raw))
+        self.n_params = self.loc.numel()
+        self.W, self.grad = z(self.n_params), z(self.n_params)
+        self.net = _hip.SviTrainNet()
+        self.net.arch, self.net.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[act]
+        self.net.in_features, self.net.hidden, self.net.n_classes = D, H, Cn
+        for name in ("loc", "sigma", "W", "grad"):
+            setattr(self.net, name, getattr(self, name).data_ptr())
+        self.ws_t = {k + i: z(B, H) for i in (("1", "2") if arch == "fc2" else ("1",)) for k in ("hid", "dact", "dA")}
+        self.ws_t["dZ"], self.ws_t["ce"] = z(B, _hip.CPAD), z(B)
+        self.ws = _hip.SviTrainWs()
+        for k in _hip.SVI_TRAIN_WS_KEYS:
+            setattr(self.ws, k, _hip.ptr(self.ws_t.get(k)))
+        self.D, self.Dp = D, 16 * ((D + 15) // 16)
+        self.X, self.labels = z(B, self.Dp), torch.zeros(B, dtype=torch.int32, device=DEV)
+
+    def unflat(self, buf):
+        out, off = {}, 0
+        for k in self.keys:
+            n = 1
+            for v in self.shapes[k]:
+                n *= v
+            out[k], off = buf[off:off + n].view(self.shapes[k]), off + n
+        return out
+
+    def gradients(self, x, labels):
+        hip, B = self.hip, int(x.shape[0])
+        self.X[:B, :self.D].copy_(x.reshape(B, -1))
+        self.labels[:B].copy_(labels.reshape(B))
+        lib, st, net = hip.HipKernels().lib, hip.stream_of(self.X), C.byref(self.net)
+        hip.check(lib.rbnn_svi_train_draw(net, C.c_uint64(self.key), C.c_uint32(0), st), "rbnn_svi_train_draw")
+        hip.check(lib.rbnn_svi_train_forward(net, hip.ptr(self.X), self.Dp, B, hip.ptr(self.labels), C.byref(self.ws), st), "rbnn_svi_train_forward")
+        hip.check(lib.rbnn_svi_weight_grads(net, hip.ptr(self.X), self.Dp, B, C.byref(self.ws), st), "rbnn_svi_weight_grads")
+
+
+@pytest.mark.parametrize("arch,act,D,H,Cn,B", [("fc", "tanh", 17, 96, 3, 32), ("fc2", "leaky", 10, 80, 10, 128), ("fc2", "sigm", 2, 16, 2, 64)])
+def test_svi_and_nn_trainers_run_one_forward_and_backward(arch, act, D, H, Cn, B):
+    """The SVI trainer (a summed CE) and an M = 1 NnTrainer (its mean) launch the same GEMM and head kernels: at the weights the SVI side drew,
+    on the same staged batch, hid / act' / CE are equal bit for bit, and with B a power of two dZ and the weight gradients differ by the exact
+    factor B.  The cases are the smallest with a ragged tile in each of M, N and K and with both forward epilogues.  Precondition (asserted, loc
+    of std 0.1 and raw scale -3 keep the logits O(1)): no nonzero dZ, dA or gradient below 2^-100, so that 1 / B scales nothing into a denormal.
+    Hidden 80 is a size SviTrainer's constructor refuses (its accuracy forward's draw: 16 or a multiple of 32): that case drives the same entry
+    points through _SviGradients; the line printed says which side ran."""
+    from robustbnns_amd.nn_train import NnTrainer
+    from robustbnns_amd.svi_train import SviTrainer
+    assert B & (B - 1) == 0
+    shape, g = (1, D, 1), torch.Generator().manual_seed(D + H)
+    shapes = O.param_shapes(arch, D, H, Cn)
+    loc = {k: 0.1 * torch.randn(*s, generator=g) for k, s in shapes}
+    raw = {k: torch.full(s, -3.0) for k, s in shapes}
+    x, y = O.synthetic_inputs(B, shape, Cn, seed=D)
+    x, lab = (4 * x - 2).to(DEV), y.argmax(-1).to(DEV)
+    try:
+        sv = SviTrainer(arch, act, shape, Cn, loc, raw, 0.01, DEV, 0x5EED, batch_size=B)
+    except NotImplementedError:
+        sv = _SviGradients(arch, act, shape, Cn, loc, raw, 0x5EED, B)
+    sv.gradients(x, lab)
+    nn = NnTrainer(arch, act, shape, Cn, [sv.unflat(sv.W)], 0.01, DEV, batch_size=B)
+    nn.gradients(x, lab)
+    torch.cuda.synchronize()
+    assert torch.equal(nn.P[0], sv.W) and torch.equal(nn.X, sv.X) and torch.equal(nn.labels, sv.labels)
+    layers = ("1", "2") if arch == "fc2" else ("1",)
+    for k in ["dZ", "grad"] + ["dA" + i for i in layers]:
+        nz = (sv.grad if k == "grad" else sv.ws_t[k]).abs()
+        nz = nz[nz != 0]
+        assert nz.numel() and float(nz.min()) >= 2.0 ** -100, (k, nz.numel())
+    for k in ["ce"] + [n + i for i in layers for n in ("hid", "dact")]:
+        assert torch.equal(nn.ws_t[k].view_as(sv.ws_t[k]), sv.ws_t[k]), k
+    assert torch.equal(nn.ws_t["dZ"].view_as(sv.ws_t["dZ"]) * B, sv.ws_t["dZ"]), "dZ"
+    assert torch.equal(nn.grad[0] * B, sv.grad), "grad"
+    print(f"[nn-train = svi-train {arch} {D}->{H}->{Cn} {act} B={B}, SVI side: {type(sv).__name__}] ce, hid, act' equal; dZ and {sv.n_params} weight gradients "
+          f"equal after the exact factor B; excluded: nothing")
+
+
 def _lockstep_case():
     arch, act, shape, H, Cn, B, M = "fc2", "leaky", (1, 28, 28), 128, 10, 100, 7
     return (arch, act, shape, H, Cn, B, M), NR.grad_case(arch, act, shape, H, Cn, B, M)
