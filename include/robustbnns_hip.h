@@ -704,6 +704,52 @@ int rbnn_hmc_commit(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, 
 /* One launch: m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5) for a window of n_window >= 2 positions, then mean = M2 = 0. */
 int rbnn_hmc_window_end(const rbnn_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t n_window, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K independent HMC chains over nets of ONE shape in LOCKSTEP (csrc/rbnn_hmc.hip; additive, ABI 10): every launch covers all K chains, the
+ * chain is grid dimension y, as the member is in the deterministic trainer above.  The net is an rbnn_nn_train_net: P = the trajectory
+ * positions [K, member_stride], grad = dCE/dW [K, member_stride], n_members = K, member_stride = chain_stride (m and v are not read).
+ * Every per-parameter buffer of the chain block is [K, chain_stride], the partial sums [K, qpart_stride] / [K, epart_stride] (at least the
+ * lengths the sizes query above reports), state [K, RBNN_HMC_STATE], log [K, log_rows, RBNN_HMC_LOG], samples [K, sample_rows, n_params].
+ * Per chain: its key (keys[k]), its step size (its state block), its number of leapfrog steps (steps[k]), whether a launch touches it at all
+ * (active[k]) and its own number of points (counts[k] <= n_points; the points behind it contribute exact zeros).  No sum crosses chains, no
+ * atomics, a chain's block and tile plan does not depend on K: chain k is bit-identical to the single-chain entry points running it alone.
+ * One transition on one stream:  momentum -> update(OPEN) -> { gradient -> update(step s) } x max_k steps[k] -> decide -> commit.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_hmc_lockstep {
+    float *q_cur, *g_cur, *r, *m_inv, *w_mean, *w_m2;      /* [K, chain_stride], each as in rbnn_hmc_chain            */
+    float *k0_part;                /* [K, qpart_stride]                                                            */
+    float *k1_part, *p_part;       /* [K, epart_stride]                                                            */
+    double *state;                 /* [K, RBNN_HMC_STATE]                                                          */
+    double *log;                   /* [K, log_rows, RBNN_HMC_LOG], nullable                                        */
+    float *samples;                /* [K, sample_rows, n_params], nullable                                         */
+    const uint64_t *keys;          /* [K] on the device: chain k's key                                             */
+    const int32_t *active;         /* [K] on the device, nullable (all active): 0 = this launch neither reads nor writes chain k */
+    const int32_t *steps;          /* [K] on the device, nullable: chain k's leapfrog steps of this trajectory (update with step >= 0) */
+    int64_t chain_stride, qpart_stride, epart_stride, log_rows, sample_rows;
+} rbnn_hmc_lockstep;
+
+/* dCE/dW (summed CE) and ce [K, n_points] of every chain at net->P: the lockstep training forward (fc 2 launches, fc2 4) + the weight
+ * gradients (1).  Chain k's batch is rows[k, 0..n_points) of the resident X [n_rows, ldx] (indices clamped into [0, n_rows); rows == NULL:
+ * rows 0..n_points-1 for every chain); labels int32 [n_rows].  counts (nullable) [K]: for b >= counts[k] ce, dZ, dA and correct are 0.
+ * ws is packed [K, n_points, .].  active is NOT consulted: an inactive chain's trajectory buffers are scratch. */
+int rbnn_hmc_lockstep_gradient(const rbnn_nn_train_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *labels,
+                               const int32_t *rows, const int32_t *counts, int32_t n_points, const rbnn_nn_train_ws *ws, void *stream);
+/* The momentum draw of every active chain under keys[k] ^ key_xor with draw id draw_ids[k] (device, nullable: draw_id for every chain). */
+int rbnn_hmc_lockstep_momentum(const rbnn_nn_train_net *net, const rbnn_hmc_lockstep *chains, uint64_t key_xor, uint32_t draw_id,
+                               const uint32_t *draw_ids, void *stream);
+/* step < 0: the single chain's update `phase` on every active chain.  step >= 0 (needs steps): leapfrog step `step` of trajectories of
+ * different lengths: MID for chains with step + 1 < steps[k], CLOSE at step + 1 == steps[k], nothing for step >= steps[k]. */
+int rbnn_hmc_lockstep_update(const rbnn_nn_train_net *net, const rbnn_hmc_lockstep *chains, int32_t phase, int32_t step, void *stream);
+/* The single chain's decision, one block per active chain: ce [K, n_points], summed over the chain's first counts[k] (nullable: n_points)
+ * entries; the uniform under keys[k]. */
+int rbnn_hmc_lockstep_decide(const rbnn_nn_train_net *net, const rbnn_hmc_lockstep *chains, const float *ce, const int32_t *counts,
+                             int32_t n_points, int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void *stream);
+/* The single chain's commit on every active chain, each by its own decision; sample_row >= 0: that row of every chain's stack. */
+int rbnn_hmc_lockstep_commit(const rbnn_nn_train_net *net, const rbnn_hmc_lockstep *chains, int32_t force, int32_t welford_n,
+                             int64_t sample_row, void *stream);
+/* The single chain's window end on every active chain. */
+int rbnn_hmc_lockstep_window_end(const rbnn_nn_train_net *net, const rbnn_hmc_lockstep *chains, int32_t n_window, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

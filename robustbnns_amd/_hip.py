@@ -107,6 +107,12 @@ class HmcChain(C.Structure):
                [("log_rows", C.c_int64), ("sample_rows", C.c_int64)]
 
 
+class HmcLockstep(C.Structure):
+    _fields_ = [(k, _fp) for k in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state", "log", "samples",
+                                   "keys", "active", "steps")] + \
+               [(k, C.c_int64) for k in ("chain_stride", "qpart_stride", "epart_stride", "log_rows", "sample_rows")]
+
+
 # rbnn_hmc.hip: the state block's indices, the log's columns, the update phases and the decide modes (include/robustbnns_hip.h)
 HMC_STATE, HMC_LOG = 16, 8
 HMC_ST = {"eps": 0, "U": 1, "t": 2, "gbar": 3, "xbar": 4, "mu": 5, "dH": 6, "accept_prob": 7, "accepted": 8, "u": 9, "U_new": 10, "K_new": 11,
@@ -217,6 +223,12 @@ SIGNATURES = {
     "rbnn_hmc_decide": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _fp, _i32, C.c_uint64, _i64, _i32, _i32, _i32, _fp]),
     "rbnn_hmc_commit": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _i32, _i64, _fp]),
     "rbnn_hmc_window_end": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _fp]),
+    "rbnn_hmc_lockstep_gradient": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _fp, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
+    "rbnn_hmc_lockstep_momentum": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), C.c_uint64, C.c_uint32, _fp, _fp]),
+    "rbnn_hmc_lockstep_update": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _i32, _fp]),
+    "rbnn_hmc_lockstep_decide": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _fp, _fp, _i32, _i64, _i32, _i32, _i32, _fp]),
+    "rbnn_hmc_lockstep_commit": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _i32, _i64, _fp]),
+    "rbnn_hmc_lockstep_window_end": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _fp]),
 }
 
 _lib = None

@@ -19,7 +19,14 @@
 // No atomics anywhere: every sum has one fixed order, two runs with the same key are bit-identical.
 // The parameter layout, its checks and the block reductions are rbnn_train_core.hpp's.  Every entry point refuses what the forward it depends on
 // refuses, an out-of-range activation included (RBNN_ERR_UNSUPPORTED).
-#include "rbnn_train_core.hpp"
+//
+// K chains of one net shape in LOCKSTEP (rbnn_hmc_lockstep_*): the chain is grid dimension y of every launch, as the member is in
+// rbnn_nn_train.hip.  dCE/dW of all chains is the lockstep training forward + weight gradients of rbnn_train_gemm.hpp with inv_S = 1 on an
+// rbnn_nn_train_net whose P is the trajectory positions; the element-wise and decision kernels run the single chain's device functions on
+// chain k's view of the shared buffers.  Per chain: its key, step size (its state block), trajectory length (steps[k]), activity (active[k])
+// and number of points (counts[k]).  Chain k is bit-identical to that chain alone.
+#define RBNN_TRAIN_LOCKSTEP
+#include "rbnn_train_gemm.hpp"
 
 namespace {
 
@@ -36,9 +43,12 @@ __device__ __forceinline__ void normal4_libm(const uint32_t x[4], float n[4]) {
     }
 }
 
-__global__ void __launch_bounds__(ELT_THREADS) hmc_momentum_kernel(const Layout L, const rbnn_hmc_chain c, unsigned long long key, uint32_t draw_id) {
-    __shared__ float red[ELT_THREADS];
-    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+// ---------------------------------------------------------------------------------------------------
+// The bodies, each defined once: the single-chain kernels call them with the caller's chain, the lockstep kernels with the view of chain
+// blockIdx.y (chain_of).  A chain's arithmetic and reduction orders are therefore the same code in both.
+// ---------------------------------------------------------------------------------------------------
+// quad q of the momentum draw: r = eps_n rsqrt(m_inv) -> this thread's share of K = 1/2 sum m_inv r^2
+__device__ __forceinline__ float momentum_quad(const Layout& L, const rbnn_hmc_chain& c, long long q, unsigned long long key, uint32_t draw_id) {
     float k = 0.f;
     if (q < L.n_quads) {
         const Seg sg = L.s[seg_of(L, q)];
@@ -58,15 +68,13 @@ __global__ void __launch_bounds__(ELT_THREADS) hmc_momentum_kernel(const Layout 
             k += 0.5f * mi * rv * rv;
         }
     }
-    block_sum_to(k, red, c.k0_part);
+    return k;
 }
 
-__global__ void __launch_bounds__(ELT_THREADS) hmc_update_kernel(long long n, float* __restrict__ W, const float* __restrict__ grad,
-                                                                 const rbnn_hmc_chain c, int phase) {
-    __shared__ float red[ELT_THREADS];
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+// element i of one update phase; CLOSE and ENERGY leave this thread's shares of K' and 1/2 sum q'^2 in kin / pot
+__device__ __forceinline__ void update_element(long long i, long long n, float* __restrict__ W, const float* __restrict__ grad,
+                                               const rbnn_hmc_chain& c, int phase, float& kin, float& pot) {
     const float e = (float)c.state[RBNN_HMC_ST_EPS], he = 0.5f * e;
-    float kin = 0.f, pot = 0.f;
     if (i < n) {
         const float mi = c.m_inv[i];
         float r = c.r[i];
@@ -94,6 +102,19 @@ __global__ void __launch_bounds__(ELT_THREADS) hmc_update_kernel(long long n, fl
             kin = 0.5f * mi * r * r; pot = 0.5f * q * q;
         }
     }
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) hmc_momentum_kernel(const Layout L, const rbnn_hmc_chain c, unsigned long long key, uint32_t draw_id) {
+    __shared__ float red[ELT_THREADS];
+    const float k = momentum_quad(L, c, (long long)blockIdx.x * ELT_THREADS + threadIdx.x, key, draw_id);
+    block_sum_to(k, red, c.k0_part);
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) hmc_update_kernel(long long n, float* __restrict__ W, const float* __restrict__ grad,
+                                                                 const rbnn_hmc_chain c, int phase) {
+    __shared__ float red[ELT_THREADS];
+    float kin = 0.f, pot = 0.f;
+    update_element((long long)blockIdx.x * ELT_THREADS + threadIdx.x, n, W, grad, c, phase, kin, pot);
     if (phase == RBNN_HMC_CLOSE || phase == RBNN_HMC_ENERGY) {
         block_sum_to(kin, red, c.k1_part);
         block_sum_to(pot, red, c.p_part);
@@ -121,8 +142,8 @@ struct DecideArgs {
     int mode, adapt, window_end;
 };
 
-__global__ void __launch_bounds__(256) hmc_decide_kernel(const DecideArgs a) {
-    __shared__ double red[256];
+// one block of 256 threads decides one chain
+__device__ __forceinline__ void decide_chain(const DecideArgs& a, double* red) {
     const double U1 = block_sum64(a.ce, a.n_points, a.c.p_part, a.n_epart, red);
     const double K1 = block_sum64(a.c.k1_part, a.n_epart, nullptr, 0, red);
     const double K0 = block_sum64(a.c.k0_part, a.n_qpart, nullptr, 0, red);
@@ -159,10 +180,13 @@ __global__ void __launch_bounds__(256) hmc_decide_kernel(const DecideArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(ELT_THREADS) hmc_commit_kernel(long long n, const float* __restrict__ W, const float* __restrict__ grad,
-                                                                 const rbnn_hmc_chain c, int force, float welford_n, float* __restrict__ row) {
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (i >= n) return;
+__global__ void __launch_bounds__(256) hmc_decide_kernel(const DecideArgs a) {
+    __shared__ double red[256];
+    decide_chain(a, red);
+}
+
+__device__ __forceinline__ void commit_element(long long i, const float* __restrict__ W, const float* __restrict__ grad, const rbnn_hmc_chain& c,
+                                               int force, float welford_n, float* __restrict__ row) {
     const bool acc = force || c.state[RBNN_HMC_ST_ACCEPTED] != 0.0;
     float q = c.q_cur[i];
     if (acc) {                                                       // a rejection writes nothing: position and gradient stay bit for bit
@@ -179,17 +203,135 @@ __global__ void __launch_bounds__(ELT_THREADS) hmc_commit_kernel(long long n, co
     if (row) row[i] = q;
 }
 
+__global__ void __launch_bounds__(ELT_THREADS) hmc_commit_kernel(long long n, const float* __restrict__ W, const float* __restrict__ grad,
+                                                                 const rbnn_hmc_chain c, int force, float welford_n, float* __restrict__ row) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= n) return;
+    commit_element(i, W, grad, c, force, welford_n, row);
+}
+
+__device__ __forceinline__ void window_end_element(long long i, const rbnn_hmc_chain& c, float scale, float shift) {
+    c.m_inv[i] = fmaf(scale, c.w_m2[i], shift);
+    c.w_mean[i] = 0.f; c.w_m2[i] = 0.f;
+}
+
 __global__ void __launch_bounds__(ELT_THREADS) hmc_window_end_kernel(long long n, const rbnn_hmc_chain c, float scale, float shift) {
     const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
     if (i >= n) return;
-    c.m_inv[i] = fmaf(scale, c.w_m2[i], shift);
-    c.w_mean[i] = 0.f; c.w_m2[i] = 0.f;
+    window_end_element(i, c, scale, shift);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// K chains in lockstep: the chain is grid dimension y of every launch.  Chain k's buffers are the shared ones at k times their stride; its
+// key is keys[k]; with active != NULL a chain whose entry is 0 is neither read nor written (its blocks return at once, before any barrier).
+// No sum crosses chains and a chain's block plan does not depend on K: chain k is bit-identical to that chain alone.
+// ---------------------------------------------------------------------------------------------------
+struct Chains {
+    rbnn_hmc_lockstep s;
+    float* W;                                  // the trajectory positions and dCE/dW [K, chain_stride]
+    const float* grad;
+    long long n_params;
+};
+
+__device__ __forceinline__ bool chain_active(const Chains& a) { return !a.s.active || a.s.active[blockIdx.y] != 0; }
+
+__device__ __forceinline__ rbnn_hmc_chain chain_of(const Chains& a) {
+    const long long k = blockIdx.y, at = k * a.s.chain_stride;
+    rbnn_hmc_chain c;
+    c.q_cur = a.s.q_cur + at; c.g_cur = a.s.g_cur + at; c.r = a.s.r + at; c.m_inv = a.s.m_inv + at; c.w_mean = a.s.w_mean + at; c.w_m2 = a.s.w_m2 + at;
+    c.k0_part = a.s.k0_part + k * a.s.qpart_stride;
+    c.k1_part = a.s.k1_part + k * a.s.epart_stride; c.p_part = a.s.p_part + k * a.s.epart_stride;
+    c.state = a.s.state + k * RBNN_HMC_STATE;
+    c.log = a.s.log ? a.s.log + k * a.s.log_rows * RBNN_HMC_LOG : nullptr;
+    c.samples = a.s.samples ? a.s.samples + k * a.s.sample_rows * a.n_params : nullptr;
+    c.log_rows = a.s.log_rows; c.sample_rows = a.s.sample_rows;
+    return c;
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_momentum_kernel(const Layout L, const Chains a, unsigned long long key_xor, uint32_t draw_id,
+                                                                        const uint32_t* __restrict__ draw_ids) {
+    __shared__ float red[ELT_THREADS];
+    if (!chain_active(a)) return;
+    const rbnn_hmc_chain c = chain_of(a);
+    const float k = momentum_quad(L, c, (long long)blockIdx.x * ELT_THREADS + threadIdx.x, a.s.keys[blockIdx.y] ^ key_xor,
+                                  draw_ids ? draw_ids[blockIdx.y] : draw_id);
+    block_sum_to(k, red, c.k0_part);
+}
+
+// step < 0: `phase` for every active chain.  step >= 0: leapfrog step `step` of chains with their own lengths steps[k]: MID while
+// step + 1 < steps[k], CLOSE at step + 1 == steps[k], nothing behind it.
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_update_kernel(const Chains a, int phase, int step) {
+    __shared__ float red[ELT_THREADS];
+    if (!chain_active(a)) return;
+    if (step >= 0) {
+        const int Lk = a.s.steps[blockIdx.y];
+        if (step >= Lk) return;
+        phase = step + 1 < Lk ? RBNN_HMC_MID : RBNN_HMC_CLOSE;
+    }
+    const rbnn_hmc_chain c = chain_of(a);
+    const long long at = (long long)blockIdx.y * a.s.chain_stride;
+    float kin = 0.f, pot = 0.f;
+    update_element((long long)blockIdx.x * ELT_THREADS + threadIdx.x, a.n_params, a.W + at, a.grad + at, c, phase, kin, pot);
+    if (phase == RBNN_HMC_CLOSE || phase == RBNN_HMC_ENERGY) {
+        block_sum_to(kin, red, c.k1_part);
+        block_sum_to(pot, red, c.p_part);
+    }
+}
+
+struct LockstepDecide {
+    Chains a;
+    const float* ce;                           // [K, n_points]
+    const int32_t* counts;                     // [K] or NULL
+    long long n_points, n_qpart, n_epart, transition;
+    int mode, adapt, window_end;
+};
+
+__global__ void __launch_bounds__(256) lockstep_decide_kernel(const LockstepDecide d) {
+    __shared__ double red[256];
+    if (!chain_active(d.a)) return;
+    const long long k = blockIdx.y;
+    DecideArgs a;
+    a.c = chain_of(d.a);
+    a.ce = d.ce + k * d.n_points;
+    a.n_points = d.counts ? min((long long)max(d.counts[k], 0), d.n_points) : d.n_points;
+    a.n_qpart = d.n_qpart; a.n_epart = d.n_epart; a.transition = d.transition; a.key = d.a.s.keys[k];
+    a.mode = d.mode; a.adapt = d.adapt; a.window_end = d.window_end;
+    decide_chain(a, red);
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_commit_kernel(const Chains a, int force, float welford_n, long long sample_row) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= a.n_params || !chain_active(a)) return;
+    const rbnn_hmc_chain c = chain_of(a);
+    const long long at = (long long)blockIdx.y * a.s.chain_stride;
+    commit_element(i, a.W + at, a.grad + at, c, force, welford_n, sample_row >= 0 ? c.samples + sample_row * a.n_params : nullptr);
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_window_end_kernel(const Chains a, float scale, float shift) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= a.n_params || !chain_active(a)) return;
+    window_end_element(i, chain_of(a), scale, shift);
 }
 
 int check_chain(const rbnn_hmc_chain* c) {
     if (!c) return RBNN_ERR_NULL;
     if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state)
         return RBNN_ERR_NULL;
+    return RBNN_OK;
+}
+
+// the chains of a lockstep call and the net whose P / grad are their trajectory buffers -> the kernels' argument
+int check_chains(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* c, Chains* out) {
+    int rc = check_members(net);
+    if (rc) return rc;
+    if (!c) return RBNN_ERR_NULL;
+    if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state || !c->keys)
+        return RBNN_ERR_NULL;
+    const Layout L = layout_of(*net);
+    if (c->chain_stride < L.n_params || net->member_stride != c->chain_stride) return RBNN_ERR_SHAPE;
+    if (c->qpart_stride < (long long)blocks_for(L.n_quads) || c->epart_stride < (long long)blocks_for(L.n_params)) return RBNN_ERR_SHAPE;
+    if (c->log_rows < 0 || c->sample_rows < 0) return RBNN_ERR_SHAPE;
+    out->s = *c; out->W = net->P; out->grad = net->grad; out->n_params = L.n_params;
     return RBNN_OK;
 }
 
@@ -266,6 +408,80 @@ int rbnn_hmc_window_end(const rbnn_svi_train_net* net, const rbnn_hmc_chain* cha
     // m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5): the two scalars are formed in double and rounded to fp32 once
     const double w = (double)n_window;
     hipLaunchKernelGGL(hmc_window_end_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, *chain,
+                       (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
+    return launch_status();
+}
+
+// ---- K chains in lockstep ----
+int rbnn_hmc_lockstep_gradient(const rbnn_nn_train_net* net, const float* X, int32_t ldx, int32_t n_rows, const int32_t* labels,
+                               const int32_t* rows, const int32_t* counts, int32_t n_points, const rbnn_nn_train_ws* ws, void* stream) {
+    const LockstepBatch b = {X, ldx, n_rows, labels, rows, counts, n_points};
+    if (net && !net->grad) return RBNN_ERR_NULL;                                     // before the forward is launched
+    const int rc = lockstep_forward(net, b, ws, 1.f, (hipStream_t)stream);
+    return rc ? rc : lockstep_weight_grads(net, b, ws, (hipStream_t)stream);
+}
+
+int rbnn_hmc_lockstep_momentum(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, uint64_t key_xor, uint32_t draw_id,
+                               const uint32_t* draw_ids, void* stream) {
+    Chains a = {};
+    const int rc = check_chains(net, chains, &a);
+    if (rc) return rc;
+    const Layout L = layout_of(*net);
+    hipLaunchKernelGGL(lockstep_momentum_kernel, dim3(blocks_for(L.n_quads), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
+                       (unsigned long long)key_xor, draw_id, draw_ids);
+    return launch_status();
+}
+
+int rbnn_hmc_lockstep_update(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, int32_t phase, int32_t step, void* stream) {
+    Chains a = {};
+    const int rc = check_chains(net, chains, &a);
+    if (rc) return rc;
+    if (!net->P || !net->grad) return RBNN_ERR_NULL;
+    if (step >= 0 && !chains->steps) return RBNN_ERR_NULL;
+    if (step < 0 && (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY)) return RBNN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(lockstep_update_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a, (int)phase,
+                       (int)step);
+    return launch_status();
+}
+
+int rbnn_hmc_lockstep_decide(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, const float* ce, const int32_t* counts,
+                             int32_t n_points, int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    LockstepDecide d = {};
+    const int rc = check_chains(net, chains, &d.a);
+    if (rc) return rc;
+    if (!ce) return RBNN_ERR_NULL;
+    if (n_points < 1 || transition < 0) return RBNN_ERR_SHAPE;
+    if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
+    const Layout L = layout_of(*net);
+    d.ce = ce; d.counts = counts; d.n_points = n_points; d.n_qpart = blocks_for(L.n_quads); d.n_epart = blocks_for(L.n_params);
+    d.transition = transition; d.mode = mode; d.adapt = adapt; d.window_end = window_end;
+    hipLaunchKernelGGL(lockstep_decide_kernel, dim3(1, net->n_members), dim3(256), 0, (hipStream_t)stream, d);
+    return launch_status();
+}
+
+int rbnn_hmc_lockstep_commit(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, int32_t force, int32_t welford_n, int64_t sample_row,
+                             void* stream) {
+    Chains a = {};
+    const int rc = check_chains(net, chains, &a);
+    if (rc) return rc;
+    if (!net->P || !net->grad) return RBNN_ERR_NULL;
+    if (sample_row >= 0) {
+        if (!chains->samples) return RBNN_ERR_NULL;
+        if (sample_row >= chains->sample_rows) return RBNN_ERR_SHAPE;
+    }
+    if (welford_n < 0) return RBNN_ERR_SHAPE;
+    hipLaunchKernelGGL(lockstep_commit_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a, (int)force,
+                       (float)welford_n, (long long)sample_row);
+    return launch_status();
+}
+
+int rbnn_hmc_lockstep_window_end(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, int32_t n_window, void* stream) {
+    Chains a = {};
+    const int rc = check_chains(net, chains, &a);
+    if (rc) return rc;
+    if (n_window < 2) return RBNN_ERR_SHAPE;
+    const double w = (double)n_window;                                               // the two scalars as rbnn_hmc_window_end forms them
+    hipLaunchKernelGGL(lockstep_window_end_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a,
                        (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
     return launch_status();
 }

@@ -1,5 +1,6 @@
 // rbnn_train_gemm.hpp — the forward / backward of an fc / fc2 net on the fp32 MFMA, shared by the units that launch it (rbnn_train.hip,
-// rbnn_nn_train.hip): one strided GEMM kernel and one output-layer + loss kernel, for M independent members in lockstep (grid dimension y).
+// rbnn_nn_train.hip, rbnn_hmc.hip): one strided GEMM kernel and one output-layer + loss kernel, for M independent members in lockstep (grid
+// dimension y), and the host side of the lockstep forward / weight gradients.
 // Both bodies are templates on LOCKSTEP.  false is a single net: member 0, no index arrays — the member strides, a_idx / b_idx / rows and the
 // clamp are compiled out (measured: with them the SVI step was 5 % and an HMC transition 5 - 7 % slower than the kernels it had before).
 #pragma once
@@ -118,6 +119,7 @@ struct HeadArgs {
     const float *Hl, *Dl, *W2, *b2;           // Hl / Dl [M, B, H]; W2 / b2 of member 0, member stride p_mem
     long long p_mem;
     const int32_t *labels, *rows;             // labels of the resident data, rows [M, B] or NULL (point b is row b)
+    const int32_t* counts;                    // [M] or NULL: member m's own number of points <= B; a point behind it contributes exact zeros
     int idx_max;
     float *dZ, *ce, *dA;
     int32_t* correct;                         // nullable
@@ -129,6 +131,16 @@ template <bool LOCKSTEP> __global__ void __launch_bounds__(256) train_head_kerne
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= a.B) return;
     const long long mem = LOCKSTEP ? blockIdx.y : 0, pt = mem * a.B + b;
+    if (LOCKSTEP && a.counts && b >= a.counts[mem]) {                  // not a point of this member: ce, dZ, dA and correct are zero
+        if (lane == 0) {
+            a.ce[pt] = 0.f;
+            if (a.correct) a.correct[pt] = 0;
+#pragma unroll
+            for (int c = 0; c < RBNN_CPAD; ++c) a.dZ[pt * RBNN_CPAD + c] = 0.f;
+        }
+        for (int h = lane; h < a.H; h += 64) a.dA[pt * a.H + h] = 0.f;
+        return;
+    }
     const float* const W2 = a.W2 + mem * a.p_mem;
     float z[RBNN_CPAD];
 #pragma unroll
@@ -204,5 +216,95 @@ inline GemmProb wgrad_prob(const float* dA, long long ld_da, const float* src, l
     p.Cout = dW; p.ldc = N; p.c_mem = p_mem; p.bias_out = db; p.bias_mem = p_mem; p.epi = EPI_STORE;
     return p;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The lockstep forward / backward and weight gradients of an rbnn_nn_train_net on a batch gathered from resident data: what rbnn_nn_train.hip
+// (mean CE: inv_S = 1 / B) and rbnn_hmc.hip (summed CE: inv_S = 1, per-member counts) launch.  Those two units define RBNN_TRAIN_LOCKSTEP
+// before they include this file; a unit that does not never instantiates the LOCKSTEP = true kernels.
+// ---------------------------------------------------------------------------------------------------
+#ifdef RBNN_TRAIN_LOCKSTEP
+struct LockstepBatch {
+    const float* X; int ldx, n_rows;          // resident data [n_rows, ldx]
+    const int32_t *labels, *rows, *counts;    // labels [n_rows]; rows [M, B] or NULL (rows 0..B-1 for every member); counts [M] or NULL
+    int B;
+};
+
+inline int check_members(const rbnn_nn_train_net* n) {
+    const int rc = check_net(n);
+    if (rc) return rc;
+    return (n->n_members < 1 || n->n_members > 65535) ? RBNN_ERR_SHAPE : RBNN_OK;      // the member is grid dimension y
+}
+
+inline int check_batch(const rbnn_nn_train_net* n, const LockstepBatch& b) {
+    if (!b.X) return RBNN_ERR_NULL;
+    if (b.B < 1 || b.n_rows < 1 || b.ldx < n->in_features) return RBNN_ERR_SHAPE;
+    if (!b.rows && b.B > b.n_rows) return RBNN_ERR_SHAPE;                          // rows 0..B-1 of X
+    if ((long long)n->n_members * b.B * n->hidden > (1LL << 40) || n->member_stride < layout_of(*n).n_params) return RBNN_ERR_SHAPE;
+    return RBNN_OK;
+}
+
+// hidden activations, act', logits, ce, dZ, correct, and the backward to dA1 (fc2: dA2, then dA1): fc 2 launches, fc2 4
+inline int lockstep_forward(const rbnn_nn_train_net* net, const LockstepBatch& b, const rbnn_nn_train_ws* ws, float inv_S, hipStream_t st) {
+    int rc = check_members(net);
+    if (rc) return rc;
+    if (!b.labels || !ws || !net->P) return RBNN_ERR_NULL;
+    if ((rc = check_batch(net, b))) return rc;
+    const bool fc2 = net->arch == RBNN_ARCH_FC2;
+    if (!ws->hid1 || !ws->dact1 || !ws->dA1 || !ws->dZ || !ws->ce || !ws->correct) return RBNN_ERR_NULL;
+    if (fc2 && (!ws->hid2 || !ws->dact2 || !ws->dA2)) return RBNN_ERR_NULL;
+    const Layout L = layout_of(*net);
+    const int D = net->in_features, H = net->hidden, C = net->n_classes, B = b.B, act = net->activation, M = net->n_members;
+    const long long ps = net->member_stride, bh = (long long)B * H;
+    const float* P = net->P;
+    GemmArgs g = {};
+    g.n_prob = 1;
+    g.p[0] = fwd_prob(b.X, b.ldx, 0, P + L.s[0].off, P + L.s[1].off, ps, B, H, D, ws->hid1, ws->dact1, act);
+    g.p[0].a_idx = b.rows; g.p[0].idx_mem = B; g.p[0].idx_max = b.n_rows - 1;
+    if ((rc = gemm_launch<true>(g, M, st))) return rc;
+    if (fc2) {
+        g.p[0] = fwd_prob(ws->hid1, H, bh, P + L.s[2].off, P + L.s[3].off, ps, B, H, H, ws->hid2, ws->dact2, act);
+        if ((rc = gemm_launch<true>(g, M, st))) return rc;
+    }
+    HeadArgs h = {};
+    h.Hl = fc2 ? ws->hid2 : ws->hid1; h.Dl = fc2 ? ws->dact2 : ws->dact1;
+    h.W2 = P + L.s[L.n - 2].off; h.b2 = P + L.s[L.n - 1].off; h.p_mem = ps; h.labels = b.labels; h.rows = b.rows; h.counts = b.counts;
+    h.idx_max = b.n_rows - 1;
+    h.dZ = ws->dZ; h.ce = ws->ce; h.correct = ws->correct; h.dA = fc2 ? ws->dA2 : ws->dA1; h.B = B; h.H = H; h.C = C;
+    h.inv_S = inv_S;
+    hipLaunchKernelGGL(train_head_kernel<true>, dim3((B + 3) / 4, M), dim3(256), 0, st, h);
+    if ((rc = launch_status())) return rc;
+    if (fc2) {
+        // dA1[b, i] = (sum_o dA2[b, o] Wm[o, i]) act'1[b, i]
+        GemmProb p = {};
+        p.A = ws->dA2; p.a_m = H; p.a_k = 1; p.a_mem = bh; p.B = P + L.s[2].off; p.b_n = 1; p.b_k = H; p.b_mem = ps; p.M = B; p.N = H; p.K = H;
+        p.ones_n = -1; p.Cout = ws->dA1; p.ldc = H; p.c_mem = bh; p.Dmul = ws->dact1; p.epi = EPI_MUL;
+        g.p[0] = p;
+        if ((rc = gemm_launch<true>(g, M, st))) return rc;
+    }
+    return RBNN_OK;
+}
+
+// grad = dL/dP of every tensor of every member (the biases as column sums): one launch
+inline int lockstep_weight_grads(const rbnn_nn_train_net* net, const LockstepBatch& b, const rbnn_nn_train_ws* ws, hipStream_t st) {
+    int rc = check_members(net);
+    if (rc) return rc;
+    if (!ws || !net->grad) return RBNN_ERR_NULL;
+    if ((rc = check_batch(net, b))) return rc;
+    const bool fc2 = net->arch == RBNN_ARCH_FC2;
+    if (!ws->hid1 || !ws->dA1 || !ws->dZ) return RBNN_ERR_NULL;
+    if (fc2 && (!ws->hid2 || !ws->dA2)) return RBNN_ERR_NULL;
+    const Layout L = layout_of(*net);
+    const int D = net->in_features, H = net->hidden, C = net->n_classes, B = b.B;
+    const long long ps = net->member_stride, bh = (long long)B * H;
+    float* G = net->grad;
+    GemmArgs g = {};
+    g.n_prob = fc2 ? 3 : 2;
+    g.p[0] = wgrad_prob(ws->dA1, H, b.X, b.ldx, 0, H, D, B, G + L.s[0].off, G + L.s[1].off, ps);
+    g.p[0].b_idx = b.rows; g.p[0].idx_mem = B; g.p[0].idx_max = b.n_rows - 1;
+    if (fc2) g.p[1] = wgrad_prob(ws->dA2, H, ws->hid1, H, bh, H, H, B, G + L.s[2].off, G + L.s[3].off, ps);
+    g.p[g.n_prob - 1] = wgrad_prob(ws->dZ, RBNN_CPAD, fc2 ? ws->hid2 : ws->hid1, H, bh, C, H, B, G + L.s[L.n - 2].off, G + L.s[L.n - 1].off, ps);
+    return gemm_launch<true>(g, net->n_members, st);
+}
+#endif  // RBNN_TRAIN_LOCKSTEP
 
 }  // namespace

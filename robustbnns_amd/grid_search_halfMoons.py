@@ -7,8 +7,14 @@ out of scope: DESIGN.md section 7), then for every combination loads the HMC pos
 Here every model is one resident posterior on the GPU and every (model, n_samples) cell one batched run over all test
 points; the grid itself is a plain loop (the work per cell is milliseconds).  Dataset loading is out of scope as well,
 so the caller passes the test tensors (`x_test [N,1,2,1]`, `y_test [N,2]` one-hot, as utils.load_dataset returns them).
+
+`lockstep_train` is the counterpart of the reference's parallel_train (:52-59: 10 joblib processes, one model each): the HMC models of the
+grid that differ only in their training-set size run as chains of ONE lockstep sampler (hmc.LockstepHmc: every kernel launch covers all of
+them), and what it saves equals serial_train's bit for bit.
 """
 import itertools
+
+import torch
 
 from torch.utils.data import DataLoader
 
@@ -64,6 +70,63 @@ def serial_train(hidden_size, activation, architecture, inference, epochs, lr, n
     for init in _combinations(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples):
         bnn = _train(*init, rel_path, device, x_train=x_train, y_train=y_train, train_loader=train_loader)
         out[bnn.name] = bnn
+    return out
+
+
+def lockstep_train(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples, rel_path,
+                   x_train=None, y_train=None, train_loader=None, device="cuda"):
+    """serial_train with the HMC models of the grid sampled in lockstep.  The combinations that differ only in n_inputs and
+    posterior_samples (and share the number of samples their last batch gets) form a group: one hmc.LockstepHmc whose chains have the same
+    net shape, warmup and sample count and differ in their data, which are rows / counts into the resident x_train.  Every train_hmc reseeds
+    with 0 and the moons loader does not shuffle, so each chain gets the start position and key it has in serial_train; before a chain's
+    resample indices are drawn, the CPU generator is put back to the state it had after that chain's key was drawn.  Returns {bnn.name: bnn};
+    names and saved tensors equal serial_train's.  svi combinations, and a ready train_loader, go through _train one by one."""
+    from .hmc import LockstepHmc
+    from .model_bnn import lockstep_history
+    combos = _combinations(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples)
+    out, groups = {}, {}
+    for init in combos:
+        h, act, arch, inf, ep, lr_, ns, wu, ninp, _ = init
+        if inf != "hmc" or train_loader is not None:
+            bnn = _train(*init, rel_path, device, x_train=x_train, y_train=y_train, train_loader=train_loader)
+            out[bnn.name] = bnn
+            continue
+        if arch not in ("fc", "fc2"):
+            raise NotImplementedError(f"grid training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        if x_train is None or y_train is None:
+            raise ValueError("lockstep_train needs x_train / y_train or a train_loader: dataset loading is out of scope")
+        members = groups.setdefault((h, act, arch, ep, lr_, ns, wu), {})
+        members.setdefault(ninp, None)                                   # one chain per training-set size, in the grid's order
+        out[MoonsBNN(h, act, arch, inf, ep, lr_, ns, wu, ninp, tuple(x_train[0].shape), int(y_train.shape[-1])).name] = None
+    labels = None if y_train is None else y_train.argmax(-1)
+    for (h, act, arch, ep, lr_, ns, wu), members in groups.items():
+        chains = {}                                                      # batch_samples -> [(bnn, first row, count, q0, key, generator state)]
+        for ninp in members:
+            loader = moons_loader(x_train[:ninp], y_train[:ninp], 1024)
+            x0, y0 = loader.dataset[0]
+            bnn = MoonsBNN(h, act, arch, "hmc", ep, lr_, ns, wu, ninp, tuple(x0.shape), int(y0.shape[-1]))
+            x_batch, _, batch_samples, q0, key = bnn._hmc_prologue(loader, device)
+            n = len(loader.dataset)
+            chains.setdefault(batch_samples, []).append((bnn, n - int(x_batch.shape[0]), int(x_batch.shape[0]), q0, key, torch.get_rng_state()))
+        for batch_samples, cs in chains.items():
+            B = max(c[2] for c in cs)
+            rows = torch.zeros(len(cs), B, dtype=torch.int32)
+            for k, c in enumerate(cs):
+                rows[k, :c[2]] = torch.arange(c[1], c[1] + c[2], dtype=torch.int32)
+            b = cs[0][0].basenet
+            sampler = LockstepHmc(b.architecture, b.activation, b.input_shape, b.output_size, [c[3] for c in cs], cs[0][0].step_size,
+                                  cs[0][0].num_steps, device, [c[4] for c in cs], batch_size=B)
+            sampler.set_data(x_train, labels)
+            stacks = sampler.run(rows=rows, counts=[c[2] for c in cs], num_samples=batch_samples, warmup=wu)
+            for k, (bnn, _, _, _, _, rng) in enumerate(cs):
+                torch.set_rng_state(rng)
+                idx = torch.randint(0, batch_samples, (bnn.n_samples,)).to(device)
+                bnn.hmc_history = lockstep_history(sampler, k, idx)
+                bnn.set_posterior_samples({key_: v.index_select(0, idx).contiguous() for key_, v in stacks[k].items()}, device)
+                bnn.save(rel_path=rel_path, filename=None)
+                out[bnn.name] = bnn
     return out
 
 

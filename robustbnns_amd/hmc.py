@@ -11,6 +11,9 @@ one fused update); of one transition with L steps: 1 (momentum) + 1 (opening upd
 Host synchronisation: warmup reads the device's state block once per transition (L follows the adapted step size, and the step-size search
 loops on a device value); sampling (step size and L fixed) makes NO device->host synchronisation — the logs and the sample stack are read
 once at the end of run().
+
+LockstepHmc runs K chains of one net shape with every launch covering all of them (the chain is grid dimension y: rbnn_hmc_lockstep_*), each
+chain bit-identical to HmcSampler running it alone; split_r_hat is the convergence figure that goes with several chains.
 """
 import ctypes as C
 import math
@@ -296,3 +299,339 @@ class HmcSampler:
             self.transition(first + i, L, False, False, 0, i)
             if Ls is not None:
                 Ls.append(L)
+
+
+class LockstepHmc:
+    """K independent chains over nets of ONE shape in lockstep: every launch covers all chains, so a transition costs the launches of a single
+    chain whatever K is.  Each chain has its own key, start position, step size, mass matrix, state block, log and sample stack, and may have
+    its own batch (rows / counts into resident data); warmup, the number of samples, num_steps and the adapt flags are shared.  Chain k is
+    bit-identical to HmcSampler(…, q0s[k], …, keys[k]) alone on its batch: sample stack, log, m_inv, q_cur, g_cur, state, L_log, search tries.
+
+    Adapted step sizes differ, so the chains' trajectory lengths L_k do: the host issues max_k L_k leapfrog steps and the update launch of
+    step s closes the chains with L_k == s + 1 and skips those behind it (their forward / gradient launches still run, on a position that
+    no longer moves).  The step-size search probes all chains together and freezes a chain whose direction has flipped (`active`).
+    `launches` counts kernel launches as HmcSampler does."""
+
+    def __init__(self, arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size=True,
+                 adapt_mass_matrix=True, batch_size=128):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        if arch not in LAYER_KEYS:
+            raise NotImplementedError(f"HMC covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+        q0s, keys = list(q0s), list(keys)
+        if len(q0s) < 1 or len(keys) != len(q0s):
+            raise ValueError(f"LockstepHmc needs one key per chain and at least one chain: {len(q0s)} start positions, {len(keys)} keys")
+        if len(q0s) > 65535:
+            raise ValueError(f"at most 65535 chains run in lockstep (the chain is a grid dimension), not {len(q0s)}")
+        K = self.K = len(q0s)
+        self.k = _hip.HipKernels()
+        self.arch, self.activation, self.device = arch, activation, dev
+        self.input_shape = tuple(int(v) for v in input_shape)
+        self.keys = state_keys(arch)
+        self.shapes = {k: tuple(q0s[0][k].shape) for k in self.keys}
+        self.D = int(np.prod(self.input_shape))
+        self.H, self.C = int(self.shapes[self.keys[1]][0]), int(n_classes)
+        one = _hip.SviTrainNet()
+        one.arch, one.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
+        one.in_features, one.hidden, one.n_classes = self.D, self.H, self.C
+        nq, ne = C.c_int64(0), C.c_int64(0)
+        n = int(self.k.lib.rbnn_hmc_sizes(C.byref(one), C.byref(nq), C.byref(ne)))
+        _hip.check(min(n, 0), "rbnn_hmc_sizes")
+        self.n_params, self.n_qpart, self.n_epart = n, int(nq.value), int(ne.value)
+        z = lambda m=n: torch.zeros(K, m, dtype=torch.float32, device=dev)
+        self.W, self.grad = z(), z()
+        self.q_cur = torch.stack([flatten(q0, self.keys) for q0 in q0s]).to(dev)
+        assert tuple(self.q_cur.shape) == (K, n), (tuple(self.q_cur.shape), K, n)
+        self.g_cur, self.r, self.w_mean, self.w_m2 = z(), z(), z(), z()
+        self.m_inv = torch.ones(K, n, dtype=torch.float32, device=dev)
+        self.k0_part, self.k1_part, self.p_part = z(self.n_qpart), z(self.n_epart), z(self.n_epart)
+        self.state = torch.zeros(K, _hip.HMC_STATE, dtype=torch.float64, device=dev)
+        self.log_t = self.samples_t = None
+        self.chain_keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
+        # uint64 keys in an int64 tensor (the same bits)
+        self.keys_t = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in self.chain_keys], dtype=torch.int64).to(dev)
+        self.steps_t = torch.ones(K, dtype=torch.int32, device=dev)
+        self.draw_ids_t = torch.zeros(K, dtype=torch.int32, device=dev)
+        self.active_t = torch.ones(K, dtype=torch.int32, device=dev)
+        self.active = None                                               # None: every chain; else the host's copy of active_t
+        self._steps_host = [1] * K
+        sizes = [float(v) for v in step_size] if isinstance(step_size, (list, tuple)) else [float(step_size)] * K
+        if len(sizes) != K:
+            raise ValueError(f"{len(sizes)} step sizes for {K} chains")
+        self.step_size, self.num_steps = sizes, int(num_steps)
+        self.trajectory_length = [e * self.num_steps for e in sizes]
+        self.adapt_step_size, self.adapt_mass_matrix = bool(adapt_step_size), bool(adapt_mass_matrix)
+        self.eps_host = list(sizes)
+        self.searches = [0] * K
+        self.search_log = [[] for _ in range(K)]
+        self.launches = 0
+        self.fwd_launches = 2 if arch == "fc" else 4
+        self.cap = self.B = 0
+        self.X = self.labels = self.rows_t = self.counts_t = None
+        self._ensure(int(batch_size))
+        self._set_state(eps=sizes, mu=[math.log(10 * e) for e in sizes])
+        self._bind()
+        self.eps_log = self.L_log = self.dH_log = self.accept_prob_log = self.accepted_log = None
+
+    # -- buffers --------------------------------------------------------------------------------------------------------------------
+    def _bind(self):
+        net = _hip.NnTrainNet()
+        net.arch, net.activation = _hip.ARCHS[self.arch], _hip.ACTIVATIONS[self.activation]
+        net.in_features, net.hidden, net.n_classes, net.n_members = self.D, self.H, self.C, self.K
+        net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), self.n_params
+        self.net = net
+        ch = _hip.HmcLockstep()
+        for name in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state"):
+            setattr(ch, name, getattr(self, name).data_ptr())
+        ch.log = None if self.log_t is None else self.log_t.data_ptr()
+        ch.samples = None if self.samples_t is None else self.samples_t.data_ptr()
+        ch.log_rows = 0 if self.log_t is None else int(self.log_t.shape[1])
+        ch.sample_rows = 0 if self.samples_t is None else int(self.samples_t.shape[1])
+        ch.keys, ch.steps = self.keys_t.data_ptr(), self.steps_t.data_ptr()
+        ch.active = None if self.active is None else self.active_t.data_ptr()
+        ch.chain_stride, ch.qpart_stride, ch.epart_stride = self.n_params, self.n_qpart, self.n_epart
+        self.chain = ch
+
+    def _ensure(self, B):
+        """Workspaces for K x B points (packed [K, B, .] for the call's B)."""
+        if self.K * B <= self.cap:
+            return
+        self.ws_t = train_workspace(self.arch, self.K * B, self.H, self.device)
+        self.ws_t["correct"] = torch.zeros(self.K * B, dtype=torch.int32, device=self.device)
+        self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
+        self.cap = self.K * B
+
+    def unflat(self, buf):
+        return unflat(buf, self.keys, self.shapes)
+
+    def _set_state(self, **kv):
+        """Host -> device writes of state-block entries (warmup / set-up only): one value for every chain, or one per chain."""
+        for name, v in kv.items():
+            if isinstance(v, (list, tuple)):
+                self.state[:, _hip.HMC_ST[name]] = torch.tensor([float(e) for e in v], dtype=torch.float64)
+            else:
+                self.state[:, _hip.HMC_ST[name]] = float(v)
+
+    def read_state(self):
+        """One dict per chain (a device->host synchronisation)."""
+        return [{name: row[i] for name, i in _hip.HMC_ST.items()} for row in self.state.tolist()]
+
+    def set_active(self, mask=None):
+        """mask: K truth values (host -> device), or None for all chains.  A chain that is not active is neither read nor written by the
+        momentum, update, decision, commit and window-end launches that follow."""
+        if mask is None or all(mask):
+            self.active = None
+        else:
+            self.active = [bool(m) for m in mask]
+            self.active_t.copy_(torch.tensor([int(m) for m in self.active], dtype=torch.int32))
+        self.chain.active = None if self.active is None else self.active_t.data_ptr()
+
+    def _set_steps(self, Ls):
+        if list(Ls) != self._steps_host:                                  # host -> device, only when a length changed
+            self.steps_t.copy_(torch.tensor([int(v) for v in Ls], dtype=torch.int32))
+            self._steps_host = list(Ls)
+
+    # -- launches -------------------------------------------------------------------------------------------------------------------
+    def _st(self):
+        return _hip.stream_of(self.W)
+
+    def _gradient(self):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_gradient(C.byref(self.net), _hip.ptr(self.X), self.D, int(self.X.shape[0]), _hip.ptr(self.labels),
+                                                         _hip.ptr(self.rows_t), _hip.ptr(self.counts_t), self.B, C.byref(self.ws), self._st()),
+                   "rbnn_hmc_lockstep_gradient")
+        self.launches += self.fwd_launches + 1
+
+    def _update(self, phase, step=-1):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_update(C.byref(self.net), C.byref(self.chain), phase, step, self._st()), "rbnn_hmc_lockstep_update")
+        self.launches += 1
+
+    def _momentum(self, key_xor, draw_id, per_chain=False):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_momentum(C.byref(self.net), C.byref(self.chain), C.c_uint64(key_xor), C.c_uint32(draw_id & 0xFFFFFFFF),
+                                                         _hip.ptr(self.draw_ids_t) if per_chain else None, self._st()), "rbnn_hmc_lockstep_momentum")
+        self.launches += 1
+
+    def _decide(self, mode, transition=0, adapt=False, window_end=False):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_decide(C.byref(self.net), C.byref(self.chain), _hip.ptr(self.ws_t["ce"]), _hip.ptr(self.counts_t),
+                                                       self.B, int(transition), mode, int(adapt), int(window_end), self._st()),
+                   "rbnn_hmc_lockstep_decide")
+        self.launches += 1
+
+    def _commit(self, force=False, welford_n=0, sample_row=-1):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_commit(C.byref(self.net), C.byref(self.chain), int(force), int(welford_n), int(sample_row), self._st()),
+                   "rbnn_hmc_lockstep_commit")
+        self.launches += 1
+
+    # -- data -----------------------------------------------------------------------------------------------------------------------
+    def set_data(self, x, labels):
+        """The resident data the chains' batches are gathered from: x [n_rows, ...], labels int [n_rows]."""
+        n = int(x.shape[0])
+        self.X = x.reshape(n, -1).to(self.device, torch.float32).contiguous()
+        self.labels = labels.reshape(n).to(self.device, torch.int32).contiguous()
+        if self.X.shape[1] != self.D:
+            raise ValueError(f"the data have {self.X.shape[1]} features, the nets {self.D}")
+
+    def stage(self, rows=None, counts=None):
+        """The chains' batches — rows [K, B] int32 into the resident data with counts [K] (None: B) of them valid per chain, or rows None: the
+        whole resident data for every chain — and the potential / gradient at the current positions."""
+        if self.X is None:
+            raise ValueError("set_data(x, labels) first")
+        if rows is None:
+            self.rows_t, self.B = None, int(self.X.shape[0])
+        else:
+            rows = torch.as_tensor(rows)
+            if rows.dim() != 2 or rows.shape[0] != self.K:
+                raise ValueError(f"rows must be [{self.K}, B], not {tuple(rows.shape)}")
+            self.rows_t, self.B = rows.to(self.device, torch.int32).contiguous(), int(rows.shape[1])
+        if counts is None:
+            self.counts_t = None
+        else:
+            counts = [int(c) for c in (counts.tolist() if torch.is_tensor(counts) else counts)]
+            if len(counts) != self.K or min(counts) < 1 or max(counts) > self.B:
+                raise ValueError(f"counts must be {self.K} values in [1, {self.B}], not {counts}")
+            self.counts_t = torch.tensor(counts, dtype=torch.int32).to(self.device)
+        self._ensure(self.B)
+        self.refresh()
+
+    def refresh(self):
+        self.W.copy_(self.q_cur)
+        self._gradient()
+        self._update(_hip.HMC_ENERGY)
+        self._decide(_hip.HMC_DECIDE_INIT)
+        self._commit(force=True)
+
+    # -- the chains -----------------------------------------------------------------------------------------------------------------
+    def length(self, k, eps=None):
+        return max(1, int(self.trajectory_length[k] / (self.eps_host[k] if eps is None else eps)))
+
+    def lengths(self):
+        return [self.length(k) for k in range(self.K)]
+
+    def leapfrog(self, Ls):
+        """Chain k takes Ls[k] leapfrog steps (an int: every chain) from (q_cur, r) at its own step size: max(Ls) gradient + update launches."""
+        Ls = [int(Ls)] * self.K if isinstance(Ls, int) else [int(v) for v in Ls]
+        self._set_steps(Ls)
+        self._update(_hip.HMC_OPEN)
+        for s in range(max(Ls)):
+            self._gradient()
+            self._update(_hip.HMC_MID, s)
+
+    def transition(self, i, Ls=None, adapt=False, window_end=False, welford_n=0, sample_row=-1):
+        """Transition i of every active chain, chain k with Ls[k] leapfrog steps (default: from the host's copies of the step sizes).  No
+        device->host synchronisation."""
+        Ls = self.lengths() if Ls is None else ([int(Ls)] * self.K if isinstance(Ls, int) else list(Ls))
+        self._momentum(0, i)
+        self.leapfrog(Ls)
+        self._decide(_hip.HMC_DECIDE_TRANSITION, i, adapt, window_end)
+        self._commit(False, welford_n, sample_row)
+        return Ls
+
+    def _probe(self, eps, live):
+        """One try of the search for the chains in `live`: -> the K values of dH (a frozen chain's is its last one)."""
+        self.set_active(live)
+        self._set_state(eps=eps)                                         # a frozen chain's entry is the value its block already holds
+        self.draw_ids_t.copy_(torch.tensor(self.searches, dtype=torch.int32))
+        self._momentum(_hip.HMC_SEARCH_KEY, 0, per_chain=True)
+        for k in range(self.K):
+            self.searches[k] += int(live[k])
+        self.leapfrog(1)
+        self._decide(_hip.HMC_DECIDE_PROBE)
+        return [s["dH"] for s in self.read_state()]
+
+    def find_reasonable_step_size(self):
+        """HmcSampler's search for every chain at once: all chains probe together, each with its own try counter; a chain whose direction has
+        flipped is frozen (active = 0) while the others go on."""
+        log08, K = math.log(0.8), self.K
+        eps, tries, live = list(self.eps_host), [[] for _ in range(K)], [True] * K
+        dH = self._probe(eps, live)
+        direction = [1 if -dH[k] > log08 else -1 for k in range(K)]
+        for k in range(K):
+            tries[k].append((eps[k], dH[k]))
+        while any(live):
+            for k in range(K):
+                if live[k]:
+                    if len(tries[k]) > MAX_SEARCH:
+                        raise RuntimeError(f"the HMC step-size search of chain {k} did not end after {MAX_SEARCH} tries (last eps {eps[k]:g}, "
+                                           f"dH {dH[k]:g})")
+                    eps[k] = eps[k] * 2.0 ** direction[k]
+            dH = self._probe(eps, live)
+            for k in range(K):
+                if live[k]:
+                    tries[k].append((eps[k], dH[k]))
+                    live[k] = (1 if -dH[k] > log08 else -1) == direction[k]
+        self.set_active(None)
+        for k in range(K):
+            self.search_log[k].append(tries[k])
+        self.eps_host = eps
+        self._set_state(eps=eps, t=0.0, gbar=0.0, xbar=0.0, mu=[math.log(10 * e) for e in eps])
+
+    def run(self, x=None, labels=None, num_samples=0, warmup=0, rows=None, counts=None):
+        """`warmup` adapting transitions, then num_samples at fixed step sizes and lengths, of all chains.  run(x, labels, …): every chain on
+        that batch; run(rows=[K, B], counts=[K] or None, …): chain k on rows[k, :counts[k]] of the resident data (set_data).  Returns one
+        stack dict per chain (state_dict key -> [num_samples, ...], device tensors); eps_log / L_log / dH_log / accept_prob_log / accepted_log /
+        search_log are lists with one entry per chain, m_inv is [K, n_params]."""
+        num_samples, warmup = int(num_samples), int(warmup)
+        total, K = warmup + num_samples, self.K
+        if x is not None:
+            if rows is not None:
+                raise ValueError("run() takes a batch (x, labels) or rows into the resident data, not both")
+            self.set_data(x, labels)
+        self.log_t = torch.zeros(K, max(1, total), _hip.HMC_LOG, dtype=torch.float64, device=self.device)
+        self.samples_t = torch.zeros(K, max(1, num_samples), self.n_params, dtype=torch.float32, device=self.device)
+        self._bind()
+        self.stage(rows, counts)
+        Ls = [[] for _ in range(K)]
+
+        def note(L):
+            for k in range(K):
+                Ls[k].append(L[k])
+
+        if warmup > 0 and self.adapt_step_size:
+            self.find_reasonable_step_size()
+        for (a, b, kind) in windows(warmup):
+            mid = kind == "middle" and self.adapt_mass_matrix
+            for i in range(a, b):
+                last = i == b - 1
+                note(self.transition(i, None, self.adapt_step_size, last, (i - a + 1) if mid else 0))
+                if last and mid:
+                    _hip.check(self.k.lib.rbnn_hmc_lockstep_window_end(C.byref(self.net), C.byref(self.chain), b - a, self._st()),
+                               "rbnn_hmc_lockstep_window_end")
+                    self.launches += 1
+                if self.adapt_step_size:
+                    self.eps_host = [s["eps"] for s in self.read_state()]   # warmup's one read per transition: the K step sizes
+                    if last:
+                        self.find_reasonable_step_size()
+        self._set_steps(self.lengths())                                   # host -> device, before the sampling phase
+        self.sample(warmup, num_samples, note)
+        log = self.log_t[:, :total].cpu()                                 # the one read of the sampling phase
+        self.log = log
+        self.eps_log, self.dH_log, self.accept_prob_log = log[:, :, 0].tolist(), log[:, :, 1].tolist(), log[:, :, 2].tolist()
+        self.accepted_log = [[bool(v) for v in row] for row in log[:, :, 3].tolist()]
+        self.L_log = Ls
+        return [self.unflat(self.samples_t[k, :num_samples]) for k in range(K)]
+
+    def sample(self, first, num_samples, note=None):
+        """num_samples transitions first, first + 1, ... at the fixed step sizes and lengths; row i of every chain's stack = its position after
+        transition first + i.  No device->host synchronisation (the lengths are on the device since the end of warmup)."""
+        Ls = self.lengths()
+        for i in range(num_samples):
+            self.transition(first + i, Ls, False, False, 0, i)
+            if note is not None:
+                note(Ls)
+
+
+def split_r_hat(values):
+    """Split-R-hat (Gelman et al., BDA3 section 11.4) of `values` [K, n]: each chain is halved (the middle draw of an odd n is dropped), giving
+    m = 2K sequences of length h = n // 2; with W the mean of their variances and B = h var(their means),
+    R-hat = sqrt(((h - 1) / h W + B / h) / W).  Host only, fp64.  Constant sequences (W = 0): 1.0 if their means agree too, else inf.
+    The usual `values`: each chain's logged U_new over the sampling phase."""
+    v = torch.as_tensor(values, dtype=torch.float64)
+    if v.dim() != 2 or v.shape[1] < 4:
+        raise ValueError(f"split_r_hat needs [K, n] with n >= 4, not {tuple(v.shape)}")
+    h = v.shape[1] // 2
+    halves = torch.cat([v[:, :h], v[:, v.shape[1] - h:]], 0)
+    W = float(halves.var(dim=1, unbiased=True).mean())
+    Bh = float(halves.mean(dim=1).var(unbiased=True))                   # B / h
+    if W == 0.0:
+        return 1.0 if Bh == 0.0 else math.inf
+    return math.sqrt(((h - 1) / h * W + Bh) / W)

@@ -15,8 +15,9 @@ model_bnn.py:198-258, computed for the whole batch and all samples by the HIP ke
 Training: `train(train_loader, device, rel_path, filename)` runs the reference's SVI training (model_bnn.py:303-365) for fc / fc2 on the GPU
 (svi_train.SviTrainer: one weight draw, the training forward, the weight gradients and one Adam step per batch — csrc/rbnn_train.hip) and
 saves the param store.  conv SVI and CPU devices raise NotImplementedError: those posteriors are inputs here.  `train()` refuses an HMC net
-too and names `train_hmc(train_loader, device, rel_path, filename)`, which samples the chain of an fc / fc2 net on the GPU (hmc.HmcSampler,
-csrc/rbnn_hmc.hip) and writes the per-sample files `load()` reads.
+too and names `train_hmc(train_loader, device, rel_path, filename, num_chains=1)`, which samples the chain of an fc / fc2 net on the GPU
+(hmc.HmcSampler, csrc/rbnn_hmc.hip; num_chains = K > 1: K chains in lockstep, hmc.LockstepHmc, pooled and judged by their split-R-hat) and
+writes the per-sample files `load()` reads.
 """
 import os
 import random
@@ -82,6 +83,22 @@ def read_param_store(path):
         value = value.detach()
         out[name] = (value if c is constraints.real else transform_to(c)(value)).to(torch.float32)
     return out
+
+
+def lockstep_history(sampler, k, idx=None):
+    """Chain k's logs of a hmc.LockstepHmc run, in the layout of BNN.hmc_history."""
+    h = {"eps": sampler.eps_log[k], "L": sampler.L_log[k], "dH": sampler.dH_log[k], "accept_prob": sampler.accept_prob_log[k],
+         "accepted": sampler.accepted_log[k], "m_inv": sampler.m_inv[k].cpu(), "key": sampler.chain_keys[k]}
+    if idx is not None:
+        h["resampled"] = idx.cpu()
+    return h
+
+
+def lockstep_r_hat(sampler, warmup):
+    """Split-R-hat of the chains' potential (the logged U_new) over the sampling phase; nan with fewer than 4 samples or one chain."""
+    from .hmc import LOG_COLUMNS, split_r_hat
+    U = sampler.log[:, warmup:, LOG_COLUMNS.index("U_new")]
+    return split_r_hat(U) if U.shape[1] >= 4 else float("nan")
 
 
 class BNN(nn.Module):
@@ -383,7 +400,7 @@ class BNN(nn.Module):
             self.set_variational_params(loc, raw, device)   # drops the guide, slots and seeded draws of the previous parameters
         self.save(rel_path=rel_path, filename=filename)
 
-    def train_hmc(self, train_loader, device, rel_path=TESTS, filename=None):
+    def train_hmc(self, train_loader, device, rel_path=TESTS, filename=None, num_chains=1):
         """The hmc half of model_bnn.py:350-365 + _train_hmc (:260-301), fc / fc2 on the GPU: seed, the chain (hmc.HmcSampler with self.step_size,
         self.num_steps, self.warmup), the resampling of get_samples(n_samples), save().
 
@@ -392,21 +409,60 @@ class BNN(nn.Module):
         The earlier runs reach the result only through pyro's RNG stream, which is unpinned.  So the loader is iterated (its shuffle draws
         happen), the chain runs on the LAST batch only, and the stack is resampled with torch.randint(0, batch_samples, (n_samples,)) from the
         CPU generator.  A dataset smaller than one batch (num_batches = 0, where the reference divides by zero) counts as one batch.
-        self.hmc_history keeps the chain's logs."""
+        self.hmc_history keeps the chain's logs.
+
+        num_chains = K > 1: K chains in lockstep on the GPU (hmc.LockstepHmc; every launch covers all chains).  Chain 0 takes its start
+        position and key exactly where the single chain does (it IS the num_chains = 1 chain, bit for bit); chains 1..K-1 draw theirs
+        afterwards.  All run batch_samples samples on the last batch; the pooled stack is chain-major [K * batch_samples, ...]
+        (hmc_history["stack"]) and is resampled with torch.randint(0, K * batch_samples, (n_samples,)).  hmc_history's logs are chain 0's,
+        "chains" holds every chain's, "r_hat_U" the split-R-hat of the chains' potential over the sampling phase (hmc.split_r_hat)."""
         if self.inference != "hmc":
             raise ValueError(f"train_hmc() samples an HMC posterior; this net's inference is {self.inference!r} (use train())")
+        if int(num_chains) < 1:
+            raise ValueError(f"train_hmc() needs num_chains >= 1, not {num_chains}")
         if self.basenet.architecture not in ("fc", "fc2"):
             raise NotImplementedError(f"HMC covers fc and fc2, not {self.basenet.architecture!r} (conv needs conv weight gradients)")
         if torch.device(device).type != "cuda":
             raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-        from .hmc import HmcSampler, initial_position
+        from .hmc import HmcSampler, LockstepHmc
+        x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
+        b, K = self.basenet, int(num_chains)
+        if K == 1:
+            sampler = HmcSampler(b.architecture, b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, key,
+                                 batch_size=int(x_batch.shape[0]))
+            stack = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
+            idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
+            self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
+                                "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
+        else:
+            from .hmc import initial_position
+            from .svi_train import draw_key
+            shapes = [(k, tuple(v.shape)) for k, v in b.state_dict().items()]
+            q0s, keys = [q0], [key]
+            for _ in range(1, K):
+                q0s.append(initial_position(shapes))
+                keys.append(draw_key())
+            sampler = LockstepHmc(b.architecture, b.activation, b.input_shape, b.output_size, q0s, self.step_size, self.num_steps, device, keys,
+                                  batch_size=int(x_batch.shape[0]))
+            stacks = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
+            stack = {k: torch.cat([s[k] for s in stacks], 0) for k in stacks[0]}          # chain-major [K * batch_samples, ...]
+            idx = torch.randint(0, K * batch_samples, (self.n_samples,)).to(device)
+            self.hmc_history = lockstep_history(sampler, 0, idx)
+            self.hmc_history.update({"stack": stack, "chains": [lockstep_history(sampler, k) for k in range(K)],
+                                     "r_hat_U": lockstep_r_hat(sampler, self.warmup)})
+        self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
+        self.save(rel_path=rel_path, filename=filename)
+
+    def _hmc_prologue(self, train_loader, device):
+        """train_hmc up to the chain: the seeding, the pass over the loader, the start position and the key, in the order their draws leave
+        the CPU generator.  -> (x_batch, y_batch of the LAST batch, batch_samples, q0, key)."""
+        from .hmc import initial_position
         from .svi_train import draw_key
         self.device = device
         self.basenet.device = device
         random.seed(0)
         set_rng_seed(0)
         print("\n == HMC training ==")
-        b = self.basenet
         num_batches = int(len(train_loader.dataset) / train_loader.batch_size)
         batch_samples = int(self.n_samples / max(1, num_batches)) + 1
         print("\nn_batches=", num_batches, "\tbatch_samples =", batch_samples)
@@ -415,15 +471,8 @@ class BNN(nn.Module):
             pass
         if x_batch is None:
             raise ValueError("train_hmc() needs a loader with at least one batch")
-        q0 = initial_position([(k, tuple(v.shape)) for k, v in b.state_dict().items()])
-        sampler = HmcSampler(b.architecture, b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, draw_key(),
-                             batch_size=int(x_batch.shape[0]))
-        stack = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
-        idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
-        self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
-                            "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
-        self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
-        self.save(rel_path=rel_path, filename=filename)
+        q0 = initial_position([(k, tuple(v.shape)) for k, v in self.basenet.state_dict().items()])
+        return x_batch, y_batch, batch_samples, q0, draw_key()
 
     def evaluate(self, test_loader, device, n_samples=10, seeds_list=None):
         """model_bnn.py:367-391"""

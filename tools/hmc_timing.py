@@ -4,6 +4,11 @@ B = 5000, D = 784).  Both run L = 10 leapfrog steps at a fixed step size with un
 Each figure: median and min..max over REPS blocks of N transitions, timed with device events after a warm-up block.  One JSON line per shape.
 
     python tools/hmc_timing.py [--reps 7] [--n 20]
+
+--chains K: instead, K chains in lockstep (hmc.LockstepHmc: every launch covers all K) against K consecutive HmcSampler transitions in the
+same process, on half-moons fc2-32 and fc2-512 at B = 1024: chain-transitions per second of both and their ratio, one JSON line per shape.
+
+    python tools/hmc_timing.py --chains 8
 """
 import argparse
 import json
@@ -69,12 +74,51 @@ def timed(fn, reps, n):
     return {"median_ms": statistics.median(out), "min_ms": min(out), "max_ms": max(out)}
 
 
+CHAIN_SHAPES = [("fc2", 2, 32, 2, 1024), ("fc2", 2, 512, 2, 1024)]
+
+
+def chains_main(a):
+    """K chains in lockstep against K single chains one after the other: the same L, step size, batch and start positions on both sides."""
+    from robustbnns_amd.hmc import HmcSampler, LockstepHmc
+    dev, K = "cuda:0", a.chains
+    for arch, D, H, C, B in CHAIN_SHAPES:
+        g = torch.Generator().manual_seed(0)
+        q0s = [{k: 0.1 * torch.randn(*s, generator=g) for k, s in shapes_of(D, H, C).items()} for _ in range(K)]
+        x, lab = torch.rand(B, D, generator=g).to(dev), torch.randint(0, C, (B,), generator=g).to(dev)
+        singles = [HmcSampler(arch, "leaky", (1, D, 1), C, q0s[k], EPS, L, dev, 1 + k, adapt_step_size=False, batch_size=B) for k in range(K)]
+        for s in singles:
+            s.stage(x, lab)
+        ls = LockstepHmc(arch, "leaky", (1, D, 1), C, q0s, EPS, L, dev, list(range(1, 1 + K)), adapt_step_size=False, batch_size=B)
+        ls.set_data(x, lab)
+        ls.stage()
+        state = {"i": 0, "j": 0}
+
+        def serial_step():
+            for s in singles:
+                s.transition(state["i"], L)
+            state["i"] += 1
+
+        def lockstep_step():
+            ls.transition(state["j"], L)
+            state["j"] += 1
+
+        serial, lock = timed(serial_step, a.reps, a.n), timed(lockstep_step, a.reps, a.n)
+        same = all(torch.equal(ls.q_cur[k], singles[k].q_cur) for k in range(K))       # both sides ran the same number of transitions
+        tps = lambda t: 1e3 * K / t["median_ms"]
+        print(json.dumps({"shape": f"{arch} {D}->{H}->{H}->{C} B={B} L={L}", "chains": K, "serial": serial, "lockstep": lock,
+                          "serial_chain_transitions_per_s": tps(serial), "lockstep_chain_transitions_per_s": tps(lock),
+                          "ratio": serial["median_ms"] / lock["median_ms"], "chains_bit_identical": same}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--n", type=int, default=20)
+    ap.add_argument("--chains", type=int, default=0, help="K > 0: K chains in lockstep against K consecutive single chains")
     a = ap.parse_args()
     G.build()
+    if a.chains > 0:
+        return chains_main(a)
     from robustbnns_amd.hmc import HmcSampler
     dev = "cuda:0"
     for arch, D, H, C, B in SHAPES:
