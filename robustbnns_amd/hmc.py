@@ -241,7 +241,8 @@ class HmcSampler:
         return self.read_state()["dH"]
 
     def find_reasonable_step_size(self):
-        """pyro's search [recalled] from the current step size: one leapfrog step from fresh momentum, direction = +1 if -dH > log 0.8 else -1,
+        """pyro's search [recalled] from the current step size (run() calls it before the first transition and after every warmup window but
+        the last, whose dual-averaged exp(xbar) is the sampling phase's step size): one leapfrog step from fresh momentum, direction = +1 if -dH > log 0.8 else -1,
         eps *= 2^direction with new momentum each try until the direction flips; then dual averaging restarts with mu = log(10 eps)."""
         log08, tries = math.log(0.8), []
         eps = self.eps_host
@@ -283,7 +284,7 @@ class HmcSampler:
                     self.launches += 1
                 if self.adapt_step_size:
                     self.eps_host = self.read_state()["eps"]            # warmup's one read per transition: L follows the adapted step size
-                    if last:
+                    if last and b < warmup:                             # the last window's exp(xbar) is the sampling step size: no search
                         self.find_reasonable_step_size()
         self.sample(warmup, num_samples, Ls)
         log = self.log_t[:total].cpu()                                  # the one read of the sampling phase
@@ -599,7 +600,7 @@ class LockstepHmc:
                     self.launches += 1
                 if self.adapt_step_size:
                     self.eps_host = [s["eps"] for s in self.read_state()]   # warmup's one read per transition: the K step sizes
-                    if last:
+                    if last and b < warmup:                                # the last window's exp(xbar) is kept, as in HmcSampler.run
                         self.find_reasonable_step_size()
         self._set_steps(self.lengths())                                   # host -> device, before the sampling phase
         self.sample(warmup, num_samples, note)

@@ -25,8 +25,9 @@ def _need_gpu():
 
 
 # Case A: the sizes of test_hip_hmc.py's _short_run.  The keys are three for which the fp64 restatement (tests/hmc_restate.py, on the CPU)
-# takes [2, 4, 6, 2], [2, 4, 7, 2] and [2, 4, 5, 3] tries in its four step-size searches and ends warmup at different step sizes, so the
-# `active` and `steps` masks are exercised; the test asserts both on the single-chain GPU runs before it compares anything.
+# takes [2, 4, 6], [2, 4, 7] and [2, 4, 5] tries in its three step-size searches (before the first transition, after the start and the middle
+# window; none after the last) and L of 13 / 6 / 6, 5 / 2 / 28 and 3 / 60 / 6 at transitions 6, 10 and 16 of warmup, so the `active` and
+# `steps` masks are exercised; the test asserts both on the single-chain GPU runs before it compares anything.
 KEYS_A = (70, 73, 76)
 
 

@@ -104,6 +104,44 @@ def test_restatement_samples_a_standard_normal_when_the_likelihood_is_constant()
     assert abs(mean) <= 4 / n ** 0.5 and abs(var - 1) <= 4 * (2 / n) ** 0.5
 
 
+@pytest.mark.parametrize("arch", ["fc", "fc2"])
+@pytest.mark.parametrize("L", [1, 6, 10])
+def test_restatement_leapfrog_matches_the_harmonic_oscillator(arch, L):
+    """The one-class net of tests/hmc_exact_cases.py: dCE/dW = 0, so L leapfrog steps under a diagonal mass are the L-th power of a 2 x 2 matrix
+    per coordinate (numpy, nothing of the restatement's).  The fp64 restatement must equal it to 1e-12: ~60 operations of size <= 10 an element."""
+    import hmc_exact_cases as HX
+    c = HX.one_class_case(arch)
+    rs = HR.Restatement(arch, "tanh", c["q0"], c["x"], c["lab"], HX.EPS, L, key=1, adapt_step_size=False)
+    rs.m_inv = c["m_inv"].double()
+    assert float(rs.g.abs().max()) == 0.0 and rs.U == float(0.5 * (rs.q * rs.q).sum())
+    q1, r1, K1, P1 = HX.leapfrog_closed_form(rs.q.numpy(), c["r0"].numpy(), c["m_inv"].numpy(), HX.EPS, L)
+    q, r, g, U = rs.leapfrog(rs.q, c["r0"].double(), rs.g, L)
+    eq, er = float(np.abs(q.numpy() - q1).max()), float(np.abs(r.numpy() - r1).max())
+    print(f"[{arch} L {L}] |q - closed form| {eq:.1e}  |r - closed form| {er:.1e}  K' {abs(rs.kinetic(r) - K1):.1e}  U' {abs(U - P1):.1e}")
+    assert eq <= 1e-12 and er <= 1e-12 and float(g.abs().max()) == 0.0
+    assert abs(rs.kinetic(r) - K1) <= 1e-12 * K1 and abs(U - P1) <= 1e-12 * P1
+
+
+def test_restatement_warmup_ends_at_a_step_size_that_samples_the_known_posterior():
+    """The adaptation condition of tests/test_hip_hmc_exact.py on the fp64 restatement, 4 of its 16 chains: every chain's mean accept_prob over the
+    sampling phase in [0.7, 0.98], pooled mean q^2 within 0.05 of 1, m_inv positive and finite, and three searches (none after the last
+    window).  Measured here: 0.8894 ... 0.9270, mean q^2 0.9624; with the search after the last window as well the 16 chains ranged from
+    9.6e-09 to 0.968."""
+    import hmc_exact_cases as HX
+    A, c = HX.ADAPT, HX.one_class_case("fc")
+    acc, S = [], []
+    for q0, key in zip(HX.adapt_starts(4), A["keys"]):
+        rs = HR.Restatement("fc", "tanh", q0, c["x"], c["lab"], A["step_size"], A["num_steps"], key)
+        S.append(rs.run(A["samples"], A["warmup"]))
+        acc.append(float(np.mean([r["accept_prob"] for r in rs.log[A["warmup"]:]])))
+        assert len(rs.search_log) == 3 and bool(torch.isfinite(rs.m_inv).all()) and bool((rs.m_inv > 0).all())
+        assert rs.log[-1]["eps"] == rs.adapt_log[-1][0] == rs.eps                # sampling runs at the last window's exp(xbar)
+    q2 = float(torch.stack(S).square().mean())
+    print(f"accept_prob over the sampling phase {min(acc):.4f} ... {max(acc):.4f}  pooled mean q^2 {q2:.4f}")
+    assert all(A["accept"][0] <= a <= A["accept"][1] for a in acc), acc
+    assert abs(q2 - 1) <= A["q2"]
+
+
 def test_initial_position_is_uniform_within_the_radius():
     torch.manual_seed(1)
     a = hmc.initial_position(list(R.shapes_of("fc2", 2, 32, 2).items()))
