@@ -750,6 +750,57 @@ int rbnn_hmc_lockstep_commit(const rbnn_nn_train_net *net, const rbnn_hmc_lockst
 /* The single chain's window end on every active chain. */
 int rbnn_hmc_lockstep_window_end(const rbnn_nn_train_net *net, const rbnn_hmc_lockstep *chains, int32_t n_window, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K SVI guides of ONE net shape trained in LOCKSTEP (csrc/rbnn_svi_lockstep.hip; additive, ABI 10): the SVI step above for every guide in
+ * one set of launches, the guide is grid dimension y.  The net is an rbnn_nn_train_net: P = the drawn weights W [K, member_stride], grad =
+ * dCE/dW [K, member_stride], n_members = K <= 65535 / RBNN_SVI_MULTI_ACC_SAMPLES (m and v are not read).  Every per-parameter buffer of the
+ * guide block is [K, member_stride] in the layout of rbnn_svi_train_net.  Guide k's batch is rows[k, 0..counts[k]) of the resident data
+ * X [n_rows, ldx] (indices clamped into [0, n_rows)); the entries of rows behind counts[k] must still be valid rows (their activations are
+ * computed and multiplied by exact zeros).  counts[k] == 0: the guide has finished, every kernel skips it and nothing of its state is written.
+ * One step on one stream:  draw -> gradient -> adam_step -> [accuracy] -> finalize.  No atomics, no sum across guides, a guide's block and
+ * tile plan does not depend on K: guide k is bit-identical to the single-guide entry points running it alone on the same batches.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_SVI_MULTI_ACC_SAMPLES 10
+
+typedef struct rbnn_svi_multi {
+    float *loc, *raw, *sigma, *m_loc, *v_loc, *m_raw, *v_raw;      /* [K, member_stride], each as in rbnn_svi_train_net     */
+    float *kl_part;                /* [K, part_stride] KL partial sums of the update (part_stride >= n_partials of rbnn_svi_train_sizes) */
+    double *stats;                 /* [K, 3] step loss, running sum of the epoch's losses, running correct predictions */
+    const uint64_t *keys;          /* [K] on the device: guide k's key                                              */
+    int64_t part_stride;
+} rbnn_svi_multi;
+
+typedef struct rbnn_svi_multi_acc {     /* caller-owned buffers of the accuracy forward, S = RBNN_SVI_MULTI_ACC_SAMPLES         */
+    float *W;                      /* [K * S, member_stride] the drawn weight sets, guide-major                     */
+    float *hid1, *hid2;            /* [K * S, B, H] hidden activations (hid2: fc2 only)                             */
+    float *dact;                   /* [K * S, B, H] scratch                                                         */
+    float *Psum;                   /* [K, B, 16] sum over the S samples of the softmax probabilities                */
+} rbnn_svi_multi_acc;
+
+/* net->P[k] = loc[k] + sigma[k] * eps(keys[k], draw_id): exactly what rbnn_svi_train_draw writes for (keys[k], draw_id).  One launch. */
+int rbnn_svi_multi_draw(const rbnn_nn_train_net *net, const rbnn_svi_multi *guides, const int32_t *counts, uint32_t draw_id,
+                           void *stream);
+/* The training forward (summed CE: no 1 / B) and the weight gradients of every guide at net->P: fc 2 + 1 launches, fc2 4 + 1.  ws is packed
+ * [K, n_points, .]; for b >= counts[k] ce, dZ, dA and correct are 0.  rows and counts are required. */
+int rbnn_svi_multi_gradient(const rbnn_nn_train_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *labels,
+                               const int32_t *rows, const int32_t *counts, int32_t n_points, const rbnn_nn_train_ws *ws, void *stream);
+/* rbnn_svi_adam_step on every guide, each with its own key and its own learning rate lr[k] (device, double [K]): step_size[k] =
+ * (float)(lr[k] / (1 - beta1^step)), an IEEE double division of the host's 1 - beta1^step, so bit for bit the single guide's.  One launch. */
+int rbnn_svi_multi_adam_step(const rbnn_nn_train_net *net, const rbnn_svi_multi *guides, const int32_t *counts, uint32_t draw_id,
+                                int64_t step, const double *lr, double beta1, double beta2, double adam_eps, void *stream);
+/* The accuracy forward of every guide on its own batch: S weight sets from the live loc / sigma with rbnn_svi_draw's generator at
+ * (keys[k] ^ key_xor, draw_id, sample s) into acc->W, the hidden layers of the K * S nets, and Psum[k, b, :] = sum_s softmax(z_s).
+ * fc 3 launches, fc2 4, whatever K. */
+int rbnn_svi_multi_accuracy(const rbnn_nn_train_net *net, const rbnn_svi_multi *guides, const float *X, int32_t ldx, int32_t n_rows,
+                               const int32_t *rows, const int32_t *counts, int32_t n_points, uint64_t key_xor, uint32_t draw_id,
+                               const rbnn_svi_multi_acc *acc, void *stream);
+/* One block per guide, fixed order, fp64: rbnn_svi_train_finalize's sums over the guide's counts[k] points of ce [K, n_points] and Psum
+ * [K, n_points, 16] (nullable) into stats[k].  epoch_slot (device int32 [K], nullable): a guide with epoch_slot[k] in [0, log_rows) ends an
+ * epoch with this step: epoch_log[k, slot] = (sum of the epoch's step losses, correct predictions) and both running sums restart at 0. */
+int rbnn_svi_multi_finalize(const rbnn_nn_train_net *net, const rbnn_svi_multi *guides, const float *ce, const float *Psum,
+                               const int32_t *labels, int32_t n_rows, const int32_t *rows, const int32_t *counts, int32_t n_points,
+                               const int32_t *epoch_slot, double *epoch_log, int32_t log_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

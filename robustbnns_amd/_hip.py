@@ -113,6 +113,19 @@ class HmcLockstep(C.Structure):
                [(k, C.c_int64) for k in ("chain_stride", "qpart_stride", "epart_stride", "log_rows", "sample_rows")]
 
 
+class SviLockstep(C.Structure):
+    _fields_ = [(k, _fp) for k in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "kl_part", "stats", "keys")] + \
+               [("part_stride", C.c_int64)]
+
+
+SVI_LOCKSTEP_ACC_KEYS = ("W", "hid1", "hid2", "dact", "Psum")
+SVI_LOCKSTEP_ACC_SAMPLES = 10
+
+
+class SviLockstepAcc(C.Structure):
+    _fields_ = [(k, _fp) for k in SVI_LOCKSTEP_ACC_KEYS]
+
+
 # rbnn_hmc.hip: the state block's indices, the log's columns, the update phases and the decide modes (include/robustbnns_hip.h)
 HMC_STATE, HMC_LOG = 16, 8
 HMC_ST = {"eps": 0, "U": 1, "t": 2, "gbar": 3, "xbar": 4, "mu": 5, "dH": 6, "accept_prob": 7, "accepted": 8, "u": 9, "U_new": 10, "K_new": 11,
@@ -229,6 +242,13 @@ SIGNATURES = {
     "rbnn_hmc_lockstep_decide": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _fp, _fp, _i32, _i64, _i32, _i32, _i32, _fp]),
     "rbnn_hmc_lockstep_commit": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _i32, _i64, _fp]),
     "rbnn_hmc_lockstep_window_end": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _fp]),
+    "rbnn_svi_multi_draw": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, C.c_uint32, _fp]),
+    "rbnn_svi_multi_gradient": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _fp, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
+    "rbnn_svi_multi_adam_step": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, C.c_uint32, _i64, _fp, C.c_double, C.c_double,
+                                           C.c_double, _fp]),
+    "rbnn_svi_multi_accuracy": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, _i32, _i32, _fp, _fp, _i32, C.c_uint64, C.c_uint32,
+                                          C.POINTER(SviLockstepAcc), _fp]),
+    "rbnn_svi_multi_finalize": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, _fp, _fp, _i32, _fp, _fp, _i32, _fp, _fp, _i32, _fp]),
 }
 
 _lib = None

@@ -11,9 +11,11 @@
 // eps is the draw's own generator (rbnn_common.hpp: Rng, the draw_quad layout — quad index r * ceil(cols/4) + c/4, counter (quad, tensor id,
 // sample 0, draw id)), so the update regenerates it instead of storing it, and the weights equal what rbnn_svi_draw writes for the same
 // (key, draw id) at sample 0.  No atomics anywhere: every sum has one fixed order, two runs are bit-identical.
-// The parameter layout, the activations, Adam and the block reductions are rbnn_train_core.hpp; the forward / backward GEMM and head kernels
+// The parameter layout, the activations, Adam and the block reductions are rbnn_train_core.hpp; the Adam + KL kernel and the
+// step's sums are rbnn_svi_step.hpp (shared with the guides in lockstep, rbnn_svi_lockstep.hip); the forward / backward GEMM and head kernels
 // are rbnn_train_gemm.hpp, instantiated here for a single net (LOCKSTEP = false; inv_S = 1: the CE is summed).
 #include "rbnn_train_gemm.hpp"
+#include "rbnn_svi_step.hpp"
 
 namespace {
 
@@ -34,56 +36,7 @@ __global__ void __launch_bounds__(ELT_THREADS) train_draw_kernel(const Layout L,
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam, single-tensor, defaults but lr) on loc and raw scale, one thread per quad of a tensor:
-//   g_loc = dCE/dw + loc,   g_raw = (dCE/dw eps + sigma - 1/sigma) sigmoid(raw)      (TraceMeanField's analytic KL against N(0, 1))
-//   m = m + (1 - b1)(g - m),  v = b2 v + (1 - b2) g^2,  p += (-step_size m) / (sqrt(v) / bc2_sqrt + eps_adam),  sigma = softplus(raw)
-// and the KL of the PRE-update parameters, -log sigma + (sigma^2 + loc^2) / 2 - 1/2, summed per block in a fixed tree order.
-// ---------------------------------------------------------------------------------------------------
-struct AdamArgs {
-    Layout L;
-    float *loc, *raw, *sigma, *m_loc, *v_loc, *m_raw, *v_raw;
-    const float* grad;
-    float* kl_part;
-    unsigned long long key;
-    uint32_t draw_id;
-    AdamScalars s;
-};
-
-__global__ void __launch_bounds__(ELT_THREADS) adam_kernel(const AdamArgs a) {
-    __shared__ float red[ELT_THREADS];
-    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    float kl = 0.f;
-    if (q < a.L.n_quads) {
-        const Seg sg = a.L.s[seg_of(a.L, q)];
-        const int Q = (sg.cols + 3) >> 2;
-        const long long ql = q - sg.first_quad;
-        const int r = (int)(ql / Q), c4 = (int)(ql % Q);
-        const Rng rng = {(uint32_t)a.key, (uint32_t)(a.key >> 32), 0u, a.draw_id};
-        float eps[4];
-        rng.quad(sg.tensor_id, (uint32_t)(r * Q + c4), eps);
-        const long long base = sg.off + (long long)r * sg.cols + 4 * c4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (4 * c4 + j >= sg.cols) continue;
-            const long long e = base + j;
-            float mu = a.loc[e], rw = a.raw[e];
-            const float sd = a.sigma[e], dw = a.grad[e];
-            kl += (-logf(sd) + 0.5f * (sd * sd + mu * mu)) - 0.5f;
-            const float gl = dw + mu;
-            const float sig = 1.f / (1.f + expf(-rw));
-            const float gr = (fmaf(dw, eps[j], sd) - 1.f / sd) * sig;
-            float ml = a.m_loc[e], vl = a.v_loc[e], mr = a.m_raw[e], vr = a.v_raw[e];
-            adam_one(mu, ml, vl, gl, a.s);
-            adam_one(rw, mr, vr, gr, a.s);
-            a.loc[e] = mu; a.raw[e] = rw; a.sigma[e] = softplus_f(rw);
-            a.m_loc[e] = ml; a.v_loc[e] = vl; a.m_raw[e] = mr; a.v_raw[e] = vr;
-        }
-    }
-    block_sum_to(kl, red, a.kl_part);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// One block: stats[0] = CE + KL of the step, stats[1] += it, stats[2] += #(argmax Psum == label).  Fixed-order sums in fp64.
+// One block: stats[0] = CE + KL of the step, stats[1] += it, stats[2] += #(argmax Psum == label).  Fixed-order sums in fp64 (svi_step_sums).
 // ---------------------------------------------------------------------------------------------------
 struct FinalArgs {
     const float *kl_part, *ce, *Psum;
@@ -95,21 +48,8 @@ struct FinalArgs {
 __global__ void __launch_bounds__(256) finalize_kernel(const FinalArgs a) {
     __shared__ double red[256];
     __shared__ double cnt[256];
-    const int t = threadIdx.x;
-    double s = 0.0, k = 0.0;
-    for (int i = t; i < a.n_part; i += 256) s += (double)a.kl_part[i];
-    for (int i = t; i < a.B; i += 256) {
-        s += (double)a.ce[i];
-        if (a.Psum) {
-            const float* row = a.Psum + (long long)i * a.ldp;
-            int best = 0;
-            for (int c = 1; c < a.C; ++c) if (row[c] > row[best]) best = c;      // the first maximum, as torch.argmax
-            k += (best == a.labels[i]) ? 1.0 : 0.0;
-        }
-    }
-    red[t] = s; cnt[t] = k;
-    block_tree64(red, cnt);
-    if (t == 0) {
+    svi_step_sums<false>(a.kl_part, a.n_part, a.ce, a.B, a.Psum, a.ldp, a.C, a.labels, nullptr, 0, red, cnt);
+    if (threadIdx.x == 0) {
         a.stats[0] = red[0];
         a.stats[1] += red[0];
         a.stats[2] += cnt[0];
@@ -208,7 +148,7 @@ int rbnn_svi_adam_step(const rbnn_svi_train_net* net, uint64_t key, uint32_t dra
     a.loc = net->loc; a.raw = net->raw; a.sigma = net->sigma; a.m_loc = net->m_loc; a.v_loc = net->v_loc; a.m_raw = net->m_raw; a.v_raw = net->v_raw;
     a.grad = net->grad; a.kl_part = kl_partials; a.key = key; a.draw_id = draw_id;
     a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

@@ -10,7 +10,7 @@ so the caller passes the test tensors (`x_test [N,1,2,1]`, `y_test [N,2]` one-ho
 
 `lockstep_train` is the counterpart of the reference's parallel_train (:52-59: 10 joblib processes, one model each): the HMC models of the
 grid that differ only in their training-set size run as chains of ONE lockstep sampler (hmc.LockstepHmc: every kernel launch covers all of
-them), and what it saves equals serial_train's bit for bit.
+them), and what it saves equals serial_train's bit for bit; the SVI models of one net shape run as members of ONE svi_train.LockstepSvi.
 """
 import itertools
 
@@ -80,13 +80,26 @@ def lockstep_train(hidden_size, activation, architecture, inference, epochs, lr,
     net shape, warmup and sample count and differ in their data, which are rows / counts into the resident x_train.  Every train_hmc reseeds
     with 0 and the moons loader does not shuffle, so each chain gets the start position and key it has in serial_train; before a chain's
     resample indices are drawn, the CPU generator is put back to the state it had after that chain's key was drawn.  Returns {bnn.name: bnn};
-    names and saved tensors equal serial_train's.  svi combinations, and a ready train_loader, go through _train one by one."""
+    names and saved tensors equal serial_train's.  The svi models that share (hidden, activation, architecture) form a group too: one
+    svi_train.LockstepSvi through model_bnn.train_svi_lockstep, whatever their epochs, lr and n_inputs; saved parameters and epoch losses
+    equal serial_train's, the epoch accuracies up to marginal points.  A ready train_loader goes through _train one by one."""
     from .hmc import LockstepHmc
-    from .model_bnn import lockstep_history
+    from .model_bnn import lockstep_history, train_svi_lockstep
     combos = _combinations(hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup, n_inputs, posterior_samples)
-    out, groups = {}, {}
+    out, groups, svi_groups = {}, {}, {}
     for init in combos:
         h, act, arch, inf, ep, lr_, ns, wu, ninp, _ = init
+        if inf == "svi" and train_loader is None:
+            if arch not in ("fc", "fc2"):
+                raise NotImplementedError(f"grid training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+            if torch.device(device).type != "cuda":
+                raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+            if x_train is None or y_train is None:
+                raise ValueError("lockstep_train needs x_train / y_train or a train_loader: dataset loading is out of scope")
+            # one member per (epochs, lr, n_samples, warmup, n_inputs) of a net shape, in the grid's order: posterior_samples repeats the model
+            svi_groups.setdefault((h, act, arch), {}).setdefault((ep, lr_, ns, wu, ninp), None)
+            out[MoonsBNN(h, act, arch, inf, ep, lr_, ns, wu, ninp, tuple(x_train[0].shape), int(y_train.shape[-1])).name] = None
+            continue
         if inf != "hmc" or train_loader is not None:
             bnn = _train(*init, rel_path, device, x_train=x_train, y_train=y_train, train_loader=train_loader)
             out[bnn.name] = bnn
@@ -100,6 +113,12 @@ def lockstep_train(hidden_size, activation, architecture, inference, epochs, lr,
         members = groups.setdefault((h, act, arch, ep, lr_, ns, wu), {})
         members.setdefault(ninp, None)                                   # one chain per training-set size, in the grid's order
         out[MoonsBNN(h, act, arch, inf, ep, lr_, ns, wu, ninp, tuple(x_train[0].shape), int(y_train.shape[-1])).name] = None
+    for (h, act, arch), members in svi_groups.items():
+        nets = [MoonsBNN(h, act, arch, "svi", ep, lr_, ns, wu, ninp, tuple(x_train[0].shape), int(y_train.shape[-1]))
+                for (ep, lr_, ns, wu, ninp) in members]
+        train_svi_lockstep(nets, x_train, y_train, [m[4] for m in members], device, rel_path=rel_path, batch_size=64)
+        for bnn in nets:
+            out[bnn.name] = bnn
     labels = None if y_train is None else y_train.argmax(-1)
     for (h, act, arch, ep, lr_, ns, wu), members in groups.items():
         chains = {}                                                      # batch_samples -> [(bnn, first row, count, q0, key, generator state)]

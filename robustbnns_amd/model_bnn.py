@@ -101,6 +101,75 @@ def lockstep_r_hat(sampler, warmup):
     return split_r_hat(U) if U.shape[1] >= 4 else float("nan")
 
 
+def svi_lockstep_prologue(net):
+    """What BNN.train draws from the host generators before its first step, in its order: the seeding, the base seed a DataLoader's iterator
+    takes from the CPU generator when the first epoch's loop creates it, the guide's initial parameters (unless the net holds some) and the
+    key.  -> (loc, raw, key)."""
+    from torch.utils.data import DataLoader
+    from .svi_train import draw_key, initial_params
+    random.seed(0)
+    set_rng_seed(0)
+    iter(DataLoader([0], batch_size=1))
+    if net.svi_loc is None:
+        loc, raw = initial_params([(k, tuple(v.shape)) for k, v in net.basenet.state_dict().items()])
+    else:
+        loc, raw = net.svi_loc, net.svi_scale
+    return loc, raw, draw_key()
+
+
+def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS, batch_size=64):
+    """BNN.train for several SVI nets of ONE net shape at once (svi_train.LockstepSvi: every kernel launch covers all of them).  The nets may
+    differ in epochs, lr and training-set size: member k trains on x_train[:n_inputs[k]] in order, unshuffled, in batches of batch_size (what
+    grid_search_halfMoons.moons_loader yields).  Each member takes its init and key exactly as BNN.train would, prints its epoch lines, and gets
+    training_history, set_variational_params and save(): parameters and epoch losses equal BNN.train's bit for bit; the epoch accuracies may
+    differ at points whose two largest mean probabilities lie within the forward kernels' error of each other (another GEMM tile plan).
+    Shuffled or arbitrary loaders stay with BNN.train."""
+    nets = list(nets)
+    if not nets or len(n_inputs) != len(nets):
+        raise ValueError(f"train_svi_lockstep needs one n_inputs per net, not {len(n_inputs)} for {len(nets)} nets")
+    for net in nets:
+        if net.inference != "svi":
+            raise NotImplementedError("train() runs SVI only: sample an HMC posterior (fc / fc2) with BNN.train_hmc(train_loader, device), "
+                                      "or run it with the reference and load the chain here")
+        if net.basenet.architecture not in ("fc", "fc2"):
+            raise NotImplementedError(f"SVI training covers fc and fc2, not {net.basenet.architecture!r} (conv needs conv weight gradients)")
+    if torch.device(device).type != "cuda":
+        raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+    b0 = nets[0].basenet
+    shape_of = lambda b: (b.architecture, b.activation, tuple(b.input_shape), int(b.output_size), int(b.hidden_size))
+    for net in nets[1:]:
+        if shape_of(net.basenet) != shape_of(b0):
+            raise ValueError(f"lockstep SVI nets share one net shape: {shape_of(net.basenet)} is not {shape_of(b0)}")
+    n_inputs = [min(int(n), int(x_train.shape[0])) for n in n_inputs]
+    if min(n_inputs) < 1:
+        raise ValueError("every member needs at least one training point")
+    from .svi_train import LockstepSvi
+    locs, raws, keys = [], [], []
+    for net in nets:
+        net.device = device
+        net.basenet.device = device
+        loc, raw, key = svi_lockstep_prologue(net)
+        locs.append(loc); raws.append(raw); keys.append(key)
+    trainer = LockstepSvi(b0.architecture, b0.activation, b0.input_shape, b0.output_size, locs, raws, [net.lr for net in nets], device, keys,
+                          batch_size=int(batch_size))
+    trainer.set_data(x_train, y_train.argmax(-1))
+    trainer.run(LockstepSvi.schedule(n_inputs, [net.epochs for net in nets], int(batch_size)))
+    totals = trainer.epoch_totals()
+    for k, net in enumerate(nets):
+        print("\n == SVI training ==")
+        n, loss_list, accuracy_list = n_inputs[k], [], []
+        for epoch in range(net.epochs):
+            loss, correct = totals[k][epoch]
+            print(f"\n[Epoch {epoch + 1}]\t loss: {loss / n:.2f} \t accuracy: {100 * correct / n:.2f}", end="\t")
+            loss_list.append(loss)
+            accuracy_list.append(100 * correct / n)
+        net.training_history = {"loss": loss_list, "accuracy": accuracy_list}
+        loc, raw = trainer.params(k)
+        net.set_variational_params(loc, raw, device)
+        net.save(rel_path=rel_path, filename=None)
+    return trainer
+
+
 class BNN(nn.Module):
 
     def __init__(self, dataset_name, hidden_size, activation, architecture, inference, epochs, lr, n_samples, warmup,

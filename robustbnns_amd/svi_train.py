@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from . import _hip
 from .flat_params import flatten, train_workspace, unflat, ws_struct
-from .posterior import LAYER_KEYS, StackedPosterior, SviGuide, round_up
+from .posterior import LAYER_KEYS, StackedPosterior, SviGuide, padded_hidden, round_up
 
 BETAS = (0.9, 0.999)                    # torch.optim.Adam defaults, what pyro.optim.Adam({"lr": lr}) wraps
 ADAM_EPS = 1e-8
@@ -49,6 +49,15 @@ def initial_params(shapes):
 def draw_key():
     """64 bits from torch's CPU generator: the Philox key of one train() call's draws (host arithmetic only)."""
     return int(torch.randint(-(2 ** 63), 2 ** 63 - 1, (1,), dtype=torch.int64).item()) & 0xFFFFFFFFFFFFFFFF
+
+
+def accuracy_draw_covered(kernels, arch, in_features, hidden, n_classes):
+    """rbnn_svi_draw_supported for the accuracy stack of a guide of this shape, padded as StackedPosterior pads it (the predicate reads the
+    descriptor's sizes only): what SviTrainer and LockstepSvi both refuse by."""
+    d = _hip.Posterior()
+    d.arch, d.in_features, d.in_stride = _hip.ARCHS[arch], int(in_features), round_up(int(in_features), 16)
+    d.hidden, d.n_classes = padded_hidden(int(hidden)), int(n_classes)
+    return bool(kernels.lib.rbnn_svi_draw_supported(C.byref(d), 0))
 
 
 class _LiveGuide:
@@ -106,7 +115,7 @@ class SviTrainer:
         self.guide.loc["W1"] = self.guide.loc["W1"].reshape(self.H, self.D)
         self.guide.sigma["W1"] = self.guide.sigma["W1"].reshape(self.H, self.D)
         self.acc_post = StackedPosterior.for_guide(self.guide, activation, self.input_shape, self.C, ACC_SAMPLES)
-        if not self.k.svi_draw_supported(self.acc_post, False):
+        if not accuracy_draw_covered(self.k, arch, self.D, self.H, self.C):
             raise NotImplementedError(f"{arch} hidden {self.H}, {self.C} classes: outside what rbnn_svi_draw covers (the accuracy forward's draw)")
         # rbnn_fc_forward (the accuracy forward) takes a padded hidden size of 32, 64 or k * 128 only; the training kernels take any.  A trainer
         # of another size (96, 160, ...) computes gradients and steps without the accuracy; step(accuracy=True) refuses it up front (BNN's hidden sizes, powers of two >= 16, are all covered)
@@ -183,3 +192,198 @@ class SviTrainer:
     def params(self):
         """(loc, raw scale) as dicts state_dict key -> fresh device tensor."""
         return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
+
+
+class LockstepSvi:
+    """K SVI guides of ONE net shape (arch, activation, input shape, hidden size, classes) trained in lockstep: every launch of a step covers
+    all K guides (csrc/rbnn_svi_lockstep.hip; the guide is grid dimension y).  Guide k has its own parameters, key, learning rate and batches —
+    rows[k, :counts[k]] of the resident data (set_data) — and is bit-identical to an SviTrainer stepped alone on the same batches, except for the
+    accuracy forward, whose logits come from the training GEMM's tile plan (Psum within the 1e-5 forward bar of SviTrainer's, the drawn weights
+    bit-equal).  A guide with counts[k] == 0 has finished: no kernel reads or writes it.
+
+    Launches per step, whatever K: draw 1, training forward 2 (fc) / 4 (fc2), weight gradients 1, Adam + KL 1, finalize 1 = 6 / 8, plus the
+    accuracy forward's 3 / 4 (draw of the K x 10 weight sets, the hidden layers, softmax + sum over the samples); run() adds two torch
+    launches that write the step's rows from the schedule (an add and a minimum).  No device->host synchronisation: the schedule (counts, first
+    rows, epoch ends) is uploaded once before the first step, the epoch sums are written to a device log and read once after the last."""
+
+    def __init__(self, arch, activation, input_shape, n_classes, locs, raws, lrs, device, keys, batch_size=64):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        if arch not in LAYER_KEYS:
+            raise NotImplementedError(f"SVI training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+        K = len(locs)
+        if K < 1:
+            raise ValueError("LockstepSvi needs at least one guide")
+        if len(raws) != K or len(keys) != K:
+            raise ValueError(f"{K} guides need one raw-scale dict and one key per guide, not {len(raws)} and {len(keys)}")
+        lrs = [float(v) for v in lrs] if isinstance(lrs, (list, tuple)) else [float(lrs)] * K
+        if len(lrs) != K:
+            raise ValueError(f"{len(lrs)} learning rates for {K} guides")
+        if K * ACC_SAMPLES > 65535:
+            raise ValueError(f"{K} guides x {ACC_SAMPLES} accuracy samples exceed the 65535 nets of one launch")
+        self.state_keys = state_keys(arch)
+        self.shapes = {k: tuple(locs[0][k].shape) for k in self.state_keys}
+        for i in range(K):
+            for d in (locs[i], raws[i]):
+                if {k: tuple(d[k].shape) for k in self.state_keys} != self.shapes:
+                    raise ValueError(f"guide {i} has another net shape than guide 0: lockstep guides share one (arch, hidden, classes, input)")
+        self.k = _hip.HipKernels()
+        self.K, self.arch, self.activation, self.device = K, arch, activation, dev
+        self.input_shape = tuple(int(v) for v in input_shape)
+        self.D = int(np.prod(self.input_shape))
+        self.H, self.C = int(self.shapes[self.state_keys[1]][0]), int(n_classes)
+        one = _hip.SviTrainNet()
+        one.arch, one.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
+        one.in_features, one.hidden, one.n_classes = self.D, self.H, self.C
+        n_part = C.c_int64(0)
+        n = int(self.k.lib.rbnn_svi_train_sizes(C.byref(one), C.byref(n_part)))
+        _hip.check(min(n, 0), "rbnn_svi_train_sizes")
+        self.n_params, self.n_partials = n, int(n_part.value)
+        # what SviTrainer refuses, refused the same way: the sizes its accuracy stack (rbnn_svi_draw) and accuracy forward (rbnn_fc_forward) cover
+        Hp = padded_hidden(self.H)
+        if not accuracy_draw_covered(self.k, arch, self.D, self.H, self.C):
+            raise NotImplementedError(f"{arch} hidden {self.H}, {self.C} classes: outside what rbnn_svi_draw covers (the accuracy forward's draw)")
+        self.accuracy_supported = Hp in (32, 64) or Hp % 128 == 0
+        self.loc = torch.stack([flatten(d, self.state_keys) for d in locs]).to(dev)
+        self.device = dev = self.loc.device                  # "cuda" names the current card: step() compares against where the buffers are
+        self.raw = torch.stack([flatten(d, self.state_keys) for d in raws]).to(dev)
+        assert tuple(self.loc.shape) == (K, n), (tuple(self.loc.shape), K, n)
+        self.sigma = F.softplus(self.raw)
+        z = lambda m=n: torch.zeros(K, m, dtype=torch.float32, device=dev)
+        self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(), z(), z(), z(), z(), z()
+        self.kl_part = z(self.n_partials)
+        self.stats = torch.zeros(K, 3, dtype=torch.float64, device=dev)
+        self.keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
+        self.keys_t = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in self.keys], dtype=torch.int64).to(dev)
+        self.lrs = lrs
+        self.lr_t = torch.tensor(lrs, dtype=torch.float64).to(dev)
+        self.t = 0
+        net = _hip.NnTrainNet()
+        net.arch, net.activation = one.arch, one.activation
+        net.in_features, net.hidden, net.n_classes, net.n_members = self.D, self.H, self.C, K
+        net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), n
+        self.net = net
+        g = _hip.SviLockstep()
+        for name in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "kl_part", "stats"):
+            setattr(g, name, getattr(self, name).data_ptr())
+        g.keys, g.part_stride = self.keys_t.data_ptr(), self.n_partials
+        self.guides = g
+        self.X = self.labels = None
+        self.epoch_log = None
+        self.B = int(batch_size)
+        if self.B < 1:
+            raise ValueError(f"batch_size must be at least 1, not {batch_size}")
+        S = ACC_SAMPLES
+        self.ws_t = train_workspace(arch, K * self.B, self.H, dev)
+        self.ws_t["correct"] = torch.zeros(K * self.B, dtype=torch.int32, device=dev)
+        self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
+        e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.acc_t = {"W": e(K * S, n), "hid1": e(K * S * self.B, self.H), "dact": e(K * S * self.B, self.H), "Psum": e(K, self.B, _hip.CPAD)}
+        if arch == "fc2":
+            self.acc_t["hid2"] = e(K * S * self.B, self.H)
+        self.acc = ws_struct(_hip.SviLockstepAcc, _hip.SVI_LOCKSTEP_ACC_KEYS, self.acc_t)
+        self.Psum = self.acc_t["Psum"]
+        self.rows_t = torch.zeros(K, self.B, dtype=torch.int32, device=dev)
+        self._arange = torch.arange(self.B, dtype=torch.int32, device=dev).unsqueeze(0)
+        self.launches = 0
+        self.fwd_launches = 2 if arch == "fc" else 4
+
+    def unflat(self, buf):
+        return unflat(buf, self.state_keys, self.shapes)
+
+    def set_data(self, x, labels):
+        """The resident data the guides' batches are gathered from: x [n_rows, ...], labels int [n_rows]."""
+        n = int(x.shape[0])
+        self.X = x.reshape(n, -1).to(self.device, torch.float32).contiguous()
+        self.labels = labels.reshape(n).to(self.device, torch.int32).contiguous()
+        if self.X.shape[1] != self.D:
+            raise ValueError(f"the data have {self.X.shape[1]} features, the nets {self.D}")
+
+    def step(self, rows, counts, accuracy=True, epoch_slot=None):
+        """One SVI step of every guide with counts[k] > 0 on rows[k, :counts[k]] of the resident data.  rows: int32 device tensor [K, batch_size]
+        whose entries behind counts[k] are valid rows too; counts, epoch_slot: int32 device tensors [K] (epoch_slot[k] >= 0: guide k's epoch ends
+        with this step, its sums go to row epoch_slot[k] of self.epoch_log).  All active guides are at the same step number self.t.  No
+        device->host synchronisation."""
+        if accuracy and not self.accuracy_supported:          # before anything is launched: no half-applied step
+            raise NotImplementedError(f"hidden {self.H}: outside what rbnn_fc_forward covers (32, 64 or a multiple of 128): no accuracy forward")
+        if self.X is None:
+            raise ValueError("set_data(x, labels) first")
+        if tuple(rows.shape) != (self.K, self.B) or rows.dtype != torch.int32 or not rows.is_contiguous() or rows.device != self.device:
+            raise ValueError(f"rows must be a contiguous int32 [{self.K}, {self.B}] tensor on {self.device}")
+        if tuple(counts.shape) != (self.K,) or counts.dtype != torch.int32 or counts.device != self.device:
+            raise ValueError(f"counts must be an int32 [{self.K}] tensor on {self.device}")
+        if epoch_slot is not None and self.epoch_log is None:
+            raise ValueError("epoch_slot needs self.epoch_log (begin_log(n_epochs))")
+        lib, st = self.k.lib, _hip.stream_of(self.W)
+        net, g, n_rows = C.byref(self.net), C.byref(self.guides), int(self.X.shape[0])
+        draw_id = C.c_uint32(self.t & 0xFFFFFFFF)
+        _hip.check(lib.rbnn_svi_multi_draw(net, g, _hip.ptr(counts), draw_id, st), "rbnn_svi_multi_draw")
+        _hip.check(lib.rbnn_svi_multi_gradient(net, _hip.ptr(self.X), self.D, n_rows, _hip.ptr(self.labels), _hip.ptr(rows), _hip.ptr(counts), self.B,
+                                               C.byref(self.ws), st), "rbnn_svi_multi_gradient")
+        _hip.check(lib.rbnn_svi_multi_adam_step(net, g, _hip.ptr(counts), draw_id, self.t + 1, _hip.ptr(self.lr_t), BETAS[0], BETAS[1], ADAM_EPS, st),
+                   "rbnn_svi_multi_adam_step")
+        self.launches += self.fwd_launches + 3
+        psum = None
+        if accuracy:
+            _hip.check(lib.rbnn_svi_multi_accuracy(net, g, _hip.ptr(self.X), self.D, n_rows, _hip.ptr(rows), _hip.ptr(counts), self.B,
+                                                   C.c_uint64(ACC_KEY), draw_id, C.byref(self.acc), st), "rbnn_svi_multi_accuracy")
+            self.launches += self.fwd_launches // 2 + 2
+            psum = self.Psum
+        _hip.check(lib.rbnn_svi_multi_finalize(net, g, _hip.ptr(self.ws_t["ce"]), _hip.ptr(psum), _hip.ptr(self.labels), n_rows, _hip.ptr(rows),
+                                               _hip.ptr(counts), self.B, _hip.ptr(epoch_slot), _hip.ptr(self.epoch_log),
+                                               0 if self.epoch_log is None else int(self.epoch_log.shape[1]), st), "rbnn_svi_multi_finalize")
+        self.launches += 1
+        self.t += 1
+
+    def begin_log(self, n_epochs):
+        """A zeroed device log [K, n_epochs, 2] for the epoch sums (loss, correct predictions)."""
+        self.epoch_log = torch.zeros(self.K, max(1, int(n_epochs)), 2, dtype=torch.float64, device=self.device)
+
+    @staticmethod
+    def schedule(n_points, epochs, batch_size, first_rows=None):
+        """The unshuffled epochs of K members as host tensors [T, K] (T = the longest member's number of steps): member k walks rows
+        first_rows[k] .. first_rows[k] + n_points[k] in batches of batch_size (a short last batch), epochs[k] times, then stops.
+        -> {"start", "last", "count", "slot"}: first row, last valid row, number of points (0: finished) and the epoch that ends (-1: none)."""
+        K = len(n_points)
+        first_rows = [0] * K if first_rows is None else [int(v) for v in first_rows]
+        per = [(int(n) + batch_size - 1) // batch_size for n in n_points]
+        T = max(p * int(e) for p, e in zip(per, epochs))
+        out = {name: torch.zeros(T, K, dtype=torch.int32) for name in ("start", "last", "count")}
+        out["slot"] = torch.full((T, K), -1, dtype=torch.int32)
+        for k in range(K):
+            n, f = int(n_points[k]), first_rows[k]
+            for t in range(per[k] * int(epochs[k])):
+                i = t % per[k]
+                c = min(batch_size, n - i * batch_size)
+                out["start"][t, k], out["count"][t, k], out["last"][t, k] = f + i * batch_size, c, f + i * batch_size + c - 1
+                if i == per[k] - 1:
+                    out["slot"][t, k] = t // per[k]
+        return out
+
+    def load_schedule(self, schedule):
+        """Uploads a schedule() (the one host->device copy of a run) and starts a fresh device log for its epochs.  -> its number of steps."""
+        self.sched = {k: v.to(self.device) for k, v in schedule.items()}
+        self.begin_log(int(schedule["slot"].max()) + 1)
+        return int(schedule["count"].shape[0])
+
+    def scheduled_step(self, t, accuracy=True):
+        """Step t of the loaded schedule: rows[k, b] = min(start[k] + b, last[k]) (two torch launches), then step().  No synchronisation."""
+        s = self.sched
+        torch.add(s["start"][t].unsqueeze(1), self._arange, out=self.rows_t)
+        torch.minimum(self.rows_t, s["last"][t].unsqueeze(1), out=self.rows_t)
+        self.launches += 2
+        self.step(self.rows_t, s["count"][t], accuracy, s["slot"][t])
+
+    def run(self, schedule, accuracy=True):
+        """Every step of a schedule(), the epoch sums into the device log (epoch_totals() reads it)."""
+        for t in range(self.load_schedule(schedule)):
+            self.scheduled_step(t, accuracy)
+
+    def epoch_totals(self):
+        """Per member the list of (sum of the step losses, correct predictions) of its epochs: the one device->host read of a run."""
+        return [[(row[0], row[1]) for row in member] for member in self.epoch_log.tolist()]
+
+    def params(self, k):
+        """(loc, raw scale) of guide k as dicts state_dict key -> fresh device tensor."""
+        return ({n: v.clone() for n, v in self.unflat(self.loc[k]).items()}, {n: v.clone() for n, v in self.unflat(self.raw[k]).items()})
