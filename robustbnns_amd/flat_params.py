@@ -1,8 +1,36 @@
-"""What SviTrainer, NnTrainer and HmcSampler share: the flat parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
+"""What SviTrainer, LockstepSvi, NnTrainer, HmcSampler and LockstepHmc share: the two refusals (require_gpu_fc), the constructor state of a
+trainer of fc / fc2 nets (FlatNets: shapes, sizes, the net descriptors, zeroed buffers; set_data: the resident data of the lockstep classes), the flat
+parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import _hip
+from .posterior import LAYER_KEYS
+
+
+def require_gpu_fc(what, arch=None, device=None):
+    """The two refusals of everything that trains or samples on the GPU, with `what` as their subject: a device that is not the GPU, an
+    architecture other than fc / fc2.  An argument left None is not checked."""
+    if device is not None and torch.device(device).type != "cuda":
+        raise NotImplementedError(f"{what} runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+    if arch is not None and arch not in LAYER_KEYS:
+        raise NotImplementedError(f"{what} covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+
+
+def state_keys(arch):
+    return [k + sfx for k in LAYER_KEYS[arch] for sfx in (".weight", ".bias")]
+
+
+def state_shapes(module):
+    """[(state_dict key, shape)] of a torch module, in state_dict order."""
+    return [(k, tuple(v.shape)) for k, v in module.state_dict().items()]
+
+
+def keys_tensor(keys, device):
+    """uint64 Philox keys in an int64 tensor (the same bits) on `device`."""
+    return torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in keys], dtype=torch.int64).to(device)
 
 
 def flatten(params, keys):
@@ -34,3 +62,52 @@ def ws_struct(cls, keys, tensors):
     for k in keys:
         setattr(ws, k, _hip.ptr(tensors.get(k)))
     return ws
+
+
+class FlatNets:
+    """The constructor state of a trainer or sampler of fc / fc2 nets of one shape, a single net (members None: buffers [n]) or `members` of
+    them in lockstep (buffers [members, n]): the kernels' handle, arch / activation / device / input_shape, the state_dict keys (`state_keys`,
+    and `keys` until a class puts something else there) and `shapes` (taken from `like`, a dict key -> tensor), D / H / C and fwd_launches."""
+
+    def __init__(self, arch, activation, input_shape, n_classes, like, device, members=None):
+        self.k = _hip.HipKernels()
+        self.arch, self.activation, self.device = arch, activation, torch.device(device)
+        self.input_shape = tuple(int(v) for v in input_shape)
+        self.state_keys = self.keys = state_keys(arch)
+        self.shapes = {k: tuple(like[k].shape) for k in self.state_keys}
+        self.D = int(np.prod(self.input_shape))
+        self.H, self.C = int(self.shapes[self.state_keys[1]][0]), int(n_classes)
+        self.lead = () if members is None else (int(members),)
+        self.fwd_launches = 2 if arch == "fc" else 4
+
+    def descriptor(self, cls, n_members=None):
+        """An _hip.SviTrainNet or _hip.NnTrainNet (n_members given) with the net's shape filled in and every pointer NULL."""
+        net = cls()
+        net.arch, net.activation = _hip.ARCHS[self.arch], _hip.ACTIVATIONS[self.activation]
+        net.in_features, net.hidden, net.n_classes = self.D, self.H, self.C
+        if n_members is not None:
+            net.n_members = n_members
+        return net
+
+    def sizes(self, entry, net, *outs):
+        """n_params from the `*_sizes` entry point named `entry` for the descriptor `net`; outs: the entry point's c_int64 out-parameters."""
+        n = int(getattr(self.k.lib, entry)(C.byref(net), *[C.byref(o) for o in outs]))
+        _hip.check(min(n, 0), entry)
+        return n
+
+    def zeros(self, n):
+        """A zeroed fp32 buffer [n], or [members, n]."""
+        return torch.zeros(*self.lead, n, dtype=torch.float32, device=self.device)
+
+    def unflat(self, buf):
+        """state_dict key -> view of `buf` ([n_params] or [..., n_params]) in that tensor's shape."""
+        return unflat(buf, self.state_keys, self.shapes)
+
+
+def set_data(self, x, labels):
+    """The resident data the members' batches are gathered from: x [n_rows, ...], labels int [n_rows].  (A method of the lockstep classes.)"""
+    n = int(x.shape[0])
+    self.X = x.reshape(n, -1).to(self.device, torch.float32).contiguous()
+    self.labels = labels.reshape(n).to(self.device, torch.int32).contiguous()
+    if self.X.shape[1] != self.D:
+        raise ValueError(f"the data have {self.X.shape[1]} features, the nets {self.D}")

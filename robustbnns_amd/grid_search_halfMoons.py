@@ -19,6 +19,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .adversarialAttacks import attack
+from .flat_params import require_gpu_fc
 from .lossGradients import loss_gradients
 from .model_bnn import BNN
 from .savedir import TESTS
@@ -47,8 +48,7 @@ def _train(hidden_size, activation, architecture, inference, epochs, lr, n_sampl
            x_train=None, y_train=None, train_loader=None):
     """:30-41: one model of the grid.  Batch 64 for svi (BNN.train), 1024 for hmc (BNN.train_hmc); the data are x_train / y_train (the first
     n_inputs points) or a ready train_loader.  Returns the trained net."""
-    if architecture not in ("fc", "fc2"):
-        raise NotImplementedError(f"grid training covers fc and fc2, not {architecture!r} (conv needs conv weight gradients)")
+    require_gpu_fc("grid training", architecture)
     batch_size = 64 if inference == "svi" else 1024
     if train_loader is None:
         if x_train is None or y_train is None:
@@ -90,10 +90,8 @@ def lockstep_train(hidden_size, activation, architecture, inference, epochs, lr,
     for init in combos:
         h, act, arch, inf, ep, lr_, ns, wu, ninp, _ = init
         if inf == "svi" and train_loader is None:
-            if arch not in ("fc", "fc2"):
-                raise NotImplementedError(f"grid training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
-            if torch.device(device).type != "cuda":
-                raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+            require_gpu_fc("grid training", arch)
+            require_gpu_fc("SVI training", device=device)
             if x_train is None or y_train is None:
                 raise ValueError("lockstep_train needs x_train / y_train or a train_loader: dataset loading is out of scope")
             # one member per (epochs, lr, n_samples, warmup, n_inputs) of a net shape, in the grid's order: posterior_samples repeats the model
@@ -104,10 +102,8 @@ def lockstep_train(hidden_size, activation, architecture, inference, epochs, lr,
             bnn = _train(*init, rel_path, device, x_train=x_train, y_train=y_train, train_loader=train_loader)
             out[bnn.name] = bnn
             continue
-        if arch not in ("fc", "fc2"):
-            raise NotImplementedError(f"grid training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
-        if torch.device(device).type != "cuda":
-            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        require_gpu_fc("grid training", arch)
+        require_gpu_fc("HMC", device=device)
         if x_train is None or y_train is None:
             raise ValueError("lockstep_train needs x_train / y_train or a train_loader: dataset loading is out of scope")
         members = groups.setdefault((h, act, arch, ep, lr_, ns, wu), {})

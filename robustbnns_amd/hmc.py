@@ -14,17 +14,18 @@ once at the end of run().
 
 LockstepHmc runs K chains of one net shape with every launch covering all of them (the chain is grid dimension y: rbnn_hmc_lockstep_*), each
 chain bit-identical to HmcSampler running it alone; split_r_hat is the convergence figure that goes with several chains.
+
+The chain algorithm (transition, step-size search, warmup windows, sampling, logs) is written once, in _Chains, over K chains with per-chain
+host lists; HmcSampler (K = 1, the single-net entry points rbnn_hmc_*, scalar / flat public values) and LockstepHmc supply the launches,
+the staging of the batch and the shape of what they return.
 """
 import ctypes as C
 import math
 
-import numpy as np
 import torch
 
 from . import _hip
-from .flat_params import flatten, train_workspace, unflat, ws_struct
-from .posterior import LAYER_KEYS
-from .svi_train import state_keys
+from .flat_params import FlatNets, flatten, keys_tensor, require_gpu_fc, set_data, train_workspace, ws_struct
 
 INIT_RADIUS = 2.0                   # pyro's init_to_uniform [recalled]
 START_BUFFER, END_BUFFER, INIT_WINDOW = 75, 50, 25      # pyro's WarmupAdapter [recalled]
@@ -66,69 +67,202 @@ def windows(warmup):
     return out
 
 
-class HmcSampler:
-    """Device-resident state of one HMC chain over an fc / fc2 net: the trajectory's position / dCE/dW (an rbnn_svi_train_net's W / grad), the
-    chain's cached position and gradient, momentum, the diagonal inverse mass, Welford's mean / M2, the fp64 state block, the per-transition
-    log and the sample stack.  `launches` counts kernel launches by the entry points' documented launch counts."""
+def _view(name, k=None):
+    """A per-chain host list of _Chains as a public attribute: the list itself (LockstepHmc), or chain k's entry (HmcSampler)."""
+    if k is None:
+        return property(lambda self: getattr(self, name), lambda self, v: setattr(self, name, list(v)))
+    return property(lambda self: getattr(self, name)[k], lambda self, v: getattr(self, name).__setitem__(k, v))
 
-    def __init__(self, arch, activation, input_shape, n_classes, q0, step_size, num_steps, device, key, adapt_step_size=True,
-                 adapt_mass_matrix=True, batch_size=128):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-        if arch not in LAYER_KEYS:
-            raise NotImplementedError(f"HMC covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
-        self.k = _hip.HipKernels()
-        self.arch, self.activation, self.device = arch, activation, dev
-        self.input_shape = tuple(int(v) for v in input_shape)
-        self.keys = state_keys(arch)
-        self.shapes = {k: tuple(q0[k].shape) for k in self.keys}
-        self.D = int(np.prod(self.input_shape))
-        self.H, self.C = int(self.shapes[self.keys[1]][0]), int(n_classes)
-        net = _hip.SviTrainNet()
-        net.arch, net.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
-        net.in_features, net.hidden, net.n_classes = self.D, self.H, self.C
+
+class _Chains(FlatNets):
+    """The buffers and the algorithm of K HMC chains over nets of one shape; the per-chain host values are lists of K: _eps (the host's copy
+    of the step sizes), _traj (step size x num_steps), _searches (the probes' draw counters), _search_log.  A subclass supplies the launches
+    (_gradient, _update, leapfrog, _draw, _decide, _commit, _window_end; each adds its documented launch count to `launches`), the state
+    block's accessors (_set_state, read_state), set_active / _set_steps, _bind / _ensure and stage()."""
+
+    def __init__(self, arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size, adapt_mass_matrix,
+                 members):
+        super().__init__(arch, activation, input_shape, n_classes, q0s[0], device, members)
+        K = self.K = len(q0s)
+        dev, z = self.device, self.zeros
         nq, ne = C.c_int64(0), C.c_int64(0)
-        n = int(self.k.lib.rbnn_hmc_sizes(C.byref(net), C.byref(nq), C.byref(ne)))
-        _hip.check(min(n, 0), "rbnn_hmc_sizes")
-        self.n_params = n
-        z = lambda m=n: torch.zeros(m, dtype=torch.float32, device=dev)
-        self.W, self.grad = z(), z()
-        net.W, net.grad = self.W.data_ptr(), self.grad.data_ptr()
-        self.net = net
-        self.q_cur = flatten(q0, self.keys).to(dev)
-        assert self.q_cur.numel() == n, (self.q_cur.numel(), n)
-        self.g_cur, self.r, self.w_mean, self.w_m2 = z(), z(), z(), z()
-        self.m_inv = torch.ones(n, dtype=torch.float32, device=dev)
-        self.k0_part, self.k1_part, self.p_part = z(int(nq.value)), z(int(ne.value)), z(int(ne.value))
-        self.state = torch.zeros(_hip.HMC_STATE, dtype=torch.float64, device=dev)
+        n = self.n_params = self.sizes("rbnn_hmc_sizes", self.descriptor(_hip.SviTrainNet), nq, ne)
+        self.n_qpart, self.n_epart = int(nq.value), int(ne.value)
+        self.W, self.grad = z(n), z(n)
+        self.q_cur = torch.stack([flatten(q0, self.keys) for q0 in q0s]).reshape(*self.lead, n).to(dev)
+        self.g_cur, self.r, self.w_mean, self.w_m2 = z(n), z(n), z(n), z(n)
+        self.m_inv = torch.ones(*self.lead, n, dtype=torch.float32, device=dev)
+        self.k0_part, self.k1_part, self.p_part = z(self.n_qpart), z(self.n_epart), z(self.n_epart)
+        self.state = torch.zeros(*self.lead, _hip.HMC_STATE, dtype=torch.float64, device=dev)
         self.log_t = self.samples_t = None
-        self.step_size, self.num_steps = float(step_size), int(num_steps)
-        self.trajectory_length = self.step_size * self.num_steps
+        self.chain_keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
+        sizes = [float(v) for v in step_size] if isinstance(step_size, (list, tuple)) else [float(step_size)] * K
+        if len(sizes) != K:
+            raise ValueError(f"{len(sizes)} step sizes for {K} chains")
+        self.step_size, self.num_steps = (sizes if self.lead else sizes[0]), int(num_steps)
+        self._traj, self._eps = [e * self.num_steps for e in sizes], list(sizes)
+        self._searches, self._search_log = [0] * K, [[] for _ in range(K)]
         self.adapt_step_size, self.adapt_mass_matrix = bool(adapt_step_size), bool(adapt_mass_matrix)
-        self.key = int(key) & 0xFFFFFFFFFFFFFFFF
-        self.eps_host = self.step_size
-        self.searches = 0
-        self.search_log = []
-        self.launches = 0
-        self.fwd_launches = 2 if arch == "fc" else 4
-        self.Bmax = self.B = 0
-        self._ensure(int(batch_size))
-        self._set_state(eps=self.step_size, mu=math.log(10 * self.step_size))
-        self._bind()
+        self.launches = self.B = 0
         # the logs of the last run(): one entry per transition, warmup included
         self.eps_log = self.L_log = self.dH_log = self.accept_prob_log = self.accepted_log = None
 
-    # -- buffers --------------------------------------------------------------------------------------------------------------------
-    def _bind(self):
-        ch = _hip.HmcChain()
+    def _start(self, batch_size):
+        """The end of a subclass's constructor: the workspaces, the state block's step size and dual-averaging centre, the C structs."""
+        self._ensure(int(batch_size))
+        self._set_state(eps=self._eps, mu=[math.log(10 * e) for e in self._eps])
+        self._bind()
+
+    def _chain_struct(self, cls, rows_dim):
+        """The pointers and row counts that HmcChain and HmcLockstep share (log / samples: [..., rows, .] with rows at dimension rows_dim)."""
+        ch = cls()
         for name in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state"):
             setattr(ch, name, getattr(self, name).data_ptr())
         ch.log = None if self.log_t is None else self.log_t.data_ptr()
         ch.samples = None if self.samples_t is None else self.samples_t.data_ptr()
-        ch.log_rows = 0 if self.log_t is None else int(self.log_t.shape[0])
-        ch.sample_rows = 0 if self.samples_t is None else int(self.samples_t.shape[0])
-        self.chain = ch
+        ch.log_rows = 0 if self.log_t is None else int(self.log_t.shape[rows_dim])
+        ch.sample_rows = 0 if self.samples_t is None else int(self.samples_t.shape[rows_dim])
+        return ch
+
+    def _st(self):
+        return _hip.stream_of(self.W)
+
+    def _read(self, name):
+        """One entry of every chain's state block (a device->host synchronisation)."""
+        s = self.read_state()
+        return [c[name] for c in s] if self.lead else [s[name]]
+
+    # -- the chains -----------------------------------------------------------------------------------------------------------------
+    def refresh(self):
+        """U and dCE/dW of the chains' current positions (after stage(), or after q_cur was written from outside)."""
+        self.W.copy_(self.q_cur)
+        self._gradient()
+        self._update(_hip.HMC_ENERGY)
+        self._decide(_hip.HMC_DECIDE_INIT)
+        self._commit(force=True)
+
+    def _length(self, k, eps=None):
+        return max(1, int(self._traj[k] / (self._eps[k] if eps is None else eps)))
+
+    def lengths(self):
+        return [self._length(k) for k in range(self.K)]
+
+    def transition(self, i, L=None, adapt=False, window_end=False, welford_n=0, sample_row=-1):
+        """Transition i of every active chain, chain k with L[k] leapfrog steps (an int: every chain; default: from the host's copies of the
+        step sizes).  No device->host synchronisation.  -> the lengths (HmcSampler: its one)"""
+        self._draw(i)
+        L = self.leapfrog(self.lengths() if L is None else L)
+        self._decide(_hip.HMC_DECIDE_TRANSITION, i, adapt, window_end)
+        self._commit(False, welford_n, sample_row)
+        return L
+
+    def _probe(self, eps, live):
+        """One try of the search for the chains in `live`: -> the K values of dH (a frozen chain's is its last one)."""
+        self.set_active(live)
+        self._set_state(eps=eps)                                         # a frozen chain's entry is the value its block already holds
+        self._draw(None)
+        for k in range(self.K):
+            self._searches[k] += int(live[k])
+        self.leapfrog(1)
+        self._decide(_hip.HMC_DECIDE_PROBE)
+        return self._read("dH")
+
+    def find_reasonable_step_size(self):
+        """pyro's search [recalled] from the current step sizes (run() calls it before the first transition and after every warmup window but
+        the last, whose dual-averaged exp(xbar) is the sampling phase's step size): one leapfrog step from fresh momentum, direction = +1 if
+        -dH > log 0.8 else -1, eps *= 2^direction with new momentum each try until the direction flips; then dual averaging restarts with
+        mu = log(10 eps).  All chains probe together, each with its own try counter; a chain whose direction has flipped is frozen
+        (active = 0) while the others go on."""
+        log08, K = math.log(0.8), self.K
+        eps, tries, live = list(self._eps), [[] for _ in range(K)], [True] * K
+        dH = self._probe(eps, live)
+        direction = [1 if -dH[k] > log08 else -1 for k in range(K)]
+        for k in range(K):
+            tries[k].append((eps[k], dH[k]))
+        while any(live):
+            for k in range(K):
+                if live[k]:
+                    if len(tries[k]) > MAX_SEARCH:
+                        raise RuntimeError(f"the HMC step-size search{f' of chain {k}' if self.lead else ''} did not end after {MAX_SEARCH} "
+                                           f"tries (last eps {eps[k]:g}, dH {dH[k]:g})")
+                    eps[k] = eps[k] * 2.0 ** direction[k]
+            dH = self._probe(eps, live)
+            for k in range(K):
+                if live[k]:
+                    tries[k].append((eps[k], dH[k]))
+                    live[k] = (1 if -dH[k] > log08 else -1) == direction[k]
+        self.set_active(None)
+        for k in range(K):
+            self._search_log[k].append(tries[k])
+        self._eps = eps
+        self._set_state(eps=eps, t=0.0, gbar=0.0, xbar=0.0, mu=[math.log(10 * e) for e in eps])
+
+    def _run(self, num_samples, warmup, *batch):
+        """`warmup` adapting transitions, then num_samples at fixed step sizes and lengths, of all chains on stage(*batch); then the logs
+        (eps_log, L_log, dH_log, accept_prob_log, accepted_log: per chain one entry per transition, warmup included) are read."""
+        num_samples, warmup = int(num_samples), int(warmup)
+        total, K = warmup + num_samples, self.K
+        self.log_t = torch.zeros(*self.lead, max(1, total), _hip.HMC_LOG, dtype=torch.float64, device=self.device)
+        self.samples_t = torch.zeros(*self.lead, max(1, num_samples), self.n_params, dtype=torch.float32, device=self.device)
+        self._bind()
+        self.stage(*batch)
+        Ls = [[] for _ in range(K)]
+
+        def note(L):
+            for k in range(K):
+                Ls[k].append(L[k])
+
+        if warmup > 0 and self.adapt_step_size:
+            self.find_reasonable_step_size()
+        for (a, b, kind) in windows(warmup):
+            mid = kind == "middle" and self.adapt_mass_matrix
+            for i in range(a, b):
+                last = i == b - 1
+                L = self.lengths()
+                note(L)
+                self.transition(i, L, self.adapt_step_size, last, (i - a + 1) if mid else 0)
+                if last and mid:
+                    self._window_end(b - a)
+                if self.adapt_step_size:
+                    self._eps = self._read("eps")                       # warmup's one read per transition: L follows the adapted step sizes
+                    if last and b < warmup:                             # the last window's exp(xbar) is the sampling step size: no search
+                        self.find_reasonable_step_size()
+        self._set_steps(self.lengths())                                   # host -> device, before the sampling phase
+        self.sample(warmup, num_samples, note)
+        log = self.log = self.log_t[..., :total, :].cpu()                 # the one read of the sampling phase
+        self.eps_log, self.dH_log, self.accept_prob_log = log[..., 0].tolist(), log[..., 1].tolist(), log[..., 2].tolist()
+        self.accepted_log, self.L_log = (log[..., 3] != 0).tolist(), Ls
+
+    def sample(self, first, num_samples, note=None):
+        """num_samples transitions first, first + 1, ... at the fixed step sizes and lengths; row i of every chain's stack = its position after
+        transition first + i.  No device->host synchronisation (the lengths are on the device since the end of warmup)."""
+        L = self.lengths()
+        for i in range(num_samples):
+            self.transition(first + i, L, False, False, 0, i)
+            if note is not None:
+                note(L)
+
+
+class HmcSampler(_Chains):
+    """Device-resident state of one HMC chain over an fc / fc2 net: the trajectory's position / dCE/dW (an rbnn_svi_train_net's W / grad), the
+    chain's cached position and gradient, momentum, the diagonal inverse mass, Welford's mean / M2, the fp64 state block, the per-transition
+    log and the sample stack.  `launches` counts kernel launches by the entry points' documented launch counts."""
+    eps_host, searches, search_log, trajectory_length = (_view(n, 0) for n in ("_eps", "_searches", "_search_log", "_traj"))
+
+    def __init__(self, arch, activation, input_shape, n_classes, q0, step_size, num_steps, device, key, adapt_step_size=True,
+                 adapt_mass_matrix=True, batch_size=128):
+        require_gpu_fc("HMC", arch, device)
+        super().__init__(arch, activation, input_shape, n_classes, [q0], float(step_size), num_steps, device, [key], adapt_step_size,
+                         adapt_mass_matrix, None)
+        self.key = self.chain_keys[0]
+        self.net = self.descriptor(_hip.SviTrainNet)
+        self.net.W, self.net.grad = self.W.data_ptr(), self.grad.data_ptr()
+        self.Bmax = 0
+        self._start(batch_size)
+
+    # -- buffers --------------------------------------------------------------------------------------------------------------------
+    def _bind(self):
+        self.chain = self._chain_struct(_hip.HmcChain, 0)
 
     def _ensure(self, B):
         if B <= self.Bmax:
@@ -139,24 +273,23 @@ class HmcSampler:
         self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.Bmax = B
 
-    def unflat(self, buf):
-        """state_dict key -> view of `buf` ([n_params] or [S, n_params]) in that tensor's shape."""
-        return unflat(buf, self.keys, self.shapes)
-
     def _set_state(self, **kv):
         """Host -> device writes of state-block entries (warmup / set-up only)."""
         for name, v in kv.items():
-            self.state[_hip.HMC_ST[name]] = float(v)
+            self.state[_hip.HMC_ST[name]] = float(v[0] if isinstance(v, list) else v)
 
     def read_state(self):
         """The state block as a dict (a device->host synchronisation)."""
         s = self.state.tolist()
         return {name: s[i] for name, i in _hip.HMC_ST.items()}
 
-    # -- launches -------------------------------------------------------------------------------------------------------------------
-    def _st(self):
-        return _hip.stream_of(self.W)
+    def set_active(self, mask=None):
+        pass                                                              # one chain: always active,
 
+    def _set_steps(self, L):
+        pass                                                              # and the host closes its last step (HMC_CLOSE in leapfrog)
+
+    # -- launches -------------------------------------------------------------------------------------------------------------------
     def _gradient(self):
         """dCE/dW and the per-point CE at self.W: the training forward (fc 2 launches, fc2 4) + the weight gradients (1)."""
         lib, net = self.k.lib, C.byref(self.net)
@@ -174,6 +307,13 @@ class HmcSampler:
                                                 C.c_uint32(draw_id & 0xFFFFFFFF), self._st()), "rbnn_hmc_momentum")
         self.launches += 1
 
+    def _draw(self, i):
+        """The momentum of transition i, or (None) of the search's next probe: a stream of its own, numbered by the try counter."""
+        if i is None:
+            self._momentum(self.key ^ _hip.HMC_SEARCH_KEY, self._searches[0])
+        else:
+            self._momentum(self.key, i)
+
     def _decide(self, mode, transition=0, adapt=False, window_end=False):
         _hip.check(self.k.lib.rbnn_hmc_decide(C.byref(self.net), C.byref(self.chain), _hip.ptr(self.ws_t["ce"]), self.B, C.c_uint64(self.key),
                                               int(transition), mode, int(adapt), int(window_end), self._st()), "rbnn_hmc_decide")
@@ -182,6 +322,10 @@ class HmcSampler:
     def _commit(self, force=False, welford_n=0, sample_row=-1):
         _hip.check(self.k.lib.rbnn_hmc_commit(C.byref(self.net), C.byref(self.chain), int(force), int(welford_n), int(sample_row), self._st()),
                    "rbnn_hmc_commit")
+        self.launches += 1
+
+    def _window_end(self, n):
+        _hip.check(self.k.lib.rbnn_hmc_window_end(C.byref(self.net), C.byref(self.chain), n, self._st()), "rbnn_hmc_window_end")
         self.launches += 1
 
     # -- the chain ------------------------------------------------------------------------------------------------------------------
@@ -194,23 +338,17 @@ class HmcSampler:
         self.labels[:B].copy_(labels.reshape(B))
         self.refresh()
 
-    def refresh(self):
-        """U and dCE/dW of the chain's current position (after stage(), or after q_cur was written from outside)."""
-        self.W.copy_(self.q_cur)
-        self._gradient()
-        self._update(_hip.HMC_ENERGY)
-        self._decide(_hip.HMC_DECIDE_INIT)
-        self._commit(force=True)
-
     def leapfrog(self, n, fused=True):
-        """n leapfrog steps from (q_cur, r) at the state block's step size; the end point is left in self.W / self.r / self.grad and its K' and
-        1/2 sum q'^2 in the partial sums.  fused=False: the plain half kick / drift / gradient / half kick sequence the fused updates restate."""
+        """n leapfrog steps (or [n], as the driver passes lengths) from (q_cur, r) at the state block's step size; the end point is left in
+        self.W / self.r / self.grad and its K' and 1/2 sum q'^2 in the partial sums.  fused=False: the plain half kick / drift / gradient /
+        half kick sequence the fused updates restate.  -> n"""
+        n = n[0] if isinstance(n, list) else n
         if fused:
             self._update(_hip.HMC_OPEN)
             for s in range(n):
                 self._gradient()
                 self._update(_hip.HMC_MID if s + 1 < n else _hip.HMC_CLOSE)
-            return
+            return n
         self.W.copy_(self.q_cur)
         self.grad.copy_(self.g_cur)
         for s in range(n):
@@ -219,90 +357,21 @@ class HmcSampler:
             self._gradient()
             self._update(_hip.HMC_KICK)
         self._update(_hip.HMC_ENERGY)
+        return n
 
     def length(self, eps=None):
-        return max(1, int(self.trajectory_length / (self.eps_host if eps is None else eps)))
-
-    def transition(self, i, L=None, adapt=False, window_end=False, welford_n=0, sample_row=-1):
-        """Transition i with L leapfrog steps (default: from the host's copy of the step size).  No device->host synchronisation."""
-        L = self.length() if L is None else L
-        self._momentum(self.key, i)
-        self.leapfrog(L)
-        self._decide(_hip.HMC_DECIDE_TRANSITION, i, adapt, window_end)
-        self._commit(False, welford_n, sample_row)
-        return L
-
-    def _probe(self, eps):
-        self._set_state(eps=eps)
-        self._momentum(self.key ^ _hip.HMC_SEARCH_KEY, self.searches)
-        self.searches += 1
-        self.leapfrog(1)
-        self._decide(_hip.HMC_DECIDE_PROBE)
-        return self.read_state()["dH"]
-
-    def find_reasonable_step_size(self):
-        """pyro's search [recalled] from the current step size (run() calls it before the first transition and after every warmup window but
-        the last, whose dual-averaged exp(xbar) is the sampling phase's step size): one leapfrog step from fresh momentum, direction = +1 if -dH > log 0.8 else -1,
-        eps *= 2^direction with new momentum each try until the direction flips; then dual averaging restarts with mu = log(10 eps)."""
-        log08, tries = math.log(0.8), []
-        eps = self.eps_host
-        dH = self._probe(eps)
-        tries.append((eps, dH))
-        direction = 1 if -dH > log08 else -1
-        new = direction
-        while new == direction:
-            if len(tries) > MAX_SEARCH:
-                raise RuntimeError(f"the HMC step-size search did not end after {MAX_SEARCH} tries (last eps {eps:g}, dH {dH:g})")
-            eps = eps * 2.0 ** direction
-            dH = self._probe(eps)
-            tries.append((eps, dH))
-            new = 1 if -dH > log08 else -1
-        self.search_log.append(tries)
-        self.eps_host = eps
-        self._set_state(eps=eps, t=0.0, gbar=0.0, xbar=0.0, mu=math.log(10 * eps))
+        return self._length(0, eps)
 
     def run(self, x, labels, num_samples, warmup):
         """One chain on the batch: `warmup` adapting transitions, then num_samples at fixed step size and L.  Returns the sample stack as a dict
         state_dict key -> [num_samples, ...] (device tensors); the logs (eps_log, L_log, dH_log, accept_prob_log, accepted_log: one entry per
         transition, warmup included) and the final m_inv stay on the sampler."""
-        num_samples, warmup = int(num_samples), int(warmup)
-        total = warmup + num_samples
-        self.log_t = torch.zeros(max(1, total), _hip.HMC_LOG, dtype=torch.float64, device=self.device)
-        self.samples_t = torch.zeros(max(1, num_samples), self.n_params, dtype=torch.float32, device=self.device)
-        self._bind()
-        self.stage(x, labels)
-        Ls = []
-        if warmup > 0 and self.adapt_step_size:
-            self.find_reasonable_step_size()
-        for (a, b, kind) in windows(warmup):
-            mid = kind == "middle" and self.adapt_mass_matrix
-            for i in range(a, b):
-                last = i == b - 1
-                Ls.append(self.transition(i, None, self.adapt_step_size, last, (i - a + 1) if mid else 0))
-                if last and mid:
-                    _hip.check(self.k.lib.rbnn_hmc_window_end(C.byref(self.net), C.byref(self.chain), b - a, self._st()), "rbnn_hmc_window_end")
-                    self.launches += 1
-                if self.adapt_step_size:
-                    self.eps_host = self.read_state()["eps"]            # warmup's one read per transition: L follows the adapted step size
-                    if last and b < warmup:                             # the last window's exp(xbar) is the sampling step size: no search
-                        self.find_reasonable_step_size()
-        self.sample(warmup, num_samples, Ls)
-        log = self.log_t[:total].cpu()                                  # the one read of the sampling phase
-        self.eps_log, self.dH_log, self.accept_prob_log = log[:, 0].tolist(), log[:, 1].tolist(), log[:, 2].tolist()
-        self.accepted_log, self.L_log, self.log = [bool(v) for v in log[:, 3].tolist()], Ls, log
-        return self.unflat(self.samples_t[:num_samples])
-
-    def sample(self, first, num_samples, Ls=None):
-        """num_samples transitions first, first + 1, ... at the fixed step size and L, row i of the sample stack = the position after transition
-        first + i.  No device->host synchronisation."""
-        L = self.length()
-        for i in range(num_samples):
-            self.transition(first + i, L, False, False, 0, i)
-            if Ls is not None:
-                Ls.append(L)
+        self._run(num_samples, warmup, x, labels)
+        self.L_log = self.L_log[0]
+        return self.unflat(self.samples_t[:int(num_samples)])
 
 
-class LockstepHmc:
+class LockstepHmc(_Chains):
     """K independent chains over nets of ONE shape in lockstep: every launch covers all chains, so a transition costs the launches of a single
     chain whatever K is.  Each chain has its own key, start position, step size, mass matrix, state block, log and sample stack, and may have
     its own batch (rows / counts into resident data); warmup, the number of samples, num_steps and the adapt flags are shared.  Chain k is
@@ -312,83 +381,37 @@ class LockstepHmc:
     step s closes the chains with L_k == s + 1 and skips those behind it (their forward / gradient launches still run, on a position that
     no longer moves).  The step-size search probes all chains together and freezes a chain whose direction has flipped (`active`).
     `launches` counts kernel launches as HmcSampler does."""
+    eps_host, searches, search_log, trajectory_length = (_view(n) for n in ("_eps", "_searches", "_search_log", "_traj"))
+    set_data = set_data
+    length = _Chains._length
 
     def __init__(self, arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size=True,
                  adapt_mass_matrix=True, batch_size=128):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-        if arch not in LAYER_KEYS:
-            raise NotImplementedError(f"HMC covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+        require_gpu_fc("HMC", arch, device)
         q0s, keys = list(q0s), list(keys)
         if len(q0s) < 1 or len(keys) != len(q0s):
             raise ValueError(f"LockstepHmc needs one key per chain and at least one chain: {len(q0s)} start positions, {len(keys)} keys")
         if len(q0s) > 65535:
             raise ValueError(f"at most 65535 chains run in lockstep (the chain is a grid dimension), not {len(q0s)}")
-        K = self.K = len(q0s)
-        self.k = _hip.HipKernels()
-        self.arch, self.activation, self.device = arch, activation, dev
-        self.input_shape = tuple(int(v) for v in input_shape)
-        self.keys = state_keys(arch)
-        self.shapes = {k: tuple(q0s[0][k].shape) for k in self.keys}
-        self.D = int(np.prod(self.input_shape))
-        self.H, self.C = int(self.shapes[self.keys[1]][0]), int(n_classes)
-        one = _hip.SviTrainNet()
-        one.arch, one.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
-        one.in_features, one.hidden, one.n_classes = self.D, self.H, self.C
-        nq, ne = C.c_int64(0), C.c_int64(0)
-        n = int(self.k.lib.rbnn_hmc_sizes(C.byref(one), C.byref(nq), C.byref(ne)))
-        _hip.check(min(n, 0), "rbnn_hmc_sizes")
-        self.n_params, self.n_qpart, self.n_epart = n, int(nq.value), int(ne.value)
-        z = lambda m=n: torch.zeros(K, m, dtype=torch.float32, device=dev)
-        self.W, self.grad = z(), z()
-        self.q_cur = torch.stack([flatten(q0, self.keys) for q0 in q0s]).to(dev)
-        assert tuple(self.q_cur.shape) == (K, n), (tuple(self.q_cur.shape), K, n)
-        self.g_cur, self.r, self.w_mean, self.w_m2 = z(), z(), z(), z()
-        self.m_inv = torch.ones(K, n, dtype=torch.float32, device=dev)
-        self.k0_part, self.k1_part, self.p_part = z(self.n_qpart), z(self.n_epart), z(self.n_epart)
-        self.state = torch.zeros(K, _hip.HMC_STATE, dtype=torch.float64, device=dev)
-        self.log_t = self.samples_t = None
-        self.chain_keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
-        # uint64 keys in an int64 tensor (the same bits)
-        self.keys_t = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in self.chain_keys], dtype=torch.int64).to(dev)
+        super().__init__(arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size, adapt_mass_matrix,
+                         len(q0s))
+        K, dev = self.K, self.device
+        self.keys_t = keys_tensor(self.chain_keys, dev)
         self.steps_t = torch.ones(K, dtype=torch.int32, device=dev)
         self.draw_ids_t = torch.zeros(K, dtype=torch.int32, device=dev)
         self.active_t = torch.ones(K, dtype=torch.int32, device=dev)
         self.active = None                                               # None: every chain; else the host's copy of active_t
         self._steps_host = [1] * K
-        sizes = [float(v) for v in step_size] if isinstance(step_size, (list, tuple)) else [float(step_size)] * K
-        if len(sizes) != K:
-            raise ValueError(f"{len(sizes)} step sizes for {K} chains")
-        self.step_size, self.num_steps = sizes, int(num_steps)
-        self.trajectory_length = [e * self.num_steps for e in sizes]
-        self.adapt_step_size, self.adapt_mass_matrix = bool(adapt_step_size), bool(adapt_mass_matrix)
-        self.eps_host = list(sizes)
-        self.searches = [0] * K
-        self.search_log = [[] for _ in range(K)]
-        self.launches = 0
-        self.fwd_launches = 2 if arch == "fc" else 4
-        self.cap = self.B = 0
+        self.cap = 0
         self.X = self.labels = self.rows_t = self.counts_t = None
-        self._ensure(int(batch_size))
-        self._set_state(eps=sizes, mu=[math.log(10 * e) for e in sizes])
-        self._bind()
-        self.eps_log = self.L_log = self.dH_log = self.accept_prob_log = self.accepted_log = None
+        self._start(batch_size)
 
     # -- buffers --------------------------------------------------------------------------------------------------------------------
     def _bind(self):
-        net = _hip.NnTrainNet()
-        net.arch, net.activation = _hip.ARCHS[self.arch], _hip.ACTIVATIONS[self.activation]
-        net.in_features, net.hidden, net.n_classes, net.n_members = self.D, self.H, self.C, self.K
+        net = self.descriptor(_hip.NnTrainNet, self.K)
         net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), self.n_params
         self.net = net
-        ch = _hip.HmcLockstep()
-        for name in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state"):
-            setattr(ch, name, getattr(self, name).data_ptr())
-        ch.log = None if self.log_t is None else self.log_t.data_ptr()
-        ch.samples = None if self.samples_t is None else self.samples_t.data_ptr()
-        ch.log_rows = 0 if self.log_t is None else int(self.log_t.shape[1])
-        ch.sample_rows = 0 if self.samples_t is None else int(self.samples_t.shape[1])
+        ch = self._chain_struct(_hip.HmcLockstep, 1)
         ch.keys, ch.steps = self.keys_t.data_ptr(), self.steps_t.data_ptr()
         ch.active = None if self.active is None else self.active_t.data_ptr()
         ch.chain_stride, ch.qpart_stride, ch.epart_stride = self.n_params, self.n_qpart, self.n_epart
@@ -402,9 +425,6 @@ class LockstepHmc:
         self.ws_t["correct"] = torch.zeros(self.K * B, dtype=torch.int32, device=self.device)
         self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
         self.cap = self.K * B
-
-    def unflat(self, buf):
-        return unflat(buf, self.keys, self.shapes)
 
     def _set_state(self, **kv):
         """Host -> device writes of state-block entries (warmup / set-up only): one value for every chain, or one per chain."""
@@ -434,9 +454,6 @@ class LockstepHmc:
             self._steps_host = list(Ls)
 
     # -- launches -------------------------------------------------------------------------------------------------------------------
-    def _st(self):
-        return _hip.stream_of(self.W)
-
     def _gradient(self):
         _hip.check(self.k.lib.rbnn_hmc_lockstep_gradient(C.byref(self.net), _hip.ptr(self.X), self.D, int(self.X.shape[0]), _hip.ptr(self.labels),
                                                          _hip.ptr(self.rows_t), _hip.ptr(self.counts_t), self.B, C.byref(self.ws), self._st()),
@@ -452,6 +469,14 @@ class LockstepHmc:
                                                          _hip.ptr(self.draw_ids_t) if per_chain else None, self._st()), "rbnn_hmc_lockstep_momentum")
         self.launches += 1
 
+    def _draw(self, i):
+        """The momenta of transition i, or (None) of the search's next probe: every chain's try counter goes to the device first."""
+        if i is None:
+            self.draw_ids_t.copy_(torch.tensor(self._searches, dtype=torch.int32))
+            self._momentum(_hip.HMC_SEARCH_KEY, 0, per_chain=True)
+        else:
+            self._momentum(0, i)
+
     def _decide(self, mode, transition=0, adapt=False, window_end=False):
         _hip.check(self.k.lib.rbnn_hmc_lockstep_decide(C.byref(self.net), C.byref(self.chain), _hip.ptr(self.ws_t["ce"]), _hip.ptr(self.counts_t),
                                                        self.B, int(transition), mode, int(adapt), int(window_end), self._st()),
@@ -463,15 +488,22 @@ class LockstepHmc:
                    "rbnn_hmc_lockstep_commit")
         self.launches += 1
 
-    # -- data -----------------------------------------------------------------------------------------------------------------------
-    def set_data(self, x, labels):
-        """The resident data the chains' batches are gathered from: x [n_rows, ...], labels int [n_rows]."""
-        n = int(x.shape[0])
-        self.X = x.reshape(n, -1).to(self.device, torch.float32).contiguous()
-        self.labels = labels.reshape(n).to(self.device, torch.int32).contiguous()
-        if self.X.shape[1] != self.D:
-            raise ValueError(f"the data have {self.X.shape[1]} features, the nets {self.D}")
+    def _window_end(self, n):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_window_end(C.byref(self.net), C.byref(self.chain), n, self._st()), "rbnn_hmc_lockstep_window_end")
+        self.launches += 1
 
+    def leapfrog(self, Ls):
+        """Chain k takes Ls[k] leapfrog steps (an int: every chain) from (q_cur, r) at its own step size: max(Ls) gradient + update launches,
+        the update of step s closing the chains whose length is s + 1 (steps_t).  -> the K lengths"""
+        Ls = [int(Ls)] * self.K if isinstance(Ls, int) else [int(v) for v in Ls]
+        self._set_steps(Ls)
+        self._update(_hip.HMC_OPEN)
+        for s in range(max(Ls)):
+            self._gradient()
+            self._update(_hip.HMC_MID, s)
+        return Ls
+
+    # -- data -----------------------------------------------------------------------------------------------------------------------
     def stage(self, rows=None, counts=None):
         """The chains' batches — rows [K, B] int32 into the resident data with counts [K] (None: B) of them valid per chain, or rows None: the
         whole resident data for every chain — and the potential / gradient at the current positions."""
@@ -494,131 +526,17 @@ class LockstepHmc:
         self._ensure(self.B)
         self.refresh()
 
-    def refresh(self):
-        self.W.copy_(self.q_cur)
-        self._gradient()
-        self._update(_hip.HMC_ENERGY)
-        self._decide(_hip.HMC_DECIDE_INIT)
-        self._commit(force=True)
-
-    # -- the chains -----------------------------------------------------------------------------------------------------------------
-    def length(self, k, eps=None):
-        return max(1, int(self.trajectory_length[k] / (self.eps_host[k] if eps is None else eps)))
-
-    def lengths(self):
-        return [self.length(k) for k in range(self.K)]
-
-    def leapfrog(self, Ls):
-        """Chain k takes Ls[k] leapfrog steps (an int: every chain) from (q_cur, r) at its own step size: max(Ls) gradient + update launches."""
-        Ls = [int(Ls)] * self.K if isinstance(Ls, int) else [int(v) for v in Ls]
-        self._set_steps(Ls)
-        self._update(_hip.HMC_OPEN)
-        for s in range(max(Ls)):
-            self._gradient()
-            self._update(_hip.HMC_MID, s)
-
-    def transition(self, i, Ls=None, adapt=False, window_end=False, welford_n=0, sample_row=-1):
-        """Transition i of every active chain, chain k with Ls[k] leapfrog steps (default: from the host's copies of the step sizes).  No
-        device->host synchronisation."""
-        Ls = self.lengths() if Ls is None else ([int(Ls)] * self.K if isinstance(Ls, int) else list(Ls))
-        self._momentum(0, i)
-        self.leapfrog(Ls)
-        self._decide(_hip.HMC_DECIDE_TRANSITION, i, adapt, window_end)
-        self._commit(False, welford_n, sample_row)
-        return Ls
-
-    def _probe(self, eps, live):
-        """One try of the search for the chains in `live`: -> the K values of dH (a frozen chain's is its last one)."""
-        self.set_active(live)
-        self._set_state(eps=eps)                                         # a frozen chain's entry is the value its block already holds
-        self.draw_ids_t.copy_(torch.tensor(self.searches, dtype=torch.int32))
-        self._momentum(_hip.HMC_SEARCH_KEY, 0, per_chain=True)
-        for k in range(self.K):
-            self.searches[k] += int(live[k])
-        self.leapfrog(1)
-        self._decide(_hip.HMC_DECIDE_PROBE)
-        return [s["dH"] for s in self.read_state()]
-
-    def find_reasonable_step_size(self):
-        """HmcSampler's search for every chain at once: all chains probe together, each with its own try counter; a chain whose direction has
-        flipped is frozen (active = 0) while the others go on."""
-        log08, K = math.log(0.8), self.K
-        eps, tries, live = list(self.eps_host), [[] for _ in range(K)], [True] * K
-        dH = self._probe(eps, live)
-        direction = [1 if -dH[k] > log08 else -1 for k in range(K)]
-        for k in range(K):
-            tries[k].append((eps[k], dH[k]))
-        while any(live):
-            for k in range(K):
-                if live[k]:
-                    if len(tries[k]) > MAX_SEARCH:
-                        raise RuntimeError(f"the HMC step-size search of chain {k} did not end after {MAX_SEARCH} tries (last eps {eps[k]:g}, "
-                                           f"dH {dH[k]:g})")
-                    eps[k] = eps[k] * 2.0 ** direction[k]
-            dH = self._probe(eps, live)
-            for k in range(K):
-                if live[k]:
-                    tries[k].append((eps[k], dH[k]))
-                    live[k] = (1 if -dH[k] > log08 else -1) == direction[k]
-        self.set_active(None)
-        for k in range(K):
-            self.search_log[k].append(tries[k])
-        self.eps_host = eps
-        self._set_state(eps=eps, t=0.0, gbar=0.0, xbar=0.0, mu=[math.log(10 * e) for e in eps])
-
     def run(self, x=None, labels=None, num_samples=0, warmup=0, rows=None, counts=None):
         """`warmup` adapting transitions, then num_samples at fixed step sizes and lengths, of all chains.  run(x, labels, …): every chain on
         that batch; run(rows=[K, B], counts=[K] or None, …): chain k on rows[k, :counts[k]] of the resident data (set_data).  Returns one
         stack dict per chain (state_dict key -> [num_samples, ...], device tensors); eps_log / L_log / dH_log / accept_prob_log / accepted_log /
         search_log are lists with one entry per chain, m_inv is [K, n_params]."""
-        num_samples, warmup = int(num_samples), int(warmup)
-        total, K = warmup + num_samples, self.K
         if x is not None:
             if rows is not None:
                 raise ValueError("run() takes a batch (x, labels) or rows into the resident data, not both")
             self.set_data(x, labels)
-        self.log_t = torch.zeros(K, max(1, total), _hip.HMC_LOG, dtype=torch.float64, device=self.device)
-        self.samples_t = torch.zeros(K, max(1, num_samples), self.n_params, dtype=torch.float32, device=self.device)
-        self._bind()
-        self.stage(rows, counts)
-        Ls = [[] for _ in range(K)]
-
-        def note(L):
-            for k in range(K):
-                Ls[k].append(L[k])
-
-        if warmup > 0 and self.adapt_step_size:
-            self.find_reasonable_step_size()
-        for (a, b, kind) in windows(warmup):
-            mid = kind == "middle" and self.adapt_mass_matrix
-            for i in range(a, b):
-                last = i == b - 1
-                note(self.transition(i, None, self.adapt_step_size, last, (i - a + 1) if mid else 0))
-                if last and mid:
-                    _hip.check(self.k.lib.rbnn_hmc_lockstep_window_end(C.byref(self.net), C.byref(self.chain), b - a, self._st()),
-                               "rbnn_hmc_lockstep_window_end")
-                    self.launches += 1
-                if self.adapt_step_size:
-                    self.eps_host = [s["eps"] for s in self.read_state()]   # warmup's one read per transition: the K step sizes
-                    if last and b < warmup:                                # the last window's exp(xbar) is kept, as in HmcSampler.run
-                        self.find_reasonable_step_size()
-        self._set_steps(self.lengths())                                   # host -> device, before the sampling phase
-        self.sample(warmup, num_samples, note)
-        log = self.log_t[:, :total].cpu()                                 # the one read of the sampling phase
-        self.log = log
-        self.eps_log, self.dH_log, self.accept_prob_log = log[:, :, 0].tolist(), log[:, :, 1].tolist(), log[:, :, 2].tolist()
-        self.accepted_log = [[bool(v) for v in row] for row in log[:, :, 3].tolist()]
-        self.L_log = Ls
-        return [self.unflat(self.samples_t[k, :num_samples]) for k in range(K)]
-
-    def sample(self, first, num_samples, note=None):
-        """num_samples transitions first, first + 1, ... at the fixed step sizes and lengths; row i of every chain's stack = its position after
-        transition first + i.  No device->host synchronisation (the lengths are on the device since the end of warmup)."""
-        Ls = self.lengths()
-        for i in range(num_samples):
-            self.transition(first + i, Ls, False, False, 0, i)
-            if note is not None:
-                note(Ls)
+        self._run(num_samples, warmup, rows, counts)
+        return [self.unflat(self.samples_t[k, :int(num_samples)]) for k in range(self.K)]
 
 
 def split_r_hat(values):

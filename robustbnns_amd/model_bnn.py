@@ -28,6 +28,7 @@ from torch import nn
 
 from . import _hip
 from .factory import make_engine, posterior_from_stacked, posterior_from_state_dicts
+from .flat_params import require_gpu_fc, state_shapes
 from .model_nn import NN
 from .savedir import TESTS
 
@@ -111,7 +112,7 @@ def svi_lockstep_prologue(net):
     set_rng_seed(0)
     iter(DataLoader([0], batch_size=1))
     if net.svi_loc is None:
-        loc, raw = initial_params([(k, tuple(v.shape)) for k, v in net.basenet.state_dict().items()])
+        loc, raw = initial_params(state_shapes(net.basenet))
     else:
         loc, raw = net.svi_loc, net.svi_scale
     return loc, raw, draw_key()
@@ -131,10 +132,8 @@ def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS,
         if net.inference != "svi":
             raise NotImplementedError("train() runs SVI only: sample an HMC posterior (fc / fc2) with BNN.train_hmc(train_loader, device), "
                                       "or run it with the reference and load the chain here")
-        if net.basenet.architecture not in ("fc", "fc2"):
-            raise NotImplementedError(f"SVI training covers fc and fc2, not {net.basenet.architecture!r} (conv needs conv weight gradients)")
-    if torch.device(device).type != "cuda":
-        raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        require_gpu_fc("SVI training", net.basenet.architecture)
+    require_gpu_fc("SVI training", device=device)
     b0 = nets[0].basenet
     shape_of = lambda b: (b.architecture, b.activation, tuple(b.input_shape), int(b.output_size), int(b.hidden_size))
     for net in nets[1:]:
@@ -287,7 +286,7 @@ class BNN(nn.Module):
         """eps per draw in the order the guide consumes the RNG ([recalled]): for every
         state_dict key two discarded randn_like (the eagerly evaluated pyro.param initialisers,
         model_bnn.py:125-126), then one standard normal per parameter in named_parameters() order."""
-        shapes = [(k, tuple(v.shape)) for k, v in self.basenet.state_dict().items()]
+        shapes = state_shapes(self.basenet)
         total = sum(int(np.prod(s)) for _, s in shapes)
         if self.svi_rng == "device" and torch.device(self.device).type == "cuda":
             if not seeds:
@@ -433,10 +432,8 @@ class BNN(nn.Module):
         if self.inference == "hmc":
             raise NotImplementedError("train() runs SVI only: sample an HMC posterior (fc / fc2) with BNN.train_hmc(train_loader, device), "
                                       "or run it with the reference and load the chain here")
-        if self.basenet.architecture not in ("fc", "fc2"):
-            raise NotImplementedError(f"SVI training covers fc and fc2, not {self.basenet.architecture!r} (conv needs conv weight gradients)")
-        if torch.device(device).type != "cuda":
-            raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        require_gpu_fc("SVI training", self.basenet.architecture)
+        require_gpu_fc("SVI training", device=device)
         from .svi_train import SviTrainer, draw_key, initial_params
         self.device = device
         self.basenet.device = device
@@ -450,7 +447,7 @@ class BNN(nn.Module):
             for x_batch, y_batch in train_loader:
                 if trainer is None:
                     if self.svi_loc is None:
-                        loc, raw = initial_params([(k, tuple(v.shape)) for k, v in b.state_dict().items()])
+                        loc, raw = initial_params(state_shapes(b))
                     else:
                         loc, raw = self.svi_loc, self.svi_scale
                     trainer = SviTrainer(b.architecture, b.activation, b.input_shape, b.output_size, loc, raw, self.lr, device,
@@ -489,10 +486,8 @@ class BNN(nn.Module):
             raise ValueError(f"train_hmc() samples an HMC posterior; this net's inference is {self.inference!r} (use train())")
         if int(num_chains) < 1:
             raise ValueError(f"train_hmc() needs num_chains >= 1, not {num_chains}")
-        if self.basenet.architecture not in ("fc", "fc2"):
-            raise NotImplementedError(f"HMC covers fc and fc2, not {self.basenet.architecture!r} (conv needs conv weight gradients)")
-        if torch.device(device).type != "cuda":
-            raise NotImplementedError(f"HMC runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
+        require_gpu_fc("HMC", self.basenet.architecture)
+        require_gpu_fc("HMC", device=device)
         from .hmc import HmcSampler, LockstepHmc
         x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
         b, K = self.basenet, int(num_chains)
@@ -506,10 +501,9 @@ class BNN(nn.Module):
         else:
             from .hmc import initial_position
             from .svi_train import draw_key
-            shapes = [(k, tuple(v.shape)) for k, v in b.state_dict().items()]
             q0s, keys = [q0], [key]
             for _ in range(1, K):
-                q0s.append(initial_position(shapes))
+                q0s.append(initial_position(state_shapes(b)))
                 keys.append(draw_key())
             sampler = LockstepHmc(b.architecture, b.activation, b.input_shape, b.output_size, q0s, self.step_size, self.num_steps, device, keys,
                                   batch_size=int(x_batch.shape[0]))
@@ -540,7 +534,7 @@ class BNN(nn.Module):
             pass
         if x_batch is None:
             raise ValueError("train_hmc() needs a loader with at least one batch")
-        q0 = initial_position([(k, tuple(v.shape)) for k, v in self.basenet.state_dict().items()])
+        q0 = initial_position(state_shapes(self.basenet))
         return x_batch, y_batch, batch_samples, q0, draw_key()
 
     def evaluate(self, test_loader, device, n_samples=10, seeds_list=None):

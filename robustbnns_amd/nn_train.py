@@ -19,41 +19,29 @@ import numpy as np
 import torch
 
 from . import _hip
-from .flat_params import flatten, train_workspace, unflat, ws_struct
-from .posterior import LAYER_KEYS, round_up
-from .svi_train import ADAM_EPS, BETAS, state_keys
+from .flat_params import FlatNets, flatten, require_gpu_fc, train_workspace, ws_struct
+from .posterior import round_up
+from .svi_train import ADAM_EPS, BETAS
 
 ENSEMBLE_BATCH = 100                    # model_ensemble.py:73
 
 
-class NnTrainer:
+class NnTrainer(FlatNets):
     """Device-resident training state of M fc / fc2 nets of one shape: flat parameters, Adam moments and gradients [M, n_params], the
     workspaces [M, B, .] and a device-side accumulator stats [M, 3] = [step loss, sum of step losses, correct predictions]."""
 
     def __init__(self, arch, activation, input_shape, n_classes, params, lr, device, batch_size=ENSEMBLE_BATCH):
         check_trainable(arch, device)
-        dev = torch.device(device)
         if isinstance(params, dict):
             params = [params]
-        self.k = _hip.HipKernels()
-        self.arch, self.activation, self.device = arch, activation, dev
-        self.input_shape = tuple(int(v) for v in input_shape)
-        self.keys = state_keys(arch)
-        self.shapes = {k: tuple(params[0][k].shape) for k in self.keys}
-        self.M = len(params)
-        self.D = int(np.prod(self.input_shape))
+        super().__init__(arch, activation, input_shape, n_classes, params[0], device, members=len(params))
+        dev, self.M = self.device, len(params)
         self.Dp = round_up(self.D, 16)
-        self.H, self.C = int(self.shapes[self.keys[1]][0]), int(n_classes)
-        net = _hip.NnTrainNet()
-        net.arch, net.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
-        net.in_features, net.hidden, net.n_classes, net.n_members = self.D, self.H, self.C, self.M
-        n = int(self.k.lib.rbnn_nn_train_sizes(C.byref(net)))
-        _hip.check(min(n, 0), "rbnn_nn_train_sizes")
-        self.n_params = n
+        net = self.descriptor(_hip.NnTrainNet, self.M)
+        self.n_params = n = self.sizes("rbnn_nn_train_sizes", net)
         self.P = torch.stack([flatten(d, self.keys) for d in params]).to(dev)
         assert tuple(self.P.shape) == (self.M, n), (tuple(self.P.shape), self.M, n)
-        z = lambda: torch.zeros(self.M, n, dtype=torch.float32, device=dev)
-        self.m, self.v, self.grad = z(), z(), z()
+        self.m, self.v, self.grad = self.zeros(n), self.zeros(n), self.zeros(n)
         for name in ("P", "m", "v", "grad"):
             setattr(net, name, getattr(self, name).data_ptr())
         net.member_stride = n
@@ -67,7 +55,7 @@ class NnTrainer:
 
     def unflat(self, buf, member=0):
         """state_dict key -> view of member `member` of `buf` (one of the flat buffers) in that tensor's shape."""
-        return unflat(buf[member], self.keys, self.shapes)
+        return super().unflat(buf[member])
 
     def _ensure(self, B):
         """Workspaces for batches of up to B points per member (grown, never shrunk; a call packs them [M, its own B, .])."""
@@ -137,10 +125,7 @@ class NnTrainer:
 
 def check_trainable(arch, device):
     """The guards of NnTrainer, also for callers that have host work to do before they construct one."""
-    if torch.device(device).type != "cuda":
-        raise NotImplementedError(f"deterministic training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-    if arch not in LAYER_KEYS:
-        raise NotImplementedError(f"deterministic training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+    require_gpu_fc("deterministic training", arch, device)
 
 
 def seed_all(seed):

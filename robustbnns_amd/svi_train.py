@@ -18,22 +18,17 @@ regenerates it instead of storing it.  Seed-for-seed parity with pyro's own RNG 
 """
 import ctypes as C
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import _hip
-from .flat_params import flatten, train_workspace, unflat, ws_struct
-from .posterior import LAYER_KEYS, StackedPosterior, SviGuide, padded_hidden, round_up
+from .flat_params import FlatNets, flatten, keys_tensor, require_gpu_fc, set_data, state_keys, train_workspace, ws_struct
+from .posterior import StackedPosterior, SviGuide, padded_hidden, round_up
 
 BETAS = (0.9, 0.999)                    # torch.optim.Adam defaults, what pyro.optim.Adam({"lr": lr}) wraps
 ADAM_EPS = 1e-8
 ACC_SAMPLES = 10                        # model_bnn.py:327
 ACC_KEY = 0x9E3779B97F4A7C15            # xor-ed into the training key: the accuracy forward's draws are a stream of their own
-
-
-def state_keys(arch):
-    return [k + sfx for k in LAYER_KEYS[arch] for sfx in (".weight", ".bias")]
 
 
 def initial_params(shapes):
@@ -72,40 +67,26 @@ class _LiveGuide:
         self._desc = None
 
 
-class SviTrainer:
+class SviTrainer(FlatNets):
     """Device-resident SVI state of one fc / fc2 guide: flat loc / raw / sigma / Adam moments, the one-sample weight buffer, the workspaces,
     the resident S = 10 stack of the accuracy forward and a device-side accumulator [step loss, sum of losses, correct predictions]."""
 
     def __init__(self, arch, activation, input_shape, n_classes, loc, raw, lr, device, key, batch_size=128):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-        if arch not in LAYER_KEYS:
-            raise NotImplementedError(f"SVI training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
-        self.k = _hip.HipKernels()
-        self.arch, self.activation, self.device = arch, activation, dev
-        self.input_shape = tuple(int(v) for v in input_shape)
-        self.keys = state_keys(arch)
-        self.shapes = {k: tuple(loc[k].shape) for k in self.keys}
-        self.D = int(np.prod(self.input_shape))
+        require_gpu_fc("SVI training", arch, device)
+        super().__init__(arch, activation, input_shape, n_classes, loc, device)
+        dev, z = self.device, self.zeros
         self.Dp = round_up(self.D, 16)
-        self.H, self.C = int(self.shapes[self.keys[1]][0]), int(n_classes)
-        net = _hip.SviTrainNet()
-        net.arch, net.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
-        net.in_features, net.hidden, net.n_classes = self.D, self.H, self.C
-        n_part = C.c_int64(0)
-        n = int(self.k.lib.rbnn_svi_train_sizes(C.byref(net), C.byref(n_part)))
-        _hip.check(min(n, 0), "rbnn_svi_train_sizes")
+        net, n_part = self.descriptor(_hip.SviTrainNet), C.c_int64(0)
+        n = self.sizes("rbnn_svi_train_sizes", net, n_part)
         self.n_params, self.n_partials = n, int(n_part.value)
         self.loc, self.raw = flatten(loc, self.keys).to(dev), flatten(raw, self.keys).to(dev)
         assert self.loc.numel() == n, (self.loc.numel(), n)
         self.sigma = F.softplus(self.raw)
-        z = lambda: torch.zeros(n, dtype=torch.float32, device=dev)
-        self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(), z(), z(), z(), z(), z()
+        self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(n), z(n), z(n), z(n), z(n), z(n)
         for name in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "W", "grad"):
             setattr(net, name, getattr(self, name).data_ptr())
         self.net = net
-        self.kl_part = torch.zeros(self.n_partials, dtype=torch.float32, device=dev)
+        self.kl_part = z(self.n_partials)
         self.stats = torch.zeros(3, dtype=torch.float64, device=dev)
         self.lr, self.key, self.t = float(lr), int(key) & 0xFFFFFFFFFFFFFFFF, 0
         roles = ("W1", "b1", "W2", "b2") if arch == "fc" else ("W1", "b1", "Wm", "bm", "W2", "b2")
@@ -123,10 +104,6 @@ class SviTrainer:
         self.accuracy_supported = Hp in (32, 64) or Hp % 128 == 0
         self.Bmax = 0
         self._ensure(int(batch_size))
-
-    def unflat(self, buf):
-        """state_dict key -> view of `buf` (one of the flat buffers) in that tensor's shape."""
-        return unflat(buf, self.keys, self.shapes)
 
     def _ensure(self, B):
         """Workspaces for batches of up to B points (grown, never shrunk: a short last batch reuses them)."""
@@ -194,7 +171,7 @@ class SviTrainer:
         return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
 
 
-class LockstepSvi:
+class LockstepSvi(FlatNets):
     """K SVI guides of ONE net shape (arch, activation, input shape, hidden size, classes) trained in lockstep: every launch of a step covers
     all K guides (csrc/rbnn_svi_lockstep.hip; the guide is grid dimension y).  Guide k has its own parameters, key, learning rate and batches —
     rows[k, :counts[k]] of the resident data (set_data) — and is bit-identical to an SviTrainer stepped alone on the same batches, except for the
@@ -207,11 +184,7 @@ class LockstepSvi:
     rows, epoch ends) is uploaded once before the first step, the epoch sums are written to a device log and read once after the last."""
 
     def __init__(self, arch, activation, input_shape, n_classes, locs, raws, lrs, device, keys, batch_size=64):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NotImplementedError(f"SVI training runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
-        if arch not in LAYER_KEYS:
-            raise NotImplementedError(f"SVI training covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+        require_gpu_fc("SVI training", arch, device)
         K = len(locs)
         if K < 1:
             raise ValueError("LockstepSvi needs at least one guide")
@@ -222,46 +195,35 @@ class LockstepSvi:
             raise ValueError(f"{len(lrs)} learning rates for {K} guides")
         if K * ACC_SAMPLES > 65535:
             raise ValueError(f"{K} guides x {ACC_SAMPLES} accuracy samples exceed the 65535 nets of one launch")
-        self.state_keys = state_keys(arch)
-        self.shapes = {k: tuple(locs[0][k].shape) for k in self.state_keys}
+        shapes = {k: tuple(locs[0][k].shape) for k in state_keys(arch)}
         for i in range(K):
             for d in (locs[i], raws[i]):
-                if {k: tuple(d[k].shape) for k in self.state_keys} != self.shapes:
+                if {k: tuple(d[k].shape) for k in shapes} != shapes:
                     raise ValueError(f"guide {i} has another net shape than guide 0: lockstep guides share one (arch, hidden, classes, input)")
-        self.k = _hip.HipKernels()
-        self.K, self.arch, self.activation, self.device = K, arch, activation, dev
-        self.input_shape = tuple(int(v) for v in input_shape)
-        self.D = int(np.prod(self.input_shape))
-        self.H, self.C = int(self.shapes[self.state_keys[1]][0]), int(n_classes)
-        one = _hip.SviTrainNet()
-        one.arch, one.activation = _hip.ARCHS[arch], _hip.ACTIVATIONS[activation]
-        one.in_features, one.hidden, one.n_classes = self.D, self.H, self.C
-        n_part = C.c_int64(0)
-        n = int(self.k.lib.rbnn_svi_train_sizes(C.byref(one), C.byref(n_part)))
-        _hip.check(min(n, 0), "rbnn_svi_train_sizes")
+        super().__init__(arch, activation, input_shape, n_classes, locs[0], device, members=K)
+        self.K, n_part = K, C.c_int64(0)
+        n = self.sizes("rbnn_svi_train_sizes", self.descriptor(_hip.SviTrainNet), n_part)
         self.n_params, self.n_partials = n, int(n_part.value)
         # what SviTrainer refuses, refused the same way: the sizes its accuracy stack (rbnn_svi_draw) and accuracy forward (rbnn_fc_forward) cover
         Hp = padded_hidden(self.H)
         if not accuracy_draw_covered(self.k, arch, self.D, self.H, self.C):
             raise NotImplementedError(f"{arch} hidden {self.H}, {self.C} classes: outside what rbnn_svi_draw covers (the accuracy forward's draw)")
         self.accuracy_supported = Hp in (32, 64) or Hp % 128 == 0
-        self.loc = torch.stack([flatten(d, self.state_keys) for d in locs]).to(dev)
+        self.loc = torch.stack([flatten(d, self.state_keys) for d in locs]).to(self.device)
         self.device = dev = self.loc.device                  # "cuda" names the current card: step() compares against where the buffers are
         self.raw = torch.stack([flatten(d, self.state_keys) for d in raws]).to(dev)
         assert tuple(self.loc.shape) == (K, n), (tuple(self.loc.shape), K, n)
         self.sigma = F.softplus(self.raw)
-        z = lambda m=n: torch.zeros(K, m, dtype=torch.float32, device=dev)
-        self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(), z(), z(), z(), z(), z()
+        z = self.zeros
+        self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(n), z(n), z(n), z(n), z(n), z(n)
         self.kl_part = z(self.n_partials)
         self.stats = torch.zeros(K, 3, dtype=torch.float64, device=dev)
         self.keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
-        self.keys_t = torch.tensor([k - (1 << 64) if k >= (1 << 63) else k for k in self.keys], dtype=torch.int64).to(dev)
+        self.keys_t = keys_tensor(self.keys, dev)
         self.lrs = lrs
         self.lr_t = torch.tensor(lrs, dtype=torch.float64).to(dev)
         self.t = 0
-        net = _hip.NnTrainNet()
-        net.arch, net.activation = one.arch, one.activation
-        net.in_features, net.hidden, net.n_classes, net.n_members = self.D, self.H, self.C, K
+        net = self.descriptor(_hip.NnTrainNet, K)
         net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), n
         self.net = net
         g = _hip.SviLockstep()
@@ -287,18 +249,8 @@ class LockstepSvi:
         self.rows_t = torch.zeros(K, self.B, dtype=torch.int32, device=dev)
         self._arange = torch.arange(self.B, dtype=torch.int32, device=dev).unsqueeze(0)
         self.launches = 0
-        self.fwd_launches = 2 if arch == "fc" else 4
 
-    def unflat(self, buf):
-        return unflat(buf, self.state_keys, self.shapes)
-
-    def set_data(self, x, labels):
-        """The resident data the guides' batches are gathered from: x [n_rows, ...], labels int [n_rows]."""
-        n = int(x.shape[0])
-        self.X = x.reshape(n, -1).to(self.device, torch.float32).contiguous()
-        self.labels = labels.reshape(n).to(self.device, torch.int32).contiguous()
-        if self.X.shape[1] != self.D:
-            raise ValueError(f"the data have {self.X.shape[1]} features, the nets {self.D}")
+    set_data = set_data
 
     def step(self, rows, counts, accuracy=True, epoch_slot=None):
         """One SVI step of every guide with counts[k] > 0 on rows[k, :counts[k]] of the resident data.  rows: int32 device tensor [K, batch_size]
