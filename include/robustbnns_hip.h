@@ -801,6 +801,64 @@ int rbnn_svi_multi_finalize(const rbnn_nn_train_net *net, const rbnn_svi_multi *
                                const int32_t *labels, int32_t n_rows, const int32_t *rows, const int32_t *counts, int32_t n_points,
                                const int32_t *epoch_slot, double *epoch_log, int32_t log_rows, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic training of ONE conv net of the 1x28x28 geometry (csrc/rbnn_conv_train.hip): torch.optim.Adam on nn.CrossEntropyLoss()
+ * (model_nn.py:175-219) for Conv2d(1,32,5) -> act -> MaxPool2d(2) -> Conv2d(32,Hc,5) -> act -> MaxPool2d(2, stride 1) -> Flatten ->
+ * Linear(49 Hc, C), all four activations.  Issued in this order on one stream:  train_forward -> weight_grads -> adam_step -> train_finalize.
+ * Parameters, Adam moments and gradients are flat buffers in state_dict order (model.0.weight, model.0.bias, model.3.weight, model.3.bias,
+ * model.7.weight, model.7.bias), unpadded, row-major in nn.Conv2d's / nn.Linear's element order: the tensors start at floats 0, 800, 832,
+ * 832 + 800 Hc, 832 + 801 Hc, 832 + 801 Hc + 49 Hc C.  The batch is a staged matrix X [B, ldx] (16-byte aligned, ldx >= 784 and a multiple
+ * of 4) with int32 labels [B].  The forward is the exact fp32-MFMA conv forward above with one sample and logits out; the backward reads
+ * the stashes it leaves.  No atomics and no device->host synchronisation: every sum has one fixed order, two runs are bit-identical.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_conv_train_net {
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_channels, in_width; /* 1, 28 (anything else: RBNN_ERR_UNSUPPORTED)                                  */
+    int32_t hidden;                /* Hc = conv2 output channels, a multiple of 16                                 */
+    int32_t n_classes;             /* C in [1, 16]                                                                 */
+    int32_t reserved;
+    float *P;                      /* [n_params] parameters (16-byte aligned)                                      */
+    float *m, *v;                  /* [n_params] Adam moments (zero before the first step)                         */
+    float *grad;                   /* [n_params] dL/dP of the step (L = mean CE of the batch)                      */
+} rbnn_conv_train_net;
+
+typedef struct rbnn_conv_train_ws {   /* caller-owned, for up to B points; every buffer 16-byte aligned             */
+    float   *logits;               /* [B, 16]                                                                      */
+    float   *P1;                   /* [B, 32, 12, 12] pooled + activated conv1 output (allocated 24 KiB per point) */
+    uint8_t *st1;                  /* [B, 32 * 144] pool-1 stash (the encoding of rbnn_conv_workspace)             */
+    float   *Q2;                   /* [B, 49 Hc] pooled + activated conv2 output                                   */
+    uint8_t *st2;                  /* [B, 49 Hc] pool-2 stash                                                      */
+    float   *dZ;                   /* [B, 16] dL/dlogits = (softmax - e_y) / B                                     */
+    float   *ce;                   /* [B] cross-entropy per point                                                  */
+    int32_t *correct;              /* [B] 1 where the first maximum of the logits is the label                     */
+    float   *dO2;                  /* [B, Hc, 8, 8] dL/d(conv2 pre-activation)                                     */
+    float   *dO1;                  /* [B, 32, 24, 24] dL/d(conv1 pre-activation)                                   */
+    float   *part2;                /* [splits2, Hc, 801] partial sums of dK2 | dK2b over slices of the batch       */
+    float   *part1;                /* [splits1, 32, 26] partial sums of dK1 | dK1b                                 */
+    float   *partP;                /* [splitsP, B, 144, 32] partial sums of dL/d(pooled conv1 output) over slices of the conv2 channels */
+} rbnn_conv_train_ws;
+
+typedef struct rbnn_conv_train_bytes {   /* n_params and the bytes of every rbnn_conv_train_ws buffer for B points */
+    int64_t n_params;
+    size_t logits, P1, st1, Q2, st2, dZ, ce, correct, dO2, dO1, part2, part1, partP;
+} rbnn_conv_train_bytes;
+
+/* [host] n_params and the workspace sizes for n_points points. */
+int rbnn_conv_train_sizes(const rbnn_conv_train_net *net, int32_t n_points, rbnn_conv_train_bytes *out);
+/* The training forward (conv1 + pool, conv2 + pool, Linear: 3 launches) and the head (1 launch): logits, ce, dZ, correct.  labels: int32
+ * [n_points] in [0, C). */
+int rbnn_conv_train_forward(const rbnn_conv_train_net *net, const float *X, int32_t ldx, const int32_t *labels, int32_t n_points,
+                            const rbnn_conv_train_ws *ws, void *stream);
+/* grad = dL/dP of all six tensors (fp32 MFMA; every conv contraction is split across blocks and the partial sums added in a second,
+ * fixed-order pass): 7 launches. */
+int rbnn_conv_weight_grads(const rbnn_conv_train_net *net, const float *X, int32_t ldx, int32_t n_points, const rbnn_conv_train_ws *ws,
+                           void *stream);
+/* One torch.optim.Adam step (single-tensor formula, no weight decay) on P; `step` = the step number t >= 1 of the bias corrections; the
+ * formula and roundings of rbnn_nn_adam_step. */
+int rbnn_conv_adam_step(const rbnn_conv_train_net *net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void *stream);
+/* One block, fixed order, fp64: stats = [the fp32-rounded mean of ce (the step's loss), += it, += sum correct]. */
+int rbnn_conv_train_finalize(const rbnn_conv_train_ws *ws, int32_t n_points, double *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

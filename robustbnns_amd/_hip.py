@@ -102,6 +102,22 @@ class NnTrainWs(C.Structure):
     _fields_ = [(k, _fp) for k in NN_TRAIN_WS_KEYS]
 
 
+class ConvTrainNet(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("activation", "in_channels", "in_width", "hidden", "n_classes", "reserved")] + \
+               [(k, _fp) for k in ("P", "m", "v", "grad")]
+
+
+CONV_TRAIN_WS_KEYS = ("logits", "P1", "st1", "Q2", "st2", "dZ", "ce", "correct", "dO2", "dO1", "part2", "part1", "partP")
+
+
+class ConvTrainWs(C.Structure):
+    _fields_ = [(k, _fp) for k in CONV_TRAIN_WS_KEYS]
+
+
+class ConvTrainBytes(C.Structure):
+    _fields_ = [("n_params", C.c_int64)] + [(k, C.c_size_t) for k in CONV_TRAIN_WS_KEYS]
+
+
 class HmcChain(C.Structure):
     _fields_ = [(k, _fp) for k in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state", "log", "samples")] + \
                [("log_rows", C.c_int64), ("sample_rows", C.c_int64)]
@@ -230,6 +246,11 @@ SIGNATURES = {
     "rbnn_nn_weight_grads": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
     "rbnn_nn_adam_step": (_i32, [C.POINTER(NnTrainNet), _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
     "rbnn_nn_train_finalize": (_i32, [C.POINTER(NnTrainNet), C.POINTER(NnTrainWs), _i32, _fp, _fp]),
+    "rbnn_conv_train_sizes": (_i32, [C.POINTER(ConvTrainNet), _i32, C.POINTER(ConvTrainBytes)]),
+    "rbnn_conv_train_forward": (_i32, [C.POINTER(ConvTrainNet), _fp, _i32, _fp, _i32, C.POINTER(ConvTrainWs), _fp]),
+    "rbnn_conv_weight_grads": (_i32, [C.POINTER(ConvTrainNet), _fp, _i32, _i32, C.POINTER(ConvTrainWs), _fp]),
+    "rbnn_conv_adam_step": (_i32, [C.POINTER(ConvTrainNet), _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
+    "rbnn_conv_train_finalize": (_i32, [C.POINTER(ConvTrainWs), _i32, _fp, _fp]),
     "rbnn_hmc_sizes": (_i64, [C.POINTER(SviTrainNet), C.POINTER(_i64), C.POINTER(_i64)]),
     "rbnn_hmc_momentum": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), C.c_uint64, C.c_uint32, _fp]),
     "rbnn_hmc_leapfrog_update": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _fp]),

@@ -1,0 +1,456 @@
+// rbnn_conv_train.hip — deterministic training of ONE conv net of the 1x28x28 geometry (model_nn.py:93-106, 175-219: torch.optim.Adam on
+// nn.CrossEntropyLoss()):  Conv2d(1,32,5) -> act -> MaxPool2d(2) -> Conv2d(32,Hc,5) -> act -> MaxPool2d(2, stride 1) -> Flatten -> Linear(49 Hc, C).
+//
+//      rbnn_conv_train_forward    the exact fp32-MFMA forward of rbnn_conv.hip (one sample, logits out: P1, st1, Q2, st2 stay behind for the
+//                                 backward; 3 launches) and the head: CE per point, dZ = (softmax - e_y) / B, correct (1 launch)
+//      rbnn_conv_weight_grads     dFw | dFb      = dZ^T [Q2 | 1]                              the strided GEMM of rbnn_train_gemm.hpp
+//                                 dO2            = (dZ Fw) gathered through the pool-2 stash, times act'                (conv_do2_kernel)
+//                                 dP1            = conv2^T(dO2), per slice of the conv2 channels                        (GEMM, mode G_DP1)
+//                                 dO1            = the slices of dP1 added, routed through the pool-1 stash, times act' (conv_route1_kernel)
+//                                 dK2 | dK2b     = sum over (point, position) of dO2 x [P1 patch | 1], per batch slice  (GEMM, mode G_DK2)
+//                                 dK1 | dK1b     = sum over (point, position) of dO1 x [x patch | 1], per batch slice   (GEMM, mode G_DK1)
+//                                 the slices' partial sums added in one fixed order, fp64                               (conv_reduce_kernel)
+//      rbnn_conv_adam_step        torch.optim.Adam's single-tensor formula on the flat buffer (adam_one of rbnn_train_core.hpp): 1 launch
+//      rbnn_conv_train_finalize   the fp32-rounded mean CE of the step, its running sum, the correct predictions (fp64, fixed order): 1 launch
+//
+// Parameters, moments and gradients are flat fp32 buffers in state_dict order, unpadded (the convention of the fc trainers).  One stream, no
+// atomics, no device->host synchronisation: every output element is one lane's sum in one order, two runs are bit-identical.
+// The three conv GEMMs are one kernel text (conv_wgrad_gemm_kernel): 64 x 64 (G_DP1: 64 x 32) output tiles of the fp32 MFMA, K staged 16 at
+// a time through LDS (the next stage's operands are fetched into registers while this one's MFMAs run), both operands GATHERED by index
+// arithmetic (implicit im2col: nothing is unfolded in memory).  Every contraction is split across blocks (grid dimension y) — dK2 (B 64
+// terms) and dK1 (B 576 terms, with a 32 x 26 output) over the batch, dP1 (25 Hc terms) over the conv2 channels — and the slices' partial
+// sums are added in a second pass, in increasing order.
+#include "rbnn_conv_common.hpp"
+#include "rbnn_train_gemm.hpp"
+
+using namespace rbnn_conv_shared;
+
+namespace {
+
+constexpr int O1W = GeoMnist::O1, NO1 = O1W * O1W, DIN = GeoMnist::DIN, IW = GeoMnist::IW;     // 24, 576, 784, 28
+constexpr int PP1 = P1W * P1W;                                                                   // 144 pooled conv1 positions
+constexpr int N2 = K2 + 1, N1 = 25 + 1;                                                          // columns of a partial: the taps | the bias
+constexpr int MAX_SPLITS2 = 16, MAX_SPLITS1 = 128;
+constexpr int MAX_POINTS = 65536, MAX_HIDDEN = 4096;
+constexpr int DP1_BLOCKS = 2048;                                                                 // blocks the dP1 GEMM aims at (8 per CU)
+
+struct ConvLayout { long long K1w, K1b, K2w, K2b, Fw, Fb, n_params; };
+inline ConvLayout conv_layout(int Hc, int C) {
+    ConvLayout L;
+    L.K1w = 0; L.K1b = C1 * 25; L.K2w = L.K1b + C1; L.K2b = L.K2w + (long long)Hc * K2; L.Fw = L.K2b + Hc;
+    L.Fb = L.Fw + (long long)C * NP2 * Hc; L.n_params = L.Fb + C;
+    return L;
+}
+
+// points per slice and slices of the two split contractions: functions of B alone, never more than min(B, MAX_SPLITS) slices
+inline void slices(int B, int max_splits, int& per, int& n) {
+    per = (B + max_splits - 1) / max_splits;
+    n = (B + per - 1) / per;
+}
+
+// slices of dP1's contraction: groups of 16 conv2 channels (400 products) per slice, as many slices as bring the grid to DP1_BLOCKS
+inline void dp1_slices(int B, int Hc, int& per, int& n) {
+    const int tiles = (B * PP1 + GT - 1) / GT, groups = Hc / 16;
+    const int want = std::min(std::max(DP1_BLOCKS / tiles, 1), groups);
+    per = (groups + want - 1) / want;
+    n = (groups + per - 1) / per;
+}
+// floats of the dP1 partial sums for any batch of up to B points: slices <= DP1_BLOCKS 64 / (144 B) and <= Hc / 16, and >= 1
+inline size_t dp1_part_floats(int B, int Hc) {
+    const size_t point = (size_t)PP1 * C1, all = (size_t)(Hc / 16) * B * point;
+    return std::max((size_t)B * point, std::min((size_t)DP1_BLOCKS * GT * C1, all));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Head: one thread per point.  CE = logsumexp(z) - z_y, dZ = (softmax(z) - e_y) / B (ce_softmax_grad), correct = (first argmax == y): the
+// definitions of train_head_kernel.
+// ---------------------------------------------------------------------------------------------------
+struct ConvHeadArgs { const float* Z; const int32_t* labels; float *dZ, *ce; int32_t* correct; int B, C; float inv_B; };
+
+__global__ void __launch_bounds__(64) conv_head_kernel(const ConvHeadArgs a) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    float z[RBNN_CPAD], g[RBNN_CPAD];
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c) z[c] = a.Z[(long long)b * RBNN_CPAD + c];
+    const int y = a.labels[b];
+    ce_softmax_grad<RBNN_CPAD>(z, a.C, y, a.inv_B, g);
+    float m = -INFINITY, zy = 0.f;
+    int best = 0;
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c)
+        if (c < a.C) {
+            if (z[c] > m) { m = z[c]; best = c; }                         // strictly greater: the first maximum, as torch.argmax
+            if (c == y) zy = z[c];
+        }
+    float den = 0.f, rest = 0.f;
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c)
+        if (c < a.C) { const float e = expf(z[c] - m); den += e; if (c != y) rest += e; }
+    a.ce[b] = (zy == m) ? log1pf(rest) : logf(den) - (zy - m);
+    a.correct[b] = best == y ? 1 : 0;
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c) a.dZ[(long long)b * RBNN_CPAD + c] = g[c];
+}
+
+// ---------------------------------------------------------------------------------------------------
+// dO2[b, hc, 8 x 8]: one block = one point x 4 conv2 channels.  Phase 1 (4 x 49 threads): dQ2[f] = sum_c dZ[c] Fw[c, f] times act' (relu /
+// leaky: the stash's sign bit; sigmoid / tanh: from the value in Q2) into LDS beside the window's argmax.  Phase 2 (4 x 64 threads), GATHER
+// form: pool 2 has stride 1, so a position lies in up to 4 windows; it adds those that selected it in the fixed order (y-1, x-1), (y-1, x),
+// (y, x-1), (y, x).
+// ---------------------------------------------------------------------------------------------------
+struct ConvDo2Args { const float *dZ, *Fw, *Q2; const uint8_t* st2; float* dO2; int Hc, C; };
+
+template <int ACT> __global__ void __launch_bounds__(256) conv_do2_kernel(const ConvDo2Args a) {
+    __shared__ float gs[4][NP2];
+    __shared__ int as[4][NP2];
+    const int t = threadIdx.x, groups = a.Hc >> 2;
+    const int b = blockIdx.x / groups, hc0 = 4 * (blockIdx.x % groups);
+    const int F = a.Hc * NP2;
+    if (t < 4 * NP2) {
+        const int hl = t / NP2, p = t % NP2;
+        const long long f = (long long)(hc0 + hl) * NP2 + p;
+        float dq = 0.f;
+        for (int c = 0; c < a.C; ++c) dq = fmaf(a.dZ[(long long)b * RBNN_CPAD + c], a.Fw[(long long)c * F + f], dq);
+        const int st = a.st2[(long long)b * F + f];
+        float d;
+        if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.Q2[(long long)b * F + f]);
+        else d = (st & 4) ? 1.f : (ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE);
+        gs[hl][p] = dq * d;
+        as[hl][p] = st & 3;
+    }
+    __syncthreads();
+    const int hl = t >> 6, pos = t & 63, y = pos >> 3, x = pos & 7;
+    float s = 0.f;
+#pragma unroll
+    for (int dy = 1; dy >= 0; --dy)
+#pragma unroll
+        for (int dx = 1; dx >= 0; --dx) {
+            const int wy = y - dy, wx = x - dx;                            // the window whose cell (dy, dx) this position is
+            if (wy >= 0 && wy < P2W && wx >= 0 && wx < P2W) {
+                const int p = wy * P2W + wx;
+                if (as[hl][p] == dy * 2 + dx) s += gs[hl][p];
+            }
+        }
+    a.dO2[((long long)b * a.Hc + hc0 + hl) * NPOS + pos] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The conv GEMMs  C(m, n) = sum_k A(m, k) B(n, k)  on v_mfma_f32_16x16x4_f32, operands gathered (zero outside [M, N, K]):
+//   G_DK2  m = hc, n = (ci, tap) | bias, k = (b, pos of 8 x 8):   A = dO2[b, hc, pos],  B = P1[b, ci, pos + tap] | 1         -> part2[slice]
+//   G_DK1  m = c,  n = tap | bias,       k = (b, pos of 24 x 24): A = dO1[b, c, pos],   B = x[b, pos + tap] | 1             -> part1[slice]
+//   G_DP1  m = (b, Y, X of 12 x 12), n = ci, k = (hc, tap):       A = dO2[b, hc, (Y, X) - tap] or 0,  B = K2w[hc, ci, tap]           -> partP[slice]
+// blockIdx.y = the slice of K; every mode stores its slice's sums [slice, M, N].  Inside a slice the accumulator is folded into a second one
+// every 32 stages (512 products): one long fp32 chain would carry sqrt(K) roundings of the running sum.
+// ---------------------------------------------------------------------------------------------------
+enum { G_DK2 = 0, G_DK1 = 1, G_DP1 = 2 };
+struct WgArgs {
+    const float *A, *Bsrc;
+    float* out;
+    int Hc, ldx, M, N, K, kc;                       // kc: the K of one slice
+};
+
+template <int MODE> __device__ __forceinline__ float wg_load_a(const WgArgs& g, int m, int k) {
+    if (MODE == G_DK2) return g.A[((long long)(k >> 6) * g.Hc + m) * NPOS + (k & 63)];
+    if (MODE == G_DK1) { const int b = k / NO1, q = k - b * NO1; return g.A[((long long)b * C1 + m) * NO1 + q]; }
+    const int b = m / PP1, pp = m - b * PP1, hc = k / 25, tap = k - hc * 25;
+    const int y = pp / P1W - tap / 5, x = pp % P1W - tap % 5;
+    return ((unsigned)y < (unsigned)O2W && (unsigned)x < (unsigned)O2W) ? g.A[((long long)b * g.Hc + hc) * NPOS + y * O2W + x] : 0.f;
+}
+template <int MODE> __device__ __forceinline__ float wg_load_b(const WgArgs& g, int n, int k) {
+    if (MODE == G_DK2) {
+        if (n == K2) return 1.f;
+        const int ci = n / 25, tap = n - ci * 25, pos = k & 63;
+        return g.Bsrc[(long long)(k >> 6) * P1SZ + ci * PP1 + (tap / 5 + (pos >> 3)) * P1W + tap % 5 + (pos & 7)];
+    }
+    if (MODE == G_DK1) {
+        if (n == 25) return 1.f;
+        const int b = k / NO1, q = k - b * NO1;
+        return g.Bsrc[(long long)b * g.ldx + (n / 5 + q / O1W) * IW + n % 5 + q % O1W];
+    }
+    const int hc = k / 25;
+    return g.Bsrc[(long long)hc * K2 + n * 25 + (k - hc * 25)];
+}
+
+template <int MODE> __global__ void __launch_bounds__(256) conv_wgrad_gemm_kernel(const WgArgs g) {
+    constexpr int NTN = MODE == G_DP1 ? 2 : 4, TN = 16 * NTN;
+    __shared__ float As[GK][GLD], Bs[GK][TN + 4];
+    const int tiles_n = (g.N + TN - 1) / TN;
+    const int m0 = GT * (blockIdx.x / tiles_n), n0 = TN * (blockIdx.x % tiles_n);
+    const int k_begin = blockIdx.y * g.kc, k_end = min(k_begin + g.kc, g.K);
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 15, lg = lane >> 4;
+    f32x4 acc[NTN], tot[NTN];
+#pragma unroll
+    for (int nt = 0; nt < NTN; ++nt) acc[nt] = tot[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int kk = t & 15, r0 = t >> 4;
+    float ra[4], rb[NTN];
+    auto fetch = [&](int k0) {
+        const int k = k0 + kk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = m0 + r0 + 16 * i;
+            ra[i] = (m < g.M && k < k_end) ? wg_load_a<MODE>(g, m, k) : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < NTN; ++i) {
+            const int n = n0 + r0 + 16 * i;
+            rb[i] = (n < g.N && k < k_end) ? wg_load_b<MODE>(g, n, k) : 0.f;
+        }
+    };
+    int stage = 0;
+    fetch(k_begin);
+    for (int k0 = k_begin; k0 < k_end; k0 += GK, ++stage) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) As[kk][r0 + 16 * i] = ra[i];
+#pragma unroll
+        for (int i = 0; i < NTN; ++i) Bs[kk][r0 + 16 * i] = rb[i];
+        __syncthreads();
+        if (k0 + GK < k_end) fetch(k0 + GK);
+#pragma unroll
+        for (int ks = 0; ks < GK / 4; ++ks) {
+            const float a = As[4 * ks + lg][16 * wave + li];
+#pragma unroll
+            for (int nt = 0; nt < NTN; ++nt) acc[nt] = MFMA16(a, Bs[4 * ks + lg][16 * nt + li], acc[nt]);
+        }
+        __syncthreads();
+        if ((stage & 31) == 31) {
+#pragma unroll
+            for (int nt = 0; nt < NTN; ++nt) { tot[nt] += acc[nt]; acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
+    }
+    // lane holds C(m0 + 16 wave + 4 lg + r, n0 + 16 nt + li)
+#pragma unroll
+    for (int nt = 0; nt < NTN; ++nt) {
+        tot[nt] += acc[nt];
+        const int n = n0 + 16 * nt + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + 16 * wave + 4 * lg + r;
+            if (m < g.M && n < g.N) g.out[((long long)blockIdx.y * g.M + m) * g.N + n] = tot[nt][r];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// dO1[b, ci, 24 x 24]: one thread per (b, pooled position, ci).  dP1 = the slices of partP in increasing order (fp64), times act' (relu /
+// leaky: the pool-1 stash's sign bit; sigmoid / tanh: from the value in P1), goes to the cell of its 2 x 2 window that the stash names and
+// zero to the other three: pool 1 does not overlap, dO1 is written whole.
+// ---------------------------------------------------------------------------------------------------
+struct ConvRouteArgs { const float *part, *P1; const uint8_t* st1; float* dO1; long long n; int splits; };
+
+template <int ACT> __global__ void __launch_bounds__(ELT_THREADS) conv_route1_kernel(const ConvRouteArgs a) {
+    const long long e = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (e >= a.n) return;
+    double s = 0.0;
+    for (int sp = 0; sp < a.splits; ++sp) s += (double)a.part[(long long)sp * a.n + e];
+    const int ci = (int)(e & (C1 - 1));
+    const long long m = e >> 5;
+    const int b = (int)(m / PP1), pp = (int)(m - (long long)b * PP1);
+    const long long at = (long long)b * P1SZ + ci * PP1 + pp;
+    const int st = a.st1[at];
+    float d;
+    if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.P1[at]);
+    else d = (st & 4) ? 1.f : (ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE);
+    const float v = (float)s * d;
+    float* const o = a.dO1 + ((long long)b * C1 + ci) * NO1 + (2 * (pp / P1W)) * O1W + 2 * (pp % P1W);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[(q >> 1) * O1W + (q & 1)] = (st & 3) == q ? v : 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The slices' partial sums -> grad: one thread per element of dK2 | dK2b and of dK1 | dK1b, slices in increasing order, fp64.
+// ---------------------------------------------------------------------------------------------------
+struct ConvRedArgs { const float *part2, *part1; float* grad; int Hc, s2, s1; long long oK2w, oK2b; };
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_reduce_kernel(const ConvRedArgs a) {
+    long long e = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    const long long n2 = (long long)a.Hc * N2;
+    if (e < n2) {
+        const int m = (int)(e / N2), n = (int)(e - (long long)m * N2);
+        double s = 0.0;
+        for (int sp = 0; sp < a.s2; ++sp) s += (double)a.part2[(long long)sp * n2 + e];
+        a.grad[n < K2 ? a.oK2w + (long long)m * K2 + n : a.oK2b + m] = (float)s;
+        return;
+    }
+    e -= n2;
+    if (e >= C1 * N1) return;
+    const int m = (int)e / N1, n = (int)e - m * N1;
+    double s = 0.0;
+    for (int sp = 0; sp < a.s1; ++sp) s += (double)a.part1[(long long)sp * (C1 * N1) + e];
+    a.grad[n < 25 ? m * 25 + n : C1 * 25 + m] = (float)s;
+}
+
+// Adam on the flat buffer (the kernel of rbnn_nn_train.hip for one net) and the step's statistics (its finalize for one member)
+struct ConvAdamArgs { float *P, *m, *v; const float* grad; long long n_params; AdamScalars s; };
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_adam_kernel(const ConvAdamArgs a) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= a.n_params) return;
+    float p = a.P[i], m = a.m[i], v = a.v[i];
+    adam_one(p, m, v, a.grad[i], a.s);
+    a.P[i] = p; a.m[i] = m; a.v[i] = v;
+}
+
+struct ConvFinalArgs { const float* ce; const int32_t* correct; double* stats; int B; };
+
+__global__ void __launch_bounds__(256) conv_finalize_kernel(const ConvFinalArgs a) {
+    __shared__ double red[256];
+    __shared__ double cnt[256];
+    const int t = threadIdx.x;
+    double s = 0.0, k = 0.0;
+    for (int i = t; i < a.B; i += 256) {
+        s += (double)a.ce[i];
+        k += (double)a.correct[i];
+    }
+    red[t] = s; cnt[t] = k;
+    block_tree64(red, cnt);
+    if (t == 0) {
+        const double loss = (double)(float)(red[0] / (double)a.B);      // loss.item() of an fp32 mean
+        a.stats[0] = loss;
+        a.stats[1] += loss;
+        a.stats[2] += cnt[0];
+    }
+}
+
+inline int check_conv_net(const rbnn_conv_train_net* n) {
+    if (!n) return RBNN_ERR_NULL;
+    if (n->activation < RBNN_ACT_RELU || n->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
+    if (n->in_channels != 1 || n->in_width != IW) return RBNN_ERR_UNSUPPORTED;
+    if (n->hidden < 16 || (n->hidden & 15) || n->hidden > MAX_HIDDEN || n->n_classes < 1 || n->n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
+    return RBNN_OK;
+}
+
+inline int check_conv_batch(const float* X, int ldx, int B) {
+    if (!X) return RBNN_ERR_NULL;
+    if (B < 1 || B > MAX_POINTS || ldx < DIN || (ldx & 3)) return RBNN_ERR_SHAPE;
+    return aligned16(X) ? RBNN_OK : RBNN_ERR_ALIGN;
+}
+
+template <int MODE> int wg_launch(const WgArgs& g, int splits, hipStream_t st) {
+    constexpr int TN = MODE == G_DP1 ? 32 : 64;
+    const int tiles = ((g.M + GT - 1) / GT) * ((g.N + TN - 1) / TN);
+    hipLaunchKernelGGL(conv_wgrad_gemm_kernel<MODE>, dim3(tiles, splits), dim3(256), 0, st, g);
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int rbnn_conv_train_sizes(const rbnn_conv_train_net* net, int32_t n_points, rbnn_conv_train_bytes* out) {
+    const int rc = check_conv_net(net);
+    if (rc) return rc;
+    if (!out) return RBNN_ERR_NULL;
+    if (n_points < 1 || n_points > MAX_POINTS) return RBNN_ERR_SHAPE;
+    const size_t B = (size_t)n_points, Hc = (size_t)net->hidden, F = Hc * NP2;
+    rbnn_conv_train_bytes z = {};
+    z.n_params = conv_layout(net->hidden, net->n_classes).n_params;
+    z.logits = z.dZ = B * RBNN_CPAD * sizeof(float);
+    z.P1 = B * (size_t)GeoMnist::P1STRIDE;
+    z.st1 = B * P1SZ;
+    z.Q2 = B * F * sizeof(float);
+    z.st2 = B * F;
+    z.ce = B * sizeof(float);
+    z.correct = B * sizeof(int32_t);
+    z.dO2 = B * Hc * NPOS * sizeof(float);
+    z.dO1 = B * C1 * NO1 * sizeof(float);
+    z.part2 = (size_t)(n_points < MAX_SPLITS2 ? n_points : MAX_SPLITS2) * Hc * N2 * sizeof(float);
+    z.part1 = (size_t)(n_points < MAX_SPLITS1 ? n_points : MAX_SPLITS1) * C1 * N1 * sizeof(float);
+    z.partP = dp1_part_floats(n_points, net->hidden) * sizeof(float);
+    *out = z;
+    return RBNN_OK;
+}
+
+int rbnn_conv_train_forward(const rbnn_conv_train_net* net, const float* X, int32_t ldx, const int32_t* labels, int32_t n_points,
+                            const rbnn_conv_train_ws* ws, void* stream) {
+    int rc = check_conv_net(net);
+    if (rc) return rc;
+    if (!net->P || !labels || !ws || !ws->logits || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->ce || !ws->correct) return RBNN_ERR_NULL;
+    if ((rc = check_conv_batch(X, ldx, n_points))) return rc;
+    if (!aligned16(net->P)) return RBNN_ERR_ALIGN;
+    const ConvLayout L = conv_layout(net->hidden, net->n_classes);
+    rbnn_conv_posterior p = {};
+    p.activation = net->activation; p.hidden = net->hidden; p.n_classes = net->n_classes; p.n_stored = 1;
+    p.in_channels = net->in_channels; p.in_width = net->in_width;
+    p.K1w = net->P + L.K1w; p.K1b = net->P + L.K1b; p.K2w = net->P + L.K2w; p.K2b = net->P + L.K2b; p.Fw = net->P + L.Fw; p.Fb = net->P + L.Fb;
+    rbnn_conv_workspace w = {};
+    w.P = ws->logits; w.P1 = ws->P1; w.st1 = ws->st1; w.Q2 = ws->Q2; w.st2 = ws->st2;
+    if ((rc = rbnn_conv_forward(&p, X, ldx, n_points, nullptr, 1, RBNN_OUT_LOGITS, &w, stream))) return rc;
+    const ConvHeadArgs h = {ws->logits, labels, ws->dZ, ws->ce, ws->correct, n_points, net->n_classes, 1.f / (float)n_points};
+    hipLaunchKernelGGL(conv_head_kernel, dim3((n_points + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
+    return launch_status();
+}
+
+int rbnn_conv_weight_grads(const rbnn_conv_train_net* net, const float* X, int32_t ldx, int32_t n_points, const rbnn_conv_train_ws* ws,
+                           void* stream) {
+    int rc = check_conv_net(net);
+    if (rc) return rc;
+    if (!net->P || !net->grad || !ws || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->dO2 || !ws->dO1 || !ws->part2 || !ws->part1 ||
+        !ws->partP)
+        return RBNN_ERR_NULL;
+    if ((rc = check_conv_batch(X, ldx, n_points))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int Hc = net->hidden, C = net->n_classes, B = n_points, F = Hc * NP2;
+    const ConvLayout L = conv_layout(Hc, C);
+    float* const G = net->grad;
+    // dFw | dFb
+    GemmArgs ga = {};
+    ga.n_prob = 1;
+    ga.p[0] = wgrad_prob(ws->dZ, RBNN_CPAD, ws->Q2, F, 0, C, F, B, G + L.Fw, G + L.Fb, 0);
+    if ((rc = gemm_launch<false>(ga, 1, st))) return rc;
+    // dO2
+    const ConvDo2Args d = {ws->dZ, net->P + L.Fw, ws->Q2, ws->st2, ws->dO2, Hc, C};
+    rc = for_activation(net->activation, [&](auto act) {
+        hipLaunchKernelGGL(conv_do2_kernel<decltype(act)::value>, dim3((unsigned)B * (Hc / 4)), dim3(256), 0, st, d);
+        return launch_status();
+    });
+    if (rc) return rc;
+    // dP1 = conv2^T(dO2) per slice of the channels, then dO1 through pool 1
+    int perP, sP;
+    dp1_slices(B, Hc, perP, sP);
+    WgArgs g = {};
+    g.Hc = Hc; g.ldx = ldx;
+    g.A = ws->dO2; g.Bsrc = net->P + L.K2w; g.out = ws->partP;
+    g.M = B * PP1; g.N = C1; g.K = Hc * 25; g.kc = perP * 400;
+    if ((rc = wg_launch<G_DP1>(g, sP, st))) return rc;
+    const ConvRouteArgs ro = {ws->partP, ws->P1, ws->st1, ws->dO1, (long long)B * PP1 * C1, sP};
+    rc = for_activation(net->activation, [&](auto act) {
+        hipLaunchKernelGGL(conv_route1_kernel<decltype(act)::value>, dim3(blocks_for(ro.n)), dim3(ELT_THREADS), 0, st, ro);
+        return launch_status();
+    });
+    if (rc) return rc;
+    // the two split contractions and their reduction
+    int per2, s2, per1, s1;
+    slices(B, MAX_SPLITS2, per2, s2);
+    slices(B, MAX_SPLITS1, per1, s1);
+    g.A = ws->dO2; g.Bsrc = ws->P1; g.out = ws->part2; g.M = Hc; g.N = N2; g.K = B * NPOS; g.kc = per2 * NPOS;
+    if ((rc = wg_launch<G_DK2>(g, s2, st))) return rc;
+    g.A = ws->dO1; g.Bsrc = X; g.out = ws->part1; g.M = C1; g.N = N1; g.K = B * NO1; g.kc = per1 * NO1;
+    if ((rc = wg_launch<G_DK1>(g, s1, st))) return rc;
+    const ConvRedArgs r = {ws->part2, ws->part1, G, Hc, s2, s1, L.K2w, L.K2b};
+    hipLaunchKernelGGL(conv_reduce_kernel, dim3(blocks_for((long long)Hc * N2 + C1 * N1)), dim3(ELT_THREADS), 0, st, r);
+    return launch_status();
+}
+
+int rbnn_conv_adam_step(const rbnn_conv_train_net* net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void* stream) {
+    const int rc = check_conv_net(net);
+    if (rc) return rc;
+    if (!net->P || !net->m || !net->v || !net->grad) return RBNN_ERR_NULL;
+    if (step < 1) return RBNN_ERR_SHAPE;
+    ConvAdamArgs a = {};
+    a.n_params = conv_layout(net->hidden, net->n_classes).n_params;
+    a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad;
+    a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
+    hipLaunchKernelGGL(conv_adam_kernel, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+int rbnn_conv_train_finalize(const rbnn_conv_train_ws* ws, int32_t n_points, double* stats, void* stream) {
+    if (!ws || !ws->ce || !ws->correct || !stats) return RBNN_ERR_NULL;
+    if (n_points < 1 || n_points > MAX_POINTS) return RBNN_ERR_SHAPE;
+    const ConvFinalArgs a = {ws->ce, ws->correct, stats, n_points};
+    hipLaunchKernelGGL(conv_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+}  // extern "C"

@@ -4,7 +4,8 @@ The module keeps the reference's `nn.Sequential` layout so `state_dict()` keys (
 and the on-disk `<name>_weights[_<seed>].pt` files are interchangeable.  `forward` does not run the
 Sequential: it stacks the parameters as a one-sample posterior and calls the HIP path (logits out),
 so NN, Ensemble_NN and BNN share the same kernels.  `train` (model_nn.py:175-219) runs on the GPU for fc and fc2
-(robustbnns_amd/nn_train.py, csrc/rbnn_nn_train.hip); conv nets and CPU devices raise NotImplementedError.
+(robustbnns_amd/nn_train.py, csrc/rbnn_nn_train.hip); conv nets and CPU devices raise NotImplementedError.  A conv net of the 1x28x28
+geometry trains through `train_conv` (robustbnns_amd/conv_train.py, csrc/rbnn_conv_train.hip).
 """
 import math
 import os
@@ -123,6 +124,11 @@ class NN(nn.Module):
             return super().train(*args, **kwargs)
         from .nn_train import train_nn
         train_nn(self, *args, **kwargs)
+
+    def train_conv(self, train_loader, device, seed=0, save=True):
+        """train's algorithm for a conv net of the 1x28x28 geometry (robustbnns_amd.conv_train); train itself keeps refusing conv."""
+        from .conv_train import train_conv_nn
+        return train_conv_nn(self, train_loader, device, seed, save)
 
     def evaluate(self, test_loader, device, *args, **kwargs):
         """model_nn.py:221-240"""

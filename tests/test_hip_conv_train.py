@@ -1,0 +1,281 @@
+"""GPU tests (-m gpu) of deterministic conv training (model_nn.py:93-106, 175-219; csrc/rbnn_conv_train.hip, robustbnns_amd/conv_train.py): the
+weight gradients of all six tensors, per-point CE, step loss and correct count against fp64 autograd at the same parameters, the Adam kernel
+against torch.optim.Adam, two runs against each other, what must not be read (NaN behind every bound), NN.train_conv end to end against the
+fp64 restatement (tests/conv_restate.py), the files, no device->host sync inside a step, and the guards.  Every check prints one line with
+its worst figure in units of its bar.
+
+Mutations these tests are written to catch: no `/ B` in dZ, a missing bias gradient, pool-2 routing that drops one of the overlapping windows,
+act' taken at the wrong element for sigm / tanh, dK2 in (tap, ci) instead of (ci, tap) order -> the gradient test."""
+import ctypes as C
+import os
+
+import pytest
+import torch
+from torch.utils.data import DataLoader, TensorDataset
+
+import conv_restate as CR
+import nn_restate as NR
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("built_library")]
+DEV = "cuda:0"
+TRAJ_SPREADS = 4               # tests/test_hip_nn_train.py's spread argument
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32).cpu() if t.dtype == torch.float32 else t.detach().cpu().clone()
+
+
+def _state(tr):
+    return {name: _bits(getattr(tr, name)) for name in ("P", "m", "v", "grad", "stats")}
+
+
+def _trainer(params, act, Cn, batch_size, lr=0.01):
+    from robustbnns_amd.conv_train import ConvNnTrainer
+    return ConvNnTrainer(act, CR.SHAPE, Cn, params, lr, DEV, batch_size=batch_size)
+
+
+@pytest.mark.parametrize("Hc,act,B,Cn", CR.GRAD_CASES)
+def test_gradients_loss_and_count_match_fp64_autograd(Hc, act, B, Cn):
+    """Per tensor: max |dW - fp64| <= 1e-5 max |fp64 dW|.  Per-point CE: absolute error <= 1e-5 max(1, CE).  Step loss: 1e-5 relative to the
+    fp64 mean.  Correct count: the fp64 count, give or take the points within nn_restate.MARGIN (at most 2 % of the case:
+    tests/test_conv_train_cpu.py).  gradients() first, then step() on the same batch."""
+    c = CR.grad_case(Hc, act, B, Cn)
+    ref = c["ref"]
+    tr = _trainer(c["params"], act, Cn, 4)                                # smaller than most B: the workspaces grow
+    x, lab = c["x"].to(DEV), c["lab"].to(DEV)
+    tr.gradients(x, lab)
+    torch.cuda.synchronize()
+    G = tr.unflat(tr.grad)
+    assert list(G) == CR.KEYS
+    errs = {}
+    for k, g64 in ref["grad"].items():
+        gmax, err = float(g64.abs().max()), float((G[k].cpu().double() - g64).abs().max())
+        errs[k] = err / (1e-5 * gmax)
+    print(f"[conv-train grad Hc={Hc} {act} B={B} C={Cn}] gradient error per tensor in units of 1e-5 max|fp64 gradient|: "
+          + ", ".join(f"{k[6:]} {v:.3f}" for k, v in errs.items()))
+    e = (tr.ws_t["ce"][:B].cpu().double() - ref["ce"]).abs() / (1e-5 * ref["ce"].clamp_min(1.0))
+    assert max(errs.values()) <= 1.0, errs
+    assert float(e.max()) <= 1.0, float(e.max())
+    tr.step(x, lab)
+    stats = tr.stats.tolist()
+    w_loss = abs(stats[0] - ref["loss"]) / (1e-5 * abs(ref["loss"]))
+    assert w_loss <= 1.0, (stats[0], ref["loss"])
+    assert stats[1] == stats[0] and stats[0] == float(torch.tensor(stats[0], dtype=torch.float32))       # an fp32 value
+    assert ref["c_safe"] <= stats[2] <= ref["c_safe"] + ref["n_marginal"] and stats[2] == int(stats[2]), (stats[2], ref["c_safe"])
+    assert tr.t == 1 and not torch.equal(tr.P.cpu(), torch.cat([c["params"][k].reshape(-1) for k in CR.KEYS]))
+    print(f"[conv-train grad Hc={Hc} {act} B={B} C={Cn}] worst gradient error {max(errs.values()):.3f} x (1e-5 max|fp64 gradient|); per-point CE "
+          f"{float(e.max()):.3f} x bar; step loss {w_loss:.3f} x 1e-5; excluded: {c['n_drop']} of {c['n_pool']} pool points at a kink or a pooling tie, "
+          f"{ref['n_marginal']} of {B} points within the argmax margin")
+
+
+@pytest.mark.parametrize("t", [1, 2, 10, 10 ** 7])
+def test_adam_step_kernel_matches_torch_optim_adam(t):
+    """tests/test_hip_nn_train.py's bar and scales: 2e-6 x scale.  Elements [100, 400) are dead (grad = m = v = 0): the update is exactly 0."""
+    from robustbnns_amd import _hip
+    from robustbnns_amd.conv_train import ADAM_EPS, BETAS
+    lr = 0.01
+    g = torch.Generator().manual_seed(100 + t % 9973)
+    tr = _trainer(CR.fresh_params("leaky", 16, 5, 3), "leaky", 5, 4, lr)
+    n = tr.n_params
+    m0 = 0.2 * torch.randn(n, generator=g)
+    vals = {"P": tr.P.cpu(), "grad": 3 * torch.randn(n, generator=g), "m": m0, "v": (m0.abs() + torch.rand(n, generator=g)) ** 2}
+    for name in ("grad", "m", "v"):
+        vals[name][100:400] = 0.0
+    for name, v in vals.items():
+        getattr(tr, name).copy_(v)
+    _hip.check(tr.k.lib.rbnn_conv_adam_step(C.byref(tr.net), t, lr, BETAS[0], BETAS[1], ADAM_EPS, _hip.stream_of(tr.P)), "rbnn_conv_adam_step")
+    torch.cuda.synchronize()
+    d = {k: v.double() for k, v in vals.items()}
+    w = d["P"].clone().requires_grad_(True)
+    opt = torch.optim.Adam([w], lr=lr)
+    opt.state[w] = {"step": torch.tensor(float(t - 1)), "exp_avg": d["m"].clone(), "exp_avg_sq": d["v"].clone()}
+    w.grad = d["grad"].clone()
+    opt.step()
+    out = {"P": w.detach(), "m": opt.state[w]["exp_avg"], "v": opt.state[w]["exp_avg_sq"]}
+    step_size = lr / (1 - BETAS[0] ** t)
+    scale = {"P": d["P"].abs() + step_size * (1 + out["m"].abs() / (out["v"].sqrt() / (1 - BETAS[1] ** t) ** 0.5 + ADAM_EPS)),
+             "m": d["grad"].abs() + d["m"].abs(), "v": d["v"] + d["grad"] ** 2}
+    worst = 0.0
+    for name, sc in scale.items():
+        got = getattr(tr, name).cpu().double()
+        assert bool(torch.isfinite(got).all()), name
+        diff = (got - out[name]).abs()
+        if name == "P":
+            assert bool((diff[100:400] == 0).all()), "a dead element moved"
+        err = float(torch.where(sc > 0, diff / sc.clamp_min(1e-300), torch.where(diff == 0, 0.0, float("inf"))).max())
+        assert err <= 2e-6, (name, err)
+        worst = max(worst, err / 2e-6)
+    print(f"[conv-train adam t={t}] worst error {worst:.3f} x (2e-6 x scale) over P, m, v of {n} parameters; excluded: nothing")
+
+
+def _three_steps(c, act, Cn):
+    tr = _trainer(c["params"], act, Cn, 8)
+    x, lab = c["x"].to(DEV), c["lab"].to(DEV)
+    for sl in (slice(0, 8), slice(8, 16), slice(3, 8)):
+        tr.step(x[sl], lab[sl])
+    torch.cuda.synchronize()
+    return _state(tr)
+
+
+def test_two_identical_runs_are_bit_identical():
+    """Three steps (B = 8, 8, 5): no atomics, every sum in one fixed order."""
+    Hc, act, B, Cn = CR.GRAD_CASES[4]
+    c = CR.grad_case(Hc, act, B, Cn)
+    a, b = _three_steps(c, act, Cn), _three_steps(c, act, Cn)
+    for name in a:
+        assert torch.equal(a[name], b[name]), f"two identical runs differ in {name}"
+    assert float(a["stats"][1]) > 0 and bool(torch.isfinite(a["P"].view(torch.float32)).all())
+    print(f"[conv-train repeat Hc={Hc} {act}] P, m, v, grad, stats bit-identical between two runs of 3 steps (B = 8, 8, 5); excluded: nothing")
+
+
+def _poisoned(Hc, act, B, Cn, poison):
+    """One step on B < Bmax points; poison: NaN (0xFF in the stash bytes) in every per-point workspace behind [B, .], in the whole of the
+    partial-sum buffers (a step writes what it reads of them), in rows >= B and columns [784, ldx) of the staging matrix, and a class >= C
+    in the labels behind B."""
+    c = CR.grad_case(Hc, act, B, Cn)
+    tr = _trainer(c["params"], act, Cn, 2 * B + 3)
+    tr.Dp = 800                                                            # a staging matrix with columns behind the image
+    tr.X = torch.zeros(tr.Bmax, tr.Dp, dtype=torch.float32, device=DEV)
+    assert B < tr.Bmax
+    if poison:
+        for k, v in tr.ws_t.items():
+            bad = {torch.float32: float("nan"), torch.uint8: 255, torch.int32: Cn}[v.dtype]
+            if k in ("part1", "part2", "partP"):
+                v[:] = bad
+            else:
+                v[B * (v.numel() // tr.Bmax):] = bad
+        tr.X[B:] = float("nan")
+        tr.X[:, 784:] = float("nan")
+        tr.labels[B:] = Cn
+    tr.step(c["x"].to(DEV), c["lab"].to(DEV))
+    torch.cuda.synchronize()
+    res = _state(tr)
+    res["ce"], res["correct"] = _bits(tr.ws_t["ce"][:B]), _bits(tr.ws_t["correct"][:B])
+    for name in ("P", "m", "v", "grad", "ce"):
+        assert bool(torch.isfinite(res[name].view(torch.float32)).all()), name
+    assert bool(torch.isfinite(tr.stats).all())
+    return res
+
+
+@pytest.mark.parametrize("Hc,act,B,Cn", [CR.GRAD_CASES[1], CR.GRAD_CASES[2], CR.GRAD_CASES[5]])
+def test_nothing_behind_the_bounds_is_read(Hc, act, B, Cn):
+    """NaN is data: every index stays inside its allocation, and a NaN that leaked into a sum would stay there."""
+    clean, dirty = _poisoned(Hc, act, B, Cn, False), _poisoned(Hc, act, B, Cn, True)
+    for name in clean:
+        assert torch.equal(clean[name], dirty[name]), f"{name} depends on memory behind the bounds"
+    print(f"[conv-train bounds Hc={Hc} {act} B={B} C={Cn}] {len(clean)} results bit-identical and finite with NaN behind [B, .] of every workspace, in rows >= {B} "
+          f"and columns [784, 800) of the staged batch; excluded: nothing")
+
+
+def _nn():
+    from robustbnns_amd.model_nn import NN
+    m = CR.TRAJ
+    return NN(m["dataset"], m["shape"], m["n_classes"], m["hidden"], m["act"], m["arch"], m["lr"], m["epochs"])
+
+
+def test_train_conv_follows_the_fp64_restatement(capsys, tmp_path, monkeypatch):
+    meta = CR.TRAJ
+    r64, before, n_tie, spread, _ = CR.traj_reference()
+    assert n_tie == 0
+    params, x, lab = CR.traj_inputs()
+    scale = NR.param_scale(r64.params())
+    bar = TRAJ_SPREADS * spread * scale
+    tr = _trainer(params, meta["act"], meta["n_classes"], meta["batch"], meta["lr"])
+    worst, i = 0.0, 0
+    for _ in range(meta["epochs"]):
+        for s in range(0, meta["N"], meta["batch"]):
+            d = NR.max_diff({k: v.cpu() for k, v in tr.params().items()}, before[i])
+            assert d <= bar, (i, d, bar)
+            worst, i = max(worst, d), i + 1
+            tr.step(x[s:s + meta["batch"]].to(DEV), lab[s:s + meta["batch"]].to(DEV))
+    final_hand = {k: v.cpu() for k, v in tr.params().items()}
+    d = NR.max_diff(final_hand, r64.params())
+    worst = max(worst, d)
+    line = (f"[conv-train trajectory] {i} steps: max |P - fp64| = {worst:.2e} = {worst / (spread * scale):.3f} x spread ({spread:.2e} x {scale:.2f}), "
+            f"bar {TRAJ_SPREADS}; torch's own fp32 runs: <= 1.000")
+    assert d <= bar, line
+    # NN.train_conv itself: the same kernels in the same order
+    y = torch.eye(meta["n_classes"])[lab]
+    loader = DataLoader(TensorDataset(x, y), batch_size=meta["batch"], shuffle=False)
+    net = _nn()
+    net.load_state_dict(params)
+    capsys.readouterr()
+    got = net.train_conv(loader, DEV, 3, save=False)
+    out = capsys.readouterr().out
+    print(line)
+    for k, v in net.state_dict().items():
+        assert torch.equal(v, final_hand[k]), k
+    assert net.device == DEV and " == NN training ==" in out and got.t == i
+    # the epoch lines, as tests/test_hip_nn_train.py::_check_lines with the fp64 restatement in the reference's place
+    lines = NR.parse_epoch_lines(out)
+    per = len(r64.losses) // meta["epochs"]
+    assert len(lines) == meta["epochs"]
+    for e, (loss, acc) in enumerate(lines):
+        loss64 = sum(r64.losses[e * per:(e + 1) * per]) / meta["N"]
+        lbar = TRAJ_SPREADS * spread * abs(loss64) + 1e-8
+        print(f"   epoch {e + 1}: loss {loss:.8f} fp64 {loss64:.10f}: |diff| = {abs(loss - loss64) / lbar:.3f} x bar; accuracy {acc}")
+        assert abs(loss - loss64) <= lbar
+        if sum(r64.n_marginal[e * per:(e + 1) * per]) == 0:
+            assert f"{acc:.2f}" == f"{100 * sum(r64.correct[e * per:(e + 1) * per]) / meta['N']:.2f}"
+    # the trained module drives the attack engine: its cache saw the new parameters
+    z = net.forward(x[:8], DEV).cpu().double()
+    z64 = CR.logits(x[:8], r64.params(), meta["act"])
+    assert float((z - z64).abs().max()) <= 1e-3 * float(z64.abs().max())
+    assert float((z64 - CR.logits(x[:8], params, meta["act"])).abs().max()) > 1e-2 * float(z64.abs().max())       # and they moved
+    # save=True, then load
+    monkeypatch.chdir(tmp_path)
+    net2 = _nn()
+    net2.load_state_dict(params)
+    net2.train_conv(loader, DEV, seed=3)
+    again = _nn()
+    again.load(DEV)
+    for k, v in net2.state_dict().items():
+        assert torch.equal(v, again.state_dict()[k]) and torch.equal(v, final_hand[k]), k
+    assert torch.equal(again.forward(x[:8], DEV), net2.forward(x[:8], DEV))
+    assert os.listdir(tmp_path)
+
+
+def test_twenty_steps_make_no_device_to_host_sync():
+    c = CR.grad_case(*CR.GRAD_CASES[0])
+    tr = _trainer(c["params"], "leaky", 10, 8)
+    x, lab = c["x"].to(DEV), c["lab"].to(DEV)
+    tr.step(x, lab)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        for i in range(20):
+            tr.step(x[:8 - i % 3], lab[:8 - i % 3])
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    loss, correct = tr.epoch_totals()
+    assert tr.t == 21 and loss == loss and 0 <= correct <= 21 * 8
+
+
+def test_guards_raise_with_no_state_changed():
+    from robustbnns_amd.conv_train import ConvNnTrainer
+    from robustbnns_amd.model_nn import NN
+    x, y = torch.rand(8, 1, 28, 28), torch.eye(10)[torch.arange(8)]
+    loader = DataLoader(TensorDataset(x, y), batch_size=4)
+    conv = NN("mnist", (1, 28, 28), 10, 16, "leaky", "conv", 0.01, 1)
+    before = {k: v.clone() for k, v in conv.state_dict().items()}
+    with pytest.raises(NotImplementedError, match="no CPU compute path"):
+        conv.train_conv(loader, "cpu")
+    with pytest.raises(NotImplementedError, match="no CPU compute path"):
+        ConvNnTrainer("leaky", (1, 28, 28), 10, conv.state_dict(), 0.01, "cpu")
+    with pytest.raises(NotImplementedError, match="1x28x28"):
+        ConvNnTrainer("leaky", (3, 32, 32), 10, conv.state_dict(), 0.01, DEV)
+    conv.input_shape = (3, 32, 32)
+    with pytest.raises(NotImplementedError, match="1x28x28"):
+        conv.train_conv(loader, DEV)
+    conv.input_shape = (1, 28, 28)
+    with pytest.raises(NotImplementedError, match="conv"):
+        conv.train(loader, DEV)                                            # NN.train keeps refusing conv
+    fc = NN("mnist", (1, 28, 28), 10, 16, "leaky", "fc", 0.01, 1)
+    with pytest.raises(ValueError, match="train"):
+        fc.train_conv(loader, DEV)
+    assert all(torch.equal(v, before[k]) for k, v in conv.state_dict().items()) and not hasattr(conv, "device") and not hasattr(fc, "device")
