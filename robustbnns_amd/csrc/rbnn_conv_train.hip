@@ -10,8 +10,9 @@
 //                                 dK2 | dK2b     = sum over (point, position) of dO2 x [P1 patch | 1], per batch slice  (GEMM, mode G_DK2)
 //                                 dK1 | dK1b     = sum over (point, position) of dO1 x [x patch | 1], per batch slice   (GEMM, mode G_DK1)
 //                                 the slices' partial sums added in one fixed order, fp64                               (conv_reduce_kernel)
-//      rbnn_conv_adam_step        torch.optim.Adam's single-tensor formula on the flat buffer (adam_one of rbnn_train_core.hpp): 1 launch
-//      rbnn_conv_train_finalize   the fp32-rounded mean CE of the step, its running sum, the correct predictions (fp64, fixed order): 1 launch
+//      rbnn_conv_adam_step        torch.optim.Adam's single-tensor formula on the flat buffer: 1 launch                  (nn_adam_kernel<false>)
+//      rbnn_conv_train_finalize   the fp32-rounded mean CE of the step, its running sum, the correct predictions: 1 launch (nn_finalize_kernel<false>)
+//                                 both kernels are rbnn_nn_step.hpp's, shared with the fc members of rbnn_nn_train.hip, the member index compiled out
 //
 // Parameters, moments and gradients are flat fp32 buffers in state_dict order, unpadded (the convention of the fc trainers).  One stream, no
 // atomics, no device->host synchronisation: every output element is one lane's sum in one order, two runs are bit-identical.
@@ -22,6 +23,7 @@
 // sums are added in a second pass, in increasing order.
 #include "rbnn_conv_common.hpp"
 #include "rbnn_train_gemm.hpp"
+#include "rbnn_nn_step.hpp"
 
 using namespace rbnn_conv_shared;
 
@@ -280,38 +282,6 @@ __global__ void __launch_bounds__(ELT_THREADS) conv_reduce_kernel(const ConvRedA
     a.grad[n < 25 ? m * 25 + n : C1 * 25 + m] = (float)s;
 }
 
-// Adam on the flat buffer (the kernel of rbnn_nn_train.hip for one net) and the step's statistics (its finalize for one member)
-struct ConvAdamArgs { float *P, *m, *v; const float* grad; long long n_params; AdamScalars s; };
-
-__global__ void __launch_bounds__(ELT_THREADS) conv_adam_kernel(const ConvAdamArgs a) {
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (i >= a.n_params) return;
-    float p = a.P[i], m = a.m[i], v = a.v[i];
-    adam_one(p, m, v, a.grad[i], a.s);
-    a.P[i] = p; a.m[i] = m; a.v[i] = v;
-}
-
-struct ConvFinalArgs { const float* ce; const int32_t* correct; double* stats; int B; };
-
-__global__ void __launch_bounds__(256) conv_finalize_kernel(const ConvFinalArgs a) {
-    __shared__ double red[256];
-    __shared__ double cnt[256];
-    const int t = threadIdx.x;
-    double s = 0.0, k = 0.0;
-    for (int i = t; i < a.B; i += 256) {
-        s += (double)a.ce[i];
-        k += (double)a.correct[i];
-    }
-    red[t] = s; cnt[t] = k;
-    block_tree64(red, cnt);
-    if (t == 0) {
-        const double loss = (double)(float)(red[0] / (double)a.B);      // loss.item() of an fp32 mean
-        a.stats[0] = loss;
-        a.stats[1] += loss;
-        a.stats[2] += cnt[0];
-    }
-}
-
 inline int check_conv_net(const rbnn_conv_train_net* n) {
     if (!n) return RBNN_ERR_NULL;
     if (n->activation < RBNN_ACT_RELU || n->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
@@ -437,19 +407,19 @@ int rbnn_conv_adam_step(const rbnn_conv_train_net* net, int64_t step, double lr,
     if (rc) return rc;
     if (!net->P || !net->m || !net->v || !net->grad) return RBNN_ERR_NULL;
     if (step < 1) return RBNN_ERR_SHAPE;
-    ConvAdamArgs a = {};
+    AdamArgs a = {};
     a.n_params = conv_layout(net->hidden, net->n_classes).n_params;
     a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad;
     a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(conv_adam_kernel, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(nn_adam_kernel<false>, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 
 int rbnn_conv_train_finalize(const rbnn_conv_train_ws* ws, int32_t n_points, double* stats, void* stream) {
     if (!ws || !ws->ce || !ws->correct || !stats) return RBNN_ERR_NULL;
     if (n_points < 1 || n_points > MAX_POINTS) return RBNN_ERR_SHAPE;
-    const ConvFinalArgs a = {ws->ce, ws->correct, stats, n_points};
-    hipLaunchKernelGGL(conv_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    const FinalArgs a = {ws->ce, ws->correct, stats, n_points};
+    hipLaunchKernelGGL(nn_finalize_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

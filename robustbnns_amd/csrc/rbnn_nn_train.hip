@@ -12,65 +12,12 @@
 // The batch is read from a RESIDENT data matrix through an index array rows [M, B]: each member reads its own batch of its own permutation,
 // nothing is copied.  The tile plan of a member does not depend on M and no sum crosses members: member m of a lockstep run is bit-identical
 // to the same member trained alone.  No atomics anywhere: every sum has one fixed order.
-// The parameter layout (one member's: Layout::s[i].off), the activations, Adam and the fp64 tree are rbnn_train_core.hpp; the GEMM and head
-// kernels are rbnn_train_gemm.hpp.
+// The parameter layout (one member's: Layout::s[i].off), the activations, Adam's formula and the fp64 tree are rbnn_train_core.hpp; the GEMM
+// and head kernels are rbnn_train_gemm.hpp; the Adam and step-statistics kernels are rbnn_nn_step.hpp (shared with the conv net of
+// rbnn_conv_train.hip), launched here as <true>: the member is a grid dimension.
 #define RBNN_TRAIN_LOCKSTEP
 #include "rbnn_train_gemm.hpp"
-
-namespace {
-
-// ---------------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam, single-tensor, defaults but lr), one thread per parameter of a member:
-//   m = m + (1 - b1)(g - m),  v = b2 v + (1 - b2) g^2,  p += (-step_size m) / (sqrt(v) / bc2_sqrt + eps_adam)
-// ---------------------------------------------------------------------------------------------------
-struct AdamArgs {
-    float *P, *m, *v;
-    const float* grad;
-    long long n_params, member_stride;
-    AdamScalars s;
-};
-
-__global__ void __launch_bounds__(ELT_THREADS) nn_adam_kernel(const AdamArgs a) {
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (i >= a.n_params) return;
-    const long long e = (long long)blockIdx.y * a.member_stride + i;
-    float p = a.P[e], m = a.m[e], v = a.v[e];
-    adam_one(p, m, v, a.grad[e], a.s);
-    a.P[e] = p; a.m[e] = m; a.v[e] = v;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// One block per member: stats[m] = [fp32-rounded mean CE of the step, += it, += correct predictions].  Fixed-order sums in fp64.
-// ---------------------------------------------------------------------------------------------------
-struct FinalArgs {
-    const float* ce;
-    const int32_t* correct;
-    double* stats;
-    int B;
-};
-
-__global__ void __launch_bounds__(256) nn_finalize_kernel(const FinalArgs a) {
-    __shared__ double red[256];
-    __shared__ double cnt[256];
-    const int t = threadIdx.x;
-    const long long at = (long long)blockIdx.x * a.B;
-    double s = 0.0, k = 0.0;
-    for (int i = t; i < a.B; i += 256) {
-        s += (double)a.ce[at + i];
-        k += (double)a.correct[at + i];
-    }
-    red[t] = s; cnt[t] = k;
-    block_tree64(red, cnt);
-    if (t == 0) {
-        double* const st = a.stats + 3 * (long long)blockIdx.x;
-        const double loss = (double)(float)(red[0] / (double)a.B);      // loss.item() of an fp32 mean
-        st[0] = loss;
-        st[1] += loss;
-        st[2] += cnt[0];
-    }
-}
-
-}  // namespace
+#include "rbnn_nn_step.hpp"
 
 extern "C" {
 
@@ -101,7 +48,7 @@ int rbnn_nn_adam_step(const rbnn_nn_train_net* net, int64_t step, double lr, dou
     if (step < 1 || net->member_stride < a.n_params) return RBNN_ERR_SHAPE;
     a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad; a.member_stride = net->member_stride;
     a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(nn_adam_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0,
+    hipLaunchKernelGGL(nn_adam_kernel<true>, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0,
                        (hipStream_t)stream, a);
     return launch_status();
 }
@@ -112,7 +59,7 @@ int rbnn_nn_train_finalize(const rbnn_nn_train_net* net, const rbnn_nn_train_ws*
     if (!ws || !ws->ce || !ws->correct || !stats) return RBNN_ERR_NULL;
     if (n_points < 1) return RBNN_ERR_SHAPE;
     FinalArgs a = {ws->ce, ws->correct, stats, n_points};
-    hipLaunchKernelGGL(nn_finalize_kernel, dim3(net->n_members), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(nn_finalize_kernel<true>, dim3(net->n_members), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

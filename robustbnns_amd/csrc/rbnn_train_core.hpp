@@ -1,7 +1,8 @@
-// rbnn_train_core.hpp — what every unit that trains or samples an fc / fc2 net shares (rbnn_train.hip, rbnn_nn_train.hip, rbnn_hmc.hip), each
-// defined once: the parameter layout of the flat buffers and its checks, the activations, torch's Adam formula with its host-side scalars,
-// and the fixed-order block reductions.  No kernels (a __global__ function is emitted into every unit that includes its definition): the
-// GEMM and head kernels are rbnn_train_gemm.hpp.
+// rbnn_train_core.hpp — what every unit that trains or samples a net shares (rbnn_train.hip, rbnn_svi_lockstep.hip, rbnn_nn_train.hip,
+// rbnn_hmc.hip, rbnn_conv_train.hip), each defined once: the parameter layout of the flat fc / fc2 buffers and its checks, the activations,
+// torch's Adam formula with its host-side scalars, and the fixed-order block reductions.  No kernels (a __global__ function is emitted into
+// every unit that includes its definition): the GEMM and head kernels are rbnn_train_gemm.hpp, the SVI step's rbnn_svi_step.hpp, the
+// deterministic step's (Adam, step statistics) rbnn_nn_step.hpp.
 #pragma once
 #include "rbnn_common.hpp"
 

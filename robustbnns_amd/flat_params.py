@@ -1,6 +1,6 @@
-"""What SviTrainer, LockstepSvi, NnTrainer, HmcSampler and LockstepHmc share: the two refusals (require_gpu_fc), the constructor state of a
-trainer of fc / fc2 nets (FlatNets: shapes, sizes, the net descriptors, zeroed buffers; set_data: the resident data of the lockstep classes), the flat
-parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
+"""What SviTrainer, LockstepSvi, NnTrainer, ConvNnTrainer, HmcSampler and LockstepHmc share: the refusals (require_gpu_fc), the constructor
+state of a trainer of nets of one shape (FlatNets: shapes, sizes, the net descriptors, zeroed buffers, the parameter views; set_data: the resident data
+of the lockstep classes), the flat parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +12,7 @@ from .posterior import LAYER_KEYS
 
 def require_gpu_fc(what, arch=None, device=None):
     """The two refusals of everything that trains or samples on the GPU, with `what` as their subject: a device that is not the GPU, an
-    architecture other than fc / fc2.  An argument left None is not checked."""
+    architecture other than fc / fc2.  An argument left None is not checked (conv training leaves arch out)."""
     if device is not None and torch.device(device).type != "cuda":
         raise NotImplementedError(f"{what} runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
     if arch is not None and arch not in LAYER_KEYS:
@@ -65,18 +65,19 @@ def ws_struct(cls, keys, tensors):
 
 
 class FlatNets:
-    """The constructor state of a trainer or sampler of fc / fc2 nets of one shape, a single net (members None: buffers [n]) or `members` of
-    them in lockstep (buffers [members, n]): the kernels' handle, arch / activation / device / input_shape, the state_dict keys (`state_keys`,
-    and `keys` until a class puts something else there) and `shapes` (taken from `like`, a dict key -> tensor), D / H / C and fwd_launches."""
+    """The constructor state of a trainer or sampler of nets of one shape, a single net (members None: buffers [n]) or `members` of them in
+    lockstep (buffers [members, n]): the kernels' handle, arch / activation / device / input_shape, the state_dict keys (`state_keys`, and
+    `keys` until a class puts something else there; those of fc / fc2 unless `keys` names them, as conv does) and `shapes` (taken from
+    `like`, a dict key -> tensor), D / H / C and fwd_launches."""
 
-    def __init__(self, arch, activation, input_shape, n_classes, like, device, members=None):
+    def __init__(self, arch, activation, input_shape, n_classes, like, device, members=None, keys=None):
         self.k = _hip.HipKernels()
         self.arch, self.activation, self.device = arch, activation, torch.device(device)
         self.input_shape = tuple(int(v) for v in input_shape)
-        self.state_keys = self.keys = state_keys(arch)
+        self.state_keys = self.keys = state_keys(arch) if keys is None else list(keys)
         self.shapes = {k: tuple(like[k].shape) for k in self.state_keys}
         self.D = int(np.prod(self.input_shape))
-        self.H, self.C = int(self.shapes[self.state_keys[1]][0]), int(n_classes)
+        self.H, self.C = int(self.shapes[self.state_keys[-3]][0]), int(n_classes)      # the bias in front of the output layer: fc model.1, fc2 / conv model.3
         self.lead = () if members is None else (int(members),)
         self.fwd_launches = 2 if arch == "fc" else 4
 

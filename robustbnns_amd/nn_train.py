@@ -26,7 +26,41 @@ from .svi_train import ADAM_EPS, BETAS
 ENSEMBLE_BATCH = 100                    # model_ensemble.py:73
 
 
-class NnTrainer(FlatNets):
+class AdamNets(FlatNets):
+    """What NnTrainer and ConvNnTrainer (conv_train.py) share beyond FlatNets: the Adam buffers and their pointers in the net descriptor, the
+    statistics, lr / t, the staged batch and begin_epoch.  gradients() and step() are written out in each class (they are the per-step path)."""
+
+    def adam_state(self, net, n, P, lr):
+        """P (CPU, [n] or [M, n]) onto the device beside zeroed m / v / grad, their addresses into `net`; stats [3] or [M, 3]; nothing staged."""
+        self.net, self.n_params, self.P = net, n, P.to(self.device)
+        assert tuple(self.P.shape) == self.lead + (n,), (tuple(self.P.shape), self.lead, n)
+        self.m, self.v, self.grad = self.zeros(n), self.zeros(n), self.zeros(n)
+        for name in ("P", "m", "v", "grad"):
+            setattr(net, name, getattr(self, name).data_ptr())
+        self.stats = torch.zeros(*self.lead, 3, dtype=torch.float64, device=self.device)
+        self.lr, self.t = float(lr), 0
+        self.Bmax = 0
+        self.X = self.labels = None
+
+    def staging(self, B):
+        """The buffers of a staged batch of up to B points (step(x, labels)); the end of a class's _ensure(B)."""
+        self.X = torch.zeros(B, self.Dp, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.Bmax = B
+
+    def stage(self, x, labels):
+        """x [B, ...] and integer labels [B] into X / labels (the workspaces grown to B points first) -> B."""
+        B = int(x.shape[0])
+        self._ensure(B)
+        self.X[:B, :self.D].copy_(x.reshape(B, -1))
+        self.labels[:B].copy_(labels.reshape(B))
+        return B
+
+    def begin_epoch(self):
+        self.stats[..., 1:].zero_()
+
+
+class NnTrainer(AdamNets):
     """Device-resident training state of M fc / fc2 nets of one shape: flat parameters, Adam moments and gradients [M, n_params], the
     workspaces [M, B, .] and a device-side accumulator stats [M, 3] = [step loss, sum of step losses, correct predictions]."""
 
@@ -35,22 +69,12 @@ class NnTrainer(FlatNets):
         if isinstance(params, dict):
             params = [params]
         super().__init__(arch, activation, input_shape, n_classes, params[0], device, members=len(params))
-        dev, self.M = self.device, len(params)
+        self.M = len(params)
         self.Dp = round_up(self.D, 16)
         net = self.descriptor(_hip.NnTrainNet, self.M)
-        self.n_params = n = self.sizes("rbnn_nn_train_sizes", net)
-        self.P = torch.stack([flatten(d, self.keys) for d in params]).to(dev)
-        assert tuple(self.P.shape) == (self.M, n), (tuple(self.P.shape), self.M, n)
-        self.m, self.v, self.grad = self.zeros(n), self.zeros(n), self.zeros(n)
-        for name in ("P", "m", "v", "grad"):
-            setattr(net, name, getattr(self, name).data_ptr())
-        net.member_stride = n
-        self.net = net
-        self.stats = torch.zeros(self.M, 3, dtype=torch.float64, device=dev)
-        self.lr, self.t = float(lr), 0
-        self.Bmax = 0
+        net.member_stride = n = self.sizes("rbnn_nn_train_sizes", net)
+        self.adam_state(net, n, torch.stack([flatten(d, self.keys) for d in params]), lr)
         self.data = self.data_labels = None
-        self.X = self.labels = None
         self._ensure(int(batch_size))
 
     def unflat(self, buf, member=0):
@@ -65,9 +89,7 @@ class NnTrainer(FlatNets):
         self.ws_t = {k: v.reshape(-1) for k, v in train_workspace(self.arch, M * B, self.H, dev).items()}
         self.ws_t["correct"] = torch.zeros(M * B, dtype=torch.int32, device=dev)
         self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
-        self.X = torch.zeros(B, self.Dp, dtype=torch.float32, device=dev)         # the staged batch (step(x, labels))
-        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.Bmax = B
+        self.staging(B)
 
     def set_data(self, x, labels):
         """The resident data set the row indices of step(rows=...) refer to: x [N, ...] and integer labels [N], copied to the device once."""
@@ -86,10 +108,7 @@ class NnTrainer(FlatNets):
             B = int(rows.shape[1])
             self._ensure(B)
             return self.data, int(self.data.stride(0)), int(self.data.shape[0]), self.data_labels, rows, B
-        B = int(x.shape[0])
-        self._ensure(B)
-        self.X[:B, :self.D].copy_(x.reshape(B, -1))
-        self.labels[:B].copy_(labels.reshape(B))
+        B = self.stage(x, labels)
         return self.X, self.Dp, self.Bmax, self.labels, None, B
 
     def gradients(self, x=None, labels=None, rows=None):
@@ -110,9 +129,6 @@ class NnTrainer(FlatNets):
         _hip.check(lib.rbnn_nn_adam_step(net, self.t + 1, self.lr, BETAS[0], BETAS[1], ADAM_EPS, st), "rbnn_nn_adam_step")
         _hip.check(lib.rbnn_nn_train_finalize(net, C.byref(self.ws), B, _hip.ptr(self.stats), st), "rbnn_nn_train_finalize")
         self.t += 1
-
-    def begin_epoch(self):
-        self.stats[:, 1:].zero_()
 
     def epoch_totals(self):
         """Per member (sum of the step losses, correct predictions) since begin_epoch(): the one device->host sync of an epoch."""
@@ -140,27 +156,33 @@ def epoch_line(epoch, total_loss, correct, n):
     return f"\n[Epoch {epoch + 1}]\t loss: {total_loss / n:.8f} \t accuracy: {100 * correct / n:.2f}"
 
 
-def train_nn(net, train_loader, device, seed=0, save=True):
-    """NN.train (model_nn.py:175-219) of an fc / fc2 net from its CURRENT parameters (the reference initialises at construction and reseeds
-    only here): M = 1 steps on the loader's batches; the trained parameters are written back into the module."""
-    check_trainable(net.architecture, device)
+def train_on_loader(net, train_loader, device, seed, save, trainer, one):
+    """NN.train (model_nn.py:175-219) behind its guards, from the net's CURRENT parameters (the reference initialises at construction and
+    reseeds only here): one step per batch of the loader; the trained parameters are written back into the module.  trainer(batch_size) makes
+    the trainer; one(v) is the net's entry of what its epoch_totals() and params() return."""
     print("\n == NN training ==")
     net.device = device
     seed_all(seed)
-    tr = NnTrainer(net.architecture, net.activation, net.input_shape, net.output_size, [net.state_dict()], net.lr, device,
-                   batch_size=getattr(train_loader, "batch_size", None) or ENSEMBLE_BATCH)
+    tr = trainer(getattr(train_loader, "batch_size", None) or ENSEMBLE_BATCH)
     n = len(train_loader.dataset)
     for epoch in range(net.epochs):
         tr.begin_epoch()
         for x_batch, y_batch in train_loader:
             tr.step(x_batch.to(device), y_batch.to(device).argmax(-1))
-        total_loss, correct = tr.epoch_totals()[0]
+        total_loss, correct = one(tr.epoch_totals())
         print(epoch_line(epoch, total_loss, correct, n), end="\t")
-    net.load_state_dict({k: v.cpu() for k, v in tr.params()[0].items()})
+    net.load_state_dict({k: v.cpu() for k, v in one(tr.params()).items()})
     net._engine = None
     if save:
         net.save()
     return tr
+
+
+def train_nn(net, train_loader, device, seed=0, save=True):
+    """NN.train of an fc / fc2 net: M = 1 steps on the loader's batches."""
+    check_trainable(net.architecture, device)
+    return train_on_loader(net, train_loader, device, seed, save, lambda B: NnTrainer(
+        net.architecture, net.activation, net.input_shape, net.output_size, [net.state_dict()], net.lr, device, batch_size=B), lambda v: v[0])
 
 
 def ensemble_schedule(ens, n_points):

@@ -1,6 +1,6 @@
 """GPU tests (-m gpu) of deterministic conv training (model_nn.py:93-106, 175-219; csrc/rbnn_conv_train.hip, robustbnns_amd/conv_train.py): the
 weight gradients of all six tensors, per-point CE, step loss and correct count against fp64 autograd at the same parameters, the Adam kernel
-against torch.optim.Adam, two runs against each other, what must not be read (NaN behind every bound), NN.train_conv end to end against the
+against torch.optim.Adam, the statistics kernel alone past one pass of its loop, two runs against each other, what must not be read (NaN behind every bound), NN.train_conv end to end against the
 fp64 restatement (tests/conv_restate.py), the files, no device->host sync inside a step, and the guards.  Every check prints one line with
 its worst figure in units of its bar.
 
@@ -9,6 +9,7 @@ act' taken at the wrong element for sigm / tanh, dK2 in (tap, ci) instead of (ci
 import ctypes as C
 import os
 
+import numpy as np
 import pytest
 import torch
 from torch.utils.data import DataLoader, TensorDataset
@@ -111,6 +112,34 @@ def test_adam_step_kernel_matches_torch_optim_adam(t):
         assert err <= 2e-6, (name, err)
         worst = max(worst, err / 2e-6)
     print(f"[conv-train adam t={t}] worst error {worst:.3f} x (2e-6 x scale) over P, m, v of {n} parameters; excluded: nothing")
+
+
+@pytest.mark.parametrize("B", [1, 256, 257, 600])
+def test_finalize_sums_every_pass_of_its_loop(B):
+    """rbnn_conv_train_finalize alone on hand-filled ce in [0, 5) and flags, twice on one accumulator: B = 257 and 600 take the 256-wide loop
+    into a second and a third pass.  stats[2]: the exact count.  stats[0]: an fp32 value within one fp32 ulp of the fp64 mean (a correctly
+    rounded mean is within half an ulp; the fp64 sums, this one and the kernel's, err by at most B 2^-53 relative, so only a mean that close
+    to an fp32 rounding tie can round to the other neighbour).  stats[1]: the fp64 sum of the two stats[0], exactly."""
+    from robustbnns_amd import _hip
+    lib, g = _hip.load(), torch.Generator().manual_seed(7000 + B)
+    stats = torch.zeros(3, dtype=torch.float64, device=DEV)
+    ws, losses, count, worst = _hip.ConvTrainWs(), [], 0, 0.0
+    for _ in range(2):
+        ce, flags = 5 * torch.rand(B, generator=g), torch.randint(0, 2, (B,), generator=g, dtype=torch.int32)
+        ce_d, flags_d = ce.to(DEV), flags.to(DEV)
+        ws.ce, ws.correct = _hip.ptr(ce_d), _hip.ptr(flags_d)
+        _hip.check(lib.rbnn_conv_train_finalize(C.byref(ws), B, _hip.ptr(stats), _hip.stream_of(stats)), "rbnn_conv_train_finalize")
+        got = stats.tolist()                                               # synchronises: ce_d / flags_d outlive the launch
+        mean64 = float(ce.double().sum()) / B
+        ulp = float(np.spacing(np.float32(max(got[0], mean64))))
+        losses.append(got[0])
+        count += int(flags.sum())
+        print(f"[conv-train finalize B={B}] step loss {got[0]!r}, fp64 mean {mean64!r}: |diff| = {abs(got[0] - mean64) / ulp:.3f} fp32 ulp; "
+              f"sum {got[1]!r}; count {got[2]} of {count}")
+        assert got[0] == float(np.float32(got[0])) and abs(got[0] - mean64) <= ulp, (got[0], mean64, ulp)
+        assert got[1] == sum(losses) and got[2] == count, (got, losses, count)
+        worst = max(worst, abs(got[0] - mean64) / ulp)
+    print(f"[conv-train finalize B={B}] worst step loss {worst:.3f} fp32 ulp from the fp64 mean (bar 1); excluded: nothing")
 
 
 def _three_steps(c, act, Cn):

@@ -1,6 +1,6 @@
 """GPU tests (-m gpu) of deterministic training (model_nn.py:175-219, model_ensemble.py:69-83; csrc/rbnn_nn_train.hip,
 robustbnns_amd/nn_train.py): every member's weight gradients, per-point CE, step loss and correct count against fp64 autograd at the same
-parameters, the Adam kernel against torch.optim.Adam, lockstep against the members alone, gathered rows against a staged copy, what must not
+parameters, the Adam kernel against torch.optim.Adam, the statistics kernel alone past one pass of its loop, lockstep against the members alone, gathered rows against a staged copy, what must not
 be read (NaN behind every bound), NN.train / Ensemble_NN.train end to end on the reference's recorded runs against the fp64 restatement
 (tests/nn_restate.py), the files, no device->host sync inside a step, and the guards.  Every check prints one line with its worst figure
 in units of its bar.
@@ -10,6 +10,7 @@ neighbour's rows -> the weight gradients (M > 1); no bias-gradient column -> the
 test (t = 1, 2, 10); the last maximum in the flag -> test_correct_flag_takes_the_first_maximum."""
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 from torch.utils.data import DataLoader, TensorDataset
@@ -128,6 +129,53 @@ def test_adam_step_kernel_matches_torch_optim_adam(t):
         assert err <= 2e-6, (name, err)
         worst = max(worst, err / 2e-6)
     print(f"[nn-train adam t={t}] worst error {worst:.3f} x (2e-6 x scale) over P, m, v of {M} members; excluded: nothing")
+
+
+def _finalize_twice(ces, flags, B):
+    """rbnn_nn_train_finalize alone, once per (ce, flags) pair of [M, B] tensors, on one accumulator -> stats.tolist() after every call."""
+    from robustbnns_amd import _hip
+    lib, M = _hip.load(), int(ces[0].shape[0])
+    net, ws = _hip.NnTrainNet(), _hip.NnTrainWs()
+    net.arch, net.activation, net.in_features, net.hidden, net.n_classes, net.n_members = 1, 1, 17, 32, 3, M
+    stats = torch.zeros(M, 3, dtype=torch.float64, device=DEV)
+    out = []
+    for ce, fl in zip(ces, flags):
+        ce_d, fl_d = ce.contiguous().to(DEV), fl.contiguous().to(DEV)
+        ws.ce, ws.correct = _hip.ptr(ce_d), _hip.ptr(fl_d)
+        _hip.check(lib.rbnn_nn_train_finalize(C.byref(net), C.byref(ws), B, _hip.ptr(stats), _hip.stream_of(stats)), "rbnn_nn_train_finalize")
+        out.append(stats.tolist())                                         # synchronises: ce_d / fl_d outlive the launch
+    return out
+
+
+@pytest.mark.parametrize("B", [1, 256, 257, 600])
+def test_finalize_sums_every_pass_of_its_loop_per_member(B):
+    """M = 3 members with different hand-filled ce in [0, 5) and flags, two calls on one accumulator: B = 257 and 600 take the 256-wide loop
+    into a second and a third pass.  Per member, stats[2]: the exact count.  stats[0]: an fp32 value within one fp32 ulp of the fp64 mean (a
+    correctly rounded mean is within half an ulp; the fp64 sums, this one and the kernel's, err by at most B 2^-53 relative, so only a mean
+    that close to an fp32 rounding tie can round to the other neighbour).  stats[1]: the fp64 sum of the two stats[0], exactly.  Member 1's
+    row is what member 1 gets alone (M = 1), bit for bit: members 0 and 2 do not reach it."""
+    M, g = 3, torch.Generator().manual_seed(9000 + B)
+    ces = [5 * torch.rand(M, B, generator=g) for _ in range(2)]
+    flags = [torch.randint(0, 2, (M, B), generator=g, dtype=torch.int32) for _ in range(2)]
+    assert not torch.equal(ces[0][0], ces[0][1]) and not torch.equal(ces[0][2], ces[0][1])
+    runs = _finalize_twice(ces, flags, B)
+    alone = _finalize_twice([c[1:2] for c in ces], [f[1:2] for f in flags], B)
+    worst = 0.0
+    for m in range(M):
+        losses, count = [], 0
+        for i, got in enumerate(runs):
+            mean64 = float(ces[i][m].double().sum()) / B
+            ulp = float(np.spacing(np.float32(max(got[m][0], mean64))))
+            losses.append(got[m][0])
+            count += int(flags[i][m].sum())
+            print(f"[nn-train finalize B={B} member {m}] step loss {got[m][0]!r}, fp64 mean {mean64!r}: |diff| = {abs(got[m][0] - mean64) / ulp:.3f} "
+                  f"fp32 ulp; sum {got[m][1]!r}; count {got[m][2]} of {count}")
+            assert got[m][0] == float(np.float32(got[m][0])) and abs(got[m][0] - mean64) <= ulp, (m, got[m][0], mean64, ulp)
+            assert got[m][1] == sum(losses) and got[m][2] == count, (m, got[m], losses, count)
+            worst = max(worst, abs(got[m][0] - mean64) / ulp)
+    assert [r[1] for r in runs] == [r[0] for r in alone], (runs, alone)
+    print(f"[nn-train finalize B={B}] worst step loss {worst:.3f} fp32 ulp from the fp64 mean (bar 1) over {M} members; member 1 in lockstep == alone; "
+          f"excluded: nothing")
 
 
 class _SviGradients:

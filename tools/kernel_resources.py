@@ -197,7 +197,7 @@ def isa_hashes(lib=LIB):
             if m:
                 syms.append(m.group(1))
                 bodies.append([])
-            elif syms and line.split("//")[0].strip():
+            elif syms and line.split("//")[0].strip() not in ("", "..."):         # "...": elided padding behind a function, not its code
                 bodies[-1].append(line.split("//")[0].strip())
         out += [(hashlib.sha256("\n".join(b).encode()).hexdigest(), n) for b, n in zip(bodies, demangle(syms))]
     return sorted(out, key=lambda e: e[1])
