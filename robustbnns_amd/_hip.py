@@ -56,16 +56,14 @@ class ConvWorkspaceSizes(C.Structure):
     _fields_ = [(k, C.c_size_t) for k in CONV_WS_KEYS]
 
 
-class SplitImages(C.Structure):
+class PieceImages(C.Structure):
+    """rbnn_split_images and rbnn_triple_images: the same fields in the same order (two or three fp16 pieces per weight behind the pointers)."""
     _fields_ = [("W1_rows", _fp), ("W1_cols", _fp), ("W2_gen", _fp), ("ld_rows", C.c_int32), ("ld_cols", C.c_int32),
                 ("w1_exp", C.c_int32), ("w2_exp", C.c_int32), ("Wm_rows", _fp), ("Wm_cols", _fp), ("wm_exp", C.c_int32),
                 ("h1_exp", C.c_int32)]
 
 
-class TripleImages(C.Structure):
-    _fields_ = [("W1_rows", _fp), ("W1_cols", _fp), ("W2_gen", _fp), ("ld_rows", C.c_int32), ("ld_cols", C.c_int32),
-                ("w1_exp", C.c_int32), ("w2_exp", C.c_int32), ("Wm_rows", _fp), ("Wm_cols", _fp), ("wm_exp", C.c_int32),
-                ("h1_exp", C.c_int32)]
+SplitImages = TripleImages = PieceImages
 
 
 class SviGuide(C.Structure):
@@ -412,13 +410,41 @@ class HipKernels:
               "rbnn_input_scales")
         return out
 
+    # The wrappers of the two fp16-piece modes come in pairs with one body each; `name` is the mode's C function.
+    def _rows_image(self, name, src, cols, scale_exp, out, ld_dst, dev_scale):
+        require_gpu(src, "src")
+        ld_src = src.shape[-1]
+        check(getattr(self.lib, name)(ptr(src), src.numel() // ld_src, cols, ld_src, scale_exp, ptr(dev_scale), ptr(out), ld_dst, stream_of(src)), name)
+
+    def _cols_image(self, name, W, rows, cols, scale_exp, out, ld_dst):
+        require_gpu(W, "W")
+        check(getattr(self.lib, name)(ptr(W), W.numel() // (rows * W.shape[-1]), rows, cols, W.shape[-1], scale_exp, ptr(out), ld_dst, stream_of(W)), name)
+
+    def _w2gen_image(self, name, W2, Cn, H, scale_exp, out):
+        require_gpu(W2, "W2")
+        check(getattr(self.lib, name)(ptr(W2), W2.numel() // (Cn * H), Cn, H, scale_exp, ptr(out), stream_of(W2)), name)
+
+    def _piece_workspace_sizes(self, name, out, desc, images, N, S):
+        check(getattr(self.lib, name)(C.byref(desc), C.byref(images), N, S, C.byref(out)), name)
+        return {k: getattr(out, k) for k, _ in out._fields_}
+
+    @staticmethod
+    def _piece_ws(record, bufs):
+        """`record` (SplitWorkspace / TripleWorkspace) filled from the dict of tensors `bufs`."""
+        t = record()
+        for k, _ in record._fields_:
+            setattr(t, k, ptr(bufs.get(k)))
+        return t
+
+    def _fc_input_grad_pieces(self, name, desc, images, sidx, S, N, chunk, w, pw, stream):
+        n = C.c_int32(0)
+        check(getattr(self.lib, name)(C.byref(desc), C.byref(images), ptr(sidx), S, N, chunk, C.byref(w), C.byref(pw), C.byref(n), stream), name)
+        return n.value
+
     def split_rows(self, src, cols, scale_exp, out, ld_dst, dev_scale=None):
         """src: [..., ld_src] fp32 rows -> out: split-rows image (int16 storage [rows, ld_dst*2]).  dev_scale: an
         rbnn_dev_scale record on the device that replaces scale_exp."""
-        require_gpu(src, "src")
-        ld_src = src.shape[-1]
-        check(self.lib.rbnn_split_rows(ptr(src), src.numel() // ld_src, cols, ld_src, scale_exp, ptr(dev_scale), ptr(out), ld_dst,
-                                       stream_of(src)), "rbnn_split_rows")
+        self._rows_image("rbnn_split_rows", src, cols, scale_exp, out, ld_dst, dev_scale)
 
     def fc_forward_split(self, net, images, Xs, ld, x_exp, N, sidx, S, out_kind, ws, dev_scales=None):
         w = self._ws(ws)
@@ -427,64 +453,35 @@ class HipKernels:
 
     def split_cols(self, W, rows, cols, scale_exp, out, ld_dst):
         """W: [n_mats, rows, ld_src] fp32 -> out: split-cols image."""
-        require_gpu(W, "W")
-        check(self.lib.rbnn_split_cols(ptr(W), W.numel() // (rows * W.shape[-1]), rows, cols, W.shape[-1], scale_exp, ptr(out),
-                                       ld_dst, stream_of(W)), "rbnn_split_cols")
+        self._cols_image("rbnn_split_cols", W, rows, cols, scale_exp, out, ld_dst)
 
     def split_w2gen(self, W2, Cn, H, scale_exp, out):
-        require_gpu(W2, "W2")
-        check(self.lib.rbnn_split_w2gen(ptr(W2), W2.numel() // (Cn * H), Cn, H, scale_exp, ptr(out), stream_of(W2)), "rbnn_split_w2gen")
+        self._w2gen_image("rbnn_split_w2gen", W2, Cn, H, scale_exp, out)
 
     def split_workspace_sizes(self, net, images, N, S):
-        out = SplitWorkspaceSizes()
-        check(self.lib.rbnn_split_workspace_query(C.byref(net.descriptor()), C.byref(images), N, S, C.byref(out)),
-              "rbnn_split_workspace_query")
-        return {k: getattr(out, k) for k in SPLIT_WS_KEYS}
+        return self._piece_workspace_sizes("rbnn_split_workspace_query", SplitWorkspaceSizes(), net.descriptor(), images, N, S)
 
     def fc_input_grad_split(self, net, images, sidx, S, N, chunk, ws, sws):
-        w = self._ws(ws)
-        sw = SplitWorkspace()
-        for k in SPLIT_WS_KEYS:
-            setattr(sw, k, ptr(sws.get(k)))
-        n = C.c_int32(0)
-        check(self.lib.rbnn_fc_input_grad_split(C.byref(net.descriptor()), C.byref(images), ptr(sidx), S, N, chunk, C.byref(w),
-                                                C.byref(sw), C.byref(n), stream_of(ws["dZ"])), "rbnn_fc_input_grad_split")
-        return n.value
+        return self._fc_input_grad_pieces("rbnn_fc_input_grad_split", net.descriptor(), images, sidx, S, N, chunk, self._ws(ws),
+                                          self._piece_ws(SplitWorkspace, sws), stream_of(ws["dZ"]))
 
     # -- triple-split ("f16x6") mode: full-width fp32 operands on the f16 matrix pipe ---------------------
     def triple_rows(self, src, cols, scale_exp, out, ld_dst, dev_scale=None, grouped=False):
         """src: [..., ld_src] fp32 rows -> out: triple-rows image (int16 storage, 3 halves per element).  grouped=True: the fc forward's
         operand order (16-row groups, [3 pieces][16 rows][64 B] per K stage; out sized for ceil16(rows) rows)."""
-        require_gpu(src, "src")
-        ld_src = src.shape[-1]
-        fn = self.lib.rbnn_triple_rows_grouped if grouped else self.lib.rbnn_triple_rows
-        check(fn(ptr(src), src.numel() // ld_src, cols, ld_src, scale_exp, ptr(dev_scale), ptr(out), ld_dst, stream_of(src)),
-              "rbnn_triple_rows_grouped" if grouped else "rbnn_triple_rows")
+        self._rows_image("rbnn_triple_rows_grouped" if grouped else "rbnn_triple_rows", src, cols, scale_exp, out, ld_dst, dev_scale)
 
     def triple_cols(self, W, rows, cols, scale_exp, out, ld_dst):
-        require_gpu(W, "W")
-        check(self.lib.rbnn_triple_cols(ptr(W), W.numel() // (rows * W.shape[-1]), rows, cols, W.shape[-1], scale_exp, ptr(out),
-                                        ld_dst, stream_of(W)), "rbnn_triple_cols")
+        self._cols_image("rbnn_triple_cols", W, rows, cols, scale_exp, out, ld_dst)
 
     def triple_w2gen(self, W2, Cn, H, scale_exp, out):
-        require_gpu(W2, "W2")
-        check(self.lib.rbnn_triple_w2gen(ptr(W2), W2.numel() // (Cn * H), Cn, H, scale_exp, ptr(out), stream_of(W2)), "rbnn_triple_w2gen")
+        self._w2gen_image("rbnn_triple_w2gen", W2, Cn, H, scale_exp, out)
 
     def triple_workspace_sizes(self, net, images, N, S):
-        out = TripleWorkspaceSizes()
-        check(self.lib.rbnn_triple_workspace_query(C.byref(net.descriptor(lazy_ok=True)), C.byref(images), N, S, C.byref(out)),
-              "rbnn_triple_workspace_query")
-        return {k: getattr(out, k) for k in TRIPLE_WS_KEYS}
-
-    @staticmethod
-    def _tws(tws):
-        t = TripleWorkspace()
-        for k in TRIPLE_WS_KEYS:
-            setattr(t, k, ptr(tws.get(k)))
-        return t
+        return self._piece_workspace_sizes("rbnn_triple_workspace_query", TripleWorkspaceSizes(), net.descriptor(lazy_ok=True), images, N, S)
 
     def fc_forward_triple(self, net, images, tws, x_exp, N, sidx, S, out_kind, ws, dev_scales=None):
-        w, t = self._ws(ws), self._tws(tws)
+        w, t = self._ws(ws), self._piece_ws(TripleWorkspace, tws)
         # (lazy_ok: a pending images-only draw left the fp32 W1 / Wm stale, which the triple kernels never read)
         check(self.lib.rbnn_fc_forward_triple(C.byref(net.descriptor(lazy_ok=True)), C.byref(images), C.byref(t), x_exp, ptr(dev_scales), N,
                                               ptr(sidx), S, out_kind, C.byref(w), stream_of(tws["X_triple"])), "rbnn_fc_forward_triple")
@@ -492,7 +489,7 @@ class HipKernels:
     def step_tail_triple(self, mode, P, labels, S, inv_S, N, Cn, tws, Psum=None):
         """reduce over samples + loss + dZ generator image in one launch (rbnn_step_tail_triple); the fp32 dZ is not written."""
         require_gpu(P, "P")
-        t = self._tws(tws)
+        t = self._piece_ws(TripleWorkspace, tws)
         check(self.lib.rbnn_step_tail_triple(mode, ptr(P), ptr(labels), S, inv_S, N, Cn, ptr(Psum), 0 if Psum is None else Psum.stride(0), C.byref(t),
                                              stream_of(P)), "rbnn_step_tail_triple")
 
@@ -504,13 +501,11 @@ class HipKernels:
 
     def fc_input_grad_triple(self, net, images, sidx, S, N, chunk, ws, tws, dz_ready=False):
         """dz_ready: tws['dZ_gen'] / tws['g_scale'] were built by step_tail_triple — the fp32 dZ is not read."""
-        w, t = self._ws(ws), self._tws(tws)
+        w = self._ws(ws)
         if dz_ready:
             w.dZ = None
-        n = C.c_int32(0)
-        check(self.lib.rbnn_fc_input_grad_triple(C.byref(net.descriptor(lazy_ok=True)), C.byref(images), ptr(sidx), S, N, chunk, C.byref(w),
-                                                 C.byref(t), C.byref(n), stream_of(ws["slabs"])), "rbnn_fc_input_grad_triple")
-        return n.value
+        return self._fc_input_grad_pieces("rbnn_fc_input_grad_triple", net.descriptor(lazy_ok=True), images, sidx, S, N, chunk, w,
+                                          self._piece_ws(TripleWorkspace, tws), stream_of(ws["slabs"]))
 
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):

@@ -400,15 +400,12 @@ class ConvEngine(AttackEngine):
         return oa, aa, torch.cat([p[2] for p in parts]), torch.cat([p[3] for p in parts]), torch.cat([p[4] for p in parts])
 
     def _forward_kernels(self, Xp, sidx, S, out_kind, ws):
-        if self.precision == "triple":
-            rows, k2_exp = self.post.triple_images()[:2]
-            ds = self._scales if self._scales is not None else self._input_scales(Xp, iterates=False)
-            return self.k.conv_forward_triple(self.post, rows, k2_exp, 0, Xp, sidx, S, out_kind, ws, p1_dev_scale=ds[4:])
-        if self.precision != "split":
+        if self.precision not in ("split", "triple"):
             return self.k.conv_forward(self.post, Xp, sidx, S, out_kind, ws)
-        rows, k2_exp = self.post.split_images()[:2]
-        ds = self._scales if self._scales is not None else self._input_scales(Xp, iterates=False)
-        self.k.conv_forward_split(self.post, rows, k2_exp, 0, Xp, sidx, S, out_kind, ws, p1_dev_scale=ds[4:])
+        tri = self.precision == "triple"
+        rows, k2_exp = (self.post.triple_images() if tri else self.post.split_images())[:2]
+        p1_ds = self._call_scales(Xp)[4:]                                       # record 1 of rbnn_input_scales: the pooled conv1 activations
+        (self.k.conv_forward_triple if tri else self.k.conv_forward_split)(self.post, rows, k2_exp, 0, Xp, sidx, S, out_kind, ws, p1_dev_scale=p1_ds)
 
     def _grad_kernels(self, sidx, S, N, ws, dz_ready=False):
         if self.precision == "triple" and os.environ.get("RBNN_CONV_BWD_EXACT") != "1":

@@ -521,16 +521,9 @@ int rbnn_conv_forward(const rbnn_conv_posterior* net, const float* X, int32_t ld
                       int32_t out_kind, const rbnn_conv_workspace* ws, void* stream) {
     int rc = validate_conv(net);
     if (rc) return rc;
-    if (!X || !ws || !ws->P || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || ldx < net->in_channels * net->in_width * net->in_width || (ldx & 3)) return RBNN_ERR_SHAPE;
-    if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(X) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
     ConvArgs a = {};
-    a.X = X; a.ldx = ldx; a.N = N;
-    a.K1w = net->K1w; a.K1b = net->K1b; a.K2w = net->K2w; a.K2b = net->K2b; a.Fw = net->Fw; a.Fb = net->Fb;
-    a.Hc = net->hidden; a.C = net->n_classes; a.sidx = sidx; a.S = S;
-    a.P1 = ws->P1; a.st1 = ws->st1; a.Q2 = ws->Q2; a.st2 = ws->st2; a.P = ws->P; a.out_kind = out_kind;
+    if ((rc = conv_forward_args(net, net->K2w, true, X, ldx, N, sidx, S, out_kind, ws, a))) return rc;
+    hipStream_t st = (hipStream_t)stream;
     return for_geometry(net, [&](auto g) {
         using G = decltype(g);
         a.NP2 = G::NP2;
@@ -544,16 +537,10 @@ int rbnn_conv_forward_split(const rbnn_conv_posterior* net, const void* K2_rows,
                             const rbnn_conv_workspace* ws, void* stream) {
     int rc = validate_conv_split(net);
     if (rc) return rc;
-    if (!K2_rows || !X || !ws || !ws->P || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || ldx < 784 || (ldx & 3) || k2_exp < -100 || k2_exp > 100 || p1_exp < -100 || p1_exp > 100) return RBNN_ERR_SHAPE;
-    if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(K2_rows) || !aligned16(X) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
     ConvArgs a = {};
-    a.X = X; a.ldx = ldx; a.N = N;
-    a.K1w = net->K1w; a.K1b = net->K1b; a.K2w = net->K2w; a.K2b = net->K2b; a.Fw = net->Fw; a.Fb = net->Fb;
-    a.Hc = net->hidden; a.C = net->n_classes; a.sidx = sidx; a.S = S;
-    a.P1 = ws->P1; a.st1 = ws->st1; a.Q2 = ws->Q2; a.st2 = ws->st2; a.P = ws->P; a.out_kind = out_kind; a.NP2 = NP2;
+    if ((rc = conv_forward_args(net, K2_rows, ldx >= 784 && conv_exp_ok(k2_exp) && conv_exp_ok(p1_exp), X, ldx, N, sidx, S, out_kind, ws, a))) return rc;
+    a.NP2 = NP2;
+    hipStream_t st = (hipStream_t)stream;
     ConvSplitArgs sp = {};
     sp.K2r = (const char*)K2_rows; sp.k2_exp = k2_exp; sp.p1_exp = p1_exp; sp.p1_ds = p1_dev_scale; sp.P1s = (char*)ws->P1;   // ws->P1 holds 24 KiB per (s, n)
     const long long t1 = (long long)S * N * (P1W * P1W);
@@ -1179,12 +1166,9 @@ extern "C" int rbnn_conv_input_grad(const rbnn_conv_posterior* net, const int32_
                                     const rbnn_conv_workspace* ws, void* stream) {
     int rc = validate_conv(net);
     if (rc) return rc;
-    if (!net->K2w_ci || !ws || !ws->dZ || !ws->P1 || !ws->Q2 || !ws->st1 || !ws->st2 || !ws->G) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1) return RBNN_ERR_SHAPE;
-    if (!aligned16(net->K2w_ci) || !aligned16(ws->G)) return RBNN_ERR_ALIGN;
     ConvBwdArgs a = {};
-    a.dZ = ws->dZ; a.st1 = ws->st1; a.st2 = ws->st2; a.K1w = net->K1w; a.K2cb = net->K2w_ci; a.Fw = net->Fw;
-    a.Hc = net->hidden; a.C = net->n_classes; a.N = N; a.S = S; a.sidx = sidx; a.dQ2 = ws->Q2; a.dP1 = ws->P1; a.G = ws->G;
+    if ((rc = conv_backward_args(net, net->K2w_ci, true, sidx, S, N, ws, a))) return rc;
+    a.K2cb = net->K2w_ci;
     hipStream_t st = (hipStream_t)stream;
     return for_geometry(net, [&](auto g) {
         using G = decltype(g);
@@ -1197,12 +1181,9 @@ extern "C" int rbnn_conv_input_grad_split(const rbnn_conv_posterior* net, const 
                                           const int32_t* sidx, int32_t S, int32_t N, const rbnn_conv_workspace* ws, void* stream) {
     int rc = validate_conv_split(net);
     if (rc) return rc;
-    if (!K2_bwd || !ws || !ws->dZ || !ws->P1 || !ws->Q2 || !ws->st1 || !ws->st2 || !ws->G) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || k2_exp < -100 || k2_exp > 100 || !(fw_l1 >= 0.f)) return RBNN_ERR_SHAPE;
-    if (!aligned16(K2_bwd) || !aligned16(ws->G)) return RBNN_ERR_ALIGN;
     ConvBwdArgs a = {};
-    a.dZ = ws->dZ; a.st1 = ws->st1; a.st2 = ws->st2; a.K1w = net->K1w; a.K2cb = nullptr; a.Fw = net->Fw;
-    a.Hc = net->hidden; a.C = net->n_classes; a.N = N; a.S = S; a.sidx = sidx; a.dQ2 = ws->Q2; a.dP1 = ws->P1; a.G = ws->G; a.NP2 = NP2;
+    if ((rc = conv_backward_args(net, K2_bwd, conv_exp_ok(k2_exp) && fw_l1 >= 0.f, sidx, S, N, ws, a))) return rc;
+    a.NP2 = NP2;
     const int grid = grid_for_items((long long)((N + 3) / 4) * S);
     const bool leaky = net->activation == RBNN_ACT_LEAKY;
     hipStream_t st = (hipStream_t)stream;

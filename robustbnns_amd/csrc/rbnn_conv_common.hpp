@@ -73,6 +73,34 @@ inline int validate_conv_split(const rbnn_conv_posterior* net) {
     return RBNN_OK;
 }
 
+// What the three forwards (rbnn_conv_forward, _split, _triple) check in common, in their order, and the ConvArgs they fill (but for NP2, set per
+// geometry).  K2: conv2's weight operand — the mode's image, or net->K2w itself; own_shape_ok: the entry point's own shape rules (exponent ranges).
+// `net` has passed validate_conv.
+inline int conv_forward_args(const rbnn_conv_posterior* net, const void* K2, bool own_shape_ok, const float* X, int32_t ldx, int32_t N,
+                             const int32_t* sidx, int32_t S, int32_t out_kind, const rbnn_conv_workspace* ws, ConvArgs& a) {
+    if (!K2 || !X || !ws || !ws->P || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2) return RBNN_ERR_NULL;
+    if (N < 1 || S < 1 || ldx < net->in_channels * net->in_width * net->in_width || (ldx & 3) || !own_shape_ok) return RBNN_ERR_SHAPE;
+    if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
+    if (!aligned16(K2) || !aligned16(X) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
+    a.X = X; a.ldx = ldx; a.N = N;
+    a.K1w = net->K1w; a.K1b = net->K1b; a.K2w = net->K2w; a.K2b = net->K2b; a.Fw = net->Fw; a.Fb = net->Fb;
+    a.Hc = net->hidden; a.C = net->n_classes; a.sidx = sidx; a.S = S;
+    a.P1 = ws->P1; a.st1 = ws->st1; a.Q2 = ws->Q2; a.st2 = ws->st2; a.P = ws->P; a.out_kind = out_kind;
+    return RBNN_OK;
+}
+// The same for the three backwards (rbnn_conv_input_grad, _split, _dense) and ConvBwdArgs.  K2: conv2^T's weight operand — the mode's image, or
+// net->K2w_ci; K2cb stays NULL (the exact entry point sets it).
+inline int conv_backward_args(const rbnn_conv_posterior* net, const void* K2, bool own_shape_ok, const int32_t* sidx, int32_t S, int32_t N,
+                              const rbnn_conv_workspace* ws, ConvBwdArgs& a) {
+    if (!K2 || !ws || !ws->dZ || !ws->P1 || !ws->Q2 || !ws->st1 || !ws->st2 || !ws->G) return RBNN_ERR_NULL;
+    if (N < 1 || S < 1 || !own_shape_ok) return RBNN_ERR_SHAPE;
+    if (!aligned16(K2) || !aligned16(ws->G)) return RBNN_ERR_ALIGN;
+    a.dZ = ws->dZ; a.st1 = ws->st1; a.st2 = ws->st2; a.K1w = net->K1w; a.Fw = net->Fw;
+    a.Hc = net->hidden; a.C = net->n_classes; a.N = N; a.S = S; a.sidx = sidx; a.dQ2 = ws->Q2; a.dP1 = ws->P1; a.G = ws->G;
+    return RBNN_OK;
+}
+inline bool conv_exp_ok(int e) { return e >= -100 && e <= 100; }
+
 // geometry / activation dispatch of the exact kernels: f(Geo{}) / f(integral_constant<int, ACT>{})
 template <class F> int for_geometry(const rbnn_conv_posterior* net, F&& f) {
     if (net->in_channels == 1 && net->in_width == 28) return f(GeoMnist{});

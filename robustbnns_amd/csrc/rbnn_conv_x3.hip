@@ -547,17 +547,9 @@ extern "C" int rbnn_conv_forward_triple(const rbnn_conv_posterior* net, const vo
                              int32_t S, int32_t out_kind, const rbnn_conv_workspace* ws, void* stream) {
     int rc = validate_conv(net);
     if (rc) return rc;
-    if (!K2_triple || !X || !ws || !ws->P || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || ldx < net->in_channels * net->in_width * net->in_width || (ldx & 3)) return RBNN_ERR_SHAPE;
-    if (k2_exp < -100 || k2_exp > 100 || p1_exp < -100 || p1_exp > 100) return RBNN_ERR_SHAPE;
-    if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(K2_triple) || !aligned16(X) || !aligned16(ws->P) || !aligned16(ws->P1) || !aligned16(ws->Q2)) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
     ConvArgs a = {};
-    a.X = X; a.ldx = ldx; a.N = N;
-    a.K1w = net->K1w; a.K1b = net->K1b; a.K2w = net->K2w; a.K2b = net->K2b; a.Fw = net->Fw; a.Fb = net->Fb;
-    a.Hc = net->hidden; a.C = net->n_classes; a.sidx = sidx; a.S = S;
-    a.P1 = ws->P1; a.st1 = ws->st1; a.Q2 = ws->Q2; a.st2 = ws->st2; a.P = ws->P; a.out_kind = out_kind;
+    if ((rc = conv_forward_args(net, K2_triple, conv_exp_ok(k2_exp) && conv_exp_ok(p1_exp), X, ldx, N, sidx, S, out_kind, ws, a))) return rc;
+    hipStream_t st = (hipStream_t)stream;
     ConvX3Args x = {};
     x.K2t = (const char*)K2_triple; x.k2_exp = k2_exp; x.p1_exp = p1_exp; x.p1_ds = p1_dev_scale;
     return for_geometry(net, [&](auto g) {
@@ -1309,12 +1301,8 @@ extern "C" int rbnn_conv_input_grad_dense(const rbnn_conv_posterior* net, const 
                                           const int32_t* sidx, int32_t S, int32_t N, const rbnn_conv_workspace* ws, void* stream) {
     int rc = validate_conv(net);
     if (rc) return rc;
-    if (!K2_dense || !ws || !ws->dZ || !ws->P1 || !ws->Q2 || !ws->st1 || !ws->st2 || !ws->G) return RBNN_ERR_NULL;
-    if (N < 1 || S < 1 || k2_exp < -100 || k2_exp > 100 || !(fw_l1 >= 0.f)) return RBNN_ERR_SHAPE;
-    if (!aligned16(K2_dense) || !aligned16(ws->G)) return RBNN_ERR_ALIGN;
     ConvBwdArgs a = {};
-    a.dZ = ws->dZ; a.st1 = ws->st1; a.st2 = ws->st2; a.K1w = net->K1w; a.K2cb = nullptr; a.Fw = net->Fw;
-    a.Hc = net->hidden; a.C = net->n_classes; a.N = N; a.S = S; a.sidx = sidx; a.dQ2 = ws->Q2; a.dP1 = ws->P1; a.G = ws->G;
+    if ((rc = conv_backward_args(net, K2_dense, conv_exp_ok(k2_exp) && fw_l1 >= 0.f, sidx, S, N, ws, a))) return rc;
     hipStream_t st = (hipStream_t)stream;
     return for_geometry(net, [&](auto g) {
         using G = decltype(g);

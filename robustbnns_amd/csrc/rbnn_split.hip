@@ -18,7 +18,7 @@
 //                  one lane's MFMA operand (8 K values) is one ds_read_b128 of hi and one of lo.
 // Lane maps (v_mfma_f32_16x16x32_f16, wave64, li = lane & 15, lg = lane >> 4):
 //   A operand  a[j] = A[i = li][k = 8*lg + j]    B operand  b[j] = B[k = 8*lg + j][j' = li]    acc[r] = D[4*lg + r][li]
-#include "rbnn_common.hpp"
+#include "rbnn_pieces.hpp"
 #include <algorithm>
 
 
@@ -525,25 +525,9 @@ __global__ void __launch_bounds__(256) split_dz_kernel(const float* __restrict__
 // Everything a stage needs arrives by LDS-DMA one stage ahead (W1 tile, W2 generator tiles, stash words); the next
 // sample's dZ generator image (16 KiB per block) rides along, one 1-KiB piece per stage.
 // ===================================================================================================
-#define GEN_Q (-17)                                           // |generator| <= 16 * 2^14 * 2^14 = 2^32  ->  |dA| <= 2^15 < fp16 max
-
-struct GradSplitArgs {
-    const char* dzg;  long long n_pad;  const float* gscale;  const uint32_t* mask;
-    const char* W1c;  int ldc;                                  // split-cols image, ldc columns
-    const char* W2g;                                            // generator image [S_total][H/16][1 KiB]
-    int H;  int HW;  const int* sidx;  int S;  int chunk;  int nchunks;
-    int N;  int NT;  int ND;  int Dt;
-    float* out;  int ldo;  float out_scale;                     // slabs [nchunks][N][ldo]; out_scale = 2^-(e_w2 + GEN_Q + e_w1)
-    // fc2.  MODE 1 (step 1, one sample per block): out = [S][N][H] = act'(A1) * (dA2 . Wm), KEPT SCALED (x out_scale, no per-point
-    // un-scaling): it is the fp32 source of step 2's A operand.  MODE 2 (step 2): A operand read from `amem` and split in registers.
-    const uint32_t* omask;  int OHW;                            // MODE 1: stash of the layer below [S][H/32][N_pad]
-    const float* amem;                                          // MODE 2: [S][N][H]
-    const float* dact;  const float* odact;                     // sigmoid / tanh: act' as fp32 [S][N][H] (this layer / the layer below)
-};
-enum { GRAD_FC = 0, GRAD_FC2_STEP1 = 1, GRAD_FC2_STEP2 = 2 };
-
+// (arguments: GradPieceArgs, rbnn_pieces.hpp)
 template <int ACT, int TD, int MODE>
-__global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradSplitArgs a) {
+__global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradPieceArgs a) {
     constexpr int NW = 4, NTW = 4;                             // 4 waves x 4 point tiles, two blocks per CU (8-wave and 1-block shapes lost: see launch_grad_split)
     constexpr bool GEN = MODE != GRAD_FC2_STEP2;               // dA generated from dZ, or read from memory
     constexpr bool BITMASK = (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY);   // act' from the 1-bit stash, or an fp32 stream
@@ -728,7 +712,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradSplitAr
 }
 
 template <int ACT, int TD, int MODE>
-int launch_grad_split_cfg(GradSplitArgs a, hipStream_t st) {
+int launch_grad_split_cfg(GradPieceArgs a, hipStream_t st) {
     constexpr int LDSB = 2 * (8 * TD * 16 * 16 + 3072) + 2 * 256 * 64;
     a.NT = (a.N + 255) / 256;
     a.ND = (a.Dt + TD - 1) / TD;
@@ -748,7 +732,7 @@ int launch_grad_split_cfg(GradSplitArgs a, hipStream_t st) {
 // slices fenced between groups of 12 MFMAs) was also slower, 2.73 vs 2.49 ms: a wave issues in order, and the dependent
 // VALU chains stall the independent MFMAs queued behind them.  (profiles/r01f/ablation_split.txt)
 template <int ACT, int MODE>
-int launch_grad_split(const GradSplitArgs& a, hipStream_t st) {
+int launch_grad_split(const GradPieceArgs& a, hipStream_t st) {
     // 7 or 4 column tiles per block.  A partial last group skips its missing tiles' MFMAs, so padding costs little; every
     // group pays the dA generator (or the A-operand reads) again, so FEWER groups win: 7 wherever that saves a group
     // (fc2 step 1 at H = 512: 32 tiles = 5 groups of 7 instead of 8 of 4 — 2.72 -> see profiles)
@@ -757,7 +741,7 @@ int launch_grad_split(const GradSplitArgs& a, hipStream_t st) {
 }
 
 template <int MODE>
-int launch_grad_split_act(int act, const GradSplitArgs& a, hipStream_t st) {
+int launch_grad_split_act(int act, const GradPieceArgs& a, hipStream_t st) {
 #ifndef RBNN_FAST_BUILD
     if (act == RBNN_ACT_RELU) return launch_grad_split<RBNN_ACT_RELU, MODE>(a, st);
     if (act == RBNN_ACT_SIGM || act == RBNN_ACT_TANH)          // both read act' from the stream: one instantiation serves them
@@ -787,77 +771,30 @@ int rbnn_input_scales(const float* X, int64_t rows, int32_t cols, int32_t ld, fl
 
 int rbnn_split_rows(const float* src, int64_t rows, int32_t cols, int32_t ld_src, int32_t scale_exp,
                     const rbnn_dev_scale* dev_scale, void* dst, int32_t ld_dst, void* stream) {
-    if (!src || !dst) return RBNN_ERR_NULL;
-    if (rows < 1 || cols < 1 || ld_src < cols || ld_dst < cols || (ld_dst & 31)) return RBNN_ERR_SHAPE;
-    if (scale_exp < -100 || scale_exp > 100) return RBNN_ERR_SHAPE;
-    if (!aligned16(dst)) return RBNN_ERR_ALIGN;
-    const int groups = ld_dst / 8;
-    const long long total = (long long)rows * groups;
-    hipLaunchKernelGGL(split_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       src, (long long)rows, cols, ld_src, ldexpf(1.f, scale_exp), dev_scale, (uint4*)dst, groups);
-    return launch_status();
+    return launch_rows_image(split_rows_kernel, src, rows, cols, ld_src, scale_exp, dev_scale, dst, ld_dst, stream);
 }
 
 int rbnn_fc_forward_split(const rbnn_posterior* net, const rbnn_split_images* sp, const void* X_split, int32_t ldx,
                           int32_t x_exp, const rbnn_dev_scale* dev_scales, int32_t N, const int32_t* sidx, int32_t S,
                           int32_t out_kind, const rbnn_workspace* ws, void* stream) {
-    if (!net || !sp || !X_split || !ws || !ws->P || !sp->W1_rows) return RBNN_ERR_NULL;
-    if (!net->b1 || !net->W2 || !net->b2) return RBNN_ERR_NULL;
-    if (net->arch != RBNN_ARCH_FC && net->arch != RBNN_ARCH_FC2) return RBNN_ERR_UNSUPPORTED;
-    if (net->activation < RBNN_ACT_RELU || net->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
-    const bool fc2 = net->arch == RBNN_ARCH_FC2, bm = net->activation == RBNN_ACT_RELU || net->activation == RBNN_ACT_LEAKY;
-    const int H = net->hidden, ld = sp->ld_rows;
-    if (H < 128 || (H % 128) || ld < net->in_features || (ld & 31) || ldx != ld) return RBNN_ERR_SHAPE;
-    if (net->n_classes < 1 || net->n_classes > RBNN_CPAD || N < 1 || S < 1) return RBNN_ERR_SHAPE;
-    // the kernels address a sample's weight image and the input image with 32-bit byte offsets from a 64-bit base
-    if ((long long)H * ld * 4 >= (1LL << 32) || (long long)N * ld * 4 >= (1LL << 32) || (long long)N * H * 4 >= (1LL << 32)) return RBNN_ERR_SHAPE;
-    if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(X_split) || !aligned16(sp->W1_rows) || !aligned16(ws->P) || !aligned16(net->b1) || !aligned16(net->W2)) return RBNN_ERR_ALIGN;
-    if (fc2 && (!sp->Wm_rows || !net->bm || !ws->hid1 || (bm ? !ws->mask2 : !ws->dact2))) return RBNN_ERR_NULL;
-    if (fc2 && (!aligned16(sp->Wm_rows) || !aligned16(ws->hid1) || !aligned16(net->bm))) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    FwdSplitArgs a = {};
-    a.X = (const char*)X_split; a.ldx = ldx; a.N = N; a.x_sample_bytes = 0;
-    a.W = (const char*)sp->W1_rows; a.w_sample_bytes = (long long)H * ld * 4; a.ldw = ld; a.KT = ld / 32;
-    a.b = net->b1; a.W2 = net->W2; a.b2 = net->b2; a.C = net->n_classes; a.H = H;
-    a.sidx = sidx; a.S = S; a.out_scale = ldexpf(1.f, -((dev_scales ? 0 : x_exp) + sp->w1_exp)); a.x_ds = dev_scales;
-    a.P = ws->P; a.mask = ws->mask1; a.dact = ws->dact1; a.out_kind = out_kind;
-    if (!fc2) return launch_forward_split<true>(net->activation, a, st);
-    // fc2: layer 1 -> hidden activations as a split-rows image in ws->hid1 (same bytes as the fp32 [S,N,H] buffer), scaled by
-    // 2^h1_exp (the caller bounds |h|: max_h sum_d |W1[h,d]| * max|x| + max|b1|); layer 2 reads it per sample
-    a.hid = (char*)ws->hid1; a.hid_scale = ldexpf(1.f, sp->h1_exp); a.hid_ds = dev_scales ? dev_scales + 1 : nullptr;
-    int rc = launch_forward_split<false>(net->activation, a, st);
+    FwdSplitArgs a = {}, b = {};
+    int rc = fc_forward_pieces_args(net, sp, X_split, ldx, ws ? ws->hid1 : nullptr, 4, 0, x_exp, dev_scales, N, sidx, S, out_kind, ws, a, b);
     if (rc) return rc;
-    FwdSplitArgs b = a;
-    b.X = (const char*)ws->hid1; b.ldx = H; b.x_sample_bytes = (long long)N * H * 4;
-    b.W = (const char*)sp->Wm_rows; b.w_sample_bytes = (long long)H * H * 4; b.ldw = H; b.KT = H / 32;
-    b.b = net->bm; b.out_scale = ldexpf(1.f, -((dev_scales ? 0 : sp->h1_exp) + sp->wm_exp));
-    b.x_ds = dev_scales ? dev_scales + 1 : nullptr; b.hid_ds = nullptr;
-    b.mask = ws->mask2; b.dact = ws->dact2; b.hid = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (net->arch != RBNN_ARCH_FC2) return launch_forward_split<true>(net->activation, a, st);
+    // fc2: the hidden image is a split-rows image [S][N][H] in ws->hid1 (same bytes as the fp32 [S,N,H] buffer)
+    if ((rc = launch_forward_split<false>(net->activation, a, st))) return rc;
+    b.x_sample_bytes = (long long)N * net->hidden * 4;
     return launch_forward_split<true>(net->activation, b, st);
 }
 
 int rbnn_split_cols(const float* W, int64_t n_mats, int32_t rows, int32_t cols, int32_t ld_src, int32_t scale_exp,
                     void* dst, int32_t ld_dst, void* stream) {
-    if (!W || !dst) return RBNN_ERR_NULL;
-    if (n_mats < 1 || rows < 32 || (rows & 31) || cols < 1 || ld_src < cols || ld_dst < cols || (ld_dst & 15)) return RBNN_ERR_SHAPE;
-    if (scale_exp < -100 || scale_exp > 100) return RBNN_ERR_SHAPE;
-    if (!aligned16(dst)) return RBNN_ERR_ALIGN;
-    const long long total = (long long)n_mats * (rows / 32) * 4 * ld_dst;
-    hipLaunchKernelGGL(split_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       W, (long long)n_mats, rows, cols, ld_src, ldexpf(1.f, scale_exp), (uint4*)dst, ld_dst);
-    return launch_status();
+    return launch_cols_image(split_cols_kernel, W, n_mats, rows, cols, ld_src, scale_exp, dst, ld_dst, stream);
 }
 
 int rbnn_split_w2gen(const float* W2, int32_t n_mats, int32_t C, int32_t H, int32_t scale_exp, void* dst, void* stream) {
-    if (!W2 || !dst) return RBNN_ERR_NULL;
-    if (n_mats < 1 || C < 1 || C > 10 || H < 16 || (H & 15)) return RBNN_ERR_SHAPE;
-    if (scale_exp < -100 || scale_exp > 100) return RBNN_ERR_SHAPE;
-    if (!aligned16(dst)) return RBNN_ERR_ALIGN;
-    const long long total = (long long)n_mats * (H / 16) * 64;
-    hipLaunchKernelGGL(split_w2gen_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       W2, n_mats, C, H, ldexpf(1.f, scale_exp), (uint4*)dst);
-    return launch_status();
+    return launch_w2gen_image(split_w2gen_kernel, 64, W2, n_mats, C, H, scale_exp, dst, stream);
 }
 
 int rbnn_split_workspace_query(const rbnn_posterior* net, const rbnn_split_images* sp, int32_t N, int32_t S,
@@ -875,59 +812,10 @@ int rbnn_split_workspace_query(const rbnn_posterior* net, const rbnn_split_image
 int rbnn_fc_input_grad_split(const rbnn_posterior* net, const rbnn_split_images* sp, const int32_t* sidx, int32_t S,
                              int32_t N, int32_t chunk, const rbnn_workspace* ws, const rbnn_split_workspace* sws,
                              int32_t* n_slabs_out, void* stream) {
-    if (!net || !sp || !ws || !sws || !ws->dZ || !ws->slabs) return RBNN_ERR_NULL;
-    if (!sp->W1_cols || !sp->W2_gen || !sws->dZ_gen || !sws->g_scale) return RBNN_ERR_NULL;
-    if (net->arch != RBNN_ARCH_FC && net->arch != RBNN_ARCH_FC2) return RBNN_ERR_UNSUPPORTED;
-    if (net->activation < RBNN_ACT_RELU || net->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
-    const bool fc2 = net->arch == RBNN_ARCH_FC2, bm = net->activation == RBNN_ACT_RELU || net->activation == RBNN_ACT_LEAKY;
-    if (bm ? !ws->mask1 : !ws->dact1) return RBNN_ERR_NULL;
-    if (fc2 && (bm ? !ws->mask2 : !ws->dact2)) return RBNN_ERR_NULL;
-    const int H = net->hidden, Dp = net->in_stride, C = net->n_classes;
-    if (H < 128 || (H % 128) || C < 1 || C > 10 || N < 1 || S < 1) return RBNN_ERR_SHAPE;
-    if (sp->ld_cols != Dp || (Dp & 15)) return RBNN_ERR_SHAPE;
-    if (!aligned16(sp->W1_cols) || !aligned16(sp->W2_gen) || !aligned16(sws->dZ_gen) || !aligned16(ws->dZ)) return RBNN_ERR_ALIGN;
-    if (fc2 && (!sp->Wm_cols || !ws->dhid1)) return RBNN_ERR_NULL;
-    if (fc2 && (!aligned16(sp->Wm_cols) || !aligned16(ws->dhid1))) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (chunk <= 0) {                                           // the exact mode's slab plan (same workspace)
-        rbnn_workspace_sizes q;
-        const int rc = rbnn_workspace_query(net, N, S, 0, &q);
-        if (rc) return rc;
-        chunk = q.chunk;
-    }
-    if (chunk > S) chunk = S;
-    const int nchunks = (S + chunk - 1) / chunk;
-    if (n_slabs_out) *n_slabs_out = nchunks;
-    const long long n_pad = mask_ld(N);
-    hipLaunchKernelGGL(split_dz_kernel, dim3((unsigned)(n_pad / 16)), dim3(256), 0, st,
-                       ws->dZ, S, N, n_pad, C, (uint4*)sws->dZ_gen, sws->g_scale);
-    if (hipGetLastError() != hipSuccess) return RBNN_ERR_LAUNCH;
-    GradSplitArgs g = {};
-    g.dzg = (const char*)sws->dZ_gen; g.n_pad = n_pad; g.gscale = sws->g_scale;
-    g.W2g = (const char*)sp->W2_gen;
-    g.H = H; g.HW = H / 32; g.sidx = sidx; g.S = S; g.N = N;
-    if (!fc2) {
-        g.mask = ws->mask1; g.dact = ws->dact1; g.W1c = (const char*)sp->W1_cols; g.ldc = sp->ld_cols; g.Dt = Dp / 16;
-        g.chunk = chunk; g.nchunks = nchunks; g.out = ws->slabs; g.ldo = Dp;
-        g.out_scale = ldexpf(1.f, -(sp->w2_exp + GEN_Q + sp->w1_exp));
-        return launch_grad_split_act<GRAD_FC>(net->activation, g, st);
-    }
-    // fc2 step 1, one sample per block: dhid1[s] = act'(A1_s) * ((act'(A2_s) * (dZ_s . W3_s)) . Wm_s), kept scaled:
-    //   stored = dhid1 * 2^(e(n) + e_w3 + GEN_Q + e_wm - Q2),  Q2 = 14 + ceil(log2 H): |dA2 scaled| <= 2^15, |Wm scaled| <= 2^14, K = H
-    //   => |stored| <= 2^15, fp16 range, ready to be split as step 2's A operand
-    int q2 = 14;
-    while ((1 << (q2 - 14)) < H) ++q2;
-    g.mask = ws->mask2; g.dact = ws->dact2; g.odact = ws->dact1; g.W1c = (const char*)sp->Wm_cols; g.ldc = H; g.Dt = H / 16;
-    g.chunk = 1; g.nchunks = S; g.out = ws->dhid1; g.ldo = H; g.out_scale = ldexpf(1.f, -q2);
-    g.omask = ws->mask1; g.OHW = H / 32;
-    int rc = launch_grad_split_act<GRAD_FC2_STEP1>(net->activation, g, st);
-    if (rc) return rc;
-    // fc2 step 2: slabs[k] = sum_{s in chunk k} dhid1[s] . W1_s; acc = g * 2^(e(n) + e_w3 + GEN_Q + e_wm - Q2 + e_w1)
-    GradSplitArgs h = g;
-    h.amem = ws->dhid1; h.W1c = (const char*)sp->W1_cols; h.ldc = sp->ld_cols; h.Dt = Dp / 16;
-    h.chunk = chunk; h.nchunks = nchunks; h.out = ws->slabs; h.ldo = Dp;
-    h.out_scale = ldexpf(1.f, -(sp->w2_exp + GEN_Q + sp->wm_exp - q2 + sp->w1_exp));
-    return launch_grad_split_act<GRAD_FC2_STEP2>(net->activation, h, st);
+    return fc_input_grad_pieces(net, sp, sidx, S, N, chunk, ws, sws, n_slabs_out, stream, split_dz_kernel, false,
+                                [](auto mode, int act, const GradPieceArgs& g, hipStream_t st) {
+                                    return launch_grad_split_act<decltype(mode)::value>(act, g, st);
+                                });
 }
 
 }  // extern "C"

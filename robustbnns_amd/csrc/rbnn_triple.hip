@@ -22,7 +22,7 @@
 //                  (8 K values) is one ds_read_b128 per plane; chunk swizzle `swz` (rbnn_common.hpp) as for fp32 64-B rows.
 //   "triple cols"  [S][H/32][4 lg][3][ld][8] halves: the backward's B operand, K-slot order = the dA generator's output order.
 // Lane maps as in rbnn_split.hip (v_mfma_f32_16x16x32_f16): a[j] = A[li][8*lg + j], b[j] = B[8*lg + j][li], acc[r] = D[4*lg + r][li].
-#include "rbnn_common.hpp"
+#include "rbnn_pieces.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -85,7 +85,7 @@ __device__ __forceinline__ void split3_pair(float ge, float go, unsigned mw, uns
     else asm volatile(RBNN_X3_PAIR_BODY RBNN_X3_PAIR_OPS);   // volatile: the pairs of one MFMA result stay behind the FIRST one
 }
 
-// The same with the two multipliers given (sigmoid / tanh: act' comes from an fp32 stream, already times 2^GEN_Q3): 7 per pair.
+// The same with the two multipliers given (sigmoid / tanh: act' comes from an fp32 stream, already times 2^GEN_Q): 7 per pair.
 template <bool FIRST>
 __device__ __forceinline__ void split3_pair_m(float ge, float go, float me, float mo, float one, unsigned& d0, unsigned& d1, unsigned& d2) {
     float re, ro;
@@ -787,27 +787,11 @@ __global__ void __launch_bounds__(256) attack_step_x3_kernel(float* __restrict__
 // wave's own 64 points (4 KiB per sample) lives in a SINGLE buffer: the wave itself re-fills it for the next sample during
 // the last stage of the current one, after its generator reads (two blocks per CU need <= 80 KB each).
 // ===================================================================================================
-#define GEN_Q3 (-17)                                           // |generator| <= 16 * 2^14 * 2^14 = 2^32  ->  |dA| <= 2^15 < fp16 max
-
-struct GradX3Args {
-    const char* dzg;  long long n_pad;  const float* gscale;  const uint32_t* mask;
-    const char* W1c;  int ldc;                                  // triple-cols image, ldc columns
-    const char* W2g;                                            // generator image [S_total][H/16][2 KiB]
-    int H;  int HW;  const int* sidx;  int S;  int chunk;  int nchunks;
-    int N;  int NT;  int ND;  int Dt;
-    float* out;  int ldo;  float out_scale;                     // slabs [nchunks][N][ldo]; out_scale = 2^-(e_w2 + GEN_Q3 + e_w1)
-    // fc2.  X3_FC2_STEP1 (one sample per block): out = dhid1 [S][N][H] = act'(A1) * (dA2 . Wm), KEPT SCALED (x out_scale, no per-point
-    // un-scaling): it is the fp32 source of step 2's A operand.  X3_FC2_STEP2: A operand read from `amem` and split in registers.
-    const uint32_t* omask;  int OHW;                            // step 1: stash of the layer below [S][H/32][N_pad]
-    const float* amem;                                          // step 2: [S][N][H]
-    const float* dact;  const float* odact;                     // sigmoid / tanh: act' as fp32 [S][N][H] (this layer / the layer below)
-};
-enum { X3_FC = 0, X3_FC2_STEP1 = 1, X3_FC2_STEP2 = 2 };
-
+// (arguments: GradPieceArgs, rbnn_pieces.hpp)
 template <int ACT, int TD, int MODE>
-__global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) {
+__global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradPieceArgs a) {
     constexpr int NW = 4;                                      // 4 waves x (64 points x TD*16 columns), two blocks per CU
-    constexpr bool GEN = MODE != X3_FC2_STEP2;                 // dA generated from dZ, or read from memory
+    constexpr bool GEN = MODE != GRAD_FC2_STEP2;                 // dA generated from dZ, or read from memory
     constexpr bool BITMASK = (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY);   // act' from the 1-bit stash, or an fp32 stream (sigmoid / tanh)
     constexpr bool STREAM = !GEN || !BITMASK;                  // a per-lane fp32 operand (A itself, or act') is prefetched from memory
     constexpr int NTW = 16 / NW, BM = 256, LD = TD * 16;
@@ -900,9 +884,9 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) 
     };
     if (STREAM) load_a(0);
     ring_wait_barrier<0>();
-    const float c_pos = ldexpf(1.f, GEN_Q3);
+    const float c_pos = ldexpf(1.f, GEN_Q);
     const unsigned cp_bits = __float_as_uint(c_pos);
-    const unsigned cn_bits = (ACT == RBNN_ACT_RELU) ? 0u : __float_as_uint(LEAKY_SLOPE * ldexpf(1.f, GEN_Q3));
+    const unsigned cn_bits = (ACT == RBNN_ACT_RELU) ? 0u : __float_as_uint(LEAKY_SLOPE * ldexpf(1.f, GEN_Q));
     const int dzc1 = (lg == 2 ? 0 : lg), dzc2 = (lg == 0 ? 1 : (lg == 1 ? 2 : (lg == 2 ? 0 : 3)));   // dZ chunk of MFMA 1 / 2 for this lane group
     const int sz = dz_swz3(li);
     const char* const dzw = dzl + wave * (NTW * 1024) + li * 64;
@@ -931,7 +915,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) 
 #pragma unroll
             for (int i = 0; i < NDMA; ++i) issue_piece(q, i);
         }
-        f32x4 dm[(GEN && STREAM) ? NTW : 1][2];                // sigmoid / tanh: this stage's act' x 2^GEN_Q3 (copied before the next prefetch)
+        f32x4 dm[(GEN && STREAM) ? NTW : 1][2];                // sigmoid / tanh: this stage's act' x 2^GEN_Q (copied before the next prefetch)
         if (GEN && STREAM) {
 #pragma unroll
             for (int nt = 0; nt < ((GEN && STREAM) ? NTW : 0); ++nt) { dm[nt][0] = am[nt][0] * c_pos; dm[nt][1] = am[nt][1] * c_pos; }
@@ -1034,7 +1018,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = nb + nt * 16 + 4 * lg + r;
-            const float gs = (MODE == X3_FC2_STEP1) ? a.out_scale : (n < a.N ? a.gscale[n] : 0.f) * a.out_scale;
+            const float gs = (MODE == GRAD_FC2_STEP1) ? a.out_scale : (n < a.N ? a.gscale[n] : 0.f) * a.out_scale;
 #pragma unroll
             for (int dt = 0; dt < TD; ++dt) tw[(4 * lg + r) * LDW + dt * 16 + li] = acc[nt][dt][r] * gs;
         }
@@ -1044,7 +1028,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) 
             const int n = nb + nt * 16 + row, d = dc0 + 4 * c4;
             if (e4 < E4 && n < a.N && d < Dp) {                       // (Dp is a multiple of 16: a quad is in or out as a whole)
                 f32x4 v = *(const f32x4*)(tw + row * LDW + 4 * c4);
-                if (MODE == X3_FC2_STEP1) {                           // derivative of the layer below: units d .. d + 3 of point n, sample ch
+                if (MODE == GRAD_FC2_STEP1) {                           // derivative of the layer below: units d .. d + 3 of point n, sample ch
                     if (BITMASK) {
                         const unsigned w = a.omask[((long long)ch * a.OHW + (d >> 5)) * a.n_pad + n] >> (d & 31);
 #pragma unroll
@@ -1060,7 +1044,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradX3Args a) 
 }
 
 template <int ACT, int TD, int MODE>
-int launch_grad_x3_cfg(GradX3Args a, hipStream_t st) {
+int launch_grad_x3_cfg(GradPieceArgs a, hipStream_t st) {
     constexpr int LDSB = 2 * (12 * TD * 16 * 16 + 5120) + 256 * 64;
     static_assert(2 * LDSB <= 160 * 1024, "two blocks per CU");
     a.NT = (a.N + 255) / 256;
@@ -1100,15 +1084,15 @@ bool x3_grad_two_blocks() {
 // 7 or 4 column tiles per block: every group pays the dA generator (or the A-operand reads) again, so fewer groups win — 7 wherever
 // that saves a group (a partial last group skips its missing tiles' MFMAs)
 template <int ACT, int MODE>
-int launch_grad_x3(const GradX3Args& a, hipStream_t st) {
+int launch_grad_x3(const GradPieceArgs& a, hipStream_t st) {
     // 9 column tiles per block (two blocks' LDS = exactly 160 KB): 6 column groups instead of 7 at D = 784, i.e. one generator + split
     // pass in seven less: 3.71 / 3.68 -> 3.59 / 3.59 ms at C2 (alternating builds, same box).  Environment RBNN_X3_GRAD_TD9=0 switches
     // back.  (Re-planning the slab size for the 6-group grid — 6 samples per slab instead of 5 — measured slower, 3.75 ms: kept as planned.)
-    if constexpr (MODE == X3_FC && (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY)) {   // (fc2 step 2 spills at 9 tiles)
+    if constexpr (MODE == GRAD_FC && (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY)) {   // (fc2 step 2 spills at 9 tiles)
         if (x3_grad_td9() && (a.Dt + 8) / 9 < (a.Dt + 6) / 7 && x3_grad_two_blocks<ACT, 9, MODE>()) return launch_grad_x3_cfg<ACT, 9, MODE>(a, st);
     }
     // 8 column tiles per block where that saves a group over 7 (hidden = 512: fc2 step 1 runs 4 groups instead of 5)
-    if constexpr (MODE != X3_FC2_STEP2 && (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY)) {   // (the streamed-operand forms spill at 8 tiles)
+    if constexpr (MODE != GRAD_FC2_STEP2 && (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY)) {   // (the streamed-operand forms spill at 8 tiles)
         if (x3_grad_td9() && (a.Dt + 7) / 8 < (a.Dt + 6) / 7 && x3_grad_two_blocks<ACT, 8, MODE>()) return launch_grad_x3_cfg<ACT, 8, MODE>(a, st);
     }
     if ((a.Dt + 6) / 7 < (a.Dt + 3) / 4) return launch_grad_x3_cfg<ACT, 7, MODE>(a, st);
@@ -1116,7 +1100,7 @@ int launch_grad_x3(const GradX3Args& a, hipStream_t st) {
 }
 
 template <int MODE>
-int launch_grad_x3_act(int act, const GradX3Args& a, hipStream_t st) {
+int launch_grad_x3_act(int act, const GradPieceArgs& a, hipStream_t st) {
 #ifndef RBNN_FAST_BUILD
     if (act == RBNN_ACT_RELU) return launch_grad_x3<RBNN_ACT_RELU, MODE>(a, st);
     if (act == RBNN_ACT_SIGM || act == RBNN_ACT_TANH) return launch_grad_x3<RBNN_ACT_SIGM, MODE>(a, st);   // both read act' from the stream
@@ -1128,50 +1112,23 @@ int launch_grad_x3_act(int act, const GradX3Args& a, hipStream_t st) {
 
 extern "C" {
 
-static int triple_rows_launch(const float* src, int64_t rows, int32_t cols, int32_t ld_src, int32_t scale_exp,
-                              const rbnn_dev_scale* dev_scale, void* dst, int32_t ld_dst, void* stream, int grouped) {
-    if (!src || !dst) return RBNN_ERR_NULL;
-    if (rows < 1 || cols < 1 || ld_src < cols || ld_dst < cols || (ld_dst & 31)) return RBNN_ERR_SHAPE;
-    if (scale_exp < -100 || scale_exp > 100) return RBNN_ERR_SHAPE;
-    if (!aligned16(dst)) return RBNN_ERR_ALIGN;
-    const int groups = ld_dst / 8;
-    const long long total = (long long)rows * groups;
-    hipLaunchKernelGGL(triple_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       src, (long long)rows, cols, ld_src, ldexpf(1.f, scale_exp), dev_scale, (uint4*)dst, groups, grouped);
-    return launch_status();
-}
-
 int rbnn_triple_rows(const float* src, int64_t rows, int32_t cols, int32_t ld_src, int32_t scale_exp,
                      const rbnn_dev_scale* dev_scale, void* dst, int32_t ld_dst, void* stream) {
-    return triple_rows_launch(src, rows, cols, ld_src, scale_exp, dev_scale, dst, ld_dst, stream, 0);
+    return launch_rows_image(triple_rows_kernel, src, rows, cols, ld_src, scale_exp, dev_scale, dst, ld_dst, stream, 0);
 }
 
 int rbnn_triple_rows_grouped(const float* src, int64_t rows, int32_t cols, int32_t ld_src, int32_t scale_exp,
                              const rbnn_dev_scale* dev_scale, void* dst, int32_t ld_dst, void* stream) {
-    return triple_rows_launch(src, rows, cols, ld_src, scale_exp, dev_scale, dst, ld_dst, stream, 1);
+    return launch_rows_image(triple_rows_kernel, src, rows, cols, ld_src, scale_exp, dev_scale, dst, ld_dst, stream, 1);
 }
 
 int rbnn_triple_cols(const float* W, int64_t n_mats, int32_t rows, int32_t cols, int32_t ld_src, int32_t scale_exp,
                      void* dst, int32_t ld_dst, void* stream) {
-    if (!W || !dst) return RBNN_ERR_NULL;
-    if (n_mats < 1 || rows < 32 || (rows & 31) || cols < 1 || ld_src < cols || ld_dst < cols || (ld_dst & 15)) return RBNN_ERR_SHAPE;
-    if (scale_exp < -100 || scale_exp > 100) return RBNN_ERR_SHAPE;
-    if (!aligned16(dst)) return RBNN_ERR_ALIGN;
-    const long long total = (long long)n_mats * (rows / 32) * 4 * ld_dst;
-    hipLaunchKernelGGL(triple_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       W, (long long)n_mats, rows, cols, ld_src, ldexpf(1.f, scale_exp), (uint4*)dst, ld_dst);
-    return launch_status();
+    return launch_cols_image(triple_cols_kernel, W, n_mats, rows, cols, ld_src, scale_exp, dst, ld_dst, stream);
 }
 
 int rbnn_triple_w2gen(const float* W2, int32_t n_mats, int32_t C, int32_t H, int32_t scale_exp, void* dst, void* stream) {
-    if (!W2 || !dst) return RBNN_ERR_NULL;
-    if (n_mats < 1 || C < 1 || C > 10 || H < 16 || (H & 15)) return RBNN_ERR_SHAPE;
-    if (scale_exp < -100 || scale_exp > 100) return RBNN_ERR_SHAPE;
-    if (!aligned16(dst)) return RBNN_ERR_ALIGN;
-    const long long total = (long long)n_mats * (H / 16) * 128;
-    hipLaunchKernelGGL(triple_w2gen_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       W2, n_mats, C, H, ldexpf(1.f, scale_exp), (uint4*)dst);
-    return launch_status();
+    return launch_w2gen_image(triple_w2gen_kernel, 128, W2, n_mats, C, H, scale_exp, dst, stream);
 }
 
 int rbnn_triple_workspace_query(const rbnn_posterior* net, const rbnn_triple_images* tp, int32_t N, int32_t S,
@@ -1190,40 +1147,17 @@ int rbnn_triple_workspace_query(const rbnn_posterior* net, const rbnn_triple_ima
 int rbnn_fc_forward_triple(const rbnn_posterior* net, const rbnn_triple_images* tp, const rbnn_triple_workspace* tws,
                            int32_t x_exp, const rbnn_dev_scale* dev_scales, int32_t N, const int32_t* sidx, int32_t S,
                            int32_t out_kind, const rbnn_workspace* ws, void* stream) {
-    if (!net || !tp || !tws || !tws->X_triple || !ws || !ws->P || !tp->W1_rows) return RBNN_ERR_NULL;
-    if (!net->b1 || !net->W2 || !net->b2) return RBNN_ERR_NULL;
-    if (net->arch != RBNN_ARCH_FC && net->arch != RBNN_ARCH_FC2) return RBNN_ERR_UNSUPPORTED;
-    if (net->activation < RBNN_ACT_RELU || net->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
-    const bool fc2 = net->arch == RBNN_ARCH_FC2, bm = net->activation == RBNN_ACT_RELU || net->activation == RBNN_ACT_LEAKY;
-    const int H = net->hidden, ld = tp->ld_rows;
-    if (H < 128 || (H % 128) || ld < net->in_features || (ld & 31)) return RBNN_ERR_SHAPE;
-    if (net->n_classes < 1 || net->n_classes > RBNN_CPAD || N < 1 || S < 1) return RBNN_ERR_SHAPE;
-    // the kernel addresses a sample's weight image and the input image with 32-bit byte offsets from a 64-bit base
-    if ((long long)H * ld * 6 >= (1LL << 32) || ((long long)N + 15) * ld * 6 >= (1LL << 32) || ((long long)N + 15) * H * 6 >= (1LL << 32)) return RBNN_ERR_SHAPE;
-    if (out_kind != RBNN_OUT_PROBS && out_kind != RBNN_OUT_LOGITS) return RBNN_ERR_UNSUPPORTED;
-    if (!aligned16(tws->X_triple) || !aligned16(tp->W1_rows) || !aligned16(ws->P) || !aligned16(net->b1) || !aligned16(net->W2)) return RBNN_ERR_ALIGN;
-    if (fc2 && (!tp->Wm_rows || !net->bm || !tws->hid_triple || (bm ? !ws->mask2 : !ws->dact2))) return RBNN_ERR_NULL;
-    if (fc2 && (!aligned16(tp->Wm_rows) || !aligned16(tws->hid_triple) || !aligned16(net->bm))) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    FwdX3Args a = {};
-    a.X = (const char*)tws->X_triple; a.ldx = ld; a.N = N; a.x_sample_bytes = 0; a.x_group_bytes = (unsigned)(ld / 32) * 3072u; a.x_stage_bytes = 3072u;
-    a.W = (const char*)tp->W1_rows; a.w_sample_bytes = (long long)H * ld * 6; a.ldw = ld; a.KT = ld / 32;
-    a.b = net->b1; a.W2 = net->W2; a.b2 = net->b2; a.C = net->n_classes; a.H = H;
-    a.sidx = sidx; a.S = S; a.out_scale = ldexpf(1.f, -((dev_scales ? 0 : x_exp) + tp->w1_exp)); a.x_ds = dev_scales;
-    a.P = ws->P; a.mask = ws->mask1; a.dact = ws->dact1; a.out_kind = out_kind;
-    if (!fc2) return launch_forward_x3<true>(net->activation, a, st);
-    // fc2: layer 1 -> hidden activations as a triple-rows image in tws->hid_triple, scaled by 2^h1_exp (the caller bounds |h|:
-    // max_h sum_d |W1[h,d]| * max|x| + max|b1|; record [1] of rbnn_input_scales on the device); layer 2 reads it per sample
-    a.hid = (char*)tws->hid_triple; a.hid_scale = ldexpf(1.f, tp->h1_exp); a.hid_ds = dev_scales ? dev_scales + 1 : nullptr;
-    int rc = launch_forward_x3<false>(net->activation, a, st);
+    FwdX3Args a = {}, b = {};
+    int rc = fc_forward_pieces_args(net, tp, tws ? tws->X_triple : nullptr, tp ? tp->ld_rows : 0, tws ? tws->hid_triple : nullptr, 6, 15,
+                                    x_exp, dev_scales, N, sidx, S, out_kind, ws, a, b);
     if (rc) return rc;
-    FwdX3Args b = a;
+    hipStream_t st = (hipStream_t)stream;
+    a.x_group_bytes = (unsigned)a.KT * 3072u; a.x_stage_bytes = 3072u;       // X: a grouped triple-rows image (rbnn_triple_rows_grouped)
+    if (net->arch != RBNN_ARCH_FC2) return launch_forward_x3<true>(net->activation, a, st);
+    if ((rc = launch_forward_x3<false>(net->activation, a, st))) return rc;
+    // fc2: the hidden image in tws->hid_triple is fp32, stage-major ([S][H/32 stages][ceil(N/16) groups][16 points][32 units])
     const int NG = (N + 15) / 16;
-    b.X = (const char*)tws->hid_triple; b.ldx = H; b.x_sample_bytes = (long long)NG * 16 * H * 4; b.x_group_bytes = 2048u; b.x_stage_bytes = (unsigned)NG * 2048u;
-    b.W = (const char*)tp->Wm_rows; b.w_sample_bytes = (long long)H * H * 6; b.ldw = H; b.KT = H / 32;
-    b.b = net->bm; b.out_scale = ldexpf(1.f, -((dev_scales ? 0 : tp->h1_exp) + tp->wm_exp));
-    b.x_ds = dev_scales ? dev_scales + 1 : nullptr; b.hid_ds = nullptr;
-    b.mask = ws->mask2; b.dact = ws->dact2; b.hid = nullptr;
+    b.x_sample_bytes = (long long)NG * 16 * net->hidden * 4; b.x_group_bytes = 2048u; b.x_stage_bytes = (unsigned)NG * 2048u;
     return launch_forward_x3<true, true>(net->activation, b, st);      // layer 2: its X operand is the fp32 hidden image
 }
 
@@ -1262,61 +1196,11 @@ int rbnn_attack_step_triple(float* X, const float* X0, int32_t ldx, const float*
 int rbnn_fc_input_grad_triple(const rbnn_posterior* net, const rbnn_triple_images* tp, const int32_t* sidx, int32_t S,
                               int32_t N, int32_t chunk, const rbnn_workspace* ws, const rbnn_triple_workspace* tws,
                               int32_t* n_slabs_out, void* stream) {
-    if (!net || !tp || !ws || !tws || !ws->slabs) return RBNN_ERR_NULL;       // ws->dZ == NULL: tws->dZ_gen / g_scale are already built (rbnn_step_tail_triple)
-    if (!tp->W1_cols || !tp->W2_gen || !tws->dZ_gen || !tws->g_scale) return RBNN_ERR_NULL;
-    if (net->arch != RBNN_ARCH_FC && net->arch != RBNN_ARCH_FC2) return RBNN_ERR_UNSUPPORTED;
-    if (net->activation < RBNN_ACT_RELU || net->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
-    const bool fc2 = net->arch == RBNN_ARCH_FC2, bm = net->activation == RBNN_ACT_RELU || net->activation == RBNN_ACT_LEAKY;
-    if (bm ? !ws->mask1 : !ws->dact1) return RBNN_ERR_NULL;
-    if (fc2 && (bm ? !ws->mask2 : !ws->dact2)) return RBNN_ERR_NULL;
-    const int H = net->hidden, Dp = net->in_stride, C = net->n_classes;
-    if (H < 128 || (H % 128) || C < 1 || C > 10 || N < 1 || S < 1) return RBNN_ERR_SHAPE;
-    if (tp->ld_cols != Dp || (Dp & 15)) return RBNN_ERR_SHAPE;
-    if (!aligned16(tp->W1_cols) || !aligned16(tp->W2_gen) || !aligned16(tws->dZ_gen) || (ws->dZ && !aligned16(ws->dZ))) return RBNN_ERR_ALIGN;
-    if (fc2 && (!tp->Wm_cols || !ws->dhid1)) return RBNN_ERR_NULL;
-    if (fc2 && (!aligned16(tp->Wm_cols) || !aligned16(ws->dhid1))) return RBNN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (chunk <= 0) {                                           // the exact mode's slab plan (same workspace)
-        rbnn_workspace_sizes q;
-        const int rc = rbnn_workspace_query(net, N, S, 0, &q);
-        if (rc) return rc;
-        chunk = q.chunk;
-    }
-    if (chunk > S) chunk = S;
-    const int nchunks = (S + chunk - 1) / chunk;
-    if (n_slabs_out) *n_slabs_out = nchunks;
-    const long long n_pad = mask_ld(N);
-    if (ws->dZ) {
-        hipLaunchKernelGGL(triple_dz_kernel, dim3((unsigned)(n_pad / 16)), dim3(256), 0, st,
-                           ws->dZ, S, N, n_pad, C, (uint4*)tws->dZ_gen, tws->g_scale);
-        if (hipGetLastError() != hipSuccess) return RBNN_ERR_LAUNCH;
-    }
-    GradX3Args g = {};
-    g.dzg = (const char*)tws->dZ_gen; g.n_pad = n_pad; g.gscale = tws->g_scale;
-    g.W2g = (const char*)tp->W2_gen;
-    g.H = H; g.HW = H / 32; g.sidx = sidx; g.S = S; g.N = N;
-    if (!fc2) {
-        g.mask = ws->mask1; g.dact = ws->dact1; g.W1c = (const char*)tp->W1_cols; g.ldc = tp->ld_cols; g.Dt = Dp / 16;
-        g.chunk = chunk; g.nchunks = nchunks; g.out = ws->slabs; g.ldo = Dp;
-        g.out_scale = ldexpf(1.f, -(tp->w2_exp + GEN_Q3 + tp->w1_exp));
-        return launch_grad_x3_act<X3_FC>(net->activation, g, st);
-    }
-    // fc2 step 1, one sample per block: dhid1[s] = act'(A1_s) * ((act'(A2_s) * (dZ_s . W3_s)) . Wm_s), kept scaled:
-    //   stored = dhid1 * 2^(e(n) + e_w3 + GEN_Q3 + e_wm - Q2),  Q2 = 14 + ceil(log2 H): |dA2 scaled| <= 2^15, |Wm scaled| <= 2^14, K = H
-    //   => |stored| <= 2^15: in fp16 range, ready to be split as step 2's A operand
-    int q2 = 14;
-    while ((1 << (q2 - 14)) < H) ++q2;
-    g.mask = ws->mask2; g.dact = ws->dact2; g.odact = ws->dact1; g.W1c = (const char*)tp->Wm_cols; g.ldc = H; g.Dt = H / 16;
-    g.chunk = 1; g.nchunks = S; g.out = ws->dhid1; g.ldo = H; g.out_scale = ldexpf(1.f, -q2);
-    g.omask = ws->mask1; g.OHW = H / 32;
-    int rc = launch_grad_x3_act<X3_FC2_STEP1>(net->activation, g, st);
-    if (rc) return rc;
-    // fc2 step 2: slabs[k] = sum_{s in chunk k} dhid1[s] . W1_s; acc = g * 2^(e(n) + e_w3 + GEN_Q3 + e_wm - Q2 + e_w1)
-    GradX3Args h = g;
-    h.amem = ws->dhid1; h.W1c = (const char*)tp->W1_cols; h.ldc = tp->ld_cols; h.Dt = Dp / 16;
-    h.chunk = chunk; h.nchunks = nchunks; h.out = ws->slabs; h.ldo = Dp;
-    h.out_scale = ldexpf(1.f, -(tp->w2_exp + GEN_Q3 + tp->wm_exp - q2 + tp->w1_exp));
-    return launch_grad_x3_act<X3_FC2_STEP2>(net->activation, h, st);
+    // ws->dZ == NULL: tws->dZ_gen / g_scale are already built (rbnn_step_tail_triple)
+    return fc_input_grad_pieces(net, tp, sidx, S, N, chunk, ws, tws, n_slabs_out, stream, triple_dz_kernel, true,
+                                [](auto mode, int act, const GradPieceArgs& g, hipStream_t st) {
+                                    return launch_grad_x3_act<decltype(mode)::value>(act, g, st);
+                                });
 }
 
 }  // extern "C"

@@ -259,64 +259,63 @@ class AttackEngine:
                     ws[name] = torch.empty(sizes[name] // 4, dtype=_WS_DTYPE.get(name, torch.float32), device=self.device)
             ws["Psum"] = torch.zeros(N, _hip.CPAD, dtype=torch.float32, device=self.device)
             ws["G"] = torch.empty(N, self.post.Dp, dtype=torch.float32, device=self.device)
-            if self.precision == "split":
-                ssz = self.k.split_workspace_sizes(self.post, self.post.split_images(), N, S)
-                ws["split"] = {"X_split": torch.empty(ssz["X_split"] // 2, dtype=torch.int16, device=self.device),
-                               "dZ_gen": torch.empty(ssz["dZ_gen"] // 2, dtype=torch.int16, device=self.device),
-                               "g_scale": torch.empty(ssz["g_scale"] // 4, dtype=torch.float32, device=self.device)}
-            if self.precision == "triple":
-                gf, gb = self._fc2_groups(N, S, ws["chunk"])
-                tsz = self.k.triple_workspace_sizes(self.post, self.post.triple_images(), N, S)
+            if self.precision in ("split", "triple"):               # the mode's own buffers: its X image, the dZ generator image and its scales
+                tri = self.precision == "triple"
+                img = self.post.triple_images() if tri else self.post.split_images()
+                psz = (self.k.triple_workspace_sizes if tri else self.k.split_workspace_sizes)(self.post, img, N, S)
+                gf, gb = self._fc2_groups(N, S, ws["chunk"]) if tri else (S, S)
                 if gf < S:                                          # fc2, grouped: ONE hidden image of gf samples, reused group after group
-                    tsz["hid_triple"] = tsz["hid_triple"] // S * gf
+                    psz["hid_triple"] = psz["hid_triple"] // S * gf
                 # X_triple / hid_triple are ZEROED once: the forward kernel DMA-reads whole 16-row groups, and rows N .. ceil16(N) - 1 are never
                 # written by the image builders — their products land in accumulator columns that are never stored, but they must not be
                 # stale NaN / Inf halves of another call's data (invariant stated in include/robustbnns_hip.h)
-                ws["triple"] = {k: (torch.zeros if k in ("X_triple", "hid_triple") else torch.empty)(max(1, v // 2), dtype=torch.int16, device=self.device)
-                                for k, v in tsz.items() if v}
-                ws["triple"]["g_scale"] = ws["triple"]["g_scale"].view(torch.float32)
-                ws.pop("hid1", None)                                # the hidden activations live in the triple image instead
-                ws["fc2_groups"] = (gf, gb)
+                pws = {k: (torch.zeros if k in ("X_triple", "hid_triple") else torch.empty)(max(1, v // 2), dtype=torch.int16, device=self.device)
+                       for k, v in psz.items() if v}
+                pws["g_scale"] = pws["g_scale"].view(torch.float32)
+                ws[self.precision] = pws
+                if tri:
+                    ws.pop("hid1", None)                            # the hidden activations live in the triple image instead
+                    ws["fc2_groups"] = (gf, gb)
             while len(self._ws_cache) > 6:      # evict the LEAST RECENTLY USED entry only: a sharded step holds at most RBNN_COMM_BLOCKS (<= 6) live
                 self._ws_cache.pop(next(iter(self._ws_cache)))    # workspaces with pending all-reduce handles, all younger than it
             self._ws_cache[key] = ws
         return ws
 
     # ------------------------------------------------------------------ kernel hooks (overridden for the conv architecture)
+    def _call_scales(self, Xp):
+        """The device-resident operand scales a forward reads: those of the attack loop in progress, or computed for these inputs."""
+        return self._scales if self._scales is not None else self._input_scales(Xp, iterates=False)
+
     def _forward_kernels(self, Xp, sidx, S, out_kind, ws):
-        if self.precision == "triple":
-            img = self.post.triple_images()
-            ds = self._scales if self._scales is not None else self._input_scales(Xp, iterates=False)
-            # inside a PGD loop the previous attack_step_triple has already written the iterate's image — of THAT tensor: the record names the
-            # buffer the image was built for, and any forward on this workspace consumes it (a forward on other inputs overwrites the image)
-            if ws.pop("x_image_ready", None) != Xp.data_ptr():
-                self.k.triple_rows(Xp, self.post.D, 0, ws["triple"]["X_triple"], img.ld_rows, dev_scale=ds, grouped=True)
-            gf = ws.get("fc2_groups", (S, S))[0]
-            if gf >= S:
-                return self.k.fc_forward_triple(self.post, img, ws["triple"], 0, Xp.shape[0], sidx, S, out_kind, ws, dev_scales=ds)
-            for s0 in range(0, S, gf):          # fc2: layer 1 -> layer 2 per group of samples through ONE reused hidden image (_fc2_groups)
-                g = min(gf, S - s0)
-                self.k.fc_forward_triple(self.post, img, ws["triple"], 0, Xp.shape[0], self._sample_slice(sidx, s0, g), g, out_kind,
-                                         self._ws_samples(ws, s0, Xp.shape[0]), dev_scales=ds)
-            return None
-        if self.precision != "split":
+        if self.precision not in ("split", "triple"):
             return self.k.fc_forward(self.post, Xp, sidx, S, out_kind, ws)
-        img = self.post.split_images()
-        ds = self._scales if self._scales is not None else self._input_scales(Xp, iterates=False)
-        self.k.split_rows(Xp, self.post.D, 0, ws["split"]["X_split"], img.ld_rows, dev_scale=ds)
-        self.k.fc_forward_split(self.post, img, ws["split"]["X_split"], img.ld_rows, 0, Xp.shape[0], sidx, S, out_kind, ws, dev_scales=ds)
+        tri, N = self.precision == "triple", Xp.shape[0]
+        img = self.post.triple_images() if tri else self.post.split_images()
+        ds = self._call_scales(Xp)
+        if not tri:
+            self.k.split_rows(Xp, self.post.D, 0, ws["split"]["X_split"], img.ld_rows, dev_scale=ds)
+            return self.k.fc_forward_split(self.post, img, ws["split"]["X_split"], img.ld_rows, 0, N, sidx, S, out_kind, ws, dev_scales=ds)
+        # inside a PGD loop the previous attack_step_triple has already written the iterate's image — of THAT tensor: the record names the
+        # buffer the image was built for, and any forward on this workspace consumes it (a forward on other inputs overwrites the image)
+        if ws.pop("x_image_ready", None) != Xp.data_ptr():
+            self.k.triple_rows(Xp, self.post.D, 0, ws["triple"]["X_triple"], img.ld_rows, dev_scale=ds, grouped=True)
+        gf = ws.get("fc2_groups", (S, S))[0]
+        if gf >= S:
+            return self.k.fc_forward_triple(self.post, img, ws["triple"], 0, N, sidx, S, out_kind, ws, dev_scales=ds)
+        for s0 in range(0, S, gf):              # fc2: layer 1 -> layer 2 per group of samples through ONE reused hidden image (_fc2_groups)
+            g = min(gf, S - s0)
+            self.k.fc_forward_triple(self.post, img, ws["triple"], 0, N, self._sample_slice(sidx, s0, g), g, out_kind,
+                                     self._ws_samples(ws, s0, N), dev_scales=ds)
 
     def _grad_kernels(self, sidx, S, N, ws, dz_ready=False):
         if self.precision == "triple":
-            gb = ws.get("fc2_groups", (S, S))[1]
-            if dz_ready:                        # the generator image of ALL samples was built by step_tail_triple: one call (its per-point scale spans them)
-                return self.k.fc_input_grad_triple(self.post, self.post.triple_images(), sidx, S, N, ws["chunk"], ws, ws["triple"], dz_ready=True)
-            if gb >= S:
-                return self.k.fc_input_grad_triple(self.post, self.post.triple_images(), sidx, S, N, ws["chunk"], ws, ws["triple"])
+            img, gb = self.post.triple_images(), ws.get("fc2_groups", (S, S))[1]
+            if dz_ready or gb >= S:             # dz_ready: the generator image of ALL samples was built by step_tail_triple: one call (its per-point scale spans them)
+                return self.k.fc_input_grad_triple(self.post, img, sidx, S, N, ws["chunk"], ws, ws["triple"], dz_ready=dz_ready)
             n_slabs = 0                         # fc2: step 1 -> step 2 per group of samples (a multiple of the slab chunk) through ONE reused dhid1
             for s0 in range(0, S, gb):
                 g = min(gb, S - s0)
-                n_slabs += self.k.fc_input_grad_triple(self.post, self.post.triple_images(), self._sample_slice(sidx, s0, g), g, N, ws["chunk"],
+                n_slabs += self.k.fc_input_grad_triple(self.post, img, self._sample_slice(sidx, s0, g), g, N, ws["chunk"],
                                                        self._ws_samples(ws, s0, N, n_slabs), ws["triple"])
             return n_slabs
         if self.precision != "split" or (self.post.arch == "fc2" and os.environ.get("RBNN_FC2_BWD_EXACT") == "1"):

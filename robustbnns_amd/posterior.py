@@ -12,6 +12,7 @@ At MNIST fc-512 one sample is 1.63 MB, so S=2000 is 3.3 GB of the 288 GB HBM3E: 
 stays resident and every kernel indexes it by sample.
 """
 import ctypes as C
+import functools
 import math
 
 import torch
@@ -188,34 +189,47 @@ class StackedPosterior:
         return (self.arch in ("fc", "fc2") and self.Hp % 128 == 0 and self.C <= 10 and self.device.type == "cuda"
                 and self.range_ok())
 
+    _IMAGE_NAMES = ("W1_rows", "W1_cols", "W2_gen", "Wm_rows", "Wm_cols")
+
+    @classmethod
+    def _aim_images(cls, img, keep):
+        for name, t in zip(cls._IMAGE_NAMES, keep):
+            setattr(img, name, t.data_ptr())
+
+    def _build_images(self, pieces, img=None, keep=None):
+        """The weight images of the mode with `pieces` fp16 pieces per weight (2: split, 3: triple): W1 as rows (forward A operand) and as cols
+        (backward B operand), the output layer as the dA-generator image, fc2: Wm as rows and as cols — each the footprint of the fp32 tensor
+        times pieces / 2.  Without `img` the first build: allocates the tensors of `keep` and fixes the scales; with the (img, keep) of an
+        earlier build the same images again, in place (redraw()).  Returns (img, keep): the tensors keep the device memory alive."""
+        k = _hip.HipKernels()
+        S, H, Dp, D, fc2 = self.S, self.Hp, self.Dp, self.D, self.arch == "fc2"
+        ld = round_up(D, 32)
+        if pieces == 2:
+            rows, cols, w2gen, gen_units = k.split_rows, k.split_cols, k.split_w2gen, 64
+        else:
+            rows, cols, w2gen, gen_units = functools.partial(k.triple_rows, grouped=True), k.triple_cols, k.triple_w2gen, 128
+        if img is None:
+            img = _hip.SplitImages() if pieces == 2 else _hip.TripleImages()
+            img.ld_rows, img.ld_cols = ld, Dp
+            img.w1_exp, img.w2_exp = scale_exp(self._abs_max("W1")), scale_exp(self._abs_max("W2"))
+            i16 = lambda *shape: torch.empty(*shape, dtype=torch.int16, device=self.device)
+            keep = [i16(S * H, ld * pieces), i16(S * (H // 32) * 4 * pieces * Dp * 8), i16(S * (H // 16) * gen_units * 8)]
+            if fc2:
+                img.wm_exp = scale_exp(self._abs_max("Wm"))
+                keep += [i16(S * H, H * pieces), i16(S * (H // 32) * 4 * pieces * H * 8)]
+            self._aim_images(img, keep)
+        rows(self.W1, D, img.w1_exp, keep[0], ld)
+        cols(self.W1, H, D, img.w1_exp, keep[1], Dp)
+        w2gen(self.W2, self.C, H, img.w2_exp, keep[2])
+        if fc2:
+            rows(self.Wm, H, img.wm_exp, keep[3], H)
+            cols(self.Wm, H, H, img.wm_exp, keep[4], H)
+        return img, keep
+
     def split_images(self):
-        """rbnn_split_images of this posterior (built once, resident): W1 as split rows (forward A operand), W1 as
-        split cols (backward B operand), W2 as the dA-generator image.  Same footprint as W1 each."""
+        """rbnn_split_images of this posterior (built once, resident)."""
         if self._split is None:
-            k = _hip.HipKernels()
-            S, H, Dp, D, Cn = self.S, self.Hp, self.Dp, self.D, self.C
-            ld = round_up(D, 32)
-            w1_exp = scale_exp(self._abs_max("W1"))
-            w2_exp = scale_exp(self._abs_max("W2"))
-            rows = torch.empty(S * H, ld * 2, dtype=torch.int16, device=self.device)
-            cols = torch.empty(S * (H // 32) * 8 * Dp * 8, dtype=torch.int16, device=self.device)
-            gen = torch.empty(S * (H // 16) * 512, dtype=torch.int16, device=self.device)
-            k.split_rows(self.W1, D, w1_exp, rows, ld)
-            k.split_cols(self.W1, H, D, w1_exp, cols, Dp)
-            k.split_w2gen(self.W2, Cn, H, w2_exp, gen)
-            img = _hip.SplitImages()
-            img.W1_rows, img.W1_cols, img.W2_gen = rows.data_ptr(), cols.data_ptr(), gen.data_ptr()
-            img.ld_rows, img.ld_cols, img.w1_exp, img.w2_exp = ld, Dp, w1_exp, w2_exp
-            keep = [rows, cols, gen]
-            if self.arch == "fc2":                               # forward of the middle layer: Wm as split rows [S*H, H]
-                wm_exp = scale_exp(self._abs_max("Wm"))
-                wm_rows = torch.empty(S * H, H * 2, dtype=torch.int16, device=self.device)
-                k.split_rows(self.Wm, H, wm_exp, wm_rows, H)
-                wm_cols = torch.empty(S * (H // 32) * 8 * H * 8, dtype=torch.int16, device=self.device)
-                k.split_cols(self.Wm, H, H, wm_exp, wm_cols, H)
-                img.Wm_rows, img.Wm_cols, img.wm_exp = wm_rows.data_ptr(), wm_cols.data_ptr(), wm_exp
-                keep += [wm_rows, wm_cols]
-            self._split = (img, keep)                            # the tensors keep the device memory alive
+            self._split = self._build_images(2)
         return self._split[0]
 
     # ------------------------------------------------------------------ triple-split ("f16x6") mode: full-width operands
@@ -241,33 +255,9 @@ class StackedPosterior:
         return self._range_ok
 
     def triple_images(self):
-        """rbnn_triple_images of this posterior (built once, resident): W1 as triple rows (forward A operand, 6 B per weight),
-        W1 as triple cols (backward B operand), W2 as the dA-generator image."""
+        """rbnn_triple_images of this posterior (built once, resident; 6 B per weight)."""
         if self._triple is None:
-            k = _hip.HipKernels()
-            S, H, Dp, D, Cn = self.S, self.Hp, self.Dp, self.D, self.C
-            ld = round_up(D, 32)
-            w1_exp = scale_exp(self._abs_max("W1"))
-            w2_exp = scale_exp(self._abs_max("W2"))
-            rows = torch.empty(S * H, ld * 3, dtype=torch.int16, device=self.device)
-            cols = torch.empty(S * (H // 32) * 12 * Dp * 8, dtype=torch.int16, device=self.device)
-            gen = torch.empty(S * (H // 16) * 1024, dtype=torch.int16, device=self.device)
-            k.triple_rows(self.W1, D, w1_exp, rows, ld, grouped=True)
-            k.triple_cols(self.W1, H, D, w1_exp, cols, Dp)
-            k.triple_w2gen(self.W2, Cn, H, w2_exp, gen)
-            img = _hip.TripleImages()
-            img.W1_rows, img.W1_cols, img.W2_gen = rows.data_ptr(), cols.data_ptr(), gen.data_ptr()
-            img.ld_rows, img.ld_cols, img.w1_exp, img.w2_exp = ld, Dp, w1_exp, w2_exp
-            keep = [rows, cols, gen]
-            if self.arch == "fc2":                               # the middle layer: Wm as triple rows [S*H, H] (forward) and triple cols (backward step 1)
-                wm_exp = scale_exp(self._abs_max("Wm"))
-                wm_rows = torch.empty(S * H, H * 3, dtype=torch.int16, device=self.device)
-                k.triple_rows(self.Wm, H, wm_exp, wm_rows, H, grouped=True)
-                wm_cols = torch.empty(S * (H // 32) * 12 * H * 8, dtype=torch.int16, device=self.device)
-                k.triple_cols(self.Wm, H, H, wm_exp, wm_cols, H)
-                img.Wm_rows, img.Wm_cols, img.wm_exp = wm_rows.data_ptr(), wm_cols.data_ptr(), wm_exp
-                keep += [wm_rows, wm_cols]
-            self._triple = (img, keep)                           # the tensors keep the device memory alive
+            self._triple = self._build_images(3)
         return self._triple[0]
 
     def scale_bounds(self):
@@ -344,14 +334,7 @@ class StackedPosterior:
         tri = self._triple[0] if self._triple is not None else None
         _hip.HipKernels().svi_draw(self, tri, self._guide, S, int(key), int(draw_id), sample_keys)
         if self._split is not None:             # the opt-in two-piece mode keeps its own images: rebuilt by its builders (same fixed scales)
-            img, keep = self._split
-            k = _hip.HipKernels()
-            k.split_rows(self.W1, self.D, img.w1_exp, keep[0], img.ld_rows)
-            k.split_cols(self.W1, self.Hp, self.D, img.w1_exp, keep[1], self.Dp)
-            k.split_w2gen(self.W2, self.C, self.Hp, img.w2_exp, keep[2])
-            if self.arch == "fc2":
-                k.split_rows(self.Wm, self.Hp, img.wm_exp, keep[3], self.Hp)
-                k.split_cols(self.Wm, self.Hp, self.Hp, img.wm_exp, keep[4], self.Hp)
+            self._build_images(2, *self._split)
         return self
 
     # ------------------------------------------------------------------ redraw overlapped with compute (second buffer set + side stream)
@@ -383,9 +366,7 @@ class StackedPosterior:
             keep2 = [torch.empty_like(t) for t in keep]
             img2 = _hip.TripleImages()
             C.memmove(C.byref(img2), C.byref(img), C.sizeof(img))
-            img2.W1_rows, img2.W1_cols, img2.W2_gen = keep2[0].data_ptr(), keep2[1].data_ptr(), keep2[2].data_ptr()
-            if self.arch == "fc2":
-                img2.Wm_rows, img2.Wm_cols = keep2[3].data_ptr(), keep2[4].data_ptr()
+            self._aim_images(img2, keep2)
             self._back["triple"] = (img2, keep2)
 
     def _swap_sets(self):
