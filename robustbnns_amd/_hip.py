@@ -9,273 +9,49 @@ import os
 
 import torch          # must be imported first: the .so then binds to torch's already-loaded libamdhip64.so.7
 
+from . import _header
+from ._header import HipError
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librbnn_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "robustbnns_hip.h")
 
-CPAD = 16
-ACTIVATIONS = {"relu": 0, "leaky": 1, "sigm": 2, "tanh": 3}          # model_nn.py:66-75
-ARCHS = {"fc": 0, "fc2": 1}                                           # model_nn.py:77-91
-OUT_PROBS, OUT_LOGITS = 0, 1
-LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT, LOSS_UPSTREAM, LOSS_UPSTREAM_LOGIT = 0, 1, 2, 3, 4
-
-_fp = C.c_void_p
-
-
-class Posterior(C.Structure):
-    _fields_ = [("arch", C.c_int32), ("activation", C.c_int32), ("in_features", C.c_int32),
-                ("in_stride", C.c_int32), ("hidden", C.c_int32), ("n_classes", C.c_int32),
-                ("n_stored", C.c_int32), ("reserved", C.c_int32),
-                ("W1", _fp), ("b1", _fp), ("Wm", _fp), ("bm", _fp), ("W2", _fp), ("b2", _fp),
-                ("W1_pack4", _fp), ("Wm_pack4", _fp)]
-
-
-class Workspace(C.Structure):
-    _fields_ = [(k, _fp) for k in ("P", "dZ", "mask1", "dact1", "hid1", "mask2", "dact2", "dhid1", "slabs")]
-
-
-class WorkspaceSizes(C.Structure):
-    _fields_ = [(k, C.c_size_t) for k in ("P", "dZ", "mask1", "dact1", "hid1", "mask2", "dact2", "dhid1", "slabs")] + \
-               [("n_slabs", C.c_int32), ("chunk", C.c_int32)]
-
-
-class ConvPosterior(C.Structure):
-    _fields_ = [("activation", C.c_int32), ("hidden", C.c_int32), ("n_classes", C.c_int32), ("n_stored", C.c_int32),
-                ("in_channels", C.c_int32), ("in_width", C.c_int32),
-                ("K1w", _fp), ("K1b", _fp), ("K2w", _fp), ("K2b", _fp), ("Fw", _fp), ("Fb", _fp), ("K2w_ci", _fp)]
-
-
-CONV_WS_KEYS = ("P", "dZ", "P1", "st1", "Q2", "st2", "G")
-
-
-class ConvWorkspace(C.Structure):
-    _fields_ = [(k, _fp) for k in CONV_WS_KEYS]
-
-
-class ConvWorkspaceSizes(C.Structure):
-    _fields_ = [(k, C.c_size_t) for k in CONV_WS_KEYS]
-
-
-class PieceImages(C.Structure):
-    """rbnn_split_images and rbnn_triple_images: the same fields in the same order (two or three fp16 pieces per weight behind the pointers)."""
-    _fields_ = [("W1_rows", _fp), ("W1_cols", _fp), ("W2_gen", _fp), ("ld_rows", C.c_int32), ("ld_cols", C.c_int32),
-                ("w1_exp", C.c_int32), ("w2_exp", C.c_int32), ("Wm_rows", _fp), ("Wm_cols", _fp), ("wm_exp", C.c_int32),
-                ("h1_exp", C.c_int32)]
-
-
-SplitImages = TripleImages = PieceImages
-
-
-class SviGuide(C.Structure):
-    _fields_ = [(k + sfx, _fp) for k in ("W1", "b1", "Wm", "bm", "W2", "b2") for sfx in ("_loc", "_scale")] + \
-               [("hidden", C.c_int32), ("reserved", C.c_int32)]
-
-
-class SviFlatTensor(C.Structure):
-    _fields_ = [("loc", _fp), ("sigma", _fp), ("out", _fp), ("n_elem", C.c_int64), ("out_sample_stride", C.c_int64),
-                ("tensor_id", C.c_int32), ("reserved", C.c_int32)]
-
-
-class SviTrainNet(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("arch", "activation", "in_features", "hidden", "n_classes", "reserved")] + \
-               [(k, _fp) for k in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "W", "grad")]
-
-
-SVI_TRAIN_WS_KEYS = ("hid1", "dact1", "dA1", "hid2", "dact2", "dA2", "dZ", "ce")
-
-
-class SviTrainWs(C.Structure):
-    _fields_ = [(k, _fp) for k in SVI_TRAIN_WS_KEYS]
-
-
-class NnTrainNet(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("arch", "activation", "in_features", "hidden", "n_classes", "n_members")] + \
-               [(k, _fp) for k in ("P", "m", "v", "grad")] + [("member_stride", C.c_int64)]
-
-
-NN_TRAIN_WS_KEYS = ("hid1", "dact1", "dA1", "hid2", "dact2", "dA2", "dZ", "ce", "correct")
-
-
-class NnTrainWs(C.Structure):
-    _fields_ = [(k, _fp) for k in NN_TRAIN_WS_KEYS]
-
-
-class ConvTrainNet(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("activation", "in_channels", "in_width", "hidden", "n_classes", "reserved")] + \
-               [(k, _fp) for k in ("P", "m", "v", "grad")]
-
-
-CONV_TRAIN_WS_KEYS = ("logits", "P1", "st1", "Q2", "st2", "dZ", "ce", "correct", "dO2", "dO1", "part2", "part1", "partP")
-
-
-class ConvTrainWs(C.Structure):
-    _fields_ = [(k, _fp) for k in CONV_TRAIN_WS_KEYS]
-
-
-class ConvTrainBytes(C.Structure):
-    _fields_ = [("n_params", C.c_int64)] + [(k, C.c_size_t) for k in CONV_TRAIN_WS_KEYS]
-
-
-class HmcChain(C.Structure):
-    _fields_ = [(k, _fp) for k in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state", "log", "samples")] + \
-               [("log_rows", C.c_int64), ("sample_rows", C.c_int64)]
-
-
-class HmcLockstep(C.Structure):
-    _fields_ = [(k, _fp) for k in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state", "log", "samples",
-                                   "keys", "active", "steps")] + \
-               [(k, C.c_int64) for k in ("chain_stride", "qpart_stride", "epart_stride", "log_rows", "sample_rows")]
-
-
-class SviLockstep(C.Structure):
-    _fields_ = [(k, _fp) for k in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "kl_part", "stats", "keys")] + \
-               [("part_stride", C.c_int64)]
-
-
-SVI_LOCKSTEP_ACC_KEYS = ("W", "hid1", "hid2", "dact", "Psum")
-SVI_LOCKSTEP_ACC_SAMPLES = 10
-
-
-class SviLockstepAcc(C.Structure):
-    _fields_ = [(k, _fp) for k in SVI_LOCKSTEP_ACC_KEYS]
-
-
-# rbnn_hmc.hip: the state block's indices, the log's columns, the update phases and the decide modes (include/robustbnns_hip.h)
-HMC_STATE, HMC_LOG = 16, 8
-HMC_ST = {"eps": 0, "U": 1, "t": 2, "gbar": 3, "xbar": 4, "mu": 5, "dH": 6, "accept_prob": 7, "accepted": 8, "u": 9, "U_new": 10, "K_new": 11,
-          "K_old": 12}
-HMC_OPEN, HMC_MID, HMC_CLOSE, HMC_KICK, HMC_DRIFT, HMC_ENERGY = range(6)
-HMC_DECIDE_INIT, HMC_DECIDE_PROBE, HMC_DECIDE_TRANSITION = range(3)
-HMC_UNIF_KEY, HMC_SEARCH_KEY = 0xE7037ED1A0B428DB, 0xA0761D6478BD642F
-
-SVI_EPS_MAX = 6.77                                                    # RBNN_SVI_EPS_MAX: Box-Muller on a 32-bit uniform cannot exceed it
-
-TRIPLE_WS_KEYS = ("X_triple", "dZ_gen", "g_scale", "hid_triple")
-
-
-class TripleWorkspace(C.Structure):
-    _fields_ = [(k, _fp) for k in TRIPLE_WS_KEYS]
-
-
-class TripleWorkspaceSizes(C.Structure):
-    _fields_ = [(k, C.c_size_t) for k in TRIPLE_WS_KEYS]
-
-
-SPLIT_WS_KEYS = ("X_split", "dZ_gen", "g_scale")
-
-
-class SplitWorkspace(C.Structure):
-    _fields_ = [(k, _fp) for k in SPLIT_WS_KEYS]
-
-
-class SplitWorkspaceSizes(C.Structure):
-    _fields_ = [(k, C.c_size_t) for k in SPLIT_WS_KEYS]
-
-
-WS_KEYS = ("P", "dZ", "mask1", "dact1", "hid1", "mask2", "dact2", "dhid1", "slabs")
-
-_i32, _f32, _sz, _i64 = C.c_int32, C.c_float, C.c_size_t, C.c_int64
-_PP, _PW, _PS = C.POINTER(Posterior), C.POINTER(Workspace), C.POINTER(WorkspaceSizes)
-
-# name -> (restype, argtypes): exactly the declarations of include/robustbnns_hip.h
-SIGNATURES = {
-    "rbnn_abi_version": (_i32, []),
-    "rbnn_build_flags": (_i32, []),
-    "rbnn_strerror": (C.c_char_p, [_i32]),
-    "rbnn_workspace_query": (_i32, [_PP, _i32, _i32, _i32, _PS]),
-    "rbnn_fc_forward": (_i32, [_PP, _fp, _i32, _i32, _fp, _i32, _i32, _PW, _fp]),
-    "rbnn_reduce_samples": (_i32, [_fp, _i32, _i32, _i32, _f32, _fp, _i32, _fp]),
-    "rbnn_loss_dlogits": (_i32, [_i32, _fp, _fp, _i32, _fp, _fp, _i32, _f32, _i32, _i32, _fp, _fp]),
-    "rbnn_fc_input_grad": (_i32, [_PP, _fp, _i32, _i32, _i32, _PW, C.POINTER(_i32), _fp]),
-    "rbnn_sum_slabs": (_i32, [_fp, _i32, _i32, _i32, _f32, _fp, _i32, _fp]),
-    "rbnn_sum_slabs_norms": (_i32, [_fp, _i32, _i32, _i32, _i32, _f32, _fp, _i32, _fp, _fp, _fp]),
-    "rbnn_pgd_alpha": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp]),
-    "rbnn_attack_step": (_i32, [_fp, _fp, _i32, _fp, _i32, _sz, _i32, _fp, _f32, _f32, _i32, _i32, _i32, _fp]),
-    "rbnn_eval_metrics": (_i32, [_fp, _fp, _i32, _fp, _i32, _i32, _fp, _fp, _fp]),
-    "rbnn_pack_rows4": (_i32, [_fp, _i64, _i32, _fp, _fp]),
-    "rbnn_conv_workspace_query": (_i32, [C.POINTER(ConvPosterior), _i32, _i32, C.POINTER(ConvWorkspaceSizes)]),
-    "rbnn_conv_input_grad": (_i32, [C.POINTER(ConvPosterior), _fp, _i32, _i32, C.POINTER(ConvWorkspace), _fp]),
-    "rbnn_conv_forward": (_i32, [C.POINTER(ConvPosterior), _fp, _i32, _i32, _fp, _i32, _i32, C.POINTER(ConvWorkspace), _fp]),
-    "rbnn_svi_materialize": (_i32, [_fp, _fp, _fp, _i64, _i32, _fp, _fp]),
-    "rbnn_conv_input_grad_split": (_i32, [C.POINTER(ConvPosterior), _fp, _i32, _f32, _fp, _i32, _i32, C.POINTER(ConvWorkspace), _fp]),
-    "rbnn_conv_forward_split": (_i32, [C.POINTER(ConvPosterior), _fp, _i32, _i32, _fp, _fp, _i32, _i32, _fp, _i32, _i32,
-                                       C.POINTER(ConvWorkspace), _fp]),
-    "rbnn_conv_input_grad_dense": (_i32, [C.POINTER(ConvPosterior), _fp, _i32, _f32, _fp, _i32, _i32, C.POINTER(ConvWorkspace), _fp]),
-    "rbnn_conv_weight_images": (_i32, [_fp, _i32, _i32, _i32, _fp, _fp, _fp]),
-    "rbnn_conv_forward_triple": (_i32, [C.POINTER(ConvPosterior), _fp, _i32, _i32, _fp, _fp, _i32, _i32, _fp, _i32, _i32,
-                                        C.POINTER(ConvWorkspace), _fp]),
-    "rbnn_input_scales": (_i32, [_fp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _fp, _fp]),
-    "rbnn_split_rows": (_i32, [_fp, _i64, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
-    "rbnn_fc_forward_split": (_i32, [_PP, C.POINTER(SplitImages), _fp, _i32, _i32, _fp, _i32, _fp, _i32, _i32, _PW, _fp]),
-    "rbnn_split_cols": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _fp, _i32, _fp]),
-    "rbnn_split_w2gen": (_i32, [_fp, _i32, _i32, _i32, _i32, _fp, _fp]),
-    "rbnn_split_workspace_query": (_i32, [_PP, C.POINTER(SplitImages), _i32, _i32, C.POINTER(SplitWorkspaceSizes)]),
-    "rbnn_fc_input_grad_split": (_i32, [_PP, C.POINTER(SplitImages), _fp, _i32, _i32, _i32, _PW, C.POINTER(SplitWorkspace),
-                                        C.POINTER(_i32), _fp]),
-    "rbnn_triple_workspace_query": (_i32, [_PP, C.POINTER(TripleImages), _i32, _i32, C.POINTER(TripleWorkspaceSizes)]),
-    "rbnn_triple_rows": (_i32, [_fp, _i64, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
-    "rbnn_triple_rows_grouped": (_i32, [_fp, _i64, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
-    "rbnn_triple_cols": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _fp, _i32, _fp]),
-    "rbnn_triple_w2gen": (_i32, [_fp, _i32, _i32, _i32, _i32, _fp, _fp]),
-    "rbnn_fc_forward_triple": (_i32, [_PP, C.POINTER(TripleImages), C.POINTER(TripleWorkspace), _i32, _fp, _i32, _fp, _i32, _i32, _PW, _fp]),
-    "rbnn_fc_input_grad_triple": (_i32, [_PP, C.POINTER(TripleImages), _fp, _i32, _i32, _i32, _PW, C.POINTER(TripleWorkspace),
-                                         C.POINTER(_i32), _fp]),
-    "rbnn_step_tail_triple": (_i32, [_i32, _fp, _fp, _i32, _f32, _i32, _i32, _fp, _i32, C.POINTER(TripleWorkspace), _fp]),
-    "rbnn_attack_step_triple": (_i32, [_fp, _fp, _i32, _fp, _i32, _sz, _i32, _fp, _f32, _f32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
-    "rbnn_lowdim_supported": (_i32, [_PP]),
-    "rbnn_lowdim_scratch_bytes": (_sz, [_PP, _i32, _i32]),
-    "rbnn_lowdim_run": (_i32, [_PP, _i32, _i32, _i32, _fp, _fp, _i32, _i32, _fp, _i32, _fp, _f32, _f32, _f32, _fp, _f32, _i32, _i32, _i32,
-                               _fp, _fp, _i32, _fp, _fp, _fp]),
-    "rbnn_lowdim_fused_draw_supported": (_i32, [_PP, _i32, _i32]),
-    "rbnn_lowdim_run_svi": (_i32, [_PP, C.POINTER(SviGuide), _fp, C.c_uint64, C.c_uint32, _i32, _i32, _i32, _fp, _fp, _i32, _i32, _fp, _i32, _fp, _f32,
-                                   _f32, _f32, _fp, _f32, _i32, _i32, _i32, _fp, _fp, _i32, _fp, _fp, _fp]),
-    "rbnn_svi_draw_flat": (_i32, [C.POINTER(SviFlatTensor), _i32, _i32, _fp, C.c_uint64, C.c_uint32, _fp]),
-    "rbnn_svi_draw": (_i32, [_PP, C.POINTER(TripleImages), C.POINTER(SviGuide), _i32, _fp, C.c_uint64, C.c_uint32, _fp]),
-    "rbnn_svi_draw_supported": (_i32, [_PP, _i32]),
-    "rbnn_svi_draw_images": (_i32, [_PP, C.POINTER(TripleImages), C.POINTER(SviGuide), _i32, _fp, C.c_uint64, C.c_uint32, _fp]),
-    "rbnn_svi_train_sizes": (_i64, [C.POINTER(SviTrainNet), C.POINTER(_i64)]),
-    "rbnn_svi_train_draw": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _fp]),
-    "rbnn_svi_train_forward": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, _fp, C.POINTER(SviTrainWs), _fp]),
-    "rbnn_svi_weight_grads": (_i32, [C.POINTER(SviTrainNet), _fp, _i32, _i32, C.POINTER(SviTrainWs), _fp]),
-    "rbnn_svi_adam_step": (_i32, [C.POINTER(SviTrainNet), C.c_uint64, C.c_uint32, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp, _fp]),
-    "rbnn_svi_train_finalize": (_i32, [_fp, _i64, _fp, _i32, _fp, _i32, _fp, _i32, _fp, _fp]),
-    "rbnn_nn_train_sizes": (_i64, [C.POINTER(NnTrainNet)]),
-    "rbnn_nn_train_forward": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
-    "rbnn_nn_weight_grads": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
-    "rbnn_nn_adam_step": (_i32, [C.POINTER(NnTrainNet), _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
-    "rbnn_nn_train_finalize": (_i32, [C.POINTER(NnTrainNet), C.POINTER(NnTrainWs), _i32, _fp, _fp]),
-    "rbnn_conv_train_sizes": (_i32, [C.POINTER(ConvTrainNet), _i32, C.POINTER(ConvTrainBytes)]),
-    "rbnn_conv_train_forward": (_i32, [C.POINTER(ConvTrainNet), _fp, _i32, _fp, _i32, C.POINTER(ConvTrainWs), _fp]),
-    "rbnn_conv_weight_grads": (_i32, [C.POINTER(ConvTrainNet), _fp, _i32, _i32, C.POINTER(ConvTrainWs), _fp]),
-    "rbnn_conv_adam_step": (_i32, [C.POINTER(ConvTrainNet), _i64, C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
-    "rbnn_conv_train_finalize": (_i32, [C.POINTER(ConvTrainWs), _i32, _fp, _fp]),
-    "rbnn_hmc_sizes": (_i64, [C.POINTER(SviTrainNet), C.POINTER(_i64), C.POINTER(_i64)]),
-    "rbnn_hmc_momentum": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), C.c_uint64, C.c_uint32, _fp]),
-    "rbnn_hmc_leapfrog_update": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _fp]),
-    "rbnn_hmc_decide": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _fp, _i32, C.c_uint64, _i64, _i32, _i32, _i32, _fp]),
-    "rbnn_hmc_commit": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _i32, _i64, _fp]),
-    "rbnn_hmc_window_end": (_i32, [C.POINTER(SviTrainNet), C.POINTER(HmcChain), _i32, _fp]),
-    "rbnn_hmc_lockstep_gradient": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _fp, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
-    "rbnn_hmc_lockstep_momentum": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), C.c_uint64, C.c_uint32, _fp, _fp]),
-    "rbnn_hmc_lockstep_update": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _i32, _fp]),
-    "rbnn_hmc_lockstep_decide": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _fp, _fp, _i32, _i64, _i32, _i32, _i32, _fp]),
-    "rbnn_hmc_lockstep_commit": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _i32, _i64, _fp]),
-    "rbnn_hmc_lockstep_window_end": (_i32, [C.POINTER(NnTrainNet), C.POINTER(HmcLockstep), _i32, _fp]),
-    "rbnn_svi_multi_draw": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, C.c_uint32, _fp]),
-    "rbnn_svi_multi_gradient": (_i32, [C.POINTER(NnTrainNet), _fp, _i32, _i32, _fp, _fp, _fp, _i32, C.POINTER(NnTrainWs), _fp]),
-    "rbnn_svi_multi_adam_step": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, C.c_uint32, _i64, _fp, C.c_double, C.c_double,
-                                           C.c_double, _fp]),
-    "rbnn_svi_multi_accuracy": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, _i32, _i32, _fp, _fp, _i32, C.c_uint64, C.c_uint32,
-                                          C.POINTER(SviLockstepAcc), _fp]),
-    "rbnn_svi_multi_finalize": (_i32, [C.POINTER(NnTrainNet), C.POINTER(SviLockstep), _fp, _fp, _fp, _i32, _fp, _fp, _i32, _fp, _fp, _i32, _fp]),
+# Python class -> C struct.  Everything below — the ctypes.Structure classes, SIGNATURES, the constants and the *_KEYS — is generated from the
+# header at import (_header.py), so a new entry point is an edit of the header, and of this mapping when it brings a struct.
+STRUCTS = {
+    "Posterior": "rbnn_posterior", "Workspace": "rbnn_workspace", "WorkspaceSizes": "rbnn_workspace_sizes",
+    "ConvPosterior": "rbnn_conv_posterior", "ConvWorkspace": "rbnn_conv_workspace", "ConvWorkspaceSizes": "rbnn_conv_workspace_sizes",
+    # rbnn_split_images has the same fields in the same order (two or three fp16 pieces per weight behind the pointers): one class for both
+    "PieceImages": "rbnn_triple_images", "SplitImages": "rbnn_triple_images", "TripleImages": "rbnn_triple_images",
+    "SplitWorkspace": "rbnn_split_workspace", "SplitWorkspaceSizes": "rbnn_split_workspace_sizes",
+    "TripleWorkspace": "rbnn_triple_workspace", "TripleWorkspaceSizes": "rbnn_triple_workspace_sizes",
+    "SviGuide": "rbnn_svi_guide", "SviFlatTensor": "rbnn_svi_flat_tensor", "SviTrainNet": "rbnn_svi_train_net", "SviTrainWs": "rbnn_svi_train_ws",
+    "NnTrainNet": "rbnn_nn_train_net", "NnTrainWs": "rbnn_nn_train_ws",
+    "ConvTrainNet": "rbnn_conv_train_net", "ConvTrainWs": "rbnn_conv_train_ws", "ConvTrainBytes": "rbnn_conv_train_bytes",
+    "HmcChain": "rbnn_hmc_chain", "HmcLockstep": "rbnn_hmc_lockstep", "SviLockstep": "rbnn_svi_multi", "SviLockstepAcc": "rbnn_svi_multi_acc",
 }
+HEADER = _header.read(HEADER_PATH)
+# name -> (restype, argtypes) of every prototype of the header.  The pointer rule: `T *` / `const T *` with T a struct of STRUCTS is
+# POINTER(its class), a returned `const char *` is c_char_p, every other pointer — rbnn_dev_scale (a device-side record the host never
+# builds) and the scalar out-parameters included — is c_void_p, which takes byref(...), a c_void_p, an integer address and None.
+_classes, SIGNATURES = _header.bind(HEADER, STRUCTS, same={"rbnn_split_images": "rbnn_triple_images"}, opaque=("rbnn_dev_scale",))
+globals().update(_classes)
+globals().update(HEADER.constants)          # RBNN_X of a #define or an enumerator is X here: CPAD, ABI_VERSION, OUT_*, LOSS_*, HMC_*, ...
+SVI_LOCKSTEP_ACC_SAMPLES = HEADER.constants["SVI_MULTI_ACC_SAMPLES"]
+
+ACTIVATIONS = {"relu": ACT_RELU, "leaky": ACT_LEAKY, "sigm": ACT_SIGM, "tanh": ACT_TANH}          # model_nn.py:66-75
+ARCHS = {"fc": ARCH_FC, "fc2": ARCH_FC2}                                                          # model_nn.py:77-91
+# rbnn_hmc.hip: the state block's indices
+HMC_ST = {"eps": HMC_ST_EPS, "U": HMC_ST_U, "t": HMC_ST_T, "gbar": HMC_ST_GBAR, "xbar": HMC_ST_XBAR, "mu": HMC_ST_MU, "dH": HMC_ST_DH,
+          "accept_prob": HMC_ST_ACC_PROB, "accepted": HMC_ST_ACCEPTED, "u": HMC_ST_UNIF, "U_new": HMC_ST_U_NEW, "K_new": HMC_ST_K_NEW,
+          "K_old": HMC_ST_K_OLD}
+
+_keys = lambda cls: tuple(name for name, _ in cls._fields_)
+WS_KEYS, CONV_WS_KEYS, SPLIT_WS_KEYS, TRIPLE_WS_KEYS = _keys(Workspace), _keys(ConvWorkspace), _keys(SplitWorkspace), _keys(TripleWorkspace)
+SVI_TRAIN_WS_KEYS, NN_TRAIN_WS_KEYS, CONV_TRAIN_WS_KEYS = _keys(SviTrainWs), _keys(NnTrainWs), _keys(ConvTrainWs)
+SVI_LOCKSTEP_ACC_KEYS = _keys(SviLockstepAcc)
 
 _lib = None
-ABI_VERSION = 10
-
-
-class HipError(RuntimeError):
-    pass
 
 
 def load():
@@ -307,6 +83,16 @@ def check(rc, what):
 
 def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def fill(rec, src):
+    """The record `rec` (a Structure class: a new one of it) with its pointer fields set by name from `src`: a dict of tensors, or an object
+    that holds them as attributes.  A name that is missing or None: NULL.  The other fields are left as they are."""
+    rec = rec() if isinstance(rec, type) else rec
+    get = src.get if isinstance(src, dict) else vars(src).get
+    for k in rec._pointers_:
+        setattr(rec, k, ptr(get(k)))
+    return rec
 
 
 def stream_of(t):
@@ -342,10 +128,11 @@ class HipKernels:
 
     @staticmethod
     def _ws(ws):
-        w = Workspace()
-        for k in WS_KEYS:
-            setattr(w, k, ptr(ws.get(k)))
-        return w
+        return fill(Workspace, ws)
+
+    @staticmethod
+    def _conv_ws(ws):
+        return fill(ConvWorkspace, ws)
 
     # -- device -----------------------------------------------------------------------------------
     def fc_forward(self, net, X, sidx, S, out_kind, ws):
@@ -428,14 +215,6 @@ class HipKernels:
         check(getattr(self.lib, name)(C.byref(desc), C.byref(images), N, S, C.byref(out)), name)
         return {k: getattr(out, k) for k, _ in out._fields_}
 
-    @staticmethod
-    def _piece_ws(record, bufs):
-        """`record` (SplitWorkspace / TripleWorkspace) filled from the dict of tensors `bufs`."""
-        t = record()
-        for k, _ in record._fields_:
-            setattr(t, k, ptr(bufs.get(k)))
-        return t
-
     def _fc_input_grad_pieces(self, name, desc, images, sidx, S, N, chunk, w, pw, stream):
         n = C.c_int32(0)
         check(getattr(self.lib, name)(C.byref(desc), C.byref(images), ptr(sidx), S, N, chunk, C.byref(w), C.byref(pw), C.byref(n), stream), name)
@@ -463,7 +242,7 @@ class HipKernels:
 
     def fc_input_grad_split(self, net, images, sidx, S, N, chunk, ws, sws):
         return self._fc_input_grad_pieces("rbnn_fc_input_grad_split", net.descriptor(), images, sidx, S, N, chunk, self._ws(ws),
-                                          self._piece_ws(SplitWorkspace, sws), stream_of(ws["dZ"]))
+                                          fill(SplitWorkspace, sws), stream_of(ws["dZ"]))
 
     # -- triple-split ("f16x6") mode: full-width fp32 operands on the f16 matrix pipe ---------------------
     def triple_rows(self, src, cols, scale_exp, out, ld_dst, dev_scale=None, grouped=False):
@@ -481,7 +260,7 @@ class HipKernels:
         return self._piece_workspace_sizes("rbnn_triple_workspace_query", TripleWorkspaceSizes(), net.descriptor(lazy_ok=True), images, N, S)
 
     def fc_forward_triple(self, net, images, tws, x_exp, N, sidx, S, out_kind, ws, dev_scales=None):
-        w, t = self._ws(ws), self._piece_ws(TripleWorkspace, tws)
+        w, t = self._ws(ws), fill(TripleWorkspace, tws)
         # (lazy_ok: a pending images-only draw left the fp32 W1 / Wm stale, which the triple kernels never read)
         check(self.lib.rbnn_fc_forward_triple(C.byref(net.descriptor(lazy_ok=True)), C.byref(images), C.byref(t), x_exp, ptr(dev_scales), N,
                                               ptr(sidx), S, out_kind, C.byref(w), stream_of(tws["X_triple"])), "rbnn_fc_forward_triple")
@@ -489,7 +268,7 @@ class HipKernels:
     def step_tail_triple(self, mode, P, labels, S, inv_S, N, Cn, tws, Psum=None):
         """reduce over samples + loss + dZ generator image in one launch (rbnn_step_tail_triple); the fp32 dZ is not written."""
         require_gpu(P, "P")
-        t = self._piece_ws(TripleWorkspace, tws)
+        t = fill(TripleWorkspace, tws)
         check(self.lib.rbnn_step_tail_triple(mode, ptr(P), ptr(labels), S, inv_S, N, Cn, ptr(Psum), 0 if Psum is None else Psum.stride(0), C.byref(t),
                                              stream_of(P)), "rbnn_step_tail_triple")
 
@@ -505,20 +284,13 @@ class HipKernels:
         if dz_ready:
             w.dZ = None
         return self._fc_input_grad_pieces("rbnn_fc_input_grad_triple", net.descriptor(lazy_ok=True), images, sidx, S, N, chunk, w,
-                                          self._piece_ws(TripleWorkspace, tws), stream_of(ws["slabs"]))
+                                          fill(TripleWorkspace, tws), stream_of(ws["slabs"]))
 
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):
         out = ConvWorkspaceSizes()
         check(self.lib.rbnn_conv_workspace_query(C.byref(net.descriptor()), N, S, C.byref(out)), "rbnn_conv_workspace_query")
         return {k: getattr(out, k) for k in CONV_WS_KEYS}
-
-    @staticmethod
-    def _conv_ws(ws):
-        w = ConvWorkspace()
-        for k in CONV_WS_KEYS:
-            setattr(w, k, ptr(ws.get(k)))
-        return w
 
     def conv_forward(self, net, X, sidx, S, out_kind, ws):
         require_gpu(X, "X")
@@ -584,7 +356,7 @@ class HipKernels:
                  stream_of(w1)), "rbnn_svi_draw_images" if images_only else "rbnn_svi_draw")
 
     # -- low-dimensional fc nets: the whole hot path in one launch (rbnn_lowdim.hip) -------------------------
-    LOWDIM_FORWARD, LOWDIM_GRADIENT, LOWDIM_ATTACK = 0, 1, 2
+    LOWDIM_FORWARD, LOWDIM_GRADIENT, LOWDIM_ATTACK = LOWDIM_FORWARD, LOWDIM_GRADIENT, LOWDIM_ATTACK
 
     def lowdim_supported(self, net):
         return bool(self.lib.rbnn_lowdim_supported(C.byref(net.descriptor(lazy_ok=True))))

@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 
 from . import _hip
-from .flat_params import flatten, require_gpu_fc, ws_struct
+from .flat_params import flatten, require_gpu_fc
 from .nn_train import ENSEMBLE_BATCH, AdamNets, train_on_loader
 from .svi_train import ADAM_EPS, BETAS
 
@@ -61,7 +61,7 @@ class ConvNnTrainer(AdamNets):
         for k in _hip.CONV_TRAIN_WS_KEYS:
             dt = _WS_DTYPES.get(k, torch.float32)
             self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
-        self.ws = ws_struct(_hip.ConvTrainWs, _hip.CONV_TRAIN_WS_KEYS, self.ws_t)
+        self.ws = _hip.fill(_hip.ConvTrainWs, self.ws_t)
         self.staging(B)
 
     def gradients(self, x, labels):

@@ -56,14 +56,6 @@ def train_workspace(arch, n, H, device):
     return {**ws, "dZ": e(n, _hip.CPAD), "ce": e(n)}
 
 
-def ws_struct(cls, keys, tensors):
-    """The C struct of a workspace dict (a missing key: NULL)."""
-    ws = cls()
-    for k in keys:
-        setattr(ws, k, _hip.ptr(tensors.get(k)))
-    return ws
-
-
 class FlatNets:
     """The constructor state of a trainer or sampler of nets of one shape, a single net (members None: buffers [n]) or `members` of them in
     lockstep (buffers [members, n]): the kernels' handle, arch / activation / device / input_shape, the state_dict keys (`state_keys`, and

@@ -25,7 +25,7 @@ import math
 import torch
 
 from . import _hip
-from .flat_params import FlatNets, flatten, keys_tensor, require_gpu_fc, set_data, train_workspace, ws_struct
+from .flat_params import FlatNets, flatten, keys_tensor, require_gpu_fc, set_data, train_workspace
 
 INIT_RADIUS = 2.0                   # pyro's init_to_uniform [recalled]
 START_BUFFER, END_BUFFER, INIT_WINDOW = 75, 50, 25      # pyro's WarmupAdapter [recalled]
@@ -113,13 +113,10 @@ class _Chains(FlatNets):
         self._set_state(eps=self._eps, mu=[math.log(10 * e) for e in self._eps])
         self._bind()
 
-    def _chain_struct(self, cls, rows_dim):
-        """The pointers and row counts that HmcChain and HmcLockstep share (log / samples: [..., rows, .] with rows at dimension rows_dim)."""
-        ch = cls()
-        for name in ("q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2", "k0_part", "k1_part", "p_part", "state"):
-            setattr(ch, name, getattr(self, name).data_ptr())
-        ch.log = None if self.log_t is None else self.log_t.data_ptr()
-        ch.samples = None if self.samples_t is None else self.samples_t.data_ptr()
+    def _chain_struct(self, cls, rows_dim, **more):
+        """An HmcChain or HmcLockstep: the chain buffers (attributes of the same names), log / samples ([..., rows, .] with rows at dimension
+        rows_dim) and their row counts; more: the pointers that only HmcLockstep has."""
+        ch = _hip.fill(cls, {**vars(self), "log": self.log_t, "samples": self.samples_t, **more})
         ch.log_rows = 0 if self.log_t is None else int(self.log_t.shape[rows_dim])
         ch.sample_rows = 0 if self.samples_t is None else int(self.samples_t.shape[rows_dim])
         return ch
@@ -268,7 +265,7 @@ class HmcSampler(_Chains):
         if B <= self.Bmax:
             return
         self.ws_t = train_workspace(self.arch, B, self.H, self.device)
-        self.ws = ws_struct(_hip.SviTrainWs, _hip.SVI_TRAIN_WS_KEYS, self.ws_t)
+        self.ws = _hip.fill(_hip.SviTrainWs, self.ws_t)
         self.X = torch.zeros(B, self.D, dtype=torch.float32, device=self.device)
         self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.Bmax = B
@@ -411,9 +408,7 @@ class LockstepHmc(_Chains):
         net = self.descriptor(_hip.NnTrainNet, self.K)
         net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), self.n_params
         self.net = net
-        ch = self._chain_struct(_hip.HmcLockstep, 1)
-        ch.keys, ch.steps = self.keys_t.data_ptr(), self.steps_t.data_ptr()
-        ch.active = None if self.active is None else self.active_t.data_ptr()
+        ch = self._chain_struct(_hip.HmcLockstep, 1, keys=self.keys_t, steps=self.steps_t, active=None if self.active is None else self.active_t)
         ch.chain_stride, ch.qpart_stride, ch.epart_stride = self.n_params, self.n_qpart, self.n_epart
         self.chain = ch
 
@@ -423,7 +418,7 @@ class LockstepHmc(_Chains):
             return
         self.ws_t = train_workspace(self.arch, self.K * B, self.H, self.device)
         self.ws_t["correct"] = torch.zeros(self.K * B, dtype=torch.int32, device=self.device)
-        self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
+        self.ws = _hip.fill(_hip.NnTrainWs, self.ws_t)
         self.cap = self.K * B
 
     def _set_state(self, **kv):

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from .flat_params import FlatNets, flatten, require_gpu_fc, train_workspace, ws_struct
+from .flat_params import FlatNets, flatten, require_gpu_fc, train_workspace
 from .posterior import round_up
 from .svi_train import ADAM_EPS, BETAS
 
@@ -35,8 +35,7 @@ class AdamNets(FlatNets):
         self.net, self.n_params, self.P = net, n, P.to(self.device)
         assert tuple(self.P.shape) == self.lead + (n,), (tuple(self.P.shape), self.lead, n)
         self.m, self.v, self.grad = self.zeros(n), self.zeros(n), self.zeros(n)
-        for name in ("P", "m", "v", "grad"):
-            setattr(net, name, getattr(self, name).data_ptr())
+        _hip.fill(net, self)
         self.stats = torch.zeros(*self.lead, 3, dtype=torch.float64, device=self.device)
         self.lr, self.t = float(lr), 0
         self.Bmax = 0
@@ -88,7 +87,7 @@ class NnTrainer(AdamNets):
         dev, M = self.device, self.M
         self.ws_t = {k: v.reshape(-1) for k, v in train_workspace(self.arch, M * B, self.H, dev).items()}
         self.ws_t["correct"] = torch.zeros(M * B, dtype=torch.int32, device=dev)
-        self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
+        self.ws = _hip.fill(_hip.NnTrainWs, self.ws_t)
         self.staging(B)
 
     def set_data(self, x, labels):

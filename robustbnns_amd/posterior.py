@@ -117,10 +117,7 @@ class SviGuide:
 
     def descriptor(self):
         if self._desc is None:
-            d = _hip.SviGuide()
-            for n in ("W1", "b1", "Wm", "bm", "W2", "b2"):
-                setattr(d, n + "_loc", None if n not in self.loc else C.c_void_p(self.loc[n].data_ptr()))
-                setattr(d, n + "_scale", None if n not in self.sigma else C.c_void_p(self.sigma[n].data_ptr()))
+            d = _hip.fill(_hip.SviGuide, {n + sfx: t for sfx, part in (("_loc", self.loc), ("_scale", self.sigma)) for n, t in part.items()})
             d.hidden = self.hidden
             self._desc = d
         return self._desc

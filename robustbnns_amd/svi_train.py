@@ -22,12 +22,12 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip
-from .flat_params import FlatNets, flatten, keys_tensor, require_gpu_fc, set_data, state_keys, train_workspace, ws_struct
+from .flat_params import FlatNets, flatten, keys_tensor, require_gpu_fc, set_data, state_keys, train_workspace
 from .posterior import StackedPosterior, SviGuide, padded_hidden, round_up
 
 BETAS = (0.9, 0.999)                    # torch.optim.Adam defaults, what pyro.optim.Adam({"lr": lr}) wraps
 ADAM_EPS = 1e-8
-ACC_SAMPLES = 10                        # model_bnn.py:327
+ACC_SAMPLES = _hip.SVI_LOCKSTEP_ACC_SAMPLES  # model_bnn.py:327
 ACC_KEY = 0x9E3779B97F4A7C15            # xor-ed into the training key: the accuracy forward's draws are a stream of their own
 
 
@@ -83,9 +83,7 @@ class SviTrainer(FlatNets):
         assert self.loc.numel() == n, (self.loc.numel(), n)
         self.sigma = F.softplus(self.raw)
         self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(n), z(n), z(n), z(n), z(n), z(n)
-        for name in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "W", "grad"):
-            setattr(net, name, getattr(self, name).data_ptr())
-        self.net = net
+        self.net = _hip.fill(net, self)
         self.kl_part = z(self.n_partials)
         self.stats = torch.zeros(3, dtype=torch.float64, device=dev)
         self.lr, self.key, self.t = float(lr), int(key) & 0xFFFFFFFFFFFFFFFF, 0
@@ -112,7 +110,7 @@ class SviTrainer(FlatNets):
         dev = self.device
         e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         self.ws_t = train_workspace(self.arch, B, self.H, dev)
-        self.ws = ws_struct(_hip.SviTrainWs, _hip.SVI_TRAIN_WS_KEYS, self.ws_t)
+        self.ws = _hip.fill(_hip.SviTrainWs, self.ws_t)
         self.X = e(B, self.Dp)                                  # rows of Dp floats, zero columns [D, Dp): what rbnn_fc_forward reads
         self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
         self.Psum = e(B, _hip.CPAD)
@@ -226,11 +224,8 @@ class LockstepSvi(FlatNets):
         net = self.descriptor(_hip.NnTrainNet, K)
         net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), n
         self.net = net
-        g = _hip.SviLockstep()
-        for name in ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "kl_part", "stats"):
-            setattr(g, name, getattr(self, name).data_ptr())
-        g.keys, g.part_stride = self.keys_t.data_ptr(), self.n_partials
-        self.guides = g
+        self.guides = _hip.fill(_hip.SviLockstep, {**vars(self), "keys": self.keys_t})
+        self.guides.part_stride = self.n_partials
         self.X = self.labels = None
         self.epoch_log = None
         self.B = int(batch_size)
@@ -239,12 +234,12 @@ class LockstepSvi(FlatNets):
         S = ACC_SAMPLES
         self.ws_t = train_workspace(arch, K * self.B, self.H, dev)
         self.ws_t["correct"] = torch.zeros(K * self.B, dtype=torch.int32, device=dev)
-        self.ws = ws_struct(_hip.NnTrainWs, _hip.NN_TRAIN_WS_KEYS, self.ws_t)
+        self.ws = _hip.fill(_hip.NnTrainWs, self.ws_t)
         e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         self.acc_t = {"W": e(K * S, n), "hid1": e(K * S * self.B, self.H), "dact": e(K * S * self.B, self.H), "Psum": e(K, self.B, _hip.CPAD)}
         if arch == "fc2":
             self.acc_t["hid2"] = e(K * S * self.B, self.H)
-        self.acc = ws_struct(_hip.SviLockstepAcc, _hip.SVI_LOCKSTEP_ACC_KEYS, self.acc_t)
+        self.acc = _hip.fill(_hip.SviLockstepAcc, self.acc_t)
         self.Psum = self.acc_t["Psum"]
         self.rows_t = torch.zeros(K, self.B, dtype=torch.int32, device=dev)
         self._arange = torch.arange(self.B, dtype=torch.int32, device=dev).unsqueeze(0)
