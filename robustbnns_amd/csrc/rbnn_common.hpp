@@ -121,7 +121,7 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
 }
 
-// The three fp16 pieces (rbnn_triple.hip split3: p0 = f16(v), p1 = f16(v - p0), p2 = f16(v - p0 - p1), round-to-nearest-even) of TWO fp32 values,
+// The three fp16 pieces (pieces_of<3> below: p0 = f16(v), p1 = f16(v - p0), p2 = f16(v - p0 - p1), round-to-nearest-even) of TWO fp32 values,
 // packed [even | odd << 16] per piece: 6 vector instructions per pair (plain C++ compiles to ~12 per value).  `one` must hold 1.0f.
 // A VGPR written by a vector instruction needs TWO wait states before an MFMA takes it as an operand; hipcc's hazard recognizer cannot see into an asm
 // block and pads ONE state behind it — an MFMA scheduled straight behind the block (any block: these are plain asm statements, the scheduler orders
@@ -175,9 +175,16 @@ template <int N> __device__ __forceinline__ void ring_wait_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Rules that must be bit-identical wherever they run: the activations and the fp16 pieces of a value.  Each is stated HERE once; a kernel calls
+// it and does not restate it.
+// ---------------------------------------------------------------------------------------------------
+// Activations.  Below zero relu and leaky differ by one multiplier: act_neg_slope is that multiplier, act_neg the value v takes there — relu
+// yields the constant 0.f, not 0.f * v (which is -0.f, or NaN, for some v).
+template <int ACT> __device__ __forceinline__ constexpr float act_neg_slope() { return ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE; }
+template <int ACT> __device__ __forceinline__ float act_neg(float v) { return ACT == RBNN_ACT_RELU ? 0.f : v * LEAKY_SLOPE; }
 template <int ACT> __device__ __forceinline__ float act_fwd(float a) {
-    if (ACT == RBNN_ACT_RELU)  return a > 0.f ? a : 0.f;
-    if (ACT == RBNN_ACT_LEAKY) return a > 0.f ? a : a * LEAKY_SLOPE;
+    if (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY) return a > 0.f ? a : act_neg<ACT>(a);
     if (ACT == RBNN_ACT_SIGM)  return 1.f / (1.f + expf(-a));
     return tanhf(a);
 }
@@ -185,6 +192,34 @@ template <int ACT> __device__ __forceinline__ float act_fwd(float a) {
 template <int ACT> __device__ __forceinline__ float act_grad_from_value(float h) {
     if (ACT == RBNN_ACT_SIGM) return h * (1.f - h);
     return 1.f - h * h;
+}
+// torch's backward of each activation: relu (a > 0), leaky_relu (a > 0 ? 1 : slope), sigmoid h (1 - h), tanh 1 - h^2
+template <int ACT> __device__ __forceinline__ float act_deriv(float a, float hv) {
+    if (ACT == RBNN_ACT_RELU || ACT == RBNN_ACT_LEAKY) return a > 0.f ? 1.f : act_neg_slope<ACT>();
+    return act_grad_from_value<ACT>(hv);
+}
+// the same from the value alone: h > 0 <=> a > 0 (relu: h = max(a, 0); leaky: h = a or slope * a)
+template <int ACT> __device__ __forceinline__ float act_deriv_from_value(float hv) { return act_deriv<ACT>(hv, hv); }
+
+// The fp16 pieces of a value: p[0] = f16(v), p[1] = f16(v - p[0]), p[2] = f16(v - p[0] - p[1]), round-to-nearest-even; every subtraction is exact
+// (the remainder of a rounding is representable).  P = 3 (rbnn_triple.hip's header): the pieces sum to v bit for bit; P = 2 (rbnn_split.hip): the
+// first two of them.  (The hand-scheduled pair splits — split3_plain_pair above, split3_pair / split3_pair_m in rbnn_triple.hip — give the same pieces.)
+// put(i, piece i) is called as each piece is formed (the order of a kernel's instructions follows it).
+template <int P, class Put> __device__ __forceinline__ void pieces_of(float v, Put&& put) {
+    static_assert(P == 2 || P == 3, "two pieces (split mode) or three (triple mode)");
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const _Float16 h = (_Float16)v;
+        put(i, h);
+        if (i + 1 < P) v -= (float)h;
+    }
+}
+template <int P> __device__ __forceinline__ void pieces_of(float v, _Float16 (&p)[P]) {
+    pieces_of<P>(v, [&](int i, _Float16 h) { p[i] = h; });
+}
+// the two pieces of v into element j of a hi and a lo fragment (f16 vectors or arrays)
+template <class H> __device__ __forceinline__ void pieces_into(float v, H& hi, H& lo, int j) {
+    pieces_of<2>(v, [&](int i, _Float16 h) { (i == 0 ? hi : lo)[j] = h; });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -243,6 +278,21 @@ __device__ __forceinline__ void draw_quad(const Rng& rng, int tensor, const floa
 // ---------------------------------------------------------------------------------------------------
 // host-side helpers
 // ---------------------------------------------------------------------------------------------------
+// Runtime activation -> template parameter: f(std::integral_constant<int, ACT>{}).  The one switch over the activations of every launcher.
+// A RBNN_FAST_BUILD diagnostic build (tools/ablate*.hip) instantiates leaky only, in every unit — the conv and lowdim units included.
+template <class F> int for_activation(int act, F&& f) {
+    switch (act) {
+#ifndef RBNN_FAST_BUILD
+        case RBNN_ACT_RELU:  return f(std::integral_constant<int, RBNN_ACT_RELU>{});
+#endif
+        case RBNN_ACT_LEAKY: return f(std::integral_constant<int, RBNN_ACT_LEAKY>{});
+#ifndef RBNN_FAST_BUILD
+        case RBNN_ACT_SIGM:  return f(std::integral_constant<int, RBNN_ACT_SIGM>{});
+        case RBNN_ACT_TANH:  return f(std::integral_constant<int, RBNN_ACT_TANH>{});
+#endif
+    }
+    return RBNN_ERR_UNSUPPORTED;
+}
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? RBNN_OK : RBNN_ERR_LAUNCH; }
 inline int grid_for_items(long long M) { return (int)(8 * ((M + 7) / 8)); }

@@ -352,10 +352,7 @@ __global__ void __launch_bounds__(256) conv1_pool_split_kernel(const ConvArgs a,
                     if ((dy == 0 && dx == 0) || v > best) { best = v; arg = dy * 2 + dx; }
                 }
             a.st1[sn * P1SZ + c * (P1W * P1W) + pp] = (uint8_t)(arg | (best > 0.f ? 4 : 0));
-            const float v = act_fwd<ACT>(best) * scale;
-            const _Float16 h = (_Float16)v;
-            hi.v[j] = h;
-            lo.v[j] = (_Float16)(v - (float)h);
+            pieces_into(act_fwd<ACT>(best) * scale, hi.v, lo.v, j);
         }
         *(uint4*)(dst + ((o ^ osw) * 16)) = hi.u;
         *(uint4*)(dst + P1PLANE + ((o ^ osw) * 16)) = lo.u;
@@ -669,7 +666,7 @@ __global__ void __launch_bounds__(256, 2) conv_bwd_kernel(const ConvBwdArgs a) {
     if (n >= a.N) return;                                                // whole wave idle (ragged last block); no block barrier anywhere
     const long long sn = (long long)s * a.N + n;
     const int F = a.Hc * NP2_, KW = a.Hc * 25;
-    const float slope = ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE;
+    const float slope = act_neg_slope<ACT>();
 
     // K order inside a chunk is TAP-major: k = t*16 + hl, so one K tile = one tap (ky,kx) x 16 channels, and
     // B[k = lg][j = li] of step r is img[(4lg + r)*CHS + (Y - ky)*PITCH + (X - kx + 4)]  (Y - ky in -4 .. O2W+3); with
@@ -836,7 +833,7 @@ __global__ void __launch_bounds__(256, 2) conv_bwd_split_kernel(const ConvBwdArg
     if (n >= a.N) return;
     const long long sn = (long long)s * a.N + n;
     const int F = a.Hc * NP2, NCH = a.Hc / HCH;
-    const float slope = ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE;
+    const float slope = act_neg_slope<ACT>();
 
     // per-(sample, point) scale: |dO2| <= 4 * max_c |dZ_c| * fw_l1
     float dzmax = fabsf(a.dZ[sn * RBNN_CPAD + li]);
@@ -911,10 +908,7 @@ __global__ void __launch_bounds__(256, 2) conv_bwd_split_kernel(const ConvBwdArg
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if (wok[q] && (st[j][q] & 3) == q) v += (st[j][q] & 4) ? dq[j][q] : dq[j][q] * slope;
-                v *= in_scale;
-                const _Float16 h = (_Float16)v;
-                hv[h4 >> 3][(h4 & 4) + j] = h;
-                lv[h4 >> 3][(h4 & 4) + j] = (_Float16)(v - (float)h);
+                pieces_into(v * in_scale, hv[h4 >> 3], lv[h4 >> 3], (h4 & 4) + j);
             }
         }
         *(f16x8*)(mine) = hv[0];
@@ -991,7 +985,7 @@ __global__ void __launch_bounds__(256, (G::CIN == 1 ? 3 : 2)) conv1_bwd_mfma_ker
     const int sw = a.sidx ? a.sidx[s] : s;
     const long long sn = (long long)s * a.N + n;
     float* const T = lds + wave * TROW;
-    const float slope = ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE;
+    const float slope = act_neg_slope<ACT>();
     int xcl[5];                                                           // the gather's column X - kx, clamped into the T row, and whether it lies inside
     bool xok[5];
 #pragma unroll

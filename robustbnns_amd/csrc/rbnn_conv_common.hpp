@@ -101,19 +101,10 @@ inline int conv_backward_args(const rbnn_conv_posterior* net, const void* K2, bo
 }
 inline bool conv_exp_ok(int e) { return e >= -100 && e <= 100; }
 
-// geometry / activation dispatch of the exact kernels: f(Geo{}) / f(integral_constant<int, ACT>{})
+// geometry dispatch of the exact kernels: f(Geo{})   (the activation's: for_activation, rbnn_common.hpp)
 template <class F> int for_geometry(const rbnn_conv_posterior* net, F&& f) {
     if (net->in_channels == 1 && net->in_width == 28) return f(GeoMnist{});
     if (net->in_channels == 3 && net->in_width == 32) return f(GeoCifar{});
-    return RBNN_ERR_UNSUPPORTED;
-}
-template <class F> int for_activation(int act, F&& f) {
-    switch (act) {
-        case RBNN_ACT_RELU:  return f(std::integral_constant<int, RBNN_ACT_RELU>{});
-        case RBNN_ACT_LEAKY: return f(std::integral_constant<int, RBNN_ACT_LEAKY>{});
-        case RBNN_ACT_SIGM:  return f(std::integral_constant<int, RBNN_ACT_SIGM>{});
-        case RBNN_ACT_TANH:  return f(std::integral_constant<int, RBNN_ACT_TANH>{});
-    }
     return RBNN_ERR_UNSUPPORTED;
 }
 

@@ -117,7 +117,7 @@ template <int ACT> __global__ void __launch_bounds__(256) conv_do2_kernel(const 
         const int st = a.st2[(long long)b * F + f];
         float d;
         if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.Q2[(long long)b * F + f]);
-        else d = (st & 4) ? 1.f : (ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE);
+        else d = (st & 4) ? 1.f : act_neg_slope<ACT>();
         gs[hl][p] = dq * d;
         as[hl][p] = st & 3;
     }
@@ -252,7 +252,7 @@ template <int ACT> __global__ void __launch_bounds__(ELT_THREADS) conv_route1_ke
     const int st = a.st1[at];
     float d;
     if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.P1[at]);
-    else d = (st & 4) ? 1.f : (ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE);
+    else d = (st & 4) ? 1.f : act_neg_slope<ACT>();
     const float v = (float)s * d;
     float* const o = a.dO1 + ((long long)b * C1 + ci) * NO1 + (2 * (pp / P1W)) * O1W + 2 * (pp % P1W);
 #pragma unroll

@@ -34,14 +34,6 @@ struct ConvX3Args {
     const rbnn_dev_scale* p1_ds;                                         // != NULL: the P1 scale lives on the device (rbnn_input_scales record [1])
 };
 
-__device__ __forceinline__ void conv_split3(float v, _Float16& p0, _Float16& p1, _Float16& p2) {
-    p0 = (_Float16)v;
-    float r = v - (float)p0;
-    p1 = (_Float16)r;
-    r -= (float)p1;
-    p2 = (_Float16)r;
-}
-
 #define RBNN_X3FWD_BPREFETCH 0                                           // 1: the B fragments of tap t + 1 read under tap t's MFMAs (round 4) — measured SLOWER: 1x28x28 8.42 -> 8.58 ms per forward call,
                                                                           // 3x32x32 15.1 -> 16.5 (spills beside 56 accumulators): with two waves per SIMD the other wave fills a tap's post-barrier round trip
 // Image layout of conv2_pool_x3_kernel: position (y, x) of the pooled conv1 image is a 64-B record (32 channels) at index y * IPITCH + x;
@@ -586,7 +578,7 @@ __global__ void __launch_bounds__(256, 2) conv1_bwd_x3_kernel(const ConvBwdArgs 
     const int sw = a.sidx ? a.sidx[s] : s;
     const long long sn = (long long)s * a.N + n;
     float* const T = lds + wave * TROW;
-    const float slope = ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE;
+    const float slope = act_neg_slope<ACT>();
     int xcl[5];                                                           // the gather's column X - kx, clamped into the T row, and whether it lies inside
     bool xok[5];
 #pragma unroll
@@ -828,7 +820,7 @@ __global__ void __launch_bounds__(512, 2) conv_bwd_dense_x3_kernel(const ConvBwd
     const int sw = a.sidx ? a.sidx[s] : s;
     const long long sn = (long long)s * a.N + n;
     const int F = a.Hc * NP2_, KS = (a.Hc + 31) / 32;
-    const float slope = ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE;
+    const float slope = act_neg_slope<ACT>();
     // A SIMD issues from its OLDEST ready wave: of the two waves that share one, the lower-numbered ran ahead every K step and its partner did the
     // rest of its taps alone, its stalls uncovered (stamps: a 7-tap wave 47k of 189k K-loop cycles at the barrier, its partner 15k).  The wave of a
     // SIMD that must not be the one left alone — the 7-tap waves (0, 5), the staging waves (2, 7) — takes the higher issue priority.
@@ -1225,7 +1217,7 @@ __global__ void __launch_bounds__(512, 2) conv_bwd_dense_x3_kernel(const ConvBwd
 // launch.  A redrawable SVI stack rebuilds them after every draw (BASELINE config 5: every PGD iteration); through their stand-alone builders
 // that was two permuted fp32 copies, two rbnn_triple_rows launches and two more permuted copies per draw (0.45 of the 0.6 ms a C5 draw took).
 // One block = one (sample, 32 output channels): its [32 hc][32 ci x 25 taps] cube is 100 KB of CONTIGUOUS fp32 — read once, coalesced, into
-// LDS — and both images leave as 1-KiB runs of 16-byte stores.  Same split3 of the same scaled values: the images are bit-identical to the
+// LDS — and both images leave as 1-KiB runs of 16-byte stores.  Same pieces_of<3> of the same scaled values: the images are bit-identical to the
 // stand-alone builders' (tests/test_hip_round4.py).
 // =====================================================================================================
 namespace {
@@ -1255,9 +1247,9 @@ __global__ void __launch_bounds__(256) conv_k2_images_kernel(const float* __rest
                 U o[3];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    _Float16 p0, p1, p2;
-                    conv_split3(cube[hcl * K2IMG_PITCH + (8 * u + j) * 25 + tap], p0, p1, p2);
-                    o[0].v[j] = p0; o[1].v[j] = p1; o[2].v[j] = p2;
+                    _Float16 q[3];
+                    pieces_of<3>(cube[hcl * K2IMG_PITCH + (8 * u + j) * 25 + tap], q);
+                    o[0].v[j] = q[0]; o[1].v[j] = q[1]; o[2].v[j] = q[2];
                 }
                 const long long G = ((long long)s * Hc + hc) >> 4;
                 uint4* const out = rows_img + ((G * 25 + tap) * 3) * 64 + (hc & 15) * 4 + u;
@@ -1272,9 +1264,9 @@ __global__ void __launch_bounds__(256) conv_k2_images_kernel(const float* __rest
             U o[3];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                _Float16 p0, p1, p2;
-                conv_split3(cube[(8 * u + j) * K2IMG_PITCH + ci * 25 + tap], p0, p1, p2);
-                o[0].v[j] = p0; o[1].v[j] = p1; o[2].v[j] = p2;
+                _Float16 q[3];
+                pieces_of<3>(cube[(8 * u + j) * K2IMG_PITCH + ci * 25 + tap], q);
+                o[0].v[j] = q[0]; o[1].v[j] = q[1]; o[2].v[j] = q[2];
             }
             const long long T = (((long long)s * KS + ks) * 25 + tap) * 2 + (ci >> 4);
             uint4* const out = dense_img + (T * 3) * 64 + u * 16 + (ci & 15);      // a piece is [4 K chunks][16 ci][16 B]: lane (li, lg) of the dense kernel owns unit 16 lg + li

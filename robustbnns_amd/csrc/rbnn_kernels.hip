@@ -394,7 +394,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_kernel(const GradArgs a) {
                 for (int r = 0; r < 4; ++r) {
                     if (BITMASK) {
                         const bool pos = (mwv >> r) & 1u;
-                        g[nt][r] = pos ? g[nt][r] : (ACT == RBNN_ACT_RELU ? 0.f : g[nt][r] * LEAKY_SLOPE);
+                        g[nt][r] = pos ? g[nt][r] : act_neg<ACT>(g[nt][r]);
                     } else {
                         g[nt][r] *= da[slot][nt][r];
                     }
@@ -448,7 +448,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_kernel(const GradArgs a) {
                 if (PER_SAMPLE) {
                     if (BITMASK) {
                         const unsigned w = a.omask[((long long)s_begin * a.OHW + (d >> 5)) * mask_ld(a.N) + n];
-                        v = ((w >> (d & 31)) & 1u) ? v : (ACT == RBNN_ACT_RELU ? 0.f : v * LEAKY_SLOPE);
+                        v = ((w >> (d & 31)) & 1u) ? v : act_neg<ACT>(v);
                     } else {
                         v *= a.odact[((long long)s_begin * a.N + n) * a.ldo + d];
                     }
@@ -722,17 +722,7 @@ int launch_forward_act(const FwdArgs& a, bool layer2, hipStream_t st) {
 }
 
 int launch_forward(int act, const FwdArgs& a, bool layer2, hipStream_t st) {
-    switch (act) {
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_RELU:  return launch_forward_act<RBNN_ACT_RELU>(a, layer2, st);
-#endif
-        case RBNN_ACT_LEAKY: return launch_forward_act<RBNN_ACT_LEAKY>(a, layer2, st);
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_SIGM:  return launch_forward_act<RBNN_ACT_SIGM>(a, layer2, st);
-        case RBNN_ACT_TANH:  return launch_forward_act<RBNN_ACT_TANH>(a, layer2, st);
-#endif
-    }
-    return RBNN_ERR_UNSUPPORTED;
+    return for_activation(act, [&](auto A) { return launch_forward_act<decltype(A)::value>(a, layer2, st); });
 }
 
 template <int ACT, int TD, bool A_MEM, bool PER_SAMPLE>
@@ -760,17 +750,7 @@ int launch_grad_td(GradArgs a, hipStream_t st) {
 
 template <bool A_MEM, bool PER_SAMPLE>
 int launch_grad(int act, const GradArgs& a, hipStream_t st) {
-    switch (act) {
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_RELU:  return launch_grad_td<RBNN_ACT_RELU, A_MEM, PER_SAMPLE>(a, st);
-#endif
-        case RBNN_ACT_LEAKY: return launch_grad_td<RBNN_ACT_LEAKY, A_MEM, PER_SAMPLE>(a, st);
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_SIGM:  return launch_grad_td<RBNN_ACT_SIGM, A_MEM, PER_SAMPLE>(a, st);
-        case RBNN_ACT_TANH:  return launch_grad_td<RBNN_ACT_TANH, A_MEM, PER_SAMPLE>(a, st);
-#endif
-    }
-    return RBNN_ERR_UNSUPPORTED;
+    return for_activation(act, [&](auto A) { return launch_grad_td<decltype(A)::value, A_MEM, PER_SAMPLE>(a, st); });
 }
 
 }  // namespace

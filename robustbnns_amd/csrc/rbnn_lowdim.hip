@@ -46,12 +46,6 @@ struct LowArgs {
     int fused_draw;
 };
 
-template <int ACT> __device__ __forceinline__ float act_deriv(float a, float hv) {
-    if (ACT == RBNN_ACT_RELU)  return a > 0.f ? 1.f : 0.f;
-    if (ACT == RBNN_ACT_LEAKY) return a > 0.f ? 1.f : LEAKY_SLOPE;
-    return act_grad_from_value<ACT>(hv);
-}
-
 // One sample's weights: straight from the stacked posterior, or from the block's LDS cache (compact: W1 [H][4 DQ], b1 [H], W2 [C][H], b2 [C]).
 struct SampleW {
     const float *W1, *b1, *W2, *b2;
@@ -412,12 +406,6 @@ struct Low2Args {
     float inv_S;
 };
 
-template <int ACT> __device__ __forceinline__ float act_deriv_from_value(float hv) {
-    if (ACT == RBNN_ACT_RELU)  return hv > 0.f ? 1.f : 0.f;            // h > 0 <=> a > 0 (relu: h = max(a, 0); leaky: h = a or slope * a)
-    if (ACT == RBNN_ACT_LEAKY) return hv > 0.f ? 1.f : LEAKY_SLOPE;
-    return act_grad_from_value<ACT>(hv);
-}
-
 template <int NW, int KTW, int NPTB, bool BWD> struct Low2Lds {
     static constexpr int H = 16 * NW * KTW, HS = H + 4, PT = 16 * NPTB;
     static constexpr int FLOATS = PT * HS * (BWD ? 2 : 1) + PT * 16 + NW * PT * 16 + (BWD ? PT * 16 : 0);
@@ -665,7 +653,7 @@ __global__ void __launch_bounds__(64 * NW) low2_kernel(const Low2Args a) {
     }                                                                     // (the forward: everything between the stash read and here)
     auto stash_deriv = [&](unsigned lo, unsigned hi, int bit) -> float {  // act' from a sign bit (relu: 1 / 0, leaky: 1 / slope)
         const bool pos = ((bit < 32 ? lo : hi) >> (bit & 31)) & 1u;
-        return pos ? 1.f : (ACT == RBNN_ACT_RELU ? 0.f : LEAKY_SLOPE);
+        return pos ? 1.f : act_neg_slope<ACT>();
     };
     if constexpr (BWD) {
         if constexpr (!STASH) gemm_load(ak_bwd, Areg);                    // the second product's first A tiles: under the dZ / dA2 phases
@@ -840,13 +828,7 @@ template <int ACT, bool BWD> int launch_low2_h(const Low2Args& a, hipStream_t st
 }
 
 template <bool BWD> int launch_low2(const Low2Args& a, hipStream_t st) {
-    switch (a.net.activation) {
-        case RBNN_ACT_RELU:  return launch_low2_h<RBNN_ACT_RELU, BWD>(a, st);
-        case RBNN_ACT_LEAKY: return launch_low2_h<RBNN_ACT_LEAKY, BWD>(a, st);
-        case RBNN_ACT_SIGM:  return launch_low2_h<RBNN_ACT_SIGM, BWD>(a, st);
-        case RBNN_ACT_TANH:  return launch_low2_h<RBNN_ACT_TANH, BWD>(a, st);
-    }
-    return RBNN_ERR_UNSUPPORTED;
+    return for_activation(a.net.activation, [&](auto A) { return launch_low2_h<decltype(A)::value, BWD>(a, st); });
 }
 
 bool low2_hidden_ok(int H) { return H == 32 || H == 64 || H == 128 || H == 256 || H == 512; }
@@ -972,13 +954,7 @@ static int lowdim_run_impl(const rbnn_posterior* net, const rbnn_svi_guide* guid
         a.g = *guide; a.sample_keys = (const unsigned long long*)sample_keys; a.key = key; a.draw_id = draw_id; a.fused_draw = 1;
     }
     hipStream_t st = (hipStream_t)stream;
-    switch (net->activation) {
-        case RBNN_ACT_RELU:  return launch_low_act<RBNN_ACT_RELU>(a, st);
-        case RBNN_ACT_LEAKY: return launch_low_act<RBNN_ACT_LEAKY>(a, st);
-        case RBNN_ACT_SIGM:  return launch_low_act<RBNN_ACT_SIGM>(a, st);
-        case RBNN_ACT_TANH:  return launch_low_act<RBNN_ACT_TANH>(a, st);
-    }
-    return RBNN_ERR_UNSUPPORTED;
+    return for_activation(net->activation, [&](auto A) { return launch_low_act<decltype(A)::value>(a, st); });
 }
 
 int rbnn_lowdim_run(const rbnn_posterior* net, int32_t op, int32_t loss_mode, int32_t out_kind, const float* X, const float* X0, int32_t ldx,

@@ -93,12 +93,7 @@ __global__ void split_rows_kernel(const float* __restrict__ src, long long rows,
     const float* const p = src + r * ld_src + 8 * g;
     union { f16x8 v; uint4 u; } hi, lo;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = (8 * g + j < cols) ? p[j] * scale : 0.f;
-        const _Float16 h = (_Float16)v;
-        hi.v[j] = h;
-        lo.v[j] = (_Float16)(v - (float)h);
-    }
+    for (int j = 0; j < 8; ++j) pieces_into((8 * g + j < cols) ? p[j] * scale : 0.f, hi.v, lo.v, j);
     dst[2 * i] = hi.u;
     dst[2 * i + 1] = lo.u;
 }
@@ -294,11 +289,7 @@ __global__ void __launch_bounds__(64 * WH * WN, WH * WN / 4) fc_forward_split_ke
                     // 16-byte hi block and the odd lane the whole lo block — one 16-byte store per lane instead of two 8-byte ones
                     union { _Float16 h[4]; unsigned long long u; unsigned w[2]; } hi, lo;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float x = hv[r] * hid_scale;
-                        hi.h[r] = (_Float16)x;
-                        lo.h[r] = (_Float16)(x - (float)hi.h[r]);
-                    }
+                    for (int r = 0; r < 4; ++r) pieces_into(hv[r] * hid_scale, hi.h, lo.h, r);
                     const bool odd = lg & 1;
                     const unsigned s0 = odd ? hi.w[0] : lo.w[0], s1 = odd ? hi.w[1] : lo.w[1];
                     const unsigned r0 = __shfl_xor(s0, 16), r1 = __shfl_xor(s1, 16);
@@ -377,17 +368,7 @@ int launch_forward_split_act(const FwdSplitArgs& a, hipStream_t st) {
 
 template <bool LAYER2>
 int launch_forward_split(int act, const FwdSplitArgs& a, hipStream_t st) {
-    switch (act) {
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_RELU:  return launch_forward_split_act<RBNN_ACT_RELU, LAYER2>(a, st);
-#endif
-        case RBNN_ACT_LEAKY: return launch_forward_split_act<RBNN_ACT_LEAKY, LAYER2>(a, st);
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_SIGM:  return launch_forward_split_act<RBNN_ACT_SIGM, LAYER2>(a, st);
-        case RBNN_ACT_TANH:  return launch_forward_split_act<RBNN_ACT_TANH, LAYER2>(a, st);
-#endif
-    }
-    return RBNN_ERR_UNSUPPORTED;
+    return for_activation(act, [&](auto A) { return launch_forward_split_act<decltype(A)::value, LAYER2>(a, st); });
 }
 
 
@@ -412,10 +393,7 @@ __global__ void split_cols_kernel(const float* __restrict__ W, long long n_mats,
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int h = 32 * hb + 16 * (j >> 2) + 4 * lg + (j & 3);
-        const float v = (d < cols) ? W[(m * rows + h) * ld_src + d] * scale : 0.f;
-        const _Float16 x = (_Float16)v;
-        hi.v[j] = x;
-        lo.v[j] = (_Float16)(v - (float)x);
+        pieces_into((d < cols) ? W[(m * rows + h) * ld_src + d] * scale : 0.f, hi.v, lo.v, j);
     }
     const long long base = ((mh * 4 + lg) * 2) * ld_dst;       // 16-byte units
     dst[base + d] = hi.u;
@@ -438,9 +416,9 @@ __global__ void split_w2gen_kernel(const float* __restrict__ W2, int n_mats, int
         const int sg = 8 * lg + j, p = sg / 10, c = sg % 10;
         _Float16 r = (_Float16)0.f;
         if (sg < 30 && c < C) {
-            const float v = W2[(m * C + c) * H + 16 * t + li] * scale;
-            const _Float16 x = (_Float16)v;
-            r = (p == 1) ? (_Float16)(v - (float)x) : x;
+            _Float16 q[2];
+            pieces_of<2>(W2[(m * C + c) * H + 16 * t + li] * scale, q);
+            r = (p == 1) ? q[1] : q[0];
         }
         o.v[j] = r;
     }
@@ -492,11 +470,7 @@ __global__ void __launch_bounds__(256) split_dz_kernel(const float* __restrict__
             }
         }
 #pragma unroll
-        for (int c = 0; c < 10; ++c) {
-            const float x = (n < N && c < C) ? ldexpf(v[c], e) : 0.f;
-            hi[c] = (_Float16)x;
-            lo[c] = (_Float16)(x - (float)hi[c]);
-        }
+        for (int c = 0; c < 10; ++c) pieces_into((n < N && c < C) ? ldexpf(v[c], e) : 0.f, hi, lo, c);
         uint4* const o = dst + ((long long)s * N_pad + n) * 4;
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
@@ -616,7 +590,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradPieceAr
     };
     if (STREAM) load_a(0);
     ring_wait_barrier<0>();
-    const float c_pos = ldexpf(1.f, GEN_Q), c_neg = (ACT == RBNN_ACT_RELU) ? 0.f : LEAKY_SLOPE * ldexpf(1.f, GEN_Q);
+    const float c_pos = ldexpf(1.f, GEN_Q), c_neg = act_neg_slope<ACT>() * ldexpf(1.f, GEN_Q);
     f16x8 da_hi[NTW], da_lo[NTW];                              // A operand of the main MFMA: this wave's 4 point tiles, one stage
     for (int st = 0; st < nst; ++st) {
         const int buf = st & 1, dzbuf = (st / HS) & 1;
@@ -630,10 +604,8 @@ __global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradPieceAr
             for (int nt = 0; nt < (GEN ? 0 : NTW); ++nt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float v0 = am[nt][0][r], v1 = am[nt][1][r];
-                    const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-                    da_hi[nt][r] = h0;      da_lo[nt][r] = (_Float16)(v0 - (float)h0);
-                    da_hi[nt][4 + r] = h1;  da_lo[nt][4 + r] = (_Float16)(v1 - (float)h1);
+                    pieces_into(am[nt][0][r], da_hi[nt], da_lo[nt], r);
+                    pieces_into(am[nt][1][r], da_hi[nt], da_lo[nt], 4 + r);
                 }
         }
         if (!(RBNN_ABL & 1) && st + 1 < nst) stage_issue(st + 1, buf ^ 1);
@@ -701,7 +673,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_split_kernel(const GradPieceAr
                 if (MODE == GRAD_FC2_STEP1) {                   // derivative of the layer below: unit d of point n, sample ch
                     if (BITMASK) {
                         const unsigned w = a.omask[((long long)ch * a.OHW + (d >> 5)) * a.n_pad + n];
-                        v = ((w >> (d & 31)) & 1u) ? v : (ACT == RBNN_ACT_RELU ? 0.f : v * LEAKY_SLOPE);
+                        v = ((w >> (d & 31)) & 1u) ? v : act_neg<ACT>(v);
                     } else {
                         v *= a.odact[((long long)ch * a.N + n) * a.ldo + d];
                     }
@@ -742,12 +714,9 @@ int launch_grad_split(const GradPieceArgs& a, hipStream_t st) {
 
 template <int MODE>
 int launch_grad_split_act(int act, const GradPieceArgs& a, hipStream_t st) {
-#ifndef RBNN_FAST_BUILD
-    if (act == RBNN_ACT_RELU) return launch_grad_split<RBNN_ACT_RELU, MODE>(a, st);
-    if (act == RBNN_ACT_SIGM || act == RBNN_ACT_TANH)          // both read act' from the stream: one instantiation serves them
-        return launch_grad_split<RBNN_ACT_SIGM, (MODE == GRAD_FC2_STEP2 ? GRAD_FC2_STEP2 : MODE)>(a, st);
-#endif
-    return launch_grad_split<RBNN_ACT_LEAKY, MODE>(a, st);
+    return for_activation(act, [&](auto A) {                   // sigmoid and tanh both read act' from the stream: one instantiation serves them
+        return launch_grad_split<(decltype(A)::value == RBNN_ACT_TANH ? RBNN_ACT_SIGM : decltype(A)::value), MODE>(a, st);
+    });
 }
 
 }  // namespace

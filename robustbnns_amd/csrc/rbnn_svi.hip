@@ -21,14 +21,6 @@
 
 namespace {
 
-// p0 + p1 + p2 = v exactly (rbnn_triple.hip's split3, plain C: the image builders are not instruction-issue bound)
-__device__ __forceinline__ void split3(float v, _Float16& a, _Float16& b, _Float16& c) {
-    a = (_Float16)v;
-    const float r1 = v - (float)a;
-    b = (_Float16)r1;
-    c = (_Float16)(r1 - (float)b);
-}
-
 struct DrawArgs {
     rbnn_posterior net;
     rbnn_triple_images tp;
@@ -79,7 +71,7 @@ __device__ void draw_matrix_tile(const DrawArgs& a, const Rng& rng, int tensor, 
         //     [piece][16 rows][4 groups of 8 columns]
         const int hl = t >> 3, g = t & 7, d = d0 + 8 * g;
         if (d < ld_rows) {
-            // (the 6-instruction pair split of rbnn_common.hpp — the same pieces as split3, bit for bit; plain C spends ~12 vector instructions per
+            // (the 6-instruction pair split of rbnn_common.hpp — the same pieces as pieces_of<3>, bit for bit; plain C spends ~12 vector instructions per
             // VALUE, and with Philox + Box-Muller this kernel is bound by vector issue, not by its stores: 3.4 of ~6 TB/s)
             union { unsigned w[4]; uint4 u; } o[3];
 #pragma unroll
@@ -146,23 +138,20 @@ __device__ void draw_small(const DrawArgs& a, const Rng& rng, int s, float* w2l 
     uint4* const gen = (uint4*)const_cast<void*>(a.tp.W2_gen) + (long long)s * (H / 16) * 128;
     for (int i = t; i < (H / 16) * 128; i += 256) {
         const int lane = i & 63, li = lane & 15, lg = lane >> 4, k = (i >> 6) & 1, tl = i >> 7;
-        _Float16 w[3][10];
+        _Float16 w[10][3];                                     // [class][piece]
 #pragma unroll
-        for (int c = 0; c < 10; ++c) {
-            const float v = (c < C) ? w2l[c * H + 16 * tl + li] * a.w2_scale : 0.f;
-            split3(v, w[0][c], w[1][c], w[2][c]);
-        }
+        for (int c = 0; c < 10; ++c) pieces_of<3>((c < C) ? w2l[c * H + 16 * tl + li] * a.w2_scale : 0.f, w[c]);
         union { f16x8 v; uint4 u; } o;
         const _Float16 z = (_Float16)0.f;
         if (lg < 3) {
             const int piece = (k == 0) ? (lg == 2 ? 1 : 0) : (lg == 0 ? 1 : (lg == 1 ? 0 : 2));
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o.v[j] = piece == 0 ? w[0][j] : (piece == 1 ? w[1][j] : w[2][j]);
+            for (int j = 0; j < 8; ++j) o.v[j] = piece == 0 ? w[j][0] : (piece == 1 ? w[j][1] : w[j][2]);
         } else if (k == 0) {
-            o.v[0] = w[0][8]; o.v[1] = w[0][9]; o.v[2] = w[0][8]; o.v[3] = w[0][9];
-            o.v[4] = w[0][8]; o.v[5] = w[0][9]; o.v[6] = w[1][8]; o.v[7] = w[1][9];
+            o.v[0] = w[8][0]; o.v[1] = w[9][0]; o.v[2] = w[8][0]; o.v[3] = w[9][0];
+            o.v[4] = w[8][0]; o.v[5] = w[9][0]; o.v[6] = w[8][1]; o.v[7] = w[9][1];
         } else {
-            o.v[0] = w[2][8]; o.v[1] = w[2][9]; o.v[2] = w[1][8]; o.v[3] = w[1][9];
+            o.v[0] = w[8][2]; o.v[1] = w[9][2]; o.v[2] = w[8][1]; o.v[3] = w[9][1];
             o.v[4] = z; o.v[5] = z; o.v[6] = z; o.v[7] = z;
         }
         gen[i] = o.u;

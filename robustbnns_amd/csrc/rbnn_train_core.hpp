@@ -59,18 +59,18 @@ __device__ __forceinline__ int seg_of(const Layout& L, long long q) {
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float softplus_f(float r) { return r > 20.f ? r : log1pf(expf(r)); }     // torch.nn.functional.softplus (threshold 20)
 
+// the activation and its derivative (rbnn_common.hpp's act_fwd / act_deriv) for an activation known only at run time
 __device__ __forceinline__ float act_value(int act, float a) {
-    if (act == RBNN_ACT_RELU) return a > 0.f ? a : 0.f;
-    if (act == RBNN_ACT_LEAKY) return a > 0.f ? a : a * LEAKY_SLOPE;
-    if (act == RBNN_ACT_SIGM) return 1.f / (1.f + expf(-a));
-    return tanhf(a);
+    if (act == RBNN_ACT_RELU) return act_fwd<RBNN_ACT_RELU>(a);
+    if (act == RBNN_ACT_LEAKY) return act_fwd<RBNN_ACT_LEAKY>(a);
+    if (act == RBNN_ACT_SIGM) return act_fwd<RBNN_ACT_SIGM>(a);
+    return act_fwd<RBNN_ACT_TANH>(a);
 }
-// torch's backward of each activation: relu (a > 0), leaky_relu (a > 0 ? 1 : slope), sigmoid h (1 - h), tanh 1 - h^2
 __device__ __forceinline__ float act_deriv(int act, float a, float h) {
-    if (act == RBNN_ACT_RELU) return a > 0.f ? 1.f : 0.f;
-    if (act == RBNN_ACT_LEAKY) return a > 0.f ? 1.f : LEAKY_SLOPE;
-    if (act == RBNN_ACT_SIGM) return h * (1.f - h);
-    return 1.f - h * h;
+    if (act == RBNN_ACT_RELU) return act_deriv<RBNN_ACT_RELU>(a, h);
+    if (act == RBNN_ACT_LEAKY) return act_deriv<RBNN_ACT_LEAKY>(a, h);
+    if (act == RBNN_ACT_SIGM) return act_deriv<RBNN_ACT_SIGM>(a, h);
+    return act_deriv<RBNN_ACT_TANH>(a, h);
 }
 
 // torch.optim.Adam, single-tensor, no weight decay:

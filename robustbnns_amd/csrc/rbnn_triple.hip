@@ -28,14 +28,6 @@
 
 namespace {
 
-__device__ __forceinline__ void split3(float v, _Float16& p0, _Float16& p1, _Float16& p2) {
-    p0 = (_Float16)v;
-    float r = v - (float)p0;                                    // exact (Sterbenz / the remainder of a rounding is representable)
-    p1 = (_Float16)r;
-    r -= (float)p1;
-    p2 = (_Float16)r;
-}
-
 // The backward's dA pieces for two adjacent hidden units (bits BIT, BIT + 1 of the stash word): act' multiplier m = bit ? cp : cn
 // (sign-extended bit-field + bit-select), then the three fp16 pieces of g * m, each by one fused v_fma_mix* that rounds to f16
 // and writes its half of the packed result — 11 vector instructions per pair.  (Plain C++ compiles to ~18: hipcc re-derives
@@ -124,9 +116,9 @@ __global__ void triple_rows_kernel(const float* __restrict__ src, long long rows
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float v = (8 * g + j < cols) ? p[j] * scale : 0.f;
-        _Float16 a, b, c;
-        split3(v, a, b, c);
-        o[0].v[j] = a; o[1].v[j] = b; o[2].v[j] = c;
+        _Float16 q[3];
+        pieces_of<3>(v, q);
+        o[0].v[j] = q[0]; o[1].v[j] = q[1]; o[2].v[j] = q[2];
     }
     if (grouped) {                                             // 16-B units: block of (row group, stage) = 192 units: [plane][16 rows][4 chunks]
         uint4* const out = dst + (((r >> 4) * (groups >> 2) + (g >> 2)) * 192 + (r & 15) * 4 + (g & 3));
@@ -480,17 +472,7 @@ int launch_forward_x3_act(const FwdX3Args& a, hipStream_t st) {
 
 template <bool LAYER2, bool XF32 = false>
 int launch_forward_x3(int act, const FwdX3Args& a, hipStream_t st) {
-    switch (act) {
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_RELU:  return launch_forward_x3_act<RBNN_ACT_RELU, LAYER2, XF32>(a, st);
-#endif
-        case RBNN_ACT_LEAKY: return launch_forward_x3_act<RBNN_ACT_LEAKY, LAYER2, XF32>(a, st);
-#ifndef RBNN_FAST_BUILD
-        case RBNN_ACT_SIGM:  return launch_forward_x3_act<RBNN_ACT_SIGM, LAYER2, XF32>(a, st);
-        case RBNN_ACT_TANH:  return launch_forward_x3_act<RBNN_ACT_TANH, LAYER2, XF32>(a, st);
-#endif
-    }
-    return RBNN_ERR_UNSUPPORTED;
+    return for_activation(act, [&](auto A) { return launch_forward_x3_act<decltype(A)::value, LAYER2, XF32>(a, st); });
 }
 
 // ===================================================================================================
@@ -512,9 +494,9 @@ __global__ void triple_cols_kernel(const float* __restrict__ W, long long n_mats
     for (int j = 0; j < 8; ++j) {
         const int h = 32 * hb + 16 * (j >> 2) + 4 * lg + (j & 3);
         const float v = (d < cols) ? W[(m * rows + h) * ld_src + d] * scale : 0.f;
-        _Float16 a, b, c;
-        split3(v, a, b, c);
-        o[0].v[j] = a; o[1].v[j] = b; o[2].v[j] = c;
+        _Float16 q[3];
+        pieces_of<3>(v, q);
+        o[0].v[j] = q[0]; o[1].v[j] = q[1]; o[2].v[j] = q[2];
     }
     const long long base = ((mh * 4 + lg) * 3) * ld_dst;       // 16-byte units
     dst[base + d] = o[0].u;
@@ -535,23 +517,20 @@ __global__ void triple_w2gen_kernel(const float* __restrict__ W2, int n_mats, in
     const int lane = (int)(i & 63), li = lane & 15, lg = lane >> 4, k = (int)((i >> 6) & 1);
     const int t = (int)((i >> 7) % (H / 16));
     const long long m = (i >> 7) / (H / 16);
-    _Float16 w[3][10];
+    _Float16 w[10][3];                                         // [class][piece]
 #pragma unroll
-    for (int c = 0; c < 10; ++c) {
-        const float v = (c < C) ? W2[(m * C + c) * H + 16 * t + li] * scale : 0.f;
-        split3(v, w[0][c], w[1][c], w[2][c]);
-    }
+    for (int c = 0; c < 10; ++c) pieces_of<3>((c < C) ? W2[(m * C + c) * H + 16 * t + li] * scale : 0.f, w[c]);
     union { f16x8 v; uint4 u; } o;
     const _Float16 z = (_Float16)0.f;
     if (lg < 3) {
         const int piece = (k == 0) ? (lg == 2 ? 1 : 0) : (lg == 0 ? 1 : (lg == 1 ? 0 : 2));
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o.v[j] = piece == 0 ? w[0][j] : (piece == 1 ? w[1][j] : w[2][j]);
+        for (int j = 0; j < 8; ++j) o.v[j] = piece == 0 ? w[j][0] : (piece == 1 ? w[j][1] : w[j][2]);
     } else if (k == 0) {
-        o.v[0] = w[0][8]; o.v[1] = w[0][9]; o.v[2] = w[0][8]; o.v[3] = w[0][9];
-        o.v[4] = w[0][8]; o.v[5] = w[0][9]; o.v[6] = w[1][8]; o.v[7] = w[1][9];
+        o.v[0] = w[8][0]; o.v[1] = w[9][0]; o.v[2] = w[8][0]; o.v[3] = w[9][0];
+        o.v[4] = w[8][0]; o.v[5] = w[9][0]; o.v[6] = w[8][1]; o.v[7] = w[9][1];
     } else {
-        o.v[0] = w[2][8]; o.v[1] = w[2][9]; o.v[2] = w[1][8]; o.v[3] = w[1][9];
+        o.v[0] = w[8][2]; o.v[1] = w[9][2]; o.v[2] = w[8][1]; o.v[3] = w[9][1];
         o.v[4] = z; o.v[5] = z; o.v[6] = z; o.v[7] = z;
     }
     dst[i] = o.u;
@@ -587,7 +566,7 @@ __global__ void __launch_bounds__(256) triple_dz_kernel(const float* __restrict_
     if (q == 0) gscale[n] = ldexpf(1.f, -e);
     const int sw = dz_swz3(n);
     for (int s = q; s < S; s += 16) {
-        _Float16 d[3][10];
+        _Float16 d[10][3];                                     // [class][piece]
         float v[12];
         if (n < N) {
             const float* const src = dZ + ((long long)s * N + n) * RBNN_CPAD;
@@ -599,21 +578,18 @@ __global__ void __launch_bounds__(256) triple_dz_kernel(const float* __restrict_
             }
         }
 #pragma unroll
-        for (int c = 0; c < 10; ++c) {
-            const float x = (n < N && c < C) ? ldexpf(v[c], e) : 0.f;
-            split3(x, d[0][c], d[1][c], d[2][c]);
-        }
+        for (int c = 0; c < 10; ++c) pieces_of<3>((n < N && c < C) ? ldexpf(v[c], e) : 0.f, d[c]);
         uint4* const o = dst + ((long long)s * N_pad + n) * 4;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             union { f16x8 v; uint4 u; } w;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) w.v[j] = d[ch][j];
+            for (int j = 0; j < 8; ++j) w.v[j] = d[j][ch];
             o[ch ^ sw] = w.u;
         }
         union { f16x8 v; uint4 u; } t;
-        t.v[0] = d[0][8]; t.v[1] = d[0][9]; t.v[2] = d[1][8]; t.v[3] = d[1][9];
-        t.v[4] = d[2][8]; t.v[5] = d[2][9]; t.v[6] = d[0][8]; t.v[7] = d[0][9];
+        t.v[0] = d[8][0]; t.v[1] = d[9][0]; t.v[2] = d[8][1]; t.v[3] = d[9][1];
+        t.v[4] = d[8][2]; t.v[5] = d[9][2]; t.v[6] = d[8][0]; t.v[7] = d[9][0];
         o[3 ^ sw] = t.u;
     }
 }
@@ -700,27 +676,24 @@ __global__ void __launch_bounds__(256) step_tail_x3_kernel(const float* __restri
     if (q == 0) gscale[n] = ldexpf(1.f, -e);
     const int sw = dz_swz3(n);
     for (int s = q; s < S; s += 16) {
-        _Float16 d[3][10];
+        _Float16 d[10][3];                                     // [class][piece]
         float dz[16];
 #pragma unroll
         for (int c = 0; c < 16; ++c) dz[c] = 0.f;
         if (n < N) tail_dz<MODE>(P + ((long long)s * N + n) * RBNN_CPAD, gmean, y, C, inv_S, dz);
 #pragma unroll
-        for (int c = 0; c < 10; ++c) {
-            const float x = (n < N && c < C) ? ldexpf(dz[c], e) : 0.f;
-            split3(x, d[0][c], d[1][c], d[2][c]);
-        }
+        for (int c = 0; c < 10; ++c) pieces_of<3>((n < N && c < C) ? ldexpf(dz[c], e) : 0.f, d[c]);
         uint4* const o = dst + ((long long)s * N_pad + n) * 4;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             union { f16x8 v; uint4 u; } w;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) w.v[j] = d[ch][j];
+            for (int j = 0; j < 8; ++j) w.v[j] = d[j][ch];
             o[ch ^ sw] = w.u;
         }
         union { f16x8 v; uint4 u; } t;
-        t.v[0] = d[0][8]; t.v[1] = d[0][9]; t.v[2] = d[1][8]; t.v[3] = d[1][9];
-        t.v[4] = d[2][8]; t.v[5] = d[2][9]; t.v[6] = d[0][8]; t.v[7] = d[0][9];
+        t.v[0] = d[8][0]; t.v[1] = d[9][0]; t.v[2] = d[8][1]; t.v[3] = d[9][1];
+        t.v[4] = d[8][2]; t.v[5] = d[9][2]; t.v[6] = d[8][0]; t.v[7] = d[9][0];
         o[3 ^ sw] = t.u;
     }
 }
@@ -766,10 +739,9 @@ __global__ void __launch_bounds__(256) attack_step_x3_kernel(float* __restrict__
     union { f16x8 v; uint4 u; } o[3];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float v = (d0 + j < D) ? xn[j] * scale : 0.f;
-        _Float16 a, b, c;
-        split3(v, a, b, c);
-        o[0].v[j] = a; o[1].v[j] = b; o[2].v[j] = c;
+        _Float16 q[3];
+        pieces_of<3>((d0 + j < D) ? xn[j] * scale : 0.f, q);
+        o[0].v[j] = q[0]; o[1].v[j] = q[1]; o[2].v[j] = q[2];
     }
     uint4* const out = dst + (((n >> 4) * (groups >> 2) + (gq >> 2)) * 192 + (n & 15) * 4 + (gq & 3));
     out[0] = o[0].u; out[64] = o[1].u; out[128] = o[2].u;
@@ -886,7 +858,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradPieceArgs 
     ring_wait_barrier<0>();
     const float c_pos = ldexpf(1.f, GEN_Q);
     const unsigned cp_bits = __float_as_uint(c_pos);
-    const unsigned cn_bits = (ACT == RBNN_ACT_RELU) ? 0u : __float_as_uint(LEAKY_SLOPE * ldexpf(1.f, GEN_Q));
+    const unsigned cn_bits = __float_as_uint(act_neg_slope<ACT>() * ldexpf(1.f, GEN_Q));
     const int dzc1 = (lg == 2 ? 0 : lg), dzc2 = (lg == 0 ? 1 : (lg == 1 ? 2 : (lg == 2 ? 0 : 3)));   // dZ chunk of MFMA 1 / 2 for this lane group
     const int sz = dz_swz3(li);
     const char* const dzw = dzl + wave * (NTW * 1024) + li * 64;
@@ -1032,7 +1004,7 @@ __global__ void __launch_bounds__(256, 2) fc_grad_x3_kernel(const GradPieceArgs 
                     if (BITMASK) {
                         const unsigned w = a.omask[((long long)ch * a.OHW + (d >> 5)) * a.n_pad + n] >> (d & 31);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] = ((w >> k) & 1u) ? v[k] : (ACT == RBNN_ACT_RELU ? 0.f : v[k] * LEAKY_SLOPE);
+                        for (int k = 0; k < 4; ++k) v[k] = ((w >> k) & 1u) ? v[k] : act_neg<ACT>(v[k]);
                     } else {
                         v *= *(const f32x4*)(a.odact + ((long long)ch * a.N + n) * a.ldo + d);
                     }
@@ -1101,11 +1073,9 @@ int launch_grad_x3(const GradPieceArgs& a, hipStream_t st) {
 
 template <int MODE>
 int launch_grad_x3_act(int act, const GradPieceArgs& a, hipStream_t st) {
-#ifndef RBNN_FAST_BUILD
-    if (act == RBNN_ACT_RELU) return launch_grad_x3<RBNN_ACT_RELU, MODE>(a, st);
-    if (act == RBNN_ACT_SIGM || act == RBNN_ACT_TANH) return launch_grad_x3<RBNN_ACT_SIGM, MODE>(a, st);   // both read act' from the stream
-#endif
-    return launch_grad_x3<RBNN_ACT_LEAKY, MODE>(a, st);
+    return for_activation(act, [&](auto A) {                   // sigmoid and tanh both read act' from the stream: one instantiation serves them
+        return launch_grad_x3<(decltype(A)::value == RBNN_ACT_TANH ? RBNN_ACT_SIGM : decltype(A)::value), MODE>(a, st);
+    });
 }
 
 }  // namespace
