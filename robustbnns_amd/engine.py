@@ -105,7 +105,7 @@ class AttackEngine:
             if os.environ.get("RBNN_FORCE_COLLECTIVES") == "1":
                 self.world = max(self.world, 2)    # diagnostics: run the all-reduce path even in a 1-rank group
         self._S_total = total_samples
-        # diagnostics only (tools/collectives_ab.sh): the sharded launch sequence with NO exchange.  In a group of more than one rank that would
+        # diagnostics only (tools/ab.py env collectives): the sharded launch sequence with NO exchange.  In a group of more than one rank that would
         # silently return every rank's partial sums as the result, so it is refused there.  An engine WITHOUT a group never exchanges anything
         # (bench's point-sharded and other-mode engines, SVI hot-path engines): the pair of switches leaves it alone
         self._fake_comm = (group is not None and os.environ.get("RBNN_FAKE_COLLECTIVES") == "1"

@@ -17,21 +17,7 @@ import torch
 from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def _blocks(run_block, n_blocks=7):
-    """ms of each of n_blocks timed blocks after one warm-up block, sorted."""
-    run_block()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(n_blocks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        run_block()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return sorted(out)
+from timing import blocks as _blocks               # noqa: E402
 
 
 def main():

@@ -20,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as G                                    # noqa: E402
+from timing import blocks                                # noqa: E402
 
 SHAPES = [("fc2", 2, 32, 2, 1024), ("fc2", 2, 128, 2, 1024), ("fc2", 2, 512, 2, 1024), ("fc2", 784, 512, 10, 5000)]
 L, EPS = 10, 1e-4
@@ -60,18 +61,11 @@ def autograd_transition(cur, x, lab, gen):
 
 
 def timed(fn, reps, n):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
+    def block():
         for _ in range(n):
             fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / n)
-    return {"median_ms": statistics.median(out), "min_ms": min(out), "max_ms": max(out)}
+    out = [ms / n for ms in blocks(block, reps, warmup=fn)]
+    return {"median_ms": statistics.median(out), "min_ms": out[0], "max_ms": out[-1]}
 
 
 CHAIN_SHAPES = [("fc2", 2, 32, 2, 1024), ("fc2", 2, 512, 2, 1024)]

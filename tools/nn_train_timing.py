@@ -15,16 +15,14 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing import block_ms                         # noqa: E402
 
 
 def timed(fn, steps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(steps):
-        fn(i)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / steps
+    def block():
+        for i in range(steps):
+            fn(i)
+    return block_ms(block) / steps
 
 
 def torch_step(W, opt, x, y):

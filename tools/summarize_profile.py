@@ -13,6 +13,9 @@ import json
 import os
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pmc import read as read_counters, steps                 # noqa: E402
+
 out = sys.argv[1]
 workload = sys.argv[2] if len(sys.argv) > 2 else "c2"
 points = int(sys.argv[3]) if len(sys.argv) > 3 else None          # N and S per GPU of the profiled command (bench.py scales a conv record
@@ -77,9 +80,7 @@ for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1]))[:20]:
 
 
 def pmc(dirname, title):
-    acc = collections.defaultdict(lambda: collections.defaultdict(list))
-    for r in rows(f"{dirname}/**/*counter_collection.csv"):
-        acc[short(r["Kernel_Name"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
+    acc = read_counters(os.path.join(out, dirname), short)
     if acc:
         print(f"\n== PMC: {title} (mean per launch) ==")
     for k, d in acc.items():
@@ -116,7 +117,8 @@ for key, d in tr.items():
 if tr:
     print("\n== traffic json ==")
     print(json.dumps({"kernels": tr, "small": small}))
-    rel = "profiles/" + out.split("gpurun_out/")[-1] if "gpurun_out/" in out else out      # the copy that is committed, not the scratch path
+    rel = os.path.relpath(out, steps.OUT)                  # the copy that is committed (profiles/<tag>/...), not the scratch path under the tools' output root
+    rel = out if rel.startswith("..") else "profiles/" + rel
     json.dump({workload: {"points": points, "samples": samples, "kernels": tr, "small": small},
                "source": f"{rel}/summary.txt (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, {workload} workload"
                          + (f", N={points}, S={samples}" if points else "") + ")"},

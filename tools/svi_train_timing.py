@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing import block_ms, blocks as _blocks     # noqa: E402
 
 
 def torch_step(params, opt, x, y):
@@ -41,21 +42,6 @@ def torch_step(params, opt, x, y):
     loss = F.cross_entropy(h, y, reduction="sum") + kl
     loss.backward()
     opt.step()
-
-
-def _blocks(run_block, n_blocks=7):
-    """ms of each of n_blocks timed blocks after one warm-up block."""
-    run_block()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(n_blocks):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        run_block()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return sorted(out)
 
 
 def members_main(a):
@@ -133,13 +119,10 @@ def main():
         torch.cuda.synchronize()
         res = {"net": f"fc2-{H}", "lr": lr, "batch": B, "steps": steps}
         for acc in (True, False):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for i in range(steps):
-                tr.step(*batch(i), accuracy=acc)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1)
+            def hip_block():
+                for i in range(steps):
+                    tr.step(*batch(i), accuracy=acc)
+            ms = block_ms(hip_block)
             key = "with_accuracy" if acc else "no_accuracy"
             res[key] = {"ms_per_step": ms / steps, "ms_per_epoch_469": ms / steps * ((N + B - 1) // B)}
         if a.torch_steps:
@@ -151,14 +134,12 @@ def main():
             for i in range(a.warmup):
                 torch_step(params, opt, X[i * B:(i + 1) * B].reshape(B, -1), Y[i * B:(i + 1) * B])
             torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for i in range(a.torch_steps):
-                xb, yb = batch(i)
-                torch_step(params, opt, xb.reshape(B, -1), yb)
-            e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / a.torch_steps
+
+            def torch_block():
+                for i in range(a.torch_steps):
+                    xb, yb = batch(i)
+                    torch_step(params, opt, xb.reshape(B, -1), yb)
+            ms = block_ms(torch_block) / a.torch_steps
             res["torch_autograd_no_accuracy"] = {"ms_per_step": ms, "ms_per_epoch_469": ms * ((N + B - 1) // B)}
             res["speedup_no_accuracy"] = ms / res["no_accuracy"]["ms_per_step"]
         print(json.dumps(res), flush=True)
