@@ -859,6 +859,46 @@ int rbnn_conv_adam_step(const rbnn_conv_train_net *net, int64_t step, double lr,
 /* One block, fixed order, fp64: stats = [the fp32-rounded mean of ce (the step's loss), += it, += sum correct]. */
 int rbnn_conv_train_finalize(const rbnn_conv_train_ws *ws, int32_t n_points, double *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * SVI training of ONE conv guide of the 1x28x28 geometry (csrc/rbnn_conv_train.hip; additive, ABI 10): the SVI step of rbnn_svi_train_net
+ * above (model_bnn.py:303-365: one weight sample, L = sum_b CE(z_b, y_b) + sum KL(N(loc, sigma) || N(0, 1)), one torch.optim.Adam step on
+ * every loc and raw scale) around the conv training forward and the conv weight gradients.  Issued in this order on one stream:
+ *   conv_svi_train_draw -> conv_svi_train_forward -> conv_svi_weight_grads -> conv_svi_adam_step -> [accuracy forward] -> rbnn_svi_train_finalize.
+ * The nine buffers are flat [n_params] in rbnn_conv_train_net's layout: model.0.weight, model.0.bias, model.3.weight, model.3.bias,
+ * model.7.weight, model.7.bias.  eps is rbnn_svi_draw_flat's generator at sample 0: element e of tensor i (tensor ids 0..5 in that order)
+ * is component e % 4 of the Philox block with counter (e / 4, i, 0, draw_id), so W equals sample 0 of a stack redrawn by
+ * rbnn_svi_draw_flat with the same (key, draw_id) bit for bit, and the update regenerates eps instead of storing it.  The workspace is
+ * rbnn_conv_train_ws: correct is written by the head and not read by the step, dZ = softmax - e_y (the SUMMED cross-entropy).  No atomics,
+ * no device->host synchronisation: two runs are bit-identical.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_conv_svi_train_net {
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_channels, in_width; /* 1, 28 (anything else: RBNN_ERR_UNSUPPORTED)                                  */
+    int32_t hidden;                /* Hc = conv2 output channels, a multiple of 16 in [16, 4096]                   */
+    int32_t n_classes;             /* C in [1, 16]                                                                 */
+    int32_t reserved;
+    float *loc, *raw, *sigma;      /* [n_params] variational mean, raw scale, sigma = softplus(raw) (written by the update); 16-byte aligned */
+    float *m_loc, *v_loc, *m_raw, *v_raw;      /* [n_params] Adam moments (zero before the first step)             */
+    float *W;                      /* [n_params] the drawn weight sample (16-byte aligned)                         */
+    float *grad;                   /* [n_params] dCE/dW of the step                                                */
+} rbnn_conv_svi_train_net;
+
+/* [host] out->n_params and the bytes of every rbnn_conv_train_ws buffer for n_points points (what rbnn_conv_train_sizes reports);
+ * *n_partials (nullable) = the KL partial sums rbnn_conv_svi_adam_step writes. */
+int rbnn_conv_svi_train_sizes(const rbnn_conv_svi_train_net *net, int32_t n_points, int64_t *n_partials, rbnn_conv_train_bytes *out);
+/* W = loc + sigma * eps(key, draw_id) for the six tensors: one launch (rbnn_svi_draw_flat on views of the flat buffers). */
+int rbnn_conv_svi_train_draw(const rbnn_conv_svi_train_net *net, uint64_t key, uint32_t draw_id, void *stream);
+/* rbnn_conv_train_forward on W with the summed cross-entropy: logits, ce[b], dZ = softmax(z) - e_y (no 1 / B), correct.  3 + 1 launches. */
+int rbnn_conv_svi_train_forward(const rbnn_conv_svi_train_net *net, const float *X, int32_t ldx, const int32_t *labels, int32_t n_points,
+                                const rbnn_conv_train_ws *ws, void *stream);
+/* rbnn_conv_weight_grads reading W and writing grad = dCE/dW of all six tensors: 7 launches. */
+int rbnn_conv_svi_weight_grads(const rbnn_conv_svi_train_net *net, const float *X, int32_t ldx, int32_t n_points, const rbnn_conv_train_ws *ws,
+                               void *stream);
+/* rbnn_svi_adam_step on the six conv tensors (each one row of n_elem columns: the regenerated eps quad is e / 4, the draw's own counter):
+ * loc, raw, sigma, the four moment buffers, and kl_partials[i] = the KL of the PRE-update parameters summed over block i.  One launch. */
+int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net *net, uint64_t key, uint32_t draw_id, int64_t step, double lr, double beta1,
+                            double beta2, double adam_eps, float *kl_partials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ STRUCTS = {
     "SviGuide": "rbnn_svi_guide", "SviFlatTensor": "rbnn_svi_flat_tensor", "SviTrainNet": "rbnn_svi_train_net", "SviTrainWs": "rbnn_svi_train_ws",
     "NnTrainNet": "rbnn_nn_train_net", "NnTrainWs": "rbnn_nn_train_ws",
     "ConvTrainNet": "rbnn_conv_train_net", "ConvTrainWs": "rbnn_conv_train_ws", "ConvTrainBytes": "rbnn_conv_train_bytes",
+    "ConvSviTrainNet": "rbnn_conv_svi_train_net",
     "HmcChain": "rbnn_hmc_chain", "HmcLockstep": "rbnn_hmc_lockstep", "SviLockstep": "rbnn_svi_multi", "SviLockstepAcc": "rbnn_svi_multi_acc",
 }
 HEADER = _header.read(HEADER_PATH)

@@ -9,7 +9,8 @@ the Adam buffers, stats, the staged batch) as a single net: the buffers are flat
 nn_train.train_on_loader, the one NN.train runs.
 
 What stays refused: every entry point of the fc trainers (NN.train, Ensemble_NN.train, NnTrainer, BNN.train, BNN.train_hmc, the lockstep
-forms) on a conv net, the 3x32x32 geometry, conv SVI / HMC / ensembles.
+forms) on a conv net, the 3x32x32 geometry, conv HMC / ensembles.  SVI posteriors of conv nets are trained by conv_svi_train.ConvSviTrainer
+(BNN.train_conv), on this module's forward and weight gradients.
 """
 import ctypes as C
 

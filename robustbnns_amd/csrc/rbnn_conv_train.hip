@@ -14,6 +14,16 @@
 //      rbnn_conv_train_finalize   the fp32-rounded mean CE of the step, its running sum, the correct predictions: 1 launch (nn_finalize_kernel<false>)
 //                                 both kernels are rbnn_nn_step.hpp's, shared with the fc members of rbnn_nn_train.hip, the member index compiled out
 //
+// and SVI training of one conv GUIDE (model_bnn.py:303-365, the step of rbnn_train.hip around the same forward and weight gradients):
+//      rbnn_conv_svi_train_draw     W = loc + sigma * eps for the six tensors: rbnn_svi_draw_flat on views of the flat buffers, 1 launch
+//      rbnn_conv_svi_train_forward  the training forward above on W with the SUMMED cross-entropy (dZ = softmax - e_y, no 1 / B): 3 + 1 launches
+//      rbnn_conv_svi_weight_grads   the weight gradients above, reading W and writing grad = dCE/dW: 7 launches, the same kernels
+//      rbnn_conv_svi_adam_step      rbnn_svi_step.hpp's adam_kernel<false> over the six conv tensors, each one row of n_elem columns (the
+//                                   regenerated eps quad is e / 4, rbnn_svi_draw_flat's counter): loc, raw, sigma, moments, KL partials.  1 launch
+//      the step's sums are rbnn_svi_train_finalize (rbnn_train.hip: 1 launch); the accuracy forward is the host's (rbnn_svi_draw_flat of 10
+//      weight sets into a resident stack, rbnn_conv_forward on the exact path, rbnn_reduce_samples: 1 + 3 + 1 launches).
+//      One SVI step = 1 + 4 + 7 + 1 + 1 = 14 launches without the accuracy forward, 19 with it.
+//
 // Parameters, moments and gradients are flat fp32 buffers in state_dict order, unpadded (the convention of the fc trainers).  One stream, no
 // atomics, no device->host synchronisation: every output element is one lane's sum in one order, two runs are bit-identical.
 // The three conv GEMMs are one kernel text (conv_wgrad_gemm_kernel): 64 x 64 (G_DP1: 64 x 32) output tiles of the fp32 MFMA, K staged 16 at
@@ -24,6 +34,11 @@
 #include "rbnn_conv_common.hpp"
 #include "rbnn_train_gemm.hpp"
 #include "rbnn_nn_step.hpp"
+// rbnn_svi_step.hpp names its argument records as rbnn_nn_step.hpp names its own (AdamArgs): it is read into a namespace of its own here, after
+// the core it stands on (rbnn_train_core.hpp: already included above, so only the step's own definitions land in the namespace).
+namespace svi {
+#include "rbnn_svi_step.hpp"
+}
 
 using namespace rbnn_conv_shared;
 
@@ -41,6 +56,22 @@ inline ConvLayout conv_layout(int Hc, int C) {
     ConvLayout L;
     L.K1w = 0; L.K1b = C1 * 25; L.K2w = L.K1b + C1; L.K2b = L.K2w + (long long)Hc * K2; L.Fw = L.K2b + Hc;
     L.Fb = L.Fw + (long long)C * NP2 * Hc; L.n_params = L.Fb + C;
+    return L;
+}
+
+// the six tensors as the segments of the SVI step's Layout: each ONE row of n_elem columns, tensor ids 0..5 in state_dict order
+inline Layout conv_svi_layout(int Hc, int C) {
+    const ConvLayout c = conv_layout(Hc, C);
+    const long long off[7] = {c.K1w, c.K1b, c.K2w, c.K2b, c.Fw, c.Fb, c.n_params};
+    Layout L = {};
+    L.n = 6;
+    long long q = 0;
+    for (int i = 0; i < 6; ++i) {
+        const int n = (int)(off[i + 1] - off[i]);
+        L.s[i] = {off[i], q, 1, n, i};
+        q += (n + 3) / 4;
+    }
+    L.n_params = c.n_params; L.n_quads = q;
     return L;
 }
 
@@ -331,8 +362,10 @@ int rbnn_conv_train_sizes(const rbnn_conv_train_net* net, int32_t n_points, rbnn
     return RBNN_OK;
 }
 
-int rbnn_conv_train_forward(const rbnn_conv_train_net* net, const float* X, int32_t ldx, const int32_t* labels, int32_t n_points,
-                            const rbnn_conv_train_ws* ws, void* stream) {
+// The training forward and the head on net->P.  dz_scale multiplies dZ = softmax - e_y: 1 / B for the mean cross-entropy of the deterministic
+// trainer, 1 for the summed one of the SVI step.
+static int train_forward(const rbnn_conv_train_net* net, const float* X, int32_t ldx, const int32_t* labels, int32_t n_points,
+                         const rbnn_conv_train_ws* ws, float dz_scale, void* stream) {
     int rc = check_conv_net(net);
     if (rc) return rc;
     if (!net->P || !labels || !ws || !ws->logits || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->ce || !ws->correct) return RBNN_ERR_NULL;
@@ -346,9 +379,14 @@ int rbnn_conv_train_forward(const rbnn_conv_train_net* net, const float* X, int3
     rbnn_conv_workspace w = {};
     w.P = ws->logits; w.P1 = ws->P1; w.st1 = ws->st1; w.Q2 = ws->Q2; w.st2 = ws->st2;
     if ((rc = rbnn_conv_forward(&p, X, ldx, n_points, nullptr, 1, RBNN_OUT_LOGITS, &w, stream))) return rc;
-    const ConvHeadArgs h = {ws->logits, labels, ws->dZ, ws->ce, ws->correct, n_points, net->n_classes, 1.f / (float)n_points};
+    const ConvHeadArgs h = {ws->logits, labels, ws->dZ, ws->ce, ws->correct, n_points, net->n_classes, dz_scale};
     hipLaunchKernelGGL(conv_head_kernel, dim3((n_points + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
     return launch_status();
+}
+
+int rbnn_conv_train_forward(const rbnn_conv_train_net* net, const float* X, int32_t ldx, const int32_t* labels, int32_t n_points,
+                            const rbnn_conv_train_ws* ws, void* stream) {
+    return train_forward(net, X, ldx, labels, n_points, ws, 1.f / (float)n_points, stream);       // (refused before it is used when n_points < 1)
 }
 
 int rbnn_conv_weight_grads(const rbnn_conv_train_net* net, const float* X, int32_t ldx, int32_t n_points, const rbnn_conv_train_ws* ws,
@@ -420,6 +458,73 @@ int rbnn_conv_train_finalize(const rbnn_conv_train_ws* ws, int32_t n_points, dou
     if (n_points < 1 || n_points > MAX_POINTS) return RBNN_ERR_SHAPE;
     const FinalArgs a = {ws->ce, ws->correct, stats, n_points};
     hipLaunchKernelGGL(nn_finalize_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The SVI step of one conv guide.  The drawn sample W plays the deterministic net's P: the forward and the weight gradients above run on
+// a view of the guide (P = W, grad = grad) and launch what they launch for the deterministic trainer.
+// ---------------------------------------------------------------------------------------------------
+static int conv_svi_view(const rbnn_conv_svi_train_net* g, rbnn_conv_train_net* v) {
+    if (!g) return RBNN_ERR_NULL;
+    *v = {};
+    v->activation = g->activation; v->in_channels = g->in_channels; v->in_width = g->in_width; v->hidden = g->hidden; v->n_classes = g->n_classes;
+    v->P = g->W; v->grad = g->grad;
+    return check_conv_net(v);
+}
+
+int rbnn_conv_svi_train_sizes(const rbnn_conv_svi_train_net* net, int32_t n_points, int64_t* n_partials, rbnn_conv_train_bytes* out) {
+    rbnn_conv_train_net v;
+    int rc = conv_svi_view(net, &v);
+    if (rc) return rc;
+    if ((rc = rbnn_conv_train_sizes(&v, n_points, out))) return rc;
+    if (n_partials) *n_partials = blocks_for(conv_svi_layout(v.hidden, v.n_classes).n_quads);
+    return RBNN_OK;
+}
+
+int rbnn_conv_svi_train_draw(const rbnn_conv_svi_train_net* net, uint64_t key, uint32_t draw_id, void* stream) {
+    rbnn_conv_train_net v;
+    const int rc = conv_svi_view(net, &v);
+    if (rc) return rc;
+    if (!net->loc || !net->sigma || !net->W) return RBNN_ERR_NULL;
+    const Layout L = conv_svi_layout(v.hidden, v.n_classes);
+    rbnn_svi_flat_tensor t[6] = {};
+    for (int i = 0; i < 6; ++i) {
+        const Seg& s = L.s[i];
+        t[i].loc = net->loc + s.off; t[i].sigma = net->sigma + s.off; t[i].out = net->W + s.off;
+        t[i].n_elem = t[i].out_sample_stride = s.cols; t[i].tensor_id = s.tensor_id;
+    }
+    return rbnn_svi_draw_flat(t, 6, 1, nullptr, key, draw_id, stream);
+}
+
+int rbnn_conv_svi_train_forward(const rbnn_conv_svi_train_net* net, const float* X, int32_t ldx, const int32_t* labels, int32_t n_points,
+                                const rbnn_conv_train_ws* ws, void* stream) {
+    rbnn_conv_train_net v;
+    const int rc = conv_svi_view(net, &v);
+    return rc ? rc : train_forward(&v, X, ldx, labels, n_points, ws, 1.f, stream);
+}
+
+int rbnn_conv_svi_weight_grads(const rbnn_conv_svi_train_net* net, const float* X, int32_t ldx, int32_t n_points, const rbnn_conv_train_ws* ws,
+                               void* stream) {
+    rbnn_conv_train_net v;
+    const int rc = conv_svi_view(net, &v);
+    return rc ? rc : rbnn_conv_weight_grads(&v, X, ldx, n_points, ws, stream);
+}
+
+int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net* net, uint64_t key, uint32_t draw_id, int64_t step, double lr, double beta1,
+                            double beta2, double adam_eps, float* kl_partials, void* stream) {
+    rbnn_conv_train_net v;
+    const int rc = conv_svi_view(net, &v);
+    if (rc) return rc;
+    if (!net->loc || !net->raw || !net->sigma || !net->m_loc || !net->v_loc || !net->m_raw || !net->v_raw || !net->grad || !kl_partials)
+        return RBNN_ERR_NULL;
+    if (step < 1) return RBNN_ERR_SHAPE;
+    svi::AdamArgs a = {};
+    a.L = conv_svi_layout(v.hidden, v.n_classes);
+    a.loc = net->loc; a.raw = net->raw; a.sigma = net->sigma; a.m_loc = net->m_loc; a.v_loc = net->v_loc; a.m_raw = net->m_raw; a.v_raw = net->v_raw;
+    a.grad = net->grad; a.kl_part = kl_partials; a.key = key; a.draw_id = draw_id;
+    a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
+    hipLaunchKernelGGL(svi::adam_kernel<false>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

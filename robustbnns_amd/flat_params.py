@@ -1,4 +1,4 @@
-"""What SviTrainer, LockstepSvi, NnTrainer, ConvNnTrainer, HmcSampler and LockstepHmc share: the refusals (require_gpu_fc), the constructor
+"""What SviTrainer, LockstepSvi, NnTrainer, ConvNnTrainer, ConvSviTrainer, HmcSampler and LockstepHmc share: the refusals (require_gpu_fc), the constructor
 state of a trainer of nets of one shape (FlatNets: shapes, sizes, the net descriptors, zeroed buffers, the parameter views; set_data: the resident data
 of the lockstep classes), the flat parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
 import ctypes as C
@@ -16,7 +16,8 @@ def require_gpu_fc(what, arch=None, device=None):
     if device is not None and torch.device(device).type != "cuda":
         raise NotImplementedError(f"{what} runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
     if arch is not None and arch not in LAYER_KEYS:
-        raise NotImplementedError(f"{what} covers fc and fc2, not {arch!r} (conv needs conv weight gradients)")
+        raise NotImplementedError(f"{what} covers fc and fc2, not {arch!r} (a conv net trains through NN.train_conv / BNN.train_conv; conv HMC, "
+                                  "conv ensembles and the lockstep forms are not built)")
 
 
 def state_keys(arch):

@@ -14,7 +14,9 @@ model_bnn.py:198-258, computed for the whole batch and all samples by the HIP ke
 
 Training: `train(train_loader, device, rel_path, filename)` runs the reference's SVI training (model_bnn.py:303-365) for fc / fc2 on the GPU
 (svi_train.SviTrainer: one weight draw, the training forward, the weight gradients and one Adam step per batch — csrc/rbnn_train.hip) and
-saves the param store.  conv SVI and CPU devices raise NotImplementedError: those posteriors are inputs here.  `train()` refuses an HMC net
+saves the param store.  `train_conv(train_loader, device, rel_path, filename)` runs the same algorithm for a conv net of the 1x28x28 geometry
+(conv_svi_train.ConvSviTrainer around the conv training forward and weight gradients, csrc/rbnn_conv_train.hip); `train()` itself keeps
+refusing conv.  CPU devices, conv HMC, conv in lockstep and the 3x32x32 geometry raise NotImplementedError.  `train()` refuses an HMC net
 too and names `train_hmc(train_loader, device, rel_path, filename, num_chains=1)`, which samples the chain of an fc / fc2 net on the GPU
 (hmc.HmcSampler, csrc/rbnn_hmc.hip; num_chains = K > 1: K chains in lockstep, hmc.LockstepHmc, pooled and judged by their split-R-hat) and
 writes the per-sample files `load()` reads.
@@ -434,7 +436,31 @@ class BNN(nn.Module):
                                       "or run it with the reference and load the chain here")
         require_gpu_fc("SVI training", self.basenet.architecture)
         require_gpu_fc("SVI training", device=device)
-        from .svi_train import SviTrainer, draw_key, initial_params
+        from .svi_train import SviTrainer
+        b = self.basenet
+        self._svi_epochs(train_loader, device, rel_path, filename, lambda loc, raw, key, B: SviTrainer(
+            b.architecture, b.activation, b.input_shape, b.output_size, loc, raw, self.lr, device, key, batch_size=B))
+
+    def train_conv(self, train_loader, device, rel_path=TESTS, filename=None):
+        """_train_svi for the conv architecture of the 1x28x28 geometry (conv_svi_train.ConvSviTrainer, csrc/rbnn_conv_train.hip): the same
+        seeding, initialisation at the first batch, key, epoch lines, training_history, set_variational_params and save().  Every refusal
+        comes before any state is changed, a generator touched or the library loaded."""
+        if self.inference == "hmc":
+            raise NotImplementedError("train_conv() runs SVI only: an HMC posterior is sampled with BNN.train_hmc(train_loader, device), which "
+                                      "covers fc / fc2 (conv HMC is not built: run it with the reference and load the chain here)")
+        if self.basenet.architecture != "conv":
+            raise ValueError(f"train_conv trains the conv architecture; a {self.basenet.architecture!r} net trains through train")
+        from .conv_train import check_conv_trainable
+        check_conv_trainable(self.basenet.input_shape, device)
+        from .conv_svi_train import ConvSviTrainer
+        b = self.basenet
+        self._svi_epochs(train_loader, device, rel_path, filename, lambda loc, raw, key, B: ConvSviTrainer(
+            b.activation, b.input_shape, b.output_size, loc, raw, self.lr, device, key, batch_size=B))
+
+    def _svi_epochs(self, train_loader, device, rel_path, filename, make_trainer):
+        """The epoch loop of _train_svi and train_conv behind their guards; make_trainer(loc, raw, key, batch_size) constructs the trainer at
+        the first batch."""
+        from .svi_train import draw_key, initial_params
         self.device = device
         self.basenet.device = device
         random.seed(0)
@@ -450,8 +476,7 @@ class BNN(nn.Module):
                         loc, raw = initial_params(state_shapes(b))
                     else:
                         loc, raw = self.svi_loc, self.svi_scale
-                    trainer = SviTrainer(b.architecture, b.activation, b.input_shape, b.output_size, loc, raw, self.lr, device,
-                                         draw_key(), batch_size=int(x_batch.shape[0]))
+                    trainer = make_trainer(loc, raw, draw_key(), int(x_batch.shape[0]))
                 trainer.step(x_batch.to(device), y_batch.to(device).argmax(-1))
             loss, correct = trainer.epoch_totals() if trainer is not None else (0.0, 0.0)
             if trainer is not None:

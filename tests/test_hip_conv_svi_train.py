@@ -1,0 +1,422 @@
+"""GPU tests (-m gpu) of SVI training of conv guides (csrc/rbnn_conv_train.hip, robustbnns_amd/conv_svi_train.py, BNN.train_conv) against the CPU
+restatement tests/conv_svi_restate.py: the draw against the resident stack's and the oracle's, the weight gradients against fp64 autograd at
+the GPU's own weights, the Adam + KL kernel alone against torch.optim.Adam, 20 steps against the fp64 restatement, every step of two epochs
+with a short last batch at the GPU's own parameters, reproducibility, no device->host sync, canaries behind every buffer, BNN.train_conv end
+to end, and a run from the reference's own initialisation.  Every check prints its worst error in units of its bar."""
+import ctypes as C
+import random
+
+import pytest
+import torch
+import torch.nn.functional as F
+from torch.utils.data import DataLoader, TensorDataset
+
+import conv_svi_restate as V
+from conftest import rel_err_points
+
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("built_library")]
+DEV = "cuda:0"
+TRAJ_SPREADS = 4               # tests/test_hip_conv_train.py's factor on the CPU-measured spread
+MARGIN = 2e-5                  # a point whose two largest fp64 mean probabilities are this close may be scored either way
+BUFFERS = ("W", "grad", "loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32).cpu() if t.dtype == torch.float32 else t.detach().cpu().clone()
+
+
+def _trainer(loc, raw, act, Cn, B, lr=0.01, key=V.GRAD_KEY):
+    from robustbnns_amd.conv_svi_train import ConvSviTrainer
+    return ConvSviTrainer(act, (1, 28, 28), Cn, loc, raw, lr, DEV, key, batch_size=B)
+
+
+def _read(tr):
+    return tuple({k: v.cpu().double() for k, v in d.items()} for d in tr.params())
+
+
+@pytest.mark.parametrize("Hc,act,B,Cn", V.GRAD_CASES)
+def test_draw_and_weight_gradients_match_the_stack_the_oracle_and_fp64_autograd(Hc, act, B, Cn):
+    """Draw: W bit-equal to sample 0 of ConvStackedPosterior.redraw(key, draw id), and within 2e-6 (|loc| + sigma |eps|) of loc + sigma eps with
+    the oracle's eps (the bar the fc Adam test derives for the regenerated eps).  Gradients: against fp64 autograd of the summed CE at the
+    GPU's OWN W, per tensor within 1e-5 max |fp64 gradient|; the per-point CE within 1e-5 relative."""
+    from robustbnns_amd.conv import ConvStackedPosterior, ConvSviGuide
+    c = V.grad_case(Hc, act, B, Cn)
+    tr = _trainer(c["loc"], c["raw"], act, Cn, max(1, B // 2))                # smaller than B: the workspaces grow
+    tr.t = V.GRAD_DRAW
+    tr.gradients(c["x"].to(DEV), c["lab"].to(DEV))
+    post = ConvStackedPosterior.for_guide(ConvSviGuide(c["loc"], c["raw"], DEV), act, (1, 28, 28), Cn, Hc, 2).redraw(V.GRAD_KEY, V.GRAD_DRAW)
+    torch.cuda.synchronize()
+    W, G = tr.unflat(tr.W), tr.unflat(tr.grad)
+    sd0 = post.state_dict(0)
+    sig = {k: v.cpu().double() for k, v in tr.unflat(tr.sigma).items()}
+    w_draw = 0.0
+    for k in V.KEYS:
+        assert torch.equal(W[k].cpu().reshape(-1), sd0[k].reshape(-1)), f"{k}: not sample 0 of the stack's redraw"
+        ref = c["loc"][k].double() + sig[k] * c["eps"][k]
+        bar = 2e-6 * (c["loc"][k].double().abs() + sig[k] * c["eps"][k].abs())
+        e = (W[k].cpu().double() - ref).abs()
+        assert bool((e <= bar).all()), k
+        w_draw = max(w_draw, float((e / bar).max()))
+    W_own = {k: W[k].cpu().double() for k in V.KEYS}
+    ce64, g64 = V.ce_grads(c["x"], c["lab"], W_own, act)
+    worst = 0.0
+    for k in V.KEYS:
+        gmax = float(g64[k].abs().max())
+        err = float((G[k].cpu().double() - g64[k]).abs().max())
+        print(f"   {k}: max|dW - fp64| = {err:.2e} = {err / gmax:.2e} max|dW|")
+        assert gmax > 0 and err <= 1e-5 * gmax, k
+        worst = max(worst, err / (1e-5 * gmax))
+    e_ce = float(((tr.ws_t["ce"][:B].cpu().double() - ce64).abs() / (1e-5 * ce64)).max())
+    print(f"[conv-svi grad Hc={Hc} {act} B={B} C={Cn}] draw: bit-equal to the stack's sample 0, worst {w_draw:.3f} x (2e-6 scale) from the oracle; "
+          f"worst gradient error {worst:.3f} x (1e-5 max|fp64 gradient|); per-point CE {e_ce:.3f} x (1e-5 CE); excluded: {c['n_drop']} of {c['n_pool']} pool points")
+    assert e_ce <= 1.0
+
+
+# The far-end seed: the first after 100 + t whose inputs keep operands / scale of g_raw under 300 (tests/test_hip_svi_train.py: ADAM_SEED),
+# chosen on the CPU from the inputs alone (1100: 649, 1101: 270); the test asserts it of its inputs.
+ADAM_SEED = {1000: 1101}
+
+
+def adam_inputs(t, n, eps):
+    """The planted buffers of the Adam test (tests/test_hip_svi_train.py's): at t >= 1000 raw on both sides of softplus's threshold 20 in the
+    first 600 elements, raw in [-12, -6] in the next 600, dead elements (everything but raw zero) in [1200, 1800)."""
+    g = torch.Generator().manual_seed(ADAM_SEED.get(t, 100 + t))
+    raw_f = torch.randn(n, generator=g) - 1.0
+    vals = {"loc": torch.randn(n, generator=g), "raw": raw_f, "grad": torch.randn(n, generator=g) * 3}
+    for p in ("loc", "raw"):
+        m = 0.2 * torch.randn(n, generator=g)
+        vals["m_" + p], vals["v_" + p] = m, (m.abs() + torch.rand(n, generator=g)) ** 2
+    if t >= 1000:
+        raw_f[:600] = 15.0 + 10.0 * torch.rand(600, generator=g)
+        raw_f[600:1200] = -12.0 + 6.0 * torch.rand(600, generator=g)
+        raw_f[0], raw_f[1], raw_f[2], raw_f[600] = 20.0, 19.999998, 20.000002, -12.0
+        for v in vals.values():
+            if v is not raw_f:
+                v[1200:1800] = 0.0
+    d = {k: v.double() for k, v in vals.items()}
+    sig = F.softplus(d["raw"])
+    g_raw = (d["grad"] * eps + sig - 1 / sig) * torch.sigmoid(d["raw"])
+    operands = ((d["grad"] * eps).abs() + sig + 1 / sig) * torch.sigmoid(d["raw"])
+    return vals, d, g_raw, float((operands / (g_raw.abs() + d["m_raw"].abs())).max())
+
+
+ADAM_SHAPE = (16, 3)           # Hc, C: tensors of 800, 32, 12800, 16, 2352 and 3 elements, no boundary at a multiple of 256
+ADAM_KEY, ADAM_DRAW = 0xFEEDFACE12345678, 17
+
+
+def adam_eps():
+    return torch.cat([v[0].reshape(-1) for v in V.draw_eps(V.shapes_of(*ADAM_SHAPE), ADAM_KEY, ADAM_DRAW).values()])
+
+
+@pytest.mark.parametrize("t", [1, 1000])
+def test_adam_and_kl_kernel_alone_matches_torch_optim_adam(t):
+    """tests/test_hip_svi_train.py's Adam test on the six-segment conv layout: 2e-6 x scale on every output, 1e-5 |KL| on the sum of the
+    partials with sum M <= 10 KL asserted of the inputs, the softplus threshold and dead-element plants at t = 1000."""
+    from robustbnns_amd import _hip
+    from robustbnns_amd.svi_train import ADAM_EPS, BETAS
+    Hc, Cn = ADAM_SHAPE
+    lr, key, draw = 0.01, ADAM_KEY, ADAM_DRAW
+    loc, raw = V.guide(Hc, Cn, seed=t)
+    tr = _trainer(loc, raw, "leaky", Cn, 1, lr, key)
+    n = tr.n_params
+    assert n == 16003 and tr.n_partials == -(-(200 + 8 + 3200 + 4 + 588 + 1) // 256)
+    eps = adam_eps()
+    vals, d, g_raw, ratio = adam_inputs(t, n, eps)
+    if t >= 1000:
+        assert ratio <= 300, ratio
+    for name, v in vals.items():
+        getattr(tr, name).copy_(v)
+    tr.sigma.copy_(F.softplus(vals["raw"].to(DEV)))
+    sig32 = tr.sigma.cpu().double()
+    _hip.check(tr.k.lib.rbnn_conv_svi_adam_step(C.byref(tr.net), C.c_uint64(key), C.c_uint32(draw), t, lr, BETAS[0], BETAS[1], ADAM_EPS,
+                                                _hip.ptr(tr.kl_part), _hip.stream_of(tr.loc)), "rbnn_conv_svi_adam_step")
+    torch.cuda.synchronize()
+    g_loc = d["grad"] + d["loc"]
+    out, worst = {}, 0.0
+    for p, gr in (("loc", g_loc), ("raw", g_raw)):
+        w = d[p].clone().requires_grad_(True)
+        opt = torch.optim.Adam([w], lr=lr)
+        opt.state[w] = {"step": torch.tensor(float(t - 1)), "exp_avg": d["m_" + p].clone(), "exp_avg_sq": d["v_" + p].clone()}
+        w.grad = gr.clone()
+        opt.step()
+        out[p], out["m_" + p], out["v_" + p] = w.detach(), opt.state[w]["exp_avg"], opt.state[w]["exp_avg_sq"]
+        gs = gr.abs() + d["m_" + p].abs()
+        step_size = lr / (1 - BETAS[0] ** t)
+        scale = {p: d[p].abs() + step_size * (1 + out["m_" + p].abs() / (out["v_" + p].sqrt() / (1 - BETAS[1] ** t) ** 0.5 + ADAM_EPS)),
+                 "m_" + p: gs, "v_" + p: d["v_" + p] + gr * gr}
+        for name, sc in scale.items():
+            got = getattr(tr, name).cpu().double()
+            assert bool(torch.isfinite(got).all()), name
+            diff = (got - out[name]).abs()
+            err = float(torch.where(sc > 0, diff / sc.clamp_min(1e-300), torch.where(diff == 0, 0.0, float("inf"))).max())
+            print(f"t={t} {name}: max |err| / scale = {err:.2e}")
+            assert err <= 2e-6, name
+            worst = max(worst, err / 2e-6)
+    sig_new = F.softplus(out["raw"])
+    err = float(((tr.sigma.cpu().double() - sig_new).abs() / (sig_new + torch.sigmoid(out["raw"]) * (out["raw"].abs() + lr))).max())
+    print(f"t={t} sigma: max |err| / scale = {err:.2e}")
+    assert err <= 2e-6
+    kl = float(((-torch.log(sig32) + 0.5 * (sig32 ** 2 + d["loc"] ** 2)) - 0.5).sum())
+    mag = float((torch.log(sig32).abs() + 0.5 * (sig32 ** 2 + d["loc"] ** 2) + 0.5).sum())
+    e_kl = abs(float(tr.kl_part.double().sum()) - kl)
+    print(f"[conv-svi adam t={t}] worst output {max(worst, err / 2e-6):.3f} x (2e-6 scale); KL partial sums {e_kl / (1e-5 * abs(kl)):.3f} x (1e-5 |KL|); "
+          f"sum of operand magnitudes {mag / kl:.2f} KL; g_raw operands / scale {ratio:.0f}; excluded: nothing")
+    assert mag <= 10 * kl
+    assert e_kl <= 1e-5 * abs(kl)
+
+
+def test_twenty_steps_follow_the_fp64_restatement():
+    """max |loc - fp64| and max |raw - fp64| after every one of 20 steps (Hc 16, B 8, tanh) within TRAJ_SPREADS x the fp32-vs-fp64 spread of the
+    restatement itself, measured on the CPU (conv_svi_restate.TRAJ_SPREAD; tests/test_conv_svi_train_cpu.py)."""
+    ref, T = V.traj_reference(), V.TRAJ
+    assert ref["n_bad"] == 0
+    tr = _trainer(ref["loc"], ref["raw"], T["act"], T["n_classes"], T["batch"], T["lr"], T["key"])
+    worst = {"loc": 0.0, "raw": 0.0}
+    for (xb, lb), (l64, r64) in zip(ref["batches"], ref["after"]):
+        tr.step(xb.to(DEV), lb.to(DEV))
+        gl, gr = _read(tr)
+        worst["loc"] = max(worst["loc"], max(float((gl[k] - l64[k]).abs().max()) for k in V.KEYS))
+        worst["raw"] = max(worst["raw"], max(float((gr[k] - r64[k]).abs().max()) for k in V.KEYS))
+    print(f"[conv-svi trajectory] 20 steps: max |loc - fp64| {worst['loc']:.3e} = {worst['loc'] / V.TRAJ_SPREAD['loc']:.3f} x spread, max |raw - fp64| "
+          f"{worst['raw']:.3e} = {worst['raw'] / V.TRAJ_SPREAD['raw']:.3f} x spread (bar {TRAJ_SPREADS}; torch's own fp32 run: 1.000)")
+    assert worst["loc"] <= TRAJ_SPREADS * V.TRAJ_SPREAD["loc"] and worst["raw"] <= TRAJ_SPREADS * V.TRAJ_SPREAD["raw"]
+
+
+# ------------------------------------------------------------------ two epochs with a short last batch, and BNN.train_conv on the same run
+EPOCHS = {"Hc": 16, "act": "leaky", "Cn": 10, "n": 2 * 8 + 3, "batch": 8, "epochs": 2, "lr": 0.01}
+
+
+def _epoch_data():
+    g = torch.Generator().manual_seed(41)
+    x = torch.rand(EPOCHS["n"], 1, 28, 28, generator=g)
+    lab = torch.randint(0, EPOCHS["Cn"], (EPOCHS["n"],), generator=g)
+    loc, raw = V.guide(EPOCHS["Hc"], EPOCHS["Cn"], 42)
+    return x, lab, loc, raw
+
+
+def _epoch_loader(x, lab):
+    return DataLoader(TensorDataset(x, torch.eye(EPOCHS["Cn"])[lab]), batch_size=EPOCHS["batch"], shuffle=False)
+
+
+def _train_key(loader):
+    """The key BNN.train_conv draws for a net that already holds its parameters: the seeding, the loader iterator's base seed, draw_key()."""
+    from robustbnns_amd.model_bnn import set_rng_seed
+    from robustbnns_amd.svi_train import draw_key
+    random.seed(0)
+    set_rng_seed(0)
+    iter(loader)
+    return draw_key()
+
+
+def test_every_step_of_two_epochs_with_a_short_last_batch():
+    """After EVERY step, at the parameters read back from the GPU: Psum against the fp64 accuracy forward of the updated guide (1e-5 per point),
+    the increment of stats[2] within [c_safe, c_safe + n_marginal] at margin 2e-5, stats[0] against the fp64 loss at the GPU's own pre-update
+    parameters (1e-5 relative), stats[1] = the running sum of the stats[0] read back, and begin_epoch()."""
+    E = EPOCHS
+    x, lab, loc, raw = _epoch_data()
+    key = _train_key(_epoch_loader(x, lab))
+    tr = _trainer(loc, raw, E["act"], E["Cn"], E["batch"], E["lr"], key)
+    xd, yd = x.to(DEV), lab.to(DEV)
+    w_psum = w_loss = 0.0
+    marginal, steps = 0, 0
+    for epoch in range(E["epochs"]):
+        tr.begin_epoch()
+        running, correct_before = 0.0, 0.0
+        for i in range(0, E["n"], E["batch"]):
+            xb, lb = x[i:i + E["batch"]], lab[i:i + E["batch"]]
+            B, t = int(xb.shape[0]), tr.t
+            loc0, raw0 = _read(tr)
+            tr.step(xd[i:i + E["batch"]], yd[i:i + E["batch"]])
+            loc1, raw1 = _read(tr)
+            stats, psum = tr.stats.tolist(), tr.Psum[:B, :E["Cn"]].cpu().double()
+            eps = {k: v[0] for k, v in V.draw_eps(tr.shapes, key, t).items()}
+            loss64 = float(V.step_gradients(loc0, raw0, eps, xb, lb, E["act"])[0])
+            e_loss = abs(stats[0] - loss64) / abs(loss64)
+            assert e_loss <= 1e-5, (epoch, i, stats[0], loss64)
+            running += stats[0]
+            assert abs(stats[1] - running) <= 2.0 ** -50 * abs(running), (epoch, i, stats[1], running)
+            psum64, pred, gap = V.accuracy_forward(loc1, raw1, E["act"], xb, key, t)
+            e_psum = float(rel_err_points(psum, psum64).max())
+            assert e_psum <= 1e-5, (epoch, i, e_psum)
+            m = gap < MARGIN
+            c_safe, n_marg = int(((pred == lb) & ~m).sum()), int(m.sum())
+            got = stats[2] - correct_before
+            assert c_safe <= got <= c_safe + n_marg and got == int(got), (epoch, i, got, c_safe, n_marg)
+            correct_before = stats[2]
+            marginal += n_marg
+            w_psum, w_loss, steps = max(w_psum, e_psum / 1e-5), max(w_loss, e_loss / 1e-5), steps + 1
+        last = tr.stats.tolist()
+        assert tr.epoch_totals() == (last[1], last[2]) and last[2] == correct_before
+        tr.begin_epoch()
+        assert tr.stats.tolist() == [last[0], 0.0, 0.0]
+    print(f"[conv-svi epochs Hc={E['Hc']} {E['act']}] {steps} steps, last batch of {E['n'] % E['batch']}: Psum worst {w_psum:.3f} x 1e-5, step loss worst "
+          f"{w_loss:.3f} x 1e-5, stats[1] = the running sum; excluded from the exact count: {marginal} marginal points of {E['epochs'] * E['n']}")
+
+
+def test_bnn_train_conv_end_to_end(tmp_path, capsys):
+    """BNN.train_conv on the run of the per-step test (the net holds the guide, so the loop trains it on): the printed epoch lines and
+    training_history equal a hand-driven ConvSviTrainer's counters from the same seed and key (the same kernels in the same order), the saved
+    file loads into a fresh BNN whose seeded forward is the trained net's bit for bit, loss_gradients returns finite rows, BNN.train still refuses."""
+    from robustbnns_amd.lossGradients import loss_gradients
+    from robustbnns_amd.model_bnn import BNN
+    E = EPOCHS
+    x, lab, loc, raw = _epoch_data()
+    loader = _epoch_loader(x, lab)
+    make = lambda: BNN("mnist", E["Hc"], E["act"], "conv", "svi", E["epochs"], E["lr"], None, None, (1, 28, 28), E["Cn"])
+    bnn = make()
+    bnn.set_variational_params(loc, raw, DEV)
+    rel = str(tmp_path) + "/"
+    bnn.train_conv(loader, DEV, rel)
+    out = capsys.readouterr().out
+    tr = _trainer(loc, raw, E["act"], E["Cn"], E["batch"], E["lr"], _train_key(loader))
+    n = E["n"]
+    for e in range(E["epochs"]):
+        tr.begin_epoch()
+        for xb, yb in loader:
+            tr.step(xb.to(DEV), yb.to(DEV).argmax(-1))
+        loss, correct = tr.epoch_totals()
+        assert correct == int(correct) and 0 <= correct <= n
+        assert bnn.training_history["loss"][e] == loss and bnn.training_history["accuracy"][e] == 100 * correct / n
+        line = f"[Epoch {e + 1}]\t loss: {loss / n:.2f} \t accuracy: {100 * correct / n:.2f}"
+        assert line in out, (line, out)
+    assert len(bnn.training_history["loss"]) == len(bnn.training_history["accuracy"]) == E["epochs"]
+    gl, gr = tr.params()
+    for k in gl:
+        assert torch.equal(gl[k], bnn.svi_loc[k].to(DEV)) and torch.equal(gr[k], bnn.svi_scale[k].to(DEV)), k
+        assert not torch.equal(gl[k].cpu(), loc[k]), k
+    again = make()
+    again.load(DEV, rel)
+    seeds = [3, 1, 4, 1]
+    p, q = bnn.forward(x, n_samples=4, seeds=seeds), again.forward(x, n_samples=4, seeds=seeds)
+    assert torch.equal(p, q) and bool(torch.isfinite(p).all()) and float((p.sum(-1) - 1).abs().max()) < 1e-5
+    g = loss_gradients(again, loader, DEV, "conv_svi", "conv_svi/", n_samples=4)
+    assert g.shape[0] == n and bool(torch.isfinite(torch.as_tensor(g)).all())
+    with pytest.raises(NotImplementedError, match="conv"):
+        bnn.train(loader, DEV, rel)
+    print(f"[conv-svi train_conv] history {bnn.training_history}: the hand-driven trainer's counters; saved, reloaded, forward bit-equal; excluded: nothing")
+
+
+def _three_steps(c, act, Cn):
+    tr = _trainer(c["loc"], c["raw"], act, Cn, 5)
+    x, lab = c["x"].to(DEV), c["lab"].to(DEV)
+    for i in range(3):
+        tr.step(x, lab)
+    torch.cuda.synchronize()
+    res = {name: _bits(getattr(tr, name)) for name in BUFFERS + ("stats", "Psum", "kl_part")}
+    res.update({"ws_" + k: _bits(v) for k, v in tr.ws_t.items()})
+    return res
+
+
+def test_two_identical_runs_of_three_steps_are_bit_identical():
+    Hc, act, B, Cn = V.GRAD_CASES[0]
+    c = V.grad_case(Hc, act, B, Cn)
+    a, b = _three_steps(c, act, Cn), _three_steps(c, act, Cn)
+    for name in a:
+        assert torch.equal(a[name], b[name]), f"two identical runs differ in {name}"
+    assert float(a["stats"][1]) > 0 and all(bool(torch.isfinite(a[k].view(torch.float32)).all()) for k in BUFFERS)
+    print(f"[conv-svi repeat Hc={Hc} {act} B={B}] {len(a)} buffers bit-identical between two runs of 3 steps; excluded: nothing")
+
+
+def test_twenty_steps_make_no_device_to_host_sync():
+    Hc, act, B, Cn = V.GRAD_CASES[0]
+    c = V.grad_case(Hc, act, B, Cn)
+    tr = _trainer(c["loc"], c["raw"], act, Cn, B)
+    x, lab = c["x"].to(DEV), c["lab"].to(DEV)
+    tr.step(x, lab)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        for _ in range(20):
+            tr.step(x, lab)
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    loss, correct = tr.epoch_totals()
+    assert loss == loss and 0 <= correct <= 21 * B and tr.t == 21
+
+
+CANARY = {torch.float32: float("nan"), torch.float64: float("nan"), torch.uint8: 255, torch.int32: 0x7FFFFFFF}
+PAD = 64                       # elements behind every buffer
+
+
+def _padded(t):
+    """A copy of the 1-d or 2-d contiguous tensor t at the front of an allocation with PAD canary elements behind it -> (view, tail)."""
+    big = torch.full((t.numel() + PAD,), CANARY[t.dtype], dtype=t.dtype, device=t.device)
+    big[:t.numel()].copy_(t.reshape(-1))
+    return big[:t.numel()].view(t.shape), big[t.numel():]
+
+
+def _canaried_step(Hc, act, B, Cn, canaries):
+    """One step (with the accuracy forward) of a trainer sized for exactly B points; canaries: every flat buffer, the staged batch, every
+    workspace of the step and of the accuracy forward, Psum, the KL partials and stats are moved to the front of allocations with PAD canary
+    elements (NaN; 255 in the stash bytes; an impossible class in the labels) behind them.  -> (results' bit patterns, the tails)."""
+    from robustbnns_amd import _hip
+    c = V.grad_case(Hc, act, B, Cn)
+    tr = _trainer(c["loc"], c["raw"], act, Cn, B)
+    tails = {}
+    if canaries:
+        for name in BUFFERS + ("X", "labels", "Psum", "kl_part", "stats"):
+            view, tails[name] = _padded(getattr(tr, name))
+            setattr(tr, name, view)
+        for d, tag in ((tr.ws_t, "ws_"), (tr.acc_ws, "acc_")):
+            for k in list(d):
+                d[k], tails[tag + k] = _padded(d[k])
+        _hip.fill(tr.net, tr)
+        tr.ws = _hip.fill(_hip.ConvTrainWs, tr.ws_t)
+        tr.guide.loc, tr.guide.sigma = tr.unflat(tr.loc), tr.unflat(tr.sigma)       # the live views the accuracy draw reads
+    tr.step(c["x"].to(DEV), c["lab"].to(DEV))
+    torch.cuda.synchronize()
+    res = {name: _bits(getattr(tr, name)) for name in BUFFERS + ("stats",)}
+    res["ce"], res["dZ"], res["Psum"] = _bits(tr.ws_t["ce"][:B]), _bits(tr.ws_t["dZ"][:16 * B]), _bits(tr.Psum[:B, :Cn])
+    for name in BUFFERS + ("ce", "Psum"):
+        assert bool(torch.isfinite(res[name].view(torch.float32)).all()), name
+    assert bool(torch.isfinite(tr.stats).all())
+    return res, tails
+
+
+@pytest.mark.parametrize("Hc,act,B,Cn", [V.GRAD_CASES[0], V.GRAD_CASES[1]])
+def test_nothing_behind_the_bounds_is_read_or_written(Hc, act, B, Cn):
+    """B = 5 and B = 65, buffers sized for exactly B points.  Read: the results are bit-identical with and without NaN behind every buffer (NaN
+    is data: one that leaked into a sum would stay there).  Written: every canary element is still a canary after the step."""
+    assert B in (5, 65)
+    clean, _ = _canaried_step(Hc, act, B, Cn, False)
+    dirty, tails = _canaried_step(Hc, act, B, Cn, True)
+    for name in clean:
+        assert torch.equal(clean[name], dirty[name]), f"{name} depends on memory behind the bounds"
+    for name, tail in tails.items():
+        intact = torch.isnan(tail).all() if tail.dtype.is_floating_point else (tail == CANARY[tail.dtype]).all()
+        assert bool(intact) and tail.numel() == PAD, f"the step wrote behind {name}"
+    print(f"[conv-svi bounds Hc={Hc} {act} B={B} C={Cn}] {len(clean)} results bit-identical and finite with canaries behind {len(tails)} buffers, every "
+          f"canary intact; excluded: nothing")
+
+
+def test_three_steps_from_the_references_initialisation_stay_finite():
+    """initial_params (unit-scale randn for loc and raw: saturated logits, ties and kinks not excluded, so no gradient comparison): every buffer
+    stays finite and stats[0] is the fp64 loss at the GPU's own pre-update parameters within 1e-5 relative."""
+    from robustbnns_amd.model_bnn import set_rng_seed
+    from robustbnns_amd.svi_train import initial_params
+    Hc, act, Cn, B, key = 16, "leaky", 10, 8, 0xD1CE
+    set_rng_seed(0)
+    loc, raw = initial_params(list(V.shapes_of(Hc, Cn).items()))
+    g = torch.Generator().manual_seed(9)
+    x, lab = torch.rand(B, 1, 28, 28, generator=g), torch.randint(0, Cn, (B,), generator=g)
+    tr = _trainer(loc, raw, act, Cn, B, 0.01, key)
+    worst = 0.0
+    for t in range(3):
+        loc0, raw0 = _read(tr)
+        tr.step(x.to(DEV), lab.to(DEV))
+        eps = {k: v[0] for k, v in V.draw_eps(tr.shapes, key, t).items()}
+        loss64 = float(V.step_gradients(loc0, raw0, eps, x, lab, act)[0])
+        loss = float(tr.stats[0])
+        for name in BUFFERS:
+            assert bool(torch.isfinite(getattr(tr, name)).all()), (t, name)
+        assert bool(torch.isfinite(tr.stats).all()) and bool(torch.isfinite(tr.Psum[:B]).all())
+        e = abs(loss - loss64) / abs(loss64)
+        print(f"   step {t}: loss {loss:.8e} fp64 {loss64:.8e}: {e / 1e-5:.3f} x 1e-5")
+        assert e <= 1e-5
+        worst = max(worst, e / 1e-5)
+    print(f"[conv-svi reference init Hc={Hc} {act} B={B}] 3 steps finite, step loss worst {worst:.3f} x 1e-5; no gradient comparison (kinks and ties not excluded)")

@@ -20,8 +20,9 @@ OUT = os.path.abspath(os.environ.get("RBNN_TOOLS_OUT") or os.path.join(ROOT, "to
 # seconds per kind of GPU step; profiles/tools_runner/README.txt says where each comes from.  tests, harness: the earlier scripts'.  bench (a lean
 # c1 / c2 run), pmc (the same under rocprofv3 --pmc): 3 x the measured wall time + 90 s.  smoke, bench_full (profile_round's --full runs),
 # bench_other (a lean run of another workload or under torch.distributed.run): NOT MEASURED; under seven minutes, so that no step but the test
-# tier, whose output streams into its log, can keep a visit silent for longer than that.
-LIMITS = {"tests": 1100, "smoke": 300, "harness": 120, "bench": 102, "pmc": 102, "bench_full": 400, "bench_other": 400}
+# tier, whose output streams into its log, can keep a visit silent for longer than that.  timing (one net of conv_svi_train_timing.py, its
+# torch-autograd side included): 3 x the measured wall time (12.0 s for conv-512, 10.1 s for conv-1024) + 90 s.
+LIMITS = {"tests": 1100, "smoke": 300, "harness": 120, "bench": 102, "pmc": 102, "bench_full": 400, "bench_other": 400, "timing": 126}
 STOP_STATUSES = (134, 139, 124, 137, -6, -11, -9)            # abort, segmentation fault, time limit, kill: as a shell and as a Python parent see them
 FAULT_TEXT = "an illegal memory access was encountered"
 
