@@ -136,6 +136,11 @@ __global__ void triple_rows_kernel(const float* __restrict__ src, long long rows
 // K runs in stages of 32 columns = one MFMA K step.  A stage tile is 3 planes x (BH + BN) rows of 64 B, brought in by LDS-DMA
 // in 1-KiB pieces of 16 rows; physical 16-B chunk of logical chunk c in row r is c ^ swz(r), applied on the SOURCE address.
 // Epilogue = the exact kernel's (bias, activation, 1-bit stash, skinny H->C layer on the fp32 MFMA, softmax).
+// A block covers BH hidden units at a time (a "chunk").  NCH = 1 runs chunk after chunk, each over all K stages: the X tile goes through LDS once
+// per chunk.  NCH = 2 (the 8-wave form with an even number of chunks, RBNN_X3_FWD_XONCE != 0) keeps two chunks' accumulators and runs their K
+// stages together, so the X tile is streamed, and its fragments read, once per item: at H = 512 that is 15 instead of 18 LDS-DMA instructions and
+// 36 instead of 48 ds_read_b128 per wave and K column stage, and a quarter fewer bytes from beyond the L2.  The same MFMAs reach every accumulator
+// in the same order: the two forms' results are bit-identical (tests/test_hip_fwd_xonce.py; measurements: profiles/fwd_xonce/README.txt).
 // ===================================================================================================
 struct FwdX3Args {
     const char* X;  int ldx;  int N;                           // grouped triple-rows image of the inputs [ceil16(N)][ldx] (ldx elements, % 32 == 0)
@@ -153,7 +158,7 @@ struct FwdX3Args {
     unsigned x_group_bytes, x_stage_bytes;
 };
 
-template <int ACT, int WH, int HTW, int WN, int NTW, bool LAYER2, bool XF32 = false>      // XF32: the X operand is fc2's fp32 hidden image (layer 2 of fc2 only)
+template <int ACT, int WH, int HTW, int WN, int NTW, bool LAYER2, bool XF32 = false, int NCH = 1>   // XF32: the X operand is fc2's fp32 hidden image (layer 2 of fc2 only); NCH: co-resident h chunks
 __global__ void __launch_bounds__(64 * WH * WN, WH * WN / 4) fc_forward_x3_kernel(const FwdX3Args a) {
     constexpr int BH = WH * HTW * 16, BN = WN * NTW * 16;
     constexpr int PLANEB = (BH + BN) * 64;                     // one plane of a stage tile
@@ -221,192 +226,272 @@ __global__ void __launch_bounds__(64 * WH * WN, WH * WN / 4) fc_forward_x3_kerne
 #pragma unroll
     for (int i = 0; i < WPP; ++i) wrow[i] = (unsigned)(wave + NW * i) * (unsigned)a.KT * 3072u + src_off;
 
-    // The K stages of all h chunks form ONE software pipeline: stage g = (chunk g / KT, columns 32 * (g % KT)), buffer g & 1; the
-    // first stage of the next chunk is in flight while a chunk's epilogue runs.  The pieces of stage g + 1 (PPS per wave) are
-    // issued BETWEEN stage g's MFMA groups, not at its top next to the LDS reads (an LDS-DMA instruction costs ~60 cycles among
-    // MFMAs against 100-185 there), all within the first two h tiles so that they land before the stage ends.
-    // A "piece" below is one 16-row GROUP of one stage: three 1-KiB LDS-DMA instructions (the three fp16 pieces) that share their address
-    // register and M0 — a group is [3 pieces][1 KiB] both in the image and in the stage tile.
-    constexpr int PPS = WPP + XPP;
-    const int G = (a.H / BH) * a.KT;
-    auto piece = [&](int c, int kt, int buf, int j) {           // chunk c, columns 32 * kt -> buffer buf; j: compile-time constant
-        char* const T = ldsb + buf * TILEB;
-        const char* src;
-        char* dst;
-        if (j < WPP) {
-            src = Ws + (long long)c * BH * a.ldw * 6 + (wrow[j < WPP ? j : 0] + (unsigned)kt * 3072u);
-            dst = T + (wave + NW * j) * 3072;
-        } else {
-            src = Xs + (xrow[j >= WPP ? j - WPP : 0] + (unsigned)kt * a.x_stage_bytes);
-            dst = T + (BH / 16 + wave + NW * (j - WPP)) * 3072;
-        }
-        const auto gsrc = (const __attribute__((address_space(1))) void*)src;
-        const auto ldst = (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)dst;
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 1024, 0);
-        if (!(XF32 && j >= WPP)) __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 2048, 0);      // (an fp32 X group is 2 KiB: two pieces)
+    // diagnostic ablation 8: keep the accumulators live, skip the epilogue
+    auto abl_keep_live = [&](f32x4 (&acc)[HTW][NTW]) {
+        float t = 0.f;
+#pragma unroll
+        for (int ht = 0; ht < HTW; ++ht)
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt) { t += acc[ht][nt][0] + acc[ht][nt][1] + acc[ht][nt][2] + acc[ht][nt][3]; acc[ht][nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        if (t == 12345.678f) a.P[tid] = t;
     };
-#pragma unroll
-    for (int i = 0; i < PPS; ++i) piece(0, 0, 0, i);
-    ring_wait_barrier<0>();
 
-    f32x4 acc[HTW][NTW];
+    if constexpr (NCH == 2) {
+        // Two h chunks co-resident (an even number of 256-unit chunks): the pair (c0, c1) = (2 pr, 2 pr + 1) runs its K stages TOGETHER, so the
+        // X tile goes through LDS — and its fragments into registers — once per item and K stage, not once per chunk.  W and X have their own
+        // rings: 2 x W (BH / 16 groups) then 2 x X (BN / 16 groups), the same 2 * TILEB bytes.  K stage kt is two sub-stages c = 0, 1: sub-stage
+        // c multiplies the pair's chunk c, W(2 pr + c, kt) in W buffer c, by X(kt) into acc[c]; c = 0 reads the B fragments (XF32: and splits
+        // them) and c = 1 keeps them in registers across the barrier.  Each sub-stage issues the W groups of the next one under its MFMAs (c = 0: W(c1, kt) -> buffer 1,
+        // c = 1: W(c0, kt + 1) -> buffer 0) and ends in one counted wait + barrier, as the one-chunk pipeline does; X(kt + 1) is issued in
+        // c = 1 — the sub-stage without B reads — into the X buffer that K stage kt - 1 used (the X buffer toggles per K stage ACROSS pairs: KT
+        // may be odd).  The very last sub-stage re-fetches its own W and X into the idle buffers (keeps the body branch-free).  After a pair's
+        // last K stage the two chunk epilogues run in chunk order — zacc takes c0's fp32 MFMAs before c1's, as with one chunk at a time — with
+        // the next pair's first W and X already landed.  Every accumulator receives the same MFMAs in the same order as with NCH = 1.
+        // (The sub-stage body restates the one-chunk loop's instead of sharing it: that loop's device code is held equal to what it was,
+        // instruction for instruction — profiles/fwd_xonce/README.txt.)
+        constexpr int WBUFB = BH / 16 * 3072, XBUFB = BN / 16 * 3072;
+        static_assert(2 * (WBUFB + XBUFB) == 2 * TILEB, "same LDS");
+        char* const Wring = ldsb;
+        char* const Xring = ldsb + 2 * WBUFB;
+        auto dma = [&](const char* src, char* dst, bool third) {
+            const auto gsrc = (const __attribute__((address_space(1))) void*)src;
+            const auto ldst = (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)dst;
+            __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 1024, 0);
+            if (third) __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 2048, 0);
+        };
+        auto w_groups = [&](int c, int kt, int buf) {           // chunk c, columns 32 * kt -> W buffer buf
 #pragma unroll
-    for (int ht = 0; ht < HTW; ++ht)
+            for (int j = 0; j < WPP; ++j)
+                dma(Ws + (long long)c * BH * a.ldw * 6 + (wrow[j] + (unsigned)kt * 3072u), Wring + buf * WBUFB + (wave + NW * j) * 3072, true);
+        };
+        auto x_groups = [&](int kt, int buf) {                  // columns 32 * kt -> X buffer buf (an fp32 X group is 2 KiB: two pieces)
 #pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[ht][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    int kt = 0, ch = 0;                                        // stage g = (chunk ch, K stage kt)
-    for (int g = 0; g < G; ++g) {
-        const int buf = g & 1;
-        // next stage; the very last one re-fetches itself into the idle buffer (1 stage in G: keeps the body branch-free)
-        const bool wrap = kt + 1 == a.KT, last = g + 1 == G;
-        const int ktn = last ? kt : (wrap ? 0 : kt + 1), chn = (wrap && !last) ? ch + 1 : ch;
-        const char* const Wt = ldsb + buf * TILEB + (wave_h * HTW) * 3072 + foff;
-        const char* const Xt = ldsb + buf * TILEB + (BH / 16 + wave_n * NTW) * 3072 + foff;
-        f16x8 b0[NTW], b1[NTW], b2[NTW], a0, a1, a2, a0n, a1n, a2n;
-        if (!(RBNN_ABL & 1)) {
+            for (int j = 0; j < XPP; ++j)
+                dma(Xs + (xrow[j] + (unsigned)kt * a.x_stage_bytes), Xring + buf * XBUFB + (wave + NW * j) * 3072, !XF32);
+        };
+        // one sub-stage's MFMAs: the six product groups per h tile, smallest terms first, the next h tile's fragments read after the first group
+        auto mma = [&](f32x4 (&accc)[HTW][NTW], const char* const Wt, const f16x8 (&b0)[NTW], const f16x8 (&b1)[NTW],
+                       const f16x8 (&b2)[NTW]) __attribute__((always_inline)) {
+            f16x8 a0 = *(const f16x8*)(Wt), a1 = *(const f16x8*)(Wt + 1024), a2 = *(const f16x8*)(Wt + 2048), a0n = a0, a1n = a1, a2n = a2;
 #pragma unroll
-            for (int i = 0; i < PPS; ++i) piece(chn, ktn, buf ^ 1, i);
-        }
-        if constexpr (XF32) {
-            // fp32 hidden activations (already x 2^h1_exp) -> the three pieces of the B fragment, in registers: 8 values, four split3 pairs
-            const char* const Xf = ldsb + buf * TILEB + (BH / 16 + wave_n * NTW) * 3072;
-            f32x4 x0[NTW], x1[NTW];
+            for (int ht = 0; ht < HTW; ++ht) {
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                x0[nt] = *(const f32x4*)(Xf + nt * 3072 + foff_f0);
-                x1[nt] = *(const f32x4*)(Xf + nt * 3072 + foff_f1);
-            }
+                for (int k = 0; k < 6; ++k) {
+                    const f16x8 av = (k == 1) ? a2 : ((k == 2 || k == 3) ? a1 : a0);
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                union { f16x8 v; unsigned w[4]; } q0, q1, q2;
-                split3_plain_pair(x0[nt][0], x0[nt][1], 1.f, q0.w[0], q1.w[0], q2.w[0]);
-                split3_plain_pair(x0[nt][2], x0[nt][3], 1.f, q0.w[1], q1.w[1], q2.w[1]);
-                split3_plain_pair(x1[nt][0], x1[nt][1], 1.f, q0.w[2], q1.w[2], q2.w[2]);
-                split3_plain_pair(x1[nt][2], x1[nt][3], 1.f, q0.w[3], q1.w[3], q2.w[3]);
-                b0[nt] = q0.v; b1[nt] = q1.v; b2[nt] = q2.v;
-            }
-        } else {
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                b0[nt] = *(const f16x8*)(Xt + nt * 3072);
-                b1[nt] = *(const f16x8*)(Xt + nt * 3072 + 1024);
-                b2[nt] = *(const f16x8*)(Xt + nt * 3072 + 2048);
-            }
-        }
-        a0 = *(const f16x8*)(Wt);
-        a1 = *(const f16x8*)(Wt + 1024);
-        a2 = *(const f16x8*)(Wt + 2048);
-        a0n = a0; a1n = a1; a2n = a2;
-#pragma unroll
-        for (int ht = 0; ht < HTW; ++ht) {
-            // six product groups of NTW MFMAs, smallest terms first; between them (fenced: the scheduler would otherwise cluster all
-            // memory instructions at the top) one DMA piece at a time, and the next h tile's three fragment reads after the third
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const f16x8 av = (k == 1) ? a2 : ((k == 2 || k == 3) ? a1 : a0);
-#pragma unroll
-                for (int nt = 0; nt < NTW; ++nt) {
-                    const f16x8 bv = (k == 0) ? b2[nt] : ((k == 2 || k == 4) ? b1[nt] : b0[nt]);
-                    acc[ht][nt] = MFMA_H(av, bv, acc[ht][nt]);
+                    for (int nt = 0; nt < NTW; ++nt) {
+                        const f16x8 bv = (k == 0) ? b2[nt] : ((k == 2 || k == 4) ? b1[nt] : b0[nt]);
+                        accc[ht][nt] = MFMA_H(av, bv, accc[ht][nt]);
+                    }
+                    if (k == 0 && ht + 1 < HTW) {
+                        a0n = *(const f16x8*)(Wt + (ht + 1) * 3072);
+                        a1n = *(const f16x8*)(Wt + (ht + 1) * 3072 + 1024);
+                        a2n = *(const f16x8*)(Wt + (ht + 1) * 3072 + 2048);
+                    }
                 }
-                if (k == 0 && ht + 1 < HTW) {
-                    a0n = *(const f16x8*)(Wt + (ht + 1) * 3072);
-                    a1n = *(const f16x8*)(Wt + (ht + 1) * 3072 + 1024);
-                    a2n = *(const f16x8*)(Wt + (ht + 1) * 3072 + 2048);
-                }
+                a0 = a0n; a1 = a1n; a2 = a2n;
             }
-            a0 = a0n; a1 = a1n; a2 = a2n;
-        }
-        {
-            // pin the order: B fragments + A(0) first, then per h tile half its MFMAs, the next tile's three reads, the rest
-            __builtin_amdgcn_sched_group_barrier(0x100, 3 * NTW + 3, 0);
+        };
+        // pin the order: `lead` LDS reads first, then per h tile half its MFMAs, the next tile's three reads, the rest
+        auto pin = [&](auto lead) __attribute__((always_inline)) {
+            __builtin_amdgcn_sched_group_barrier(0x100, decltype(lead)::value, 0);
 #pragma unroll
             for (int ht = 0; ht < HTW; ++ht) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 3 * NTW, 0);
                 if (ht + 1 < HTW) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 3 * NTW, 0);
             }
-        }
-        if (!(RBNN_ABL & 2)) ring_wait_barrier<0>();           // stage g+1 landed; everyone is done with stage g
-        const int hc0 = ch * BH;
-        kt = wrap ? 0 : kt + 1;
-        ch = wrap ? ch + 1 : ch;
-        if (!wrap) continue;
+        };
+        auto epilogue = [&](f32x4 (&acc)[HTW][NTW], const int hc0) {
+            if (RBNN_ABL & 8) { abl_keep_live(acc); return; }
+#include "rbnn_triple_fwd_epilogue.inc"
+        };
+        w_groups(0, 0, 0);
+        x_groups(0, 0);
+        ring_wait_barrier<0>();
 
-        // ---- epilogue of this h chunk: scale, bias, activation, derivative stash, skinny output layer ----
-        if (RBNN_ABL & 8) {                                    // diagnostic: keep the accumulators live, skip the epilogue
-            float t = 0.f;
+        f32x4 acc[2][HTW][NTW];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int ht = 0; ht < HTW; ++ht)
 #pragma unroll
-                for (int nt = 0; nt < NTW; ++nt) { t += acc[ht][nt][0] + acc[ht][nt][1] + acc[ht][nt][2] + acc[ht][nt][3]; acc[ht][nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-            if (t == 12345.678f) a.P[tid] = t;
-            continue;
+                for (int nt = 0; nt < NTW; ++nt) acc[c][ht][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+        const int T = (a.H / (2 * BH)) * a.KT;                  // K stages of all pairs
+        int kt = 0, pr = 0, xb = 0;                             // K stage t = (pair pr, columns 32 * kt), X buffer xb
+        for (int t = 0; t < T; ++t) {
+            const bool wrap = kt + 1 == a.KT, last = t + 1 == T;
+            const int ktn = last ? kt : (wrap ? 0 : kt + 1), cn = last ? 2 * pr + 1 : (wrap ? 2 * pr + 2 : 2 * pr);
+            const char* const Wt = Wring + (wave_h * HTW) * 3072 + foff;
+            const char* const Xt = Xring + xb * XBUFB + (wave_n * NTW) * 3072;
+            f16x8 b0[NTW], b1[NTW], b2[NTW];
+            // ---- sub-stage 0: chunk c0 ----
+            if (!(RBNN_ABL & 1)) w_groups(2 * pr + 1, kt, 1);
+            if constexpr (XF32) {
+                // fp32 hidden activations (already x 2^h1_exp) -> the three pieces of the B fragment, in registers, once per K stage
+                f32x4 x0[NTW], x1[NTW];
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) {
+                    x0[nt] = *(const f32x4*)(Xt + nt * 3072 + foff_f0);
+                    x1[nt] = *(const f32x4*)(Xt + nt * 3072 + foff_f1);
+                }
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) {
+                    union { f16x8 v; unsigned w[4]; } q0, q1, q2;
+                    split3_plain_pair(x0[nt][0], x0[nt][1], 1.f, q0.w[0], q1.w[0], q2.w[0]);
+                    split3_plain_pair(x0[nt][2], x0[nt][3], 1.f, q0.w[1], q1.w[1], q2.w[1]);
+                    split3_plain_pair(x1[nt][0], x1[nt][1], 1.f, q0.w[2], q1.w[2], q2.w[2]);
+                    split3_plain_pair(x1[nt][2], x1[nt][3], 1.f, q0.w[3], q1.w[3], q2.w[3]);
+                    b0[nt] = q0.v; b1[nt] = q1.v; b2[nt] = q2.v;
+                }
+            } else {
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) {
+                    b0[nt] = *(const f16x8*)(Xt + foff + nt * 3072);
+                    b1[nt] = *(const f16x8*)(Xt + foff + nt * 3072 + 1024);
+                    b2[nt] = *(const f16x8*)(Xt + foff + nt * 3072 + 2048);
+                }
+            }
+            mma(acc[0], Wt, b0, b1, b2);
+            pin(std::integral_constant<int, 3 * NTW + 3>());
+            if (!(RBNN_ABL & 2)) ring_wait_barrier<0>();       // W(c1, kt) landed; everyone is done with W buffer 0
+            __builtin_amdgcn_sched_barrier(0);
+            // ---- sub-stage 1: chunk c1 on the B fragments held in registers ----
+            if (!(RBNN_ABL & 1)) {
+                w_groups(cn, ktn, 0);
+                x_groups(ktn, xb ^ 1);
+            }
+            mma(acc[1], Wt + WBUFB, b0, b1, b2);
+            pin(std::integral_constant<int, 3>());
+            if (!(RBNN_ABL & 2)) ring_wait_barrier<0>();       // the next K stage's W(c0) and X landed; everyone is done with W buffer 1 and X buffer xb
+            xb ^= 1;
+            const int hc0 = 2 * pr * BH;
+            kt = wrap ? 0 : kt + 1;
+            pr = wrap ? pr + 1 : pr;
+            if (wrap) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) epilogue(acc[c], hc0 + c * BH);   // (one call site: inlined like the one-chunk form's)
+            }
         }
-        const int hw0 = hc0 + (wave_h * HTW) * 16;
-        unsigned mine[NTW];
+    } else {
+        // The K stages of all h chunks form ONE software pipeline: stage g = (chunk g / KT, columns 32 * (g % KT)), buffer g & 1; the
+        // first stage of the next chunk is in flight while a chunk's epilogue runs.  The pieces of stage g + 1 (PPS per wave) are
+        // issued BETWEEN stage g's MFMA groups, not at its top next to the LDS reads (an LDS-DMA instruction costs ~60 cycles among
+        // MFMAs against 100-185 there), all within the first two h tiles so that they land before the stage ends.
+        // A "piece" below is one 16-row GROUP of one stage: three 1-KiB LDS-DMA instructions (the three fp16 pieces) that share their address
+        // register and M0 — a group is [3 pieces][1 KiB] both in the image and in the stage tile.
+        constexpr int PPS = WPP + XPP;
+        const int G = (a.H / BH) * a.KT;
+        auto piece = [&](int c, int kt, int buf, int j) {           // chunk c, columns 32 * kt -> buffer buf; j: compile-time constant
+            char* const T = ldsb + buf * TILEB;
+            const char* src;
+            char* dst;
+            if (j < WPP) {
+                src = Ws + (long long)c * BH * a.ldw * 6 + (wrow[j < WPP ? j : 0] + (unsigned)kt * 3072u);
+                dst = T + (wave + NW * j) * 3072;
+            } else {
+                src = Xs + (xrow[j >= WPP ? j - WPP : 0] + (unsigned)kt * a.x_stage_bytes);
+                dst = T + (BH / 16 + wave + NW * (j - WPP)) * 3072;
+            }
+            const auto gsrc = (const __attribute__((address_space(1))) void*)src;
+            const auto ldst = (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)dst;
+            __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 1024, 0);
+            if (!(XF32 && j >= WPP)) __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 2048, 0);      // (an fp32 X group is 2 KiB: two pieces)
+        };
 #pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) mine[nt] = 0u;
+        for (int i = 0; i < PPS; ++i) piece(0, 0, 0, i);
+        ring_wait_barrier<0>();
+
+        f32x4 acc[HTW][NTW];
 #pragma unroll
-        for (int ht = 0; ht < HTW; ++ht) {
-            const int hrow = hw0 + ht * 16 + 4 * lg;           // acc[ht][nt][r] is hidden unit hrow + r
-            const f32x4 bias = *(const f32x4*)(a.b + (long long)sw * a.H + hrow);
-            f32x4 w2f = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (LAYER2 && li < a.C) w2f = *(const f32x4*)(a.W2 + ((long long)sw * a.C + li) * a.H + hrow);
+        for (int ht = 0; ht < HTW; ++ht)
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                const int n = n0 + (wave_n * NTW + nt) * 16 + li;
-                f32x4 v = acc[ht][nt] * out_scale + bias, hv;
-                acc[ht][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                unsigned bits = 0;
+            for (int nt = 0; nt < NTW; ++nt) acc[ht][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+        int kt = 0, ch = 0;                                        // stage g = (chunk ch, K stage kt)
+        for (int g = 0; g < G; ++g) {
+            const int buf = g & 1;
+            // next stage; the very last one re-fetches itself into the idle buffer (1 stage in G: keeps the body branch-free)
+            const bool wrap = kt + 1 == a.KT, last = g + 1 == G;
+            const int ktn = last ? kt : (wrap ? 0 : kt + 1), chn = (wrap && !last) ? ch + 1 : ch;
+            const char* const Wt = ldsb + buf * TILEB + (wave_h * HTW) * 3072 + foff;
+            const char* const Xt = ldsb + buf * TILEB + (BH / 16 + wave_n * NTW) * 3072 + foff;
+            f16x8 b0[NTW], b1[NTW], b2[NTW], a0, a1, a2, a0n, a1n, a2n;
+            if (!(RBNN_ABL & 1)) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    bits |= (v[r] > 0.f ? 1u : 0u) << r;
-                    hv[r] = act_fwd<ACT>(v[r]);
+                for (int i = 0; i < PPS; ++i) piece(chn, ktn, buf ^ 1, i);
+            }
+            if constexpr (XF32) {
+                // fp32 hidden activations (already x 2^h1_exp) -> the three pieces of the B fragment, in registers: 8 values, four split3 pairs
+                const char* const Xf = ldsb + buf * TILEB + (BH / 16 + wave_n * NTW) * 3072;
+                f32x4 x0[NTW], x1[NTW];
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) {
+                    x0[nt] = *(const f32x4*)(Xf + nt * 3072 + foff_f0);
+                    x1[nt] = *(const f32x4*)(Xf + nt * 3072 + foff_f1);
                 }
-                if (BITMASK) {
-                    unsigned part = bits << (16 * (ht & 1) + 4 * lg);
-                    part |= __shfl_xor(part, 16);
-                    part |= __shfl_xor(part, 32);
-                    if (lg == (ht >> 1)) mine[nt] |= part;
-                }
-                if (!BITMASK && a.dact && n < a.N) {
-                    f32x4 dv;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dv[r] = act_grad_from_value<ACT>(hv[r]);
-                    *(f32x4*)(a.dact + ((long long)s * a.N + n) * a.H + hrow) = dv;
+                for (int nt = 0; nt < NTW; ++nt) {
+                    union { f16x8 v; unsigned w[4]; } q0, q1, q2;
+                    split3_plain_pair(x0[nt][0], x0[nt][1], 1.f, q0.w[0], q1.w[0], q2.w[0]);
+                    split3_plain_pair(x0[nt][2], x0[nt][3], 1.f, q0.w[1], q1.w[1], q2.w[1]);
+                    split3_plain_pair(x1[nt][0], x1[nt][1], 1.f, q0.w[2], q1.w[2], q2.w[2]);
+                    split3_plain_pair(x1[nt][2], x1[nt][3], 1.f, q0.w[3], q1.w[3], q2.w[3]);
+                    b0[nt] = q0.v; b1[nt] = q1.v; b2[nt] = q2.v;
                 }
-                if (LAYER2) {
+            } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) zacc[nt] = MFMA16(w2f[r], hv[r], zacc[nt]);
-                } else {
-                    // stage-major fp32 image [S][H/32 stages][N/16 groups][16 points][32 units]: this lane's four units of tile ht are 16 bytes at
-                    // byte ((hrow >> 4) & 1) * 64 + lg * 16 of its point's 128-byte row; a tile's 16 points are one 2-KiB block, and the two h tiles of a
-                    // stage fill its lines between them — no LDS staging, no split here (layer 2 splits at its operand read)
-#ifdef RBNN_X3_L1_ABL_NOSTORE
-                    if (n < a.N && hv[0] == 1.2345e-30f) {                 // ablation (timing only): never stored
-#else
-                    if (n < a.N) {
-#endif
-                        const long long blk = ((long long)s * HW + (hrow >> 5)) * ((a.N + 15) >> 4) + (n >> 4);
-#ifdef RBNN_X3_L1_ABL_SMALL
-                        char* const row = a.hid + ((blk * 2048) & 0xFFC00) + (n & 15) * 128 + ((hrow >> 4) & 1) * 64 + lg * 16;   // ablation: all stores into 1 MB
-#else
-                        char* const row = a.hid + blk * 2048 + (n & 15) * 128 + ((hrow >> 4) & 1) * 64 + lg * 16;
-#endif
-                        *(f32x4*)row = hv * hid_scale;
+                for (int nt = 0; nt < NTW; ++nt) {
+                    b0[nt] = *(const f16x8*)(Xt + nt * 3072);
+                    b1[nt] = *(const f16x8*)(Xt + nt * 3072 + 1024);
+                    b2[nt] = *(const f16x8*)(Xt + nt * 3072 + 2048);
+                }
+            }
+            a0 = *(const f16x8*)(Wt);
+            a1 = *(const f16x8*)(Wt + 1024);
+            a2 = *(const f16x8*)(Wt + 2048);
+            a0n = a0; a1n = a1; a2n = a2;
+#pragma unroll
+            for (int ht = 0; ht < HTW; ++ht) {
+                // six product groups of NTW MFMAs, smallest terms first; between them (fenced: the scheduler would otherwise cluster all
+                // memory instructions at the top) one DMA piece at a time, and the next h tile's three fragment reads after the third
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const f16x8 av = (k == 1) ? a2 : ((k == 2 || k == 3) ? a1 : a0);
+#pragma unroll
+                    for (int nt = 0; nt < NTW; ++nt) {
+                        const f16x8 bv = (k == 0) ? b2[nt] : ((k == 2 || k == 4) ? b1[nt] : b0[nt]);
+                        acc[ht][nt] = MFMA_H(av, bv, acc[ht][nt]);
+                    }
+                    if (k == 0 && ht + 1 < HTW) {
+                        a0n = *(const f16x8*)(Wt + (ht + 1) * 3072);
+                        a1n = *(const f16x8*)(Wt + (ht + 1) * 3072 + 1024);
+                        a2n = *(const f16x8*)(Wt + (ht + 1) * 3072 + 2048);
                     }
                 }
+                a0 = a0n; a1 = a1n; a2 = a2n;
             }
-        }
-        if (BITMASK && a.mask) {
+            {
+                // pin the order: B fragments + A(0) first, then per h tile half its MFMAs, the next tile's three reads, the rest
+                __builtin_amdgcn_sched_group_barrier(0x100, 3 * NTW + 3, 0);
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                const int n = n0 + (wave_n * NTW + nt) * 16 + li;
-                if (lg < HTW / 2 && n < a.N) a.mask[((long long)s * HW + (hw0 >> 5) + lg) * mask_ld(a.N) + n] = mine[nt];
+                for (int ht = 0; ht < HTW; ++ht) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 3 * NTW, 0);
+                    if (ht + 1 < HTW) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 3 * NTW, 0);
+                }
             }
+            if (!(RBNN_ABL & 2)) ring_wait_barrier<0>();           // stage g+1 landed; everyone is done with stage g
+            const int hc0 = ch * BH;
+            kt = wrap ? 0 : kt + 1;
+            ch = wrap ? ch + 1 : ch;
+            if (!wrap) continue;
+            // ---- epilogue of this h chunk ----
+            if (RBNN_ABL & 8) { abl_keep_live(acc); continue; }
+#include "rbnn_triple_fwd_epilogue.inc"
         }
     }
     if (RBNN_ABL & 2) ring_wait_barrier<0>();
@@ -449,13 +534,13 @@ __global__ void __launch_bounds__(64 * WH * WN, WH * WN / 4) fc_forward_x3_kerne
     }
 }
 
-template <int ACT, int WH, int HTW, int WN, int NTW, bool LAYER2, bool XF32>
+template <int ACT, int WH, int HTW, int WN, int NTW, bool LAYER2, bool XF32, int NCH = 1>
 int launch_forward_x3_cfg(FwdX3Args a, hipStream_t st) {
     constexpr int BH = WH * HTW * 16, BN = WN * NTW * 16;
     constexpr int LDSB = 2 * 3 * (BH + BN) * 64;
     static_assert(LDSB <= 160 * 1024, "LDS");
     a.NT = (a.N + BN - 1) / BN;
-    auto kern = fc_forward_x3_kernel<ACT, WH, HTW, WN, NTW, LAYER2, XF32>;
+    auto kern = fc_forward_x3_kernel<ACT, WH, HTW, WN, NTW, LAYER2, XF32, NCH>;
     static unsigned long long attr_done = 0;                    // per instantiation, one bit per device
     if (!ensure_dynamic_lds((const void*)kern, LDSB, attr_done)) return RBNN_ERR_LAUNCH;
     const int grid = grid_for_items((long long)a.NT * a.S);
@@ -465,6 +550,12 @@ int launch_forward_x3_cfg(FwdX3Args a, hipStream_t st) {
 
 template <int ACT, bool LAYER2, bool XF32>
 int launch_forward_x3_act(const FwdX3Args& a, hipStream_t st) {
+    // an even number of 256-unit chunks: two chunks co-resident, the X tile streamed once per item (NCH = 2).  RBNN_X3_FWD_XONCE=0 keeps one
+    // chunk at a time; read at every launch, so one process can run both forms (the results are bit-identical: tests/test_hip_fwd_xonce.py)
+    if (a.H % 512 == 0) {
+        const char* const e = getenv("RBNN_X3_FWD_XONCE");
+        if (!e || e[0] != '0') return launch_forward_x3_cfg<ACT, 4, 4, 2, 4, LAYER2, XF32, 2>(a, st);
+    }
     if (a.H % 256 == 0) return launch_forward_x3_cfg<ACT, 4, 4, 2, 4, LAYER2, XF32>(a, st);   // 256 h x 128 n, 8 waves of 64 h x 64 n, 144 KB of LDS
     if (a.H % 128 == 0) return launch_forward_x3_cfg<ACT, 2, 4, 2, 4, LAYER2, XF32>(a, st);   // 128 h x 128 n, 4 waves
     return RBNN_ERR_UNSUPPORTED;
