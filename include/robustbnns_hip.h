@@ -899,6 +899,65 @@ int rbnn_conv_svi_weight_grads(const rbnn_conv_svi_train_net *net, const float *
 int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net *net, uint64_t key, uint32_t draw_id, int64_t step, double lr, double beta1,
                             double beta2, double adam_eps, float *kl_partials, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic training of M conv nets of one shape in LOCKSTEP (csrc/rbnn_conv_train.hip; additive, ABI 10): the step of
+ * rbnn_conv_train_net above for the members of a deep ensemble (model_ensemble.py:69-83), the member a grid dimension of every launch.
+ * Issued in this order on one stream:  conv_ens_stage -> conv_ens_forward -> conv_ens_weight_grads -> conv_ens_adam_step -> conv_ens_finalize:
+ * 1 + 4 + 7 + 1 + 1 = 14 launches whatever M is.  Member m computes what rbnn_conv_train_* compute for that net on rows[m] of the data, bit
+ * for bit.  The four flat buffers are TENSOR-MAJOR: six blocks [M, size of tensor t] in state_dict order (model.0.weight [M, 800],
+ * model.0.bias [M, 32], model.3.weight [M, 800 Hc], model.3.bias [M, Hc], model.7.weight [M, 49 Hc C], model.7.bias [M, C]), block t at M
+ * times the single net's offset — the stacks of rbnn_conv_posterior.  The batches are gathered from resident data X [n_rows, ldx] (16-byte
+ * aligned, ldx >= 784 and a multiple of 4) with int32 labels [n_rows] by int32 rows [M, B]; an index outside [0, n_rows) is clamped.  The
+ * workspaces are packed [M, B, .] for the call's B.  No atomics and no device->host synchronisation: two runs are bit-identical.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_conv_ens_net {
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_channels, in_width; /* 1, 28 (anything else: RBNN_ERR_UNSUPPORTED)                                  */
+    int32_t hidden;                /* Hc = conv2 output channels, a multiple of 16 in [16, 4096]                   */
+    int32_t n_classes;             /* C in [1, 16]                                                                 */
+    int32_t n_members;             /* M in [1, 65535], M B <= 2^22                                                 */
+    float *P;                      /* [M n_params] parameters, tensor-major (16-byte aligned)                      */
+    float *m, *v;                  /* [M n_params] Adam moments (zero before the first step)                       */
+    float *grad;                   /* [M n_params] dL/dP of the step (L = every member's mean CE of its batch)     */
+} rbnn_conv_ens_net;
+
+typedef struct rbnn_conv_ens_ws {     /* caller-owned, for up to B points per member; every buffer 16-byte aligned  */
+    float   *Xs;                   /* [M B, 784] the members' gathered batches                                     */
+    int32_t *labels;               /* [M B] their labels                                                           */
+    float   *logits;               /* the buffers of rbnn_conv_train_ws, each with a leading member dimension      */
+    float   *P1;
+    uint8_t *st1;
+    float   *Q2;
+    uint8_t *st2;
+    float   *dZ;                   /* [M, B, 16] (softmax - e_y) / B                                               */
+    float   *ce;                   /* [M, B]                                                                       */
+    int32_t *correct;              /* [M, B]                                                                       */
+    float   *dO2;
+    float   *dO1;
+    float   *part2;                /* [M, splits2, Hc, 801]; the slice counts are those of the single net           */
+    float   *part1;                /* [M, splits1, 32, 26]                                                         */
+    float   *partP;                /* [M, splitsP, B, 144, 32]                                                     */
+} rbnn_conv_ens_ws;
+
+typedef struct rbnn_conv_ens_bytes {  /* n_params of ONE member and the bytes of every rbnn_conv_ens_ws buffer for B points per member */
+    int64_t n_params;
+    size_t Xs, labels, logits, P1, st1, Q2, st2, dZ, ce, correct, dO2, dO1, part2, part1, partP;
+} rbnn_conv_ens_bytes;
+
+/* [host] n_params of one member (rbnn_conv_train_sizes') and the workspace sizes: M times the single net's, Xs and labels beside them. */
+int rbnn_conv_ens_sizes(const rbnn_conv_ens_net *net, int32_t n_points, rbnn_conv_ens_bytes *out);
+/* Xs[m, b] = X[rows[m, b]], labels[m, b] = labels[rows[m, b]] (indices clamped to [0, n_rows)): 1 launch.  No later call sees rows. */
+int rbnn_conv_ens_stage(const rbnn_conv_ens_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *labels, const int32_t *rows,
+                        int32_t n_points, const rbnn_conv_ens_ws *ws, void *stream);
+/* rbnn_conv_train_forward of every member on its staged batch: 3 + 1 launches. */
+int rbnn_conv_ens_forward(const rbnn_conv_ens_net *net, int32_t n_points, const rbnn_conv_ens_ws *ws, void *stream);
+/* rbnn_conv_weight_grads of every member: 7 launches. */
+int rbnn_conv_ens_weight_grads(const rbnn_conv_ens_net *net, int32_t n_points, const rbnn_conv_ens_ws *ws, void *stream);
+/* rbnn_conv_adam_step on all M n_params elements (the members share step and lr): 1 launch. */
+int rbnn_conv_ens_adam_step(const rbnn_conv_ens_net *net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void *stream);
+/* One block per member: stats [M, 3] = rbnn_conv_train_finalize's three figures of every member. */
+int rbnn_conv_ens_finalize(const rbnn_conv_ens_net *net, const rbnn_conv_ens_ws *ws, int32_t n_points, double *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

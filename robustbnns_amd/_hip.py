@@ -29,6 +29,7 @@ STRUCTS = {
     "NnTrainNet": "rbnn_nn_train_net", "NnTrainWs": "rbnn_nn_train_ws",
     "ConvTrainNet": "rbnn_conv_train_net", "ConvTrainWs": "rbnn_conv_train_ws", "ConvTrainBytes": "rbnn_conv_train_bytes",
     "ConvSviTrainNet": "rbnn_conv_svi_train_net",
+    "ConvEnsNet": "rbnn_conv_ens_net", "ConvEnsWs": "rbnn_conv_ens_ws", "ConvEnsBytes": "rbnn_conv_ens_bytes",
     "HmcChain": "rbnn_hmc_chain", "HmcLockstep": "rbnn_hmc_lockstep", "SviLockstep": "rbnn_svi_multi", "SviLockstepAcc": "rbnn_svi_multi_acc",
 }
 HEADER = _header.read(HEADER_PATH)
@@ -50,6 +51,7 @@ HMC_ST = {"eps": HMC_ST_EPS, "U": HMC_ST_U, "t": HMC_ST_T, "gbar": HMC_ST_GBAR, 
 _keys = lambda cls: tuple(name for name, _ in cls._fields_)
 WS_KEYS, CONV_WS_KEYS, SPLIT_WS_KEYS, TRIPLE_WS_KEYS = _keys(Workspace), _keys(ConvWorkspace), _keys(SplitWorkspace), _keys(TripleWorkspace)
 SVI_TRAIN_WS_KEYS, NN_TRAIN_WS_KEYS, CONV_TRAIN_WS_KEYS = _keys(SviTrainWs), _keys(NnTrainWs), _keys(ConvTrainWs)
+CONV_ENS_WS_KEYS = _keys(ConvEnsWs)
 SVI_LOCKSTEP_ACC_KEYS = _keys(SviLockstepAcc)
 
 _lib = None

@@ -8,22 +8,29 @@ device->host synchronisation).  ConvNnTrainer stands on what NnTrainer stands on
 the Adam buffers, stats, the staged batch) as a single net: the buffers are flat [n_params] in state_dict order, stats is [3].  The epoch loop is
 nn_train.train_on_loader, the one NN.train runs.
 
+A deep ensemble of conv nets (model_ensemble.py:69-83, reached through Ensemble_NN.train_conv) trains in LOCKSTEP: `ConvEnsembleTrainer.step` is
+that step for M members of one shape, each on its own rows of a resident data set, with the member as a grid dimension of every launch (the
+rbnn_conv_ens_* entry points: 14 launches whatever M is).  Its flat buffers are tensor-major (six blocks [M, size of tensor]); member m is
+bit-identical to that net trained alone by ConvNnTrainer.  The host loop is nn_train.train_members, the one Ensemble_NN.train runs; members
+train in groups when their workspaces exceed the RBNN_CONV_WS_GB budget (conv_ensemble_group).
+
 What stays refused: every entry point of the fc trainers (NN.train, Ensemble_NN.train, NnTrainer, BNN.train, BNN.train_hmc, the lockstep
-forms) on a conv net, the 3x32x32 geometry, conv HMC / ensembles.  SVI posteriors of conv nets are trained by conv_svi_train.ConvSviTrainer
+forms) on a conv net, the 3x32x32 geometry, conv HMC.  SVI posteriors of conv nets are trained by conv_svi_train.ConvSviTrainer
 (BNN.train_conv), on this module's forward and weight gradients.
 """
 import ctypes as C
+import os
 
 import torch
 
 from . import _hip
 from .flat_params import flatten, require_gpu_fc
-from .nn_train import ENSEMBLE_BATCH, AdamNets, train_on_loader
+from .nn_train import ENSEMBLE_BATCH, AdamNets, train_members, train_on_loader
 from .svi_train import ADAM_EPS, BETAS
 
 CONV_KEYS = [k + sfx for k in ("model.0", "model.3", "model.7") for sfx in (".weight", ".bias")]
 GEOMETRY = (1, 28, 28)
-_WS_DTYPES = {"st1": torch.uint8, "st2": torch.uint8, "correct": torch.int32}
+_WS_DTYPES = {"st1": torch.uint8, "st2": torch.uint8, "correct": torch.int32, "labels": torch.int32}
 
 
 def check_conv_trainable(input_shape, device):
@@ -90,6 +97,128 @@ class ConvNnTrainer(AdamNets):
     def params(self):
         """A state_dict-shaped dict of fresh device tensors."""
         return {k: v.clone() for k, v in self.unflat(self.P).items()}
+
+
+class ConvEnsembleTrainer(AdamNets):
+    """Device-resident training state of M conv nets of one shape in lockstep: parameters, Adam moments and gradients flat [M * n_params],
+    TENSOR-MAJOR (six blocks [M, size of tensor] in state_dict order: unflat(buf, member) gives a member's views), the workspaces packed
+    [M, B, .] and stats [M, 3] = [step loss, sum of step losses, correct predictions] per member.  The batch of member m is rows[m] of the
+    resident data (set_data); member m computes what a ConvNnTrainer of that net computes on those rows, bit for bit."""
+
+    def __init__(self, activation, input_shape, n_classes, params_list, lr, device, batch_size=ENSEMBLE_BATCH):
+        check_conv_trainable(input_shape, device)
+        if isinstance(params_list, dict):
+            params_list = [params_list]
+        super().__init__("conv", activation, input_shape, n_classes, params_list[0], device, keys=CONV_KEYS)
+        self.M = len(params_list)
+        net = _hip.ConvEnsNet()
+        net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
+        net.hidden, net.n_classes, net.n_members = self.H, self.C, self.M
+        self.net = net
+        n = self._sizes(1).n_params
+        flat = torch.stack([flatten(p, self.keys) for p in params_list])                       # [M, n] member-major ...
+        sizes = [int(torch.Size(self.shapes[k]).numel()) for k in self.keys]
+        self.adam_state(net, self.M * n, torch.cat([t.reshape(-1) for t in flat.split(sizes, dim=1)]), lr)      # ... -> six blocks [M, size]
+        self.n_params, self.blocks = n, sizes
+        self.stats = torch.zeros(self.M, 3, dtype=torch.float64, device=self.device)
+        self.data = self.data_labels = None
+        self._ensure(int(batch_size))
+
+    def _sizes(self, B):
+        out = _hip.ConvEnsBytes()
+        _hip.check(self.k.lib.rbnn_conv_ens_sizes(C.byref(self.net), B, C.byref(out)), "rbnn_conv_ens_sizes")
+        return out
+
+    def _ensure(self, B):
+        """Workspaces for batches of up to B points per member (grown, never shrunk; a call packs them [M, its own B, .])."""
+        if B <= self.Bmax:
+            return
+        sz = self._sizes(B)
+        self.ws_t = {}
+        for k in _hip.CONV_ENS_WS_KEYS:
+            dt = _WS_DTYPES.get(k, torch.float32)
+            self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
+        self.ws = _hip.fill(_hip.ConvEnsWs, self.ws_t)
+        self.Bmax = B
+
+    def unflat(self, buf, member=0):
+        """state_dict key -> view of member `member`'s tensor inside its block of `buf` (one of the flat buffers), in that tensor's shape."""
+        out, off = {}, 0
+        for k, size in zip(self.keys, self.blocks):
+            out[k] = buf[off + member * size:off + (member + 1) * size].reshape(self.shapes[k])
+            off += self.M * size
+        return out
+
+    def set_data(self, x, labels):
+        """The resident data set the row indices of step(rows=...) refer to: x [N, ...] and integer labels [N], copied to the device once."""
+        N = int(x.shape[0])
+        self.data = x.reshape(N, -1).to(self.device, torch.float32).contiguous()
+        self.data_labels = labels.reshape(N).to(self.device, torch.int32).contiguous()
+        assert int(self.data.shape[1]) == self.D, (tuple(self.data.shape), self.D)
+
+    def _batch(self, rows):
+        """B of a call, its rows checked (NnTrainer._batch's refusals) and the workspaces grown to it; nothing is launched before this."""
+        if self.data is None:
+            raise ValueError("step(rows=...) needs set_data(x, labels) first")
+        if (not torch.is_tensor(rows) or rows.dim() != 2 or int(rows.shape[0]) != self.M or rows.dtype != torch.int32 or rows.device.type != "cuda"
+                or not rows.is_contiguous()):
+            raise ValueError(f"rows must be a contiguous int32 [{self.M}, B] tensor on {self.device}")
+        B = int(rows.shape[1])
+        self._ensure(B)
+        return B
+
+    def gradients(self, rows):
+        """Staging, training forward and weight gradients of the NEXT step (no update): self.grad holds dL/dP of every member, ws_t["ce"] the
+        per-point CE and ws_t["correct"] the per-point flags, packed [M, B]."""
+        B = self._batch(rows)
+        lib, st, net, ws = self.k.lib, _hip.stream_of(self.data), C.byref(self.net), C.byref(self.ws)
+        _hip.check(lib.rbnn_conv_ens_stage(net, _hip.ptr(self.data), int(self.data.stride(0)), int(self.data.shape[0]), _hip.ptr(self.data_labels),
+                                           _hip.ptr(rows), B, ws, st), "rbnn_conv_ens_stage")
+        _hip.check(lib.rbnn_conv_ens_forward(net, B, ws, st), "rbnn_conv_ens_forward")
+        _hip.check(lib.rbnn_conv_ens_weight_grads(net, B, ws, st), "rbnn_conv_ens_weight_grads")
+        return B
+
+    def step(self, rows):
+        """One Adam step of every member on rows [M, B] of the resident data.  No device->host synchronisation."""
+        B = self.gradients(rows)
+        lib, st, net = self.k.lib, _hip.stream_of(self.P), C.byref(self.net)
+        _hip.check(lib.rbnn_conv_ens_adam_step(net, self.t + 1, self.lr, BETAS[0], BETAS[1], ADAM_EPS, st), "rbnn_conv_ens_adam_step")
+        _hip.check(lib.rbnn_conv_ens_finalize(net, C.byref(self.ws), B, _hip.ptr(self.stats), st), "rbnn_conv_ens_finalize")
+        self.t += 1
+
+    def epoch_totals(self):
+        """Per member (sum of the step losses, correct predictions) since begin_epoch(): the one device->host sync of an epoch."""
+        return [(s[1], s[2]) for s in self.stats.tolist()]
+
+    def params(self):
+        """One state_dict-shaped dict of fresh device tensors per member."""
+        return [{k: v.clone() for k, v in self.unflat(self.P, m).items()} for m in range(self.M)]
+
+
+def conv_ensemble_group(activation, hidden, n_classes, n_members, batch_size, budget_gb=None):
+    """The largest number of members (<= n_members, >= 1) whose packed workspaces for batch_size points and four flat buffers fit the conv
+    workspace budget, RBNN_CONV_WS_GB (default 48 GB of the 288 GB): rbnn_conv_ens_sizes is linear in M, so one member's figure decides."""
+    net = _hip.ConvEnsNet()
+    net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
+    net.hidden, net.n_classes, net.n_members = int(hidden), int(n_classes), 1
+    out = _hip.ConvEnsBytes()
+    _hip.check(_hip.load().rbnn_conv_ens_sizes(C.byref(net), int(batch_size), C.byref(out)), "rbnn_conv_ens_sizes")
+    per_member = sum(getattr(out, k) for k in _hip.CONV_ENS_WS_KEYS) + 4 * 4 * out.n_params
+    budget = float(os.environ.get("RBNN_CONV_WS_GB", "48") if budget_gb is None else budget_gb) * 2 ** 30
+    return max(1, min(int(n_members), int(budget // per_member)))
+
+
+def train_conv_ensemble(ens, x_train, y_train, device, group=None):
+    """Ensemble_NN.train_conv: model_ensemble.py:69-83 for a conv ensemble of the 1x28x28 geometry, the host side of nn_train.train_ensemble
+    (train_members) around ConvEnsembleTrainer.  group: members trained at a time — None: all of them when their workspaces fit the
+    RBNN_CONV_WS_GB budget, else the largest group that does; the groups follow one another and no member's bits depend on the grouping."""
+    if ens.architecture != "conv":
+        raise ValueError(f"train_conv trains the conv architecture; a {ens.architecture!r} ensemble trains through train")
+    check_conv_trainable(ens.input_shape, device)
+    if group is None:
+        group = conv_ensemble_group(ens.activation, ens.hidden_size, ens.output_size, max(len(ens.random_seeds), 1), min(ENSEMBLE_BATCH, max(int(len(x_train)), 1)))
+    return train_members(ens, x_train, y_train, device, lambda params, B: ConvEnsembleTrainer(
+        ens.activation, ens.input_shape, ens.output_size, params, ens.lr, device, batch_size=B), group=group)
 
 
 def train_conv_nn(net, train_loader, device, seed=0, save=True):

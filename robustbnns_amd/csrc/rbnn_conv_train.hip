@@ -24,6 +24,21 @@
 //      weight sets into a resident stack, rbnn_conv_forward on the exact path, rbnn_reduce_samples: 1 + 3 + 1 launches).
 //      One SVI step = 1 + 4 + 7 + 1 + 1 = 14 launches without the accuracy forward, 19 with it.
 //
+// and deterministic training of M conv nets of one shape in LOCKSTEP (model_ensemble.py:69-83 for conv: the members share nothing but their
+// shapes, so every launch of the single net's step takes the member as a grid dimension and the launch count does not grow with M):
+//      rbnn_conv_ens_stage          member m's B rows of the resident data (rows [M, B], clamped) -> Xs [M B, 784], labels [M B]: 1 launch
+//                                   (conv_ens_stage_kernel); no kernel after it sees rows, every heavy kernel works on a packed batch
+//      rbnn_conv_ens_forward        the exact forward with S = M samples on the packed batch (conv1_pool_packed_kernel reads row s N + n;
+//                                   conv2_pool_kernel and conv_fc_kernel as they are) and conv_head_kernel over M B points: 3 + 1 launches
+//      rbnn_conv_ens_weight_grads   the 7 launches above, member = blockIdx.y (train_gemm_kernel<true>, conv_ens_do2 / _route1 / _reduce_kernel)
+//                                   or blockIdx.z (conv_ens_wgrad_gemm_kernel: y is the K slice); partial sums [M][slices][...].  The slice
+//                                   counts stay functions of B and Hc alone: member m's sums are added in the single net's order
+//      rbnn_conv_ens_adam_step      nn_adam_kernel<false> over all M n_params elements (element-wise: the members share t and lr): 1 launch
+//      rbnn_conv_ens_finalize       nn_finalize_kernel<true>, one block per member: 1 launch
+//      One lockstep step = 1 + 4 + 7 + 1 + 1 = 14 launches whatever M is.  The flat buffers are TENSOR-MAJOR (six blocks [M, size of tensor]
+//      in state_dict order: rbnn_conv_posterior's stacks, so the forward addresses member m as sample m).  conv_ens_do2 / _wgrad_gemm /
+//      _route1_kernel are the single net's text (rbnn_conv_wgrad_kernels.inc, included twice) on member views; the single net's kernels keep their code.
+//
 // Parameters, moments and gradients are flat fp32 buffers in state_dict order, unpadded (the convention of the fc trainers).  One stream, no
 // atomics, no device->host synchronisation: every output element is one lane's sum in one order, two runs are bit-identical.
 // The three conv GEMMs are one kernel text (conv_wgrad_gemm_kernel): 64 x 64 (G_DP1: 64 x 32) output tiles of the fp32 MFMA, K staged 16 at
@@ -134,40 +149,6 @@ __global__ void __launch_bounds__(64) conv_head_kernel(const ConvHeadArgs a) {
 // ---------------------------------------------------------------------------------------------------
 struct ConvDo2Args { const float *dZ, *Fw, *Q2; const uint8_t* st2; float* dO2; int Hc, C; };
 
-template <int ACT> __global__ void __launch_bounds__(256) conv_do2_kernel(const ConvDo2Args a) {
-    __shared__ float gs[4][NP2];
-    __shared__ int as[4][NP2];
-    const int t = threadIdx.x, groups = a.Hc >> 2;
-    const int b = blockIdx.x / groups, hc0 = 4 * (blockIdx.x % groups);
-    const int F = a.Hc * NP2;
-    if (t < 4 * NP2) {
-        const int hl = t / NP2, p = t % NP2;
-        const long long f = (long long)(hc0 + hl) * NP2 + p;
-        float dq = 0.f;
-        for (int c = 0; c < a.C; ++c) dq = fmaf(a.dZ[(long long)b * RBNN_CPAD + c], a.Fw[(long long)c * F + f], dq);
-        const int st = a.st2[(long long)b * F + f];
-        float d;
-        if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.Q2[(long long)b * F + f]);
-        else d = (st & 4) ? 1.f : act_neg_slope<ACT>();
-        gs[hl][p] = dq * d;
-        as[hl][p] = st & 3;
-    }
-    __syncthreads();
-    const int hl = t >> 6, pos = t & 63, y = pos >> 3, x = pos & 7;
-    float s = 0.f;
-#pragma unroll
-    for (int dy = 1; dy >= 0; --dy)
-#pragma unroll
-        for (int dx = 1; dx >= 0; --dx) {
-            const int wy = y - dy, wx = x - dx;                            // the window whose cell (dy, dx) this position is
-            if (wy >= 0 && wy < P2W && wx >= 0 && wx < P2W) {
-                const int p = wy * P2W + wx;
-                if (as[hl][p] == dy * 2 + dx) s += gs[hl][p];
-            }
-        }
-    a.dO2[((long long)b * a.Hc + hc0 + hl) * NPOS + pos] = s;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // The conv GEMMs  C(m, n) = sum_k A(m, k) B(n, k)  on v_mfma_f32_16x16x4_f32, operands gathered (zero outside [M, N, K]):
 //   G_DK2  m = hc, n = (ci, tap) | bias, k = (b, pos of 8 x 8):   A = dO2[b, hc, pos],  B = P1[b, ci, pos + tap] | 1         -> part2[slice]
@@ -205,65 +186,6 @@ template <int MODE> __device__ __forceinline__ float wg_load_b(const WgArgs& g, 
     return g.Bsrc[(long long)hc * K2 + n * 25 + (k - hc * 25)];
 }
 
-template <int MODE> __global__ void __launch_bounds__(256) conv_wgrad_gemm_kernel(const WgArgs g) {
-    constexpr int NTN = MODE == G_DP1 ? 2 : 4, TN = 16 * NTN;
-    __shared__ float As[GK][GLD], Bs[GK][TN + 4];
-    const int tiles_n = (g.N + TN - 1) / TN;
-    const int m0 = GT * (blockIdx.x / tiles_n), n0 = TN * (blockIdx.x % tiles_n);
-    const int k_begin = blockIdx.y * g.kc, k_end = min(k_begin + g.kc, g.K);
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 15, lg = lane >> 4;
-    f32x4 acc[NTN], tot[NTN];
-#pragma unroll
-    for (int nt = 0; nt < NTN; ++nt) acc[nt] = tot[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int kk = t & 15, r0 = t >> 4;
-    float ra[4], rb[NTN];
-    auto fetch = [&](int k0) {
-        const int k = k0 + kk;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + r0 + 16 * i;
-            ra[i] = (m < g.M && k < k_end) ? wg_load_a<MODE>(g, m, k) : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < NTN; ++i) {
-            const int n = n0 + r0 + 16 * i;
-            rb[i] = (n < g.N && k < k_end) ? wg_load_b<MODE>(g, n, k) : 0.f;
-        }
-    };
-    int stage = 0;
-    fetch(k_begin);
-    for (int k0 = k_begin; k0 < k_end; k0 += GK, ++stage) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) As[kk][r0 + 16 * i] = ra[i];
-#pragma unroll
-        for (int i = 0; i < NTN; ++i) Bs[kk][r0 + 16 * i] = rb[i];
-        __syncthreads();
-        if (k0 + GK < k_end) fetch(k0 + GK);
-#pragma unroll
-        for (int ks = 0; ks < GK / 4; ++ks) {
-            const float a = As[4 * ks + lg][16 * wave + li];
-#pragma unroll
-            for (int nt = 0; nt < NTN; ++nt) acc[nt] = MFMA16(a, Bs[4 * ks + lg][16 * nt + li], acc[nt]);
-        }
-        __syncthreads();
-        if ((stage & 31) == 31) {
-#pragma unroll
-            for (int nt = 0; nt < NTN; ++nt) { tot[nt] += acc[nt]; acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        }
-    }
-    // lane holds C(m0 + 16 wave + 4 lg + r, n0 + 16 nt + li)
-#pragma unroll
-    for (int nt = 0; nt < NTN; ++nt) {
-        tot[nt] += acc[nt];
-        const int n = n0 + 16 * nt + li;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + 16 * wave + 4 * lg + r;
-            if (m < g.M && n < g.N) g.out[((long long)blockIdx.y * g.M + m) * g.N + n] = tot[nt][r];
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------
 // dO1[b, ci, 24 x 24]: one thread per (b, pooled position, ci).  dP1 = the slices of partP in increasing order (fp64), times act' (relu /
 // leaky: the pool-1 stash's sign bit; sigmoid / tanh: from the value in P1), goes to the cell of its 2 x 2 window that the stash names and
@@ -271,24 +193,26 @@ template <int MODE> __global__ void __launch_bounds__(256) conv_wgrad_gemm_kerne
 // ---------------------------------------------------------------------------------------------------
 struct ConvRouteArgs { const float *part, *P1; const uint8_t* st1; float* dO1; long long n; int splits; };
 
-template <int ACT> __global__ void __launch_bounds__(ELT_THREADS) conv_route1_kernel(const ConvRouteArgs a) {
-    const long long e = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (e >= a.n) return;
-    double s = 0.0;
-    for (int sp = 0; sp < a.splits; ++sp) s += (double)a.part[(long long)sp * a.n + e];
-    const int ci = (int)(e & (C1 - 1));
-    const long long m = e >> 5;
-    const int b = (int)(m / PP1), pp = (int)(m - (long long)b * PP1);
-    const long long at = (long long)b * P1SZ + ci * PP1 + pp;
-    const int st = a.st1[at];
-    float d;
-    if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.P1[at]);
-    else d = (st & 4) ? 1.f : act_neg_slope<ACT>();
-    const float v = (float)s * d;
-    float* const o = a.dO1 + ((long long)b * C1 + ci) * NO1 + (2 * (pp / P1W)) * O1W + 2 * (pp % P1W);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) o[(q >> 1) * O1W + (q & 1)] = (st & 3) == q ? v : 0.f;
-}
+// The text of conv_do2_kernel, conv_wgrad_gemm_kernel and conv_route1_kernel is rbnn_conv_wgrad_kernels.inc, included once per form: the single
+// net's kernels, and conv_ens_do2_kernel / conv_ens_wgrad_gemm_kernel / conv_ens_route1_kernel, which run it on the views of one member.
+#define RBNN_DO2_KERNEL conv_do2_kernel
+#define RBNN_WGEMM_KERNEL conv_wgrad_gemm_kernel
+#define RBNN_ROUTE1_KERNEL conv_route1_kernel
+#define RBNN_CONV_WG_ENS 0
+#include "rbnn_conv_wgrad_kernels.inc"
+#undef RBNN_DO2_KERNEL
+#undef RBNN_WGEMM_KERNEL
+#undef RBNN_ROUTE1_KERNEL
+#undef RBNN_CONV_WG_ENS
+#define RBNN_DO2_KERNEL conv_ens_do2_kernel
+#define RBNN_WGEMM_KERNEL conv_ens_wgrad_gemm_kernel
+#define RBNN_ROUTE1_KERNEL conv_ens_route1_kernel
+#define RBNN_CONV_WG_ENS 1
+#include "rbnn_conv_wgrad_kernels.inc"
+#undef RBNN_DO2_KERNEL
+#undef RBNN_WGEMM_KERNEL
+#undef RBNN_ROUTE1_KERNEL
+#undef RBNN_CONV_WG_ENS
 
 // ---------------------------------------------------------------------------------------------------
 // The slices' partial sums -> grad: one thread per element of dK2 | dK2b and of dK1 | dK1b, slices in increasing order, fp64.
@@ -313,6 +237,44 @@ __global__ void __launch_bounds__(ELT_THREADS) conv_reduce_kernel(const ConvRedA
     a.grad[n < 25 ? m * 25 + n : C1 * 25 + m] = (float)s;
 }
 
+// The same sums for member blockIdx.y of part2 [M][s2][Hc, 801] and part1 [M][s1][32, 26], into the member's rows of the tensor-major blocks of
+// grad (oK1b, oK2w, oK2b: the starts of the blocks; model.0.weight's is 0).
+struct ConvEnsRedArgs { const float *part2, *part1; float* grad; int Hc, s2, s1; long long oK1b, oK2w, oK2b; };
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_ens_reduce_kernel(const ConvEnsRedArgs a) {
+    long long e = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    const long long mem = blockIdx.y, n2 = (long long)a.Hc * N2;
+    if (e < n2) {
+        const int m = (int)(e / N2), n = (int)(e - (long long)m * N2);
+        const float* const part = a.part2 + mem * a.s2 * n2;
+        double s = 0.0;
+        for (int sp = 0; sp < a.s2; ++sp) s += (double)part[(long long)sp * n2 + e];
+        a.grad[n < K2 ? a.oK2w + (mem * a.Hc + m) * K2 + n : a.oK2b + mem * a.Hc + m] = (float)s;
+        return;
+    }
+    e -= n2;
+    if (e >= C1 * N1) return;
+    const int m = (int)e / N1, n = (int)e - m * N1;
+    const float* const part = a.part1 + mem * a.s1 * (C1 * N1);
+    double s = 0.0;
+    for (int sp = 0; sp < a.s1; ++sp) s += (double)part[(long long)sp * (C1 * N1) + e];
+    a.grad[n < 25 ? (mem * C1 + m) * 25 + n : a.oK1b + mem * C1 + m] = (float)s;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The members' batches out of the resident data: one block per packed point (member m, point b).  Row rows[m, b] of X [n_rows, ldx], clamped
+// to [0, n_rows) (the fc trainers' rule: a bad index reads a wrong row, never outside X), goes to Xs [M * B, 784] in 16-byte pieces, its
+// label to labels [M * B].  No kernel after this one sees rows.
+// ---------------------------------------------------------------------------------------------------
+struct ConvEnsStageArgs { const float* X; const int32_t *labels, *rows; float* Xs; int32_t* labels_out; int ldx, n_rows; };
+
+__global__ void __launch_bounds__(256) conv_ens_stage_kernel(const ConvEnsStageArgs a) {
+    const long long pt = blockIdx.x;
+    const int t = threadIdx.x, row = min(max(a.rows[pt], 0), a.n_rows - 1);
+    if (t < DIN / 4) *(f32x4*)(a.Xs + pt * DIN + 4 * t) = *(const f32x4*)(a.X + (long long)row * a.ldx + 4 * t);
+    if (t == 0) a.labels_out[pt] = a.labels[row];
+}
+
 inline int check_conv_net(const rbnn_conv_train_net* n) {
     if (!n) return RBNN_ERR_NULL;
     if (n->activation < RBNN_ACT_RELU || n->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
@@ -332,6 +294,39 @@ template <int MODE> int wg_launch(const WgArgs& g, int splits, hipStream_t st) {
     const int tiles = ((g.M + GT - 1) / GT) * ((g.N + TN - 1) / TN);
     hipLaunchKernelGGL(conv_wgrad_gemm_kernel<MODE>, dim3(tiles, splits), dim3(256), 0, st, g);
     return launch_status();
+}
+// the same tiles and slices for every member (grid dimension z): member m's operands at A + m a_mem, Bsrc + m b_mem, its slices at out + m o_mem
+template <int MODE> int wg_ens_launch(const WgArgs& g, int splits, int members, long long a_mem, long long b_mem, long long o_mem, hipStream_t st) {
+    constexpr int TN = MODE == G_DP1 ? 32 : 64;
+    const int tiles = ((g.M + GT - 1) / GT) * ((g.N + TN - 1) / TN);
+    hipLaunchKernelGGL(conv_ens_wgrad_gemm_kernel<MODE>, dim3(tiles, splits, members), dim3(256), 0, st, g, a_mem, b_mem, o_mem);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// M members in lockstep.  The flat buffers are TENSOR-MAJOR: six blocks [M, size of tensor t] in state_dict order, so block t starts at M times
+// the single net's offset and member m's tensor at + m * size — the layout of rbnn_conv_posterior's stacks (K1w [S][32][25], ..., Fb [S][C]):
+// the exact forward addresses member m as sample m.  Every block start and every member's K2w / K2b / Fw is 16-byte aligned (Hc % 16 == 0).
+// ---------------------------------------------------------------------------------------------------
+constexpr int MAX_MEMBERS = 65535;                                                               // the member is a grid dimension (y or z)
+constexpr long long MAX_ENS_POINTS = 1LL << 22;                                                  // M B: every packed index stays far inside 32 bits of blocks
+
+inline ConvLayout conv_ens_layout(int Hc, int C, int M) {
+    ConvLayout L = conv_layout(Hc, C);
+    L.K1w *= M; L.K1b *= M; L.K2w *= M; L.K2b *= M; L.Fw *= M; L.Fb *= M; L.n_params *= M;
+    return L;
+}
+
+inline int check_conv_ens_net(const rbnn_conv_ens_net* n) {
+    if (!n) return RBNN_ERR_NULL;
+    if (n->activation < RBNN_ACT_RELU || n->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
+    if (n->in_channels != 1 || n->in_width != IW) return RBNN_ERR_UNSUPPORTED;
+    if (n->hidden < 16 || (n->hidden & 15) || n->hidden > MAX_HIDDEN || n->n_classes < 1 || n->n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
+    return (n->n_members < 1 || n->n_members > MAX_MEMBERS) ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+
+inline int check_conv_ens_points(const rbnn_conv_ens_net* n, int B) {
+    return (B < 1 || B > MAX_POINTS || (long long)n->n_members * B > MAX_ENS_POINTS) ? RBNN_ERR_SHAPE : RBNN_OK;
 }
 
 }  // namespace
@@ -458,6 +453,146 @@ int rbnn_conv_train_finalize(const rbnn_conv_train_ws* ws, int32_t n_points, dou
     if (n_points < 1 || n_points > MAX_POINTS) return RBNN_ERR_SHAPE;
     const FinalArgs a = {ws->ce, ws->correct, stats, n_points};
     hipLaunchKernelGGL(nn_finalize_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The step of M members in lockstep: the launches of the single net's step with the member as a grid dimension, on batches packed [M, B, .].
+// Member m's sums are the single net's in the single net's order (the slice counts are functions of B and Hc alone).
+// ---------------------------------------------------------------------------------------------------
+int rbnn_conv_ens_sizes(const rbnn_conv_ens_net* net, int32_t n_points, rbnn_conv_ens_bytes* out) {
+    int rc = check_conv_ens_net(net);
+    if (rc) return rc;
+    if (!out) return RBNN_ERR_NULL;
+    if ((rc = check_conv_ens_points(net, n_points))) return rc;
+    rbnn_conv_train_net one = {};
+    one.activation = net->activation; one.in_channels = net->in_channels; one.in_width = net->in_width; one.hidden = net->hidden;
+    one.n_classes = net->n_classes;
+    rbnn_conv_train_bytes s;
+    if ((rc = rbnn_conv_train_sizes(&one, n_points, &s))) return rc;
+    const size_t M = (size_t)net->n_members;
+    rbnn_conv_ens_bytes z = {};
+    z.n_params = s.n_params;
+    z.Xs = M * n_points * DIN * sizeof(float);
+    z.labels = M * n_points * sizeof(int32_t);
+    z.logits = M * s.logits; z.P1 = M * s.P1; z.st1 = M * s.st1; z.Q2 = M * s.Q2; z.st2 = M * s.st2; z.dZ = M * s.dZ; z.ce = M * s.ce;
+    z.correct = M * s.correct; z.dO2 = M * s.dO2; z.dO1 = M * s.dO1; z.part2 = M * s.part2; z.part1 = M * s.part1; z.partP = M * s.partP;
+    *out = z;
+    return RBNN_OK;
+}
+
+int rbnn_conv_ens_stage(const rbnn_conv_ens_net* net, const float* X, int32_t ldx, int32_t n_rows, const int32_t* labels, const int32_t* rows,
+                        int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+    int rc = check_conv_ens_net(net);
+    if (rc) return rc;
+    if (!X || !labels || !rows || !ws || !ws->Xs || !ws->labels) return RBNN_ERR_NULL;
+    if ((rc = check_conv_ens_points(net, n_points))) return rc;
+    if (n_rows < 1 || ldx < DIN || (ldx & 3)) return RBNN_ERR_SHAPE;
+    if (!aligned16(X) || !aligned16(ws->Xs)) return RBNN_ERR_ALIGN;
+    const ConvEnsStageArgs a = {X, labels, rows, ws->Xs, ws->labels, ldx, n_rows};
+    hipLaunchKernelGGL(conv_ens_stage_kernel, dim3((unsigned)(net->n_members * n_points)), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+int rbnn_conv_ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+    int rc = check_conv_ens_net(net);
+    if (rc) return rc;
+    if (!net->P || !ws || !ws->Xs || !ws->labels || !ws->logits || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->ce || !ws->correct)
+        return RBNN_ERR_NULL;
+    if ((rc = check_conv_ens_points(net, n_points))) return rc;
+    if (!aligned16(net->P)) return RBNN_ERR_ALIGN;
+    const int M = net->n_members;
+    const ConvLayout L = conv_ens_layout(net->hidden, net->n_classes, M);
+    rbnn_conv_posterior p = {};
+    p.activation = net->activation; p.hidden = net->hidden; p.n_classes = net->n_classes; p.n_stored = M;
+    p.in_channels = net->in_channels; p.in_width = net->in_width;
+    p.K1w = net->P + L.K1w; p.K1b = net->P + L.K1b; p.K2w = net->P + L.K2w; p.K2b = net->P + L.K2b; p.Fw = net->P + L.Fw; p.Fb = net->P + L.Fb;
+    if ((rc = validate_conv(&p))) return rc;
+    rbnn_conv_workspace w = {};
+    w.P = ws->logits; w.P1 = ws->P1; w.st1 = ws->st1; w.Q2 = ws->Q2; w.st2 = ws->st2;
+    ConvArgs a = {};
+    if ((rc = conv_forward_args(&p, p.K2w, true, ws->Xs, DIN, n_points, nullptr, M, RBNN_OUT_LOGITS, &w, a))) return rc;
+    if ((rc = launch_conv_forward_packed(net->activation, a, (hipStream_t)stream))) return rc;
+    const int n = M * n_points;
+    const ConvHeadArgs h = {ws->logits, ws->labels, ws->dZ, ws->ce, ws->correct, n, net->n_classes, 1.f / (float)n_points};
+    hipLaunchKernelGGL(conv_head_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
+    return launch_status();
+}
+
+int rbnn_conv_ens_weight_grads(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+    int rc = check_conv_ens_net(net);
+    if (rc) return rc;
+    if (!net->P || !net->grad || !ws || !ws->Xs || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->dO2 || !ws->dO1 || !ws->part2 ||
+        !ws->part1 || !ws->partP)
+        return RBNN_ERR_NULL;
+    if ((rc = check_conv_ens_points(net, n_points))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int Hc = net->hidden, C = net->n_classes, B = n_points, M = net->n_members;
+    const long long F = (long long)Hc * NP2;
+    const ConvLayout L = conv_ens_layout(Hc, C, M);
+    float* const G = net->grad;
+    // dFw | dFb of every member: the member form of the strided GEMM (grid dimension y)
+    GemmArgs ga = {};
+    ga.n_prob = 1;
+    ga.p[0] = wgrad_prob(ws->dZ, RBNN_CPAD, ws->Q2, F, (long long)B * F, C, (int)F, B, G + L.Fw, G + L.Fb, 0);
+    ga.p[0].c_mem = (long long)C * F;
+    ga.p[0].bias_mem = C;
+    if ((rc = gemm_launch<true>(ga, M, st))) return rc;
+    // dO2
+    const ConvDo2Args d = {ws->dZ, net->P + L.Fw, ws->Q2, ws->st2, ws->dO2, Hc, C};
+    rc = for_activation(net->activation, [&](auto act) {
+        hipLaunchKernelGGL(conv_ens_do2_kernel<decltype(act)::value>, dim3((unsigned)B * (Hc / 4), M), dim3(256), 0, st, d, B);
+        return launch_status();
+    });
+    if (rc) return rc;
+    // dP1 per slice of the channels, then dO1 through pool 1
+    int perP, sP;
+    dp1_slices(B, Hc, perP, sP);
+    const long long nP = (long long)B * PP1 * C1, dO2_mem = (long long)B * Hc * NPOS;
+    WgArgs g = {};
+    g.Hc = Hc; g.ldx = DIN;
+    g.A = ws->dO2; g.Bsrc = net->P + L.K2w; g.out = ws->partP;
+    g.M = B * PP1; g.N = C1; g.K = Hc * 25; g.kc = perP * 400;
+    if ((rc = wg_ens_launch<G_DP1>(g, sP, M, dO2_mem, (long long)Hc * K2, sP * nP, st))) return rc;
+    const ConvRouteArgs ro = {ws->partP, ws->P1, ws->st1, ws->dO1, nP, sP};
+    rc = for_activation(net->activation, [&](auto act) {
+        hipLaunchKernelGGL(conv_ens_route1_kernel<decltype(act)::value>, dim3(blocks_for(ro.n), M), dim3(ELT_THREADS), 0, st, ro, B);
+        return launch_status();
+    });
+    if (rc) return rc;
+    // the two split contractions and their reduction
+    int per2, s2, per1, s1;
+    slices(B, MAX_SPLITS2, per2, s2);
+    slices(B, MAX_SPLITS1, per1, s1);
+    g.A = ws->dO2; g.Bsrc = ws->P1; g.out = ws->part2; g.M = Hc; g.N = N2; g.K = B * NPOS; g.kc = per2 * NPOS;
+    if ((rc = wg_ens_launch<G_DK2>(g, s2, M, dO2_mem, (long long)B * P1SZ, (long long)s2 * Hc * N2, st))) return rc;
+    g.A = ws->dO1; g.Bsrc = ws->Xs; g.out = ws->part1; g.M = C1; g.N = N1; g.K = B * NO1; g.kc = per1 * NO1;
+    if ((rc = wg_ens_launch<G_DK1>(g, s1, M, (long long)B * C1 * NO1, (long long)B * DIN, (long long)s1 * C1 * N1, st))) return rc;
+    const ConvEnsRedArgs r = {ws->part2, ws->part1, G, Hc, s2, s1, L.K1b, L.K2w, L.K2b};
+    hipLaunchKernelGGL(conv_ens_reduce_kernel, dim3(blocks_for((long long)Hc * N2 + C1 * N1), M), dim3(ELT_THREADS), 0, st, r);
+    return launch_status();
+}
+
+int rbnn_conv_ens_adam_step(const rbnn_conv_ens_net* net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void* stream) {
+    const int rc = check_conv_ens_net(net);
+    if (rc) return rc;
+    if (!net->P || !net->m || !net->v || !net->grad) return RBNN_ERR_NULL;
+    if (step < 1) return RBNN_ERR_SHAPE;
+    AdamArgs a = {};
+    a.n_params = conv_ens_layout(net->hidden, net->n_classes, net->n_members).n_params;      // element-wise: the whole buffer is one launch
+    a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad;
+    a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
+    hipLaunchKernelGGL(nn_adam_kernel<false>, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+int rbnn_conv_ens_finalize(const rbnn_conv_ens_net* net, const rbnn_conv_ens_ws* ws, int32_t n_points, double* stats, void* stream) {
+    int rc = check_conv_ens_net(net);
+    if (rc) return rc;
+    if (!ws || !ws->ce || !ws->correct || !stats) return RBNN_ERR_NULL;
+    if ((rc = check_conv_ens_points(net, n_points))) return rc;
+    const FinalArgs a = {ws->ce, ws->correct, stats, n_points};
+    hipLaunchKernelGGL(nn_finalize_kernel<true>, dim3(net->n_members), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

@@ -16,8 +16,8 @@ def require_gpu_fc(what, arch=None, device=None):
     if device is not None and torch.device(device).type != "cuda":
         raise NotImplementedError(f"{what} runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
     if arch is not None and arch not in LAYER_KEYS:
-        raise NotImplementedError(f"{what} covers fc and fc2, not {arch!r} (a conv net trains through NN.train_conv / BNN.train_conv; conv HMC, "
-                                  "conv ensembles and the lockstep forms are not built)")
+        raise NotImplementedError(f"{what} covers fc and fc2, not {arch!r} (a conv net trains through NN.train_conv / BNN.train_conv, a conv "
+                                  "ensemble through Ensemble_NN.train_conv; conv HMC and the other lockstep forms are not built)")
 
 
 def state_keys(arch):

@@ -2,6 +2,10 @@
 
 forward = mean of the LOGITS of the first n_samples members (model_ensemble.py:57-67): the same stacked
 kernels as the BNN with RBNN_OUT_LOGITS / RBNN_LOSS_MEAN_LOGIT.
+
+train (model_ensemble.py:69-83) runs every member's sequential run in lockstep on the GPU: fc / fc2 ensembles through `train`
+(robustbnns_amd/nn_train.py), conv ensembles of the 1x28x28 geometry through `train_conv` (robustbnns_amd/conv_train.py); both stand on one
+host loop (nn_train.train_members), and member k is bit-identical to that net trained alone.  `train` keeps refusing a conv ensemble.
 """
 from .model_nn import NN
 from .savedir import TESTS
@@ -37,6 +41,13 @@ class Ensemble_NN(NN):
             return super().train(*args, **kwargs)
         from .nn_train import train_ensemble
         train_ensemble(self, *args, **kwargs)
+
+    def train_conv(self, x_train, y_train, device):
+        """model_ensemble.py:69-83 for the conv architecture (1x28x28): train's algorithm, the members in lockstep through
+        robustbnns_amd.conv_train.ConvEnsembleTrainer (in groups when their workspaces exceed RBNN_CONV_WS_GB), saved to <name>/weights/.
+        An fc / fc2 ensemble raises ValueError (it trains through train); a CPU device and the 3x32x32 geometry NotImplementedError."""
+        from .conv_train import train_conv_ensemble
+        return train_conv_ensemble(self, x_train, y_train, device)
 
     def load(self, device, rel_path=TESTS):
         """model_ensemble.py:44-55"""

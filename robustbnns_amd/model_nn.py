@@ -5,7 +5,8 @@ and the on-disk `<name>_weights[_<seed>].pt` files are interchangeable.  `forwar
 Sequential: it stacks the parameters as a one-sample posterior and calls the HIP path (logits out),
 so NN, Ensemble_NN and BNN share the same kernels.  `train` (model_nn.py:175-219) runs on the GPU for fc and fc2
 (robustbnns_amd/nn_train.py, csrc/rbnn_nn_train.hip); conv nets and CPU devices raise NotImplementedError.  A conv net of the 1x28x28
-geometry trains through `train_conv` (robustbnns_amd/conv_train.py, csrc/rbnn_conv_train.hip).
+geometry trains through `train_conv` (robustbnns_amd/conv_train.py, csrc/rbnn_conv_train.hip); a deep ensemble of such nets through
+`Ensemble_NN.train_conv`, its members in lockstep.
 """
 import math
 import os

@@ -205,28 +205,36 @@ def ensemble_schedule(ens, n_points):
     return members, torch.stack(schedule)
 
 
-def train_ensemble(ens, x_train, y_train, device):
-    """Ensemble_NN.train: every member's run of the reference's sequential loop, in lockstep (all members in every launch)."""
-    check_trainable(ens.architecture, device)
+def train_members(ens, x_train, y_train, device, trainer, group=None):
+    """model_ensemble.py:69-83 behind its guards, for Ensemble_NN.train (fc / fc2) and Ensemble_NN.train_conv: every member's run of the
+    reference's sequential loop, in lockstep.  trainer(params_list, batch_size) makes the lockstep trainer of those members (set_data,
+    step(rows=...), begin_epoch, epoch_totals, params).  group: how many members train at a time (None: all of them); the groups follow one
+    another, and since ensemble_schedule has fixed every member's weights and batches on the CPU, grouping changes no member's bits.
+    Returns the (last) trainer."""
     n = int(len(x_train))
     members, schedule = ensemble_schedule(ens, n)
     x = torch.as_tensor(x_train)
     lab = torch.as_tensor(y_train).argmax(-1)
-    tr = NnTrainer(ens.architecture, ens.activation, ens.input_shape, ens.output_size, [m.state_dict() for m in members], ens.lr, device,
-                   batch_size=min(ENSEMBLE_BATCH, n))
-    tr.set_data(x, lab)
-    sched = schedule.to(torch.int32).to(tr.device)
-    lines = [[] for _ in members]
-    for epoch in range(ens.epochs):
-        tr.begin_epoch()
-        for i in range(0, n, ENSEMBLE_BATCH):
-            tr.step(rows=sched[:, epoch, i:i + ENSEMBLE_BATCH].contiguous())
-        for m, (total_loss, correct) in enumerate(tr.epoch_totals()):
-            lines[m].append(epoch_line(epoch, total_loss, correct, n))
+    group = len(members) if not group else max(1, min(int(group), len(members)))
+    tr, lines, params = None, [], []
+    for g0 in range(0, len(members), max(group, 1)):
+        part = members[g0:g0 + group]
+        tr = trainer([m.state_dict() for m in part], min(ENSEMBLE_BATCH, n))
+        tr.set_data(x, lab)
+        sched = schedule[g0:g0 + group].to(torch.int32).to(tr.device)
+        part_lines = [[] for _ in part]
+        for epoch in range(ens.epochs):
+            tr.begin_epoch()
+            for i in range(0, n, ENSEMBLE_BATCH):
+                tr.step(rows=sched[:, epoch, i:i + ENSEMBLE_BATCH].contiguous())
+            for m, (total_loss, correct) in enumerate(tr.epoch_totals()):
+                part_lines[m].append(epoch_line(epoch, total_loss, correct, n))
+        lines += part_lines
+        params += tr.params()
     ens.device = device
     ens.ensemble_models = {}
     ens._ens_engine = None
-    for seed, net, p, ls in zip(ens.random_seeds, members, tr.params(), lines):
+    for seed, net, p, ls in zip(ens.random_seeds, members, params, lines):
         print("\n == NN training ==")                       # the members' epoch lines, member by member as the reference prints them
         for line in ls:
             print(line, end="\t")
@@ -235,3 +243,10 @@ def train_ensemble(ens, x_train, y_train, device):
         ens.ensemble_models[str(seed)] = net
     ens.save()
     return tr
+
+
+def train_ensemble(ens, x_train, y_train, device):
+    """Ensemble_NN.train: every member's run of the reference's sequential loop, in lockstep (all members in every launch)."""
+    check_trainable(ens.architecture, device)
+    return train_members(ens, x_train, y_train, device, lambda params, B: NnTrainer(
+        ens.architecture, ens.activation, ens.input_shape, ens.output_size, params, ens.lr, device, batch_size=B))
