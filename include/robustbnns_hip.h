@@ -900,6 +900,38 @@ int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net *net, uint64_t key, ui
                             double beta2, double adam_eps, float *kl_partials, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * HMC over the weights of ONE conv net of the 1x28x28 geometry (csrc/rbnn_hmc.hip; additive, ABI 10): the six single-chain entry points
+ * rbnn_hmc_* above with an rbnn_conv_svi_train_net in place of the rbnn_svi_train_net, on the same rbnn_hmc_chain and with their semantics
+ * word for word: U(q) = sum_b CE(z_b(q), y_b) + 1/2 sum q^2, grad U = dCE/dW + q; the phases OPEN / MID / CLOSE / KICK / DRIFT / ENERGY; the
+ * decide modes INIT / PROBE / TRANSITION; the state block's RBNN_HMC_ST_* indices; RBNN_HMC_UNIF_KEY and RBNN_HMC_SEARCH_KEY.  Position q =
+ * the flat parameter buffer of rbnn_conv_train_net's layout.  Of the net, W is the trajectory's position and grad receives dCE/dW =
+ * rbnn_conv_svi_train_forward + rbnn_conv_svi_weight_grads at W (the summed cross-entropy); the other pointers are not read.  One transition,
+ * issued in this order on one stream:
+ *   momentum -> leapfrog_update(OPEN) -> { conv_svi_train_forward -> conv_svi_weight_grads -> leapfrog_update(MID, or CLOSE after the last
+ *   step) } x L -> decide -> commit        (a leapfrog step: 4 + 7 + 1 = 12 launches; a transition with L steps: 1 + 1 + 12 L + 1 + 1)
+ * Momentum: libm normals (logf / sincospif, as rbnn_hmc_momentum), element e of tensor i (tensor ids 0..5 in state_dict order) from component
+ * e % 4 of the Philox block with counter (e / 4, i, 0, draw_id) — rbnn_conv_svi_train_draw's counter layout.  The kernels are the single
+ * chain's own: no atomics, one stream, no device->host synchronisation, two runs with the same key are bit-identical.  Every entry point
+ * checks the net before any HIP call, as the conv SVI entry points do: a geometry other than 1 / 28 or an activation outside the four is
+ * RBNN_ERR_UNSUPPORTED, hidden not a multiple of 16 in [16, 4096] or n_classes outside [1, 16] RBNN_ERR_SHAPE, a null pointer RBNN_ERR_NULL,
+ * a phase or mode out of range RBNN_ERR_UNSUPPORTED.  Conv chains in lockstep are not built.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* [host] n_params; the lengths of k0_part and of k1_part / p_part (nullable).  < 0: rbnn_status. */
+int64_t rbnn_conv_hmc_sizes(const rbnn_conv_svi_train_net *net, int64_t *n_quad_partials, int64_t *n_elem_partials);
+/* rbnn_hmc_momentum on the six conv tensors: one launch. */
+int rbnn_conv_hmc_momentum(const rbnn_conv_svi_train_net *net, const rbnn_hmc_chain *chain, uint64_t key, uint32_t draw_id, void *stream);
+/* rbnn_hmc_leapfrog_update on net->W / net->grad / chain->r: one launch. */
+int rbnn_conv_hmc_leapfrog_update(const rbnn_conv_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t phase, void *stream);
+/* rbnn_hmc_decide; ce = the conv workspace's per-point cross-entropy of the trajectory's end: one launch, one block. */
+int rbnn_conv_hmc_decide(const rbnn_conv_svi_train_net *net, const rbnn_hmc_chain *chain, const float *ce, int32_t n_points, uint64_t key,
+                         int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void *stream);
+/* rbnn_hmc_commit: one launch. */
+int rbnn_conv_hmc_commit(const rbnn_conv_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t force, int32_t welford_n, int64_t sample_row,
+                         void *stream);
+/* rbnn_hmc_window_end: one launch. */
+int rbnn_conv_hmc_window_end(const rbnn_conv_svi_train_net *net, const rbnn_hmc_chain *chain, int32_t n_window, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Deterministic training of M conv nets of one shape in LOCKSTEP (csrc/rbnn_conv_train.hip; additive, ABI 10): the step of
  * rbnn_conv_train_net above for the members of a deep ensemble (model_ensemble.py:69-83), the member a grid dimension of every launch.
  * Issued in this order on one stream:  conv_ens_stage -> conv_ens_forward -> conv_ens_weight_grads -> conv_ens_adam_step -> conv_ens_finalize:

@@ -17,7 +17,8 @@ svi_train.SviTrainer makes for fc / fc2 (its docstring has the formulas), around
 stream, no atomics, no device->host synchronisation: two runs are bit-identical.  ConvSviTrainer stands on flat_params.FlatNets with conv's key
 list and offers SviTrainer's surface (gradients, step, begin_epoch, epoch_totals, params); the epoch loop is BNN's, shared with BNN.train.
 
-What stays refused: conv HMC, conv SVI guides in lockstep, the 3x32x32 geometry, CPU devices.
+What stays refused: conv SVI guides in lockstep, the 3x32x32 geometry, CPU devices.  HMC posteriors of conv nets are sampled by
+conv_hmc.ConvHmcSampler (BNN.train_hmc_conv), on the forward and weight gradients this step runs; conv chains in lockstep stay refused too.
 """
 import ctypes as C
 

@@ -46,7 +46,7 @@
 // arithmetic (implicit im2col: nothing is unfolded in memory).  Every contraction is split across blocks (grid dimension y) — dK2 (B 64
 // terms) and dK1 (B 576 terms, with a 32 x 26 output) over the batch, dP1 (25 Hc terms) over the conv2 channels — and the slices' partial
 // sums are added in a second pass, in increasing order.
-#include "rbnn_conv_common.hpp"
+#include "rbnn_conv_layout.hpp"
 #include "rbnn_train_gemm.hpp"
 #include "rbnn_nn_step.hpp"
 // rbnn_svi_step.hpp names its argument records as rbnn_nn_step.hpp names its own (AdamArgs): it is read into a namespace of its own here, after
@@ -63,32 +63,8 @@ constexpr int O1W = GeoMnist::O1, NO1 = O1W * O1W, DIN = GeoMnist::DIN, IW = Geo
 constexpr int PP1 = P1W * P1W;                                                                   // 144 pooled conv1 positions
 constexpr int N2 = K2 + 1, N1 = 25 + 1;                                                          // columns of a partial: the taps | the bias
 constexpr int MAX_SPLITS2 = 16, MAX_SPLITS1 = 128;
-constexpr int MAX_POINTS = 65536, MAX_HIDDEN = 4096;
+constexpr int MAX_POINTS = 65536;
 constexpr int DP1_BLOCKS = 2048;                                                                 // blocks the dP1 GEMM aims at (8 per CU)
-
-struct ConvLayout { long long K1w, K1b, K2w, K2b, Fw, Fb, n_params; };
-inline ConvLayout conv_layout(int Hc, int C) {
-    ConvLayout L;
-    L.K1w = 0; L.K1b = C1 * 25; L.K2w = L.K1b + C1; L.K2b = L.K2w + (long long)Hc * K2; L.Fw = L.K2b + Hc;
-    L.Fb = L.Fw + (long long)C * NP2 * Hc; L.n_params = L.Fb + C;
-    return L;
-}
-
-// the six tensors as the segments of the SVI step's Layout: each ONE row of n_elem columns, tensor ids 0..5 in state_dict order
-inline Layout conv_svi_layout(int Hc, int C) {
-    const ConvLayout c = conv_layout(Hc, C);
-    const long long off[7] = {c.K1w, c.K1b, c.K2w, c.K2b, c.Fw, c.Fb, c.n_params};
-    Layout L = {};
-    L.n = 6;
-    long long q = 0;
-    for (int i = 0; i < 6; ++i) {
-        const int n = (int)(off[i + 1] - off[i]);
-        L.s[i] = {off[i], q, 1, n, i};
-        q += (n + 3) / 4;
-    }
-    L.n_params = c.n_params; L.n_quads = q;
-    return L;
-}
 
 // points per slice and slices of the two split contractions: functions of B alone, never more than min(B, MAX_SPLITS) slices
 inline void slices(int B, int max_splits, int& per, int& n) {
@@ -276,11 +252,7 @@ __global__ void __launch_bounds__(256) conv_ens_stage_kernel(const ConvEnsStageA
 }
 
 inline int check_conv_net(const rbnn_conv_train_net* n) {
-    if (!n) return RBNN_ERR_NULL;
-    if (n->activation < RBNN_ACT_RELU || n->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
-    if (n->in_channels != 1 || n->in_width != IW) return RBNN_ERR_UNSUPPORTED;
-    if (n->hidden < 16 || (n->hidden & 15) || n->hidden > MAX_HIDDEN || n->n_classes < 1 || n->n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
-    return RBNN_OK;
+    return n ? check_conv_dims(n->activation, n->in_channels, n->in_width, n->hidden, n->n_classes) : RBNN_ERR_NULL;
 }
 
 inline int check_conv_batch(const float* X, int ldx, int B) {
@@ -319,9 +291,8 @@ inline ConvLayout conv_ens_layout(int Hc, int C, int M) {
 
 inline int check_conv_ens_net(const rbnn_conv_ens_net* n) {
     if (!n) return RBNN_ERR_NULL;
-    if (n->activation < RBNN_ACT_RELU || n->activation > RBNN_ACT_TANH) return RBNN_ERR_UNSUPPORTED;
-    if (n->in_channels != 1 || n->in_width != IW) return RBNN_ERR_UNSUPPORTED;
-    if (n->hidden < 16 || (n->hidden & 15) || n->hidden > MAX_HIDDEN || n->n_classes < 1 || n->n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
+    const int rc = check_conv_dims(n->activation, n->in_channels, n->in_width, n->hidden, n->n_classes);
+    if (rc) return rc;
     return (n->n_members < 1 || n->n_members > MAX_MEMBERS) ? RBNN_ERR_SHAPE : RBNN_OK;
 }
 

@@ -25,8 +25,14 @@
 // rbnn_nn_train_net whose P is the trajectory positions; the element-wise and decision kernels run the single chain's device functions on
 // chain k's view of the shared buffers.  Per chain: its key, step size (its state block), trajectory length (steps[k]), activity (active[k])
 // and number of points (counts[k]).  Chain k is bit-identical to that chain alone.
+//
+// ONE chain over a CONV net of the 1x28x28 geometry (rbnn_conv_hmc_*): the single chain's kernels, launched on the conv Layout of
+// rbnn_conv_layout.hpp — six tensors of one row each, so element e of tensor i draws component e % 4 of the Philox block with counter
+// (e / 4, i, 0, draw id), rbnn_conv_svi_*'s counter layout.  dCE/dW is rbnn_conv_svi_train_forward + rbnn_conv_svi_weight_grads on an
+// rbnn_conv_svi_train_net whose W is the trajectory's position and whose grad receives dCE/dW.  No device code of its own.
 #define RBNN_TRAIN_LOCKSTEP
 #include "rbnn_train_gemm.hpp"
+#include "rbnn_conv_layout.hpp"
 
 namespace {
 
@@ -335,46 +341,60 @@ int check_chains(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* c, Chain
     return RBNN_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t rbnn_hmc_sizes(const rbnn_svi_train_net* net, int64_t* n_quad_partials, int64_t* n_elem_partials) {
+// ---------------------------------------------------------------------------------------------------
+// One chain: what the fc / fc2 entry points (rbnn_hmc_*) and the conv ones (rbnn_conv_hmc_*) do once their net has become a Layout and the
+// trajectory's buffers.  The checks keep the order of the entry points' documentation; nothing is launched before all of them have passed.
+// ---------------------------------------------------------------------------------------------------
+// the layout of an fc / fc2 net, or of a conv net of the 1x28x28 geometry (six tensors of one row each: rbnn_conv_svi_*'s counter layout)
+int chain_layout(const rbnn_svi_train_net* net, Layout* L) {
     const int rc = check_net(net);
+    if (!rc) *L = layout_of(*net);
+    return rc;
+}
+int chain_layout(const rbnn_conv_svi_train_net* net, Layout* L) {
+    if (!net) return RBNN_ERR_NULL;
+    const int rc = check_conv_dims(net->activation, net->in_channels, net->in_width, net->hidden, net->n_classes);
+    if (!rc) *L = conv_svi_layout(net->hidden, net->n_classes);
+    return rc;
+}
+
+template <class Net> int64_t chain_sizes(const Net* net, int64_t* n_quad_partials, int64_t* n_elem_partials) {
+    Layout L;
+    const int rc = chain_layout(net, &L);
     if (rc) return rc;
-    const Layout L = layout_of(*net);
     if (n_quad_partials) *n_quad_partials = blocks_for(L.n_quads);
     if (n_elem_partials) *n_elem_partials = blocks_for(L.n_params);
     return L.n_params;
 }
 
-int rbnn_hmc_momentum(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, uint64_t key, uint32_t draw_id, void* stream) {
-    int rc = check_net(net);
+template <class Net> int chain_momentum(const Net* net, const rbnn_hmc_chain* chain, uint64_t key, uint32_t draw_id, void* stream) {
+    Layout L;
+    int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
-    const Layout L = layout_of(*net);
     hipLaunchKernelGGL(hmc_momentum_kernel, dim3(blocks_for(L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, *chain,
                        (unsigned long long)key, draw_id);
     return launch_status();
 }
 
-int rbnn_hmc_leapfrog_update(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t phase, void* stream) {
-    int rc = check_net(net);
+template <class Net> int chain_update(const Net* net, const rbnn_hmc_chain* chain, int32_t phase, void* stream) {
+    Layout L;
+    int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (!net->W || !net->grad) return RBNN_ERR_NULL;
     if (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY) return RBNN_ERR_UNSUPPORTED;
-    const long long n = layout_of(*net).n_params;
+    const long long n = L.n_params;
     hipLaunchKernelGGL(hmc_update_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, net->W, net->grad, *chain, (int)phase);
     return launch_status();
 }
 
-int rbnn_hmc_decide(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, const float* ce, int32_t n_points, uint64_t key,
-                    int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
-    int rc = check_net(net);
+template <class Net> int chain_decide(const Net* net, const rbnn_hmc_chain* chain, const float* ce, int32_t n_points, uint64_t key,
+                                      int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    Layout L;
+    int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (!ce) return RBNN_ERR_NULL;
     if (n_points < 1 || transition < 0) return RBNN_ERR_SHAPE;
     if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
-    const Layout L = layout_of(*net);
     DecideArgs a = {};
     a.c = *chain; a.ce = ce; a.n_points = n_points; a.n_qpart = blocks_for(L.n_quads); a.n_epart = blocks_for(L.n_params);
     a.transition = transition; a.key = key; a.mode = mode; a.adapt = adapt; a.window_end = window_end;
@@ -382,12 +402,13 @@ int rbnn_hmc_decide(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, 
     return launch_status();
 }
 
-int rbnn_hmc_commit(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t force, int32_t welford_n, int64_t sample_row,
-                    void* stream) {
-    int rc = check_net(net);
+template <class Net> int chain_commit(const Net* net, const rbnn_hmc_chain* chain, int32_t force, int32_t welford_n, int64_t sample_row,
+                                      void* stream) {
+    Layout L;
+    int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (!net->W || !net->grad) return RBNN_ERR_NULL;
-    const long long n = layout_of(*net).n_params;
+    const long long n = L.n_params;
     float* row = nullptr;
     if (sample_row >= 0) {
         if (!chain->samples) return RBNN_ERR_NULL;
@@ -400,16 +421,64 @@ int rbnn_hmc_commit(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, 
     return launch_status();
 }
 
-int rbnn_hmc_window_end(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t n_window, void* stream) {
-    int rc = check_net(net);
+template <class Net> int chain_window_end(const Net* net, const rbnn_hmc_chain* chain, int32_t n_window, void* stream) {
+    Layout L;
+    int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (n_window < 2) return RBNN_ERR_SHAPE;
-    const long long n = layout_of(*net).n_params;
+    const long long n = L.n_params;
     // m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5): the two scalars are formed in double and rounded to fp32 once
     const double w = (double)n_window;
     hipLaunchKernelGGL(hmc_window_end_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, *chain,
                        (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
     return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t rbnn_hmc_sizes(const rbnn_svi_train_net* net, int64_t* n_quad_partials, int64_t* n_elem_partials) {
+    return chain_sizes(net, n_quad_partials, n_elem_partials);
+}
+int rbnn_hmc_momentum(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, uint64_t key, uint32_t draw_id, void* stream) {
+    return chain_momentum(net, chain, key, draw_id, stream);
+}
+int rbnn_hmc_leapfrog_update(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t phase, void* stream) {
+    return chain_update(net, chain, phase, stream);
+}
+int rbnn_hmc_decide(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, const float* ce, int32_t n_points, uint64_t key,
+                    int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    return chain_decide(net, chain, ce, n_points, key, transition, mode, adapt, window_end, stream);
+}
+int rbnn_hmc_commit(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t force, int32_t welford_n, int64_t sample_row,
+                    void* stream) {
+    return chain_commit(net, chain, force, welford_n, sample_row, stream);
+}
+int rbnn_hmc_window_end(const rbnn_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t n_window, void* stream) {
+    return chain_window_end(net, chain, n_window, stream);
+}
+
+// ---- one chain over a conv net of the 1x28x28 geometry: the same kernels on the conv Layout ----
+int64_t rbnn_conv_hmc_sizes(const rbnn_conv_svi_train_net* net, int64_t* n_quad_partials, int64_t* n_elem_partials) {
+    return chain_sizes(net, n_quad_partials, n_elem_partials);
+}
+int rbnn_conv_hmc_momentum(const rbnn_conv_svi_train_net* net, const rbnn_hmc_chain* chain, uint64_t key, uint32_t draw_id, void* stream) {
+    return chain_momentum(net, chain, key, draw_id, stream);
+}
+int rbnn_conv_hmc_leapfrog_update(const rbnn_conv_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t phase, void* stream) {
+    return chain_update(net, chain, phase, stream);
+}
+int rbnn_conv_hmc_decide(const rbnn_conv_svi_train_net* net, const rbnn_hmc_chain* chain, const float* ce, int32_t n_points, uint64_t key,
+                         int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    return chain_decide(net, chain, ce, n_points, key, transition, mode, adapt, window_end, stream);
+}
+int rbnn_conv_hmc_commit(const rbnn_conv_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t force, int32_t welford_n, int64_t sample_row,
+                         void* stream) {
+    return chain_commit(net, chain, force, welford_n, sample_row, stream);
+}
+int rbnn_conv_hmc_window_end(const rbnn_conv_svi_train_net* net, const rbnn_hmc_chain* chain, int32_t n_window, void* stream) {
+    return chain_window_end(net, chain, n_window, stream);
 }
 
 // ---- K chains in lockstep ----

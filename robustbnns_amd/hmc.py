@@ -16,8 +16,9 @@ LockstepHmc runs K chains of one net shape with every launch covering all of the
 chain bit-identical to HmcSampler running it alone; split_r_hat is the convergence figure that goes with several chains.
 
 The chain algorithm (transition, step-size search, warmup windows, sampling, logs) is written once, in _Chains, over K chains with per-chain
-host lists; HmcSampler (K = 1, the single-net entry points rbnn_hmc_*, scalar / flat public values) and LockstepHmc supply the launches,
-the staging of the batch and the shape of what they return.
+host lists; _OneChain (K = 1, the single-chain entry points, scalar / flat public values) and LockstepHmc supply the launches, the staging of
+the batch and the shape of what they return.  HmcSampler is _OneChain on rbnn_hmc_* with the fc / fc2 gradient; conv_hmc.ConvHmcSampler is
+_OneChain on rbnn_conv_hmc_* with the conv gradient (BNN.train_hmc_conv).  HmcSampler and LockstepHmc refuse a conv net.
 """
 import ctypes as C
 import math
@@ -78,16 +79,17 @@ class _Chains(FlatNets):
     """The buffers and the algorithm of K HMC chains over nets of one shape; the per-chain host values are lists of K: _eps (the host's copy
     of the step sizes), _traj (step size x num_steps), _searches (the probes' draw counters), _search_log.  A subclass supplies the launches
     (_gradient, _update, leapfrog, _draw, _decide, _commit, _window_end; each adds its documented launch count to `launches`), the state
-    block's accessors (_set_state, read_state), set_active / _set_steps, _bind / _ensure and stage()."""
+    block's accessors (_set_state, read_state), set_active / _set_steps, _bind / _ensure and stage().  PARAM_KEYS / _hmc_sizes are what a net
+    other than fc / fc2 replaces (conv_hmc.ConvHmcSampler): its state_dict keys and the sizes query of its own entry points."""
+    PARAM_KEYS = None                                                    # None: the state_dict keys of fc / fc2
 
     def __init__(self, arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size, adapt_mass_matrix,
                  members):
-        super().__init__(arch, activation, input_shape, n_classes, q0s[0], device, members)
+        super().__init__(arch, activation, input_shape, n_classes, q0s[0], device, members, keys=self.PARAM_KEYS)
         K = self.K = len(q0s)
         dev, z = self.device, self.zeros
-        nq, ne = C.c_int64(0), C.c_int64(0)
-        n = self.n_params = self.sizes("rbnn_hmc_sizes", self.descriptor(_hip.SviTrainNet), nq, ne)
-        self.n_qpart, self.n_epart = int(nq.value), int(ne.value)
+        n, self.n_qpart, self.n_epart = self._hmc_sizes()
+        self.n_params = n
         self.W, self.grad = z(n), z(n)
         self.q_cur = torch.stack([flatten(q0, self.keys) for q0 in q0s]).reshape(*self.lead, n).to(dev)
         self.g_cur, self.r, self.w_mean, self.w_m2 = z(n), z(n), z(n), z(n)
@@ -106,6 +108,12 @@ class _Chains(FlatNets):
         self.launches = self.B = 0
         # the logs of the last run(): one entry per transition, warmup included
         self.eps_log = self.L_log = self.dH_log = self.accept_prob_log = self.accepted_log = None
+
+    def _hmc_sizes(self):
+        """(n_params, the lengths of k0_part and of k1_part / p_part) of the nets' shape."""
+        nq, ne = C.c_int64(0), C.c_int64(0)
+        n = self.sizes("rbnn_hmc_sizes", self.descriptor(_hip.SviTrainNet), nq, ne)
+        return n, int(nq.value), int(ne.value)
 
     def _start(self, batch_size):
         """The end of a subclass's constructor: the workspaces, the state block's step size and dual-averaging centre, the C structs."""
@@ -240,35 +248,28 @@ class _Chains(FlatNets):
                 note(L)
 
 
-class HmcSampler(_Chains):
-    """Device-resident state of one HMC chain over an fc / fc2 net: the trajectory's position / dCE/dW (an rbnn_svi_train_net's W / grad), the
-    chain's cached position and gradient, momentum, the diagonal inverse mass, Welford's mean / M2, the fp64 state block, the per-transition
-    log and the sample stack.  `launches` counts kernel launches by the entry points' documented launch counts."""
+class _OneChain(_Chains):
+    """K = 1: one chain through the single-chain entry points ENTRY + "momentum" / "leapfrog_update" / "decide" / "commit" / "window_end" on
+    one rbnn_hmc_chain, with scalar / flat public values.  A subclass builds self.net (W = the trajectory's position, grad = dCE/dW) in its
+    constructor and supplies _ensure (the workspaces ws_t with "ce", the staged X [Bmax, D] and labels) and _gradient."""
+    ENTRY = "rbnn_hmc_"
     eps_host, searches, search_log, trajectory_length = (_view(n, 0) for n in ("_eps", "_searches", "_search_log", "_traj"))
 
-    def __init__(self, arch, activation, input_shape, n_classes, q0, step_size, num_steps, device, key, adapt_step_size=True,
-                 adapt_mass_matrix=True, batch_size=128):
-        require_gpu_fc("HMC", arch, device)
-        super().__init__(arch, activation, input_shape, n_classes, [q0], float(step_size), num_steps, device, [key], adapt_step_size,
-                         adapt_mass_matrix, None)
+    def _one_chain(self, net, batch_size):
+        """The end of the constructor: the chain's key, the net's trajectory pointers, the workspaces, the state block."""
         self.key = self.chain_keys[0]
-        self.net = self.descriptor(_hip.SviTrainNet)
-        self.net.W, self.net.grad = self.W.data_ptr(), self.grad.data_ptr()
+        self.net = net
+        net.W, net.grad = self.W.data_ptr(), self.grad.data_ptr()
         self.Bmax = 0
         self._start(batch_size)
+
+    def _call(self, name, *args):
+        _hip.check(getattr(self.k.lib, self.ENTRY + name)(C.byref(self.net), C.byref(self.chain), *args, self._st()), self.ENTRY + name)
+        self.launches += 1
 
     # -- buffers --------------------------------------------------------------------------------------------------------------------
     def _bind(self):
         self.chain = self._chain_struct(_hip.HmcChain, 0)
-
-    def _ensure(self, B):
-        if B <= self.Bmax:
-            return
-        self.ws_t = train_workspace(self.arch, B, self.H, self.device)
-        self.ws = _hip.fill(_hip.SviTrainWs, self.ws_t)
-        self.X = torch.zeros(B, self.D, dtype=torch.float32, device=self.device)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.Bmax = B
 
     def _set_state(self, **kv):
         """Host -> device writes of state-block entries (warmup / set-up only)."""
@@ -287,22 +288,11 @@ class HmcSampler(_Chains):
         pass                                                              # and the host closes its last step (HMC_CLOSE in leapfrog)
 
     # -- launches -------------------------------------------------------------------------------------------------------------------
-    def _gradient(self):
-        """dCE/dW and the per-point CE at self.W: the training forward (fc 2 launches, fc2 4) + the weight gradients (1)."""
-        lib, net = self.k.lib, C.byref(self.net)
-        _hip.check(lib.rbnn_svi_train_forward(net, _hip.ptr(self.X), self.D, self.B, _hip.ptr(self.labels), C.byref(self.ws), self._st()),
-                   "rbnn_svi_train_forward")
-        _hip.check(lib.rbnn_svi_weight_grads(net, _hip.ptr(self.X), self.D, self.B, C.byref(self.ws), self._st()), "rbnn_svi_weight_grads")
-        self.launches += self.fwd_launches + 1
-
     def _update(self, phase):
-        _hip.check(self.k.lib.rbnn_hmc_leapfrog_update(C.byref(self.net), C.byref(self.chain), phase, self._st()), "rbnn_hmc_leapfrog_update")
-        self.launches += 1
+        self._call("leapfrog_update", phase)
 
     def _momentum(self, key, draw_id):
-        _hip.check(self.k.lib.rbnn_hmc_momentum(C.byref(self.net), C.byref(self.chain), C.c_uint64(key & 0xFFFFFFFFFFFFFFFF),
-                                                C.c_uint32(draw_id & 0xFFFFFFFF), self._st()), "rbnn_hmc_momentum")
-        self.launches += 1
+        self._call("momentum", C.c_uint64(key & 0xFFFFFFFFFFFFFFFF), C.c_uint32(draw_id & 0xFFFFFFFF))
 
     def _draw(self, i):
         """The momentum of transition i, or (None) of the search's next probe: a stream of its own, numbered by the try counter."""
@@ -312,18 +302,13 @@ class HmcSampler(_Chains):
             self._momentum(self.key, i)
 
     def _decide(self, mode, transition=0, adapt=False, window_end=False):
-        _hip.check(self.k.lib.rbnn_hmc_decide(C.byref(self.net), C.byref(self.chain), _hip.ptr(self.ws_t["ce"]), self.B, C.c_uint64(self.key),
-                                              int(transition), mode, int(adapt), int(window_end), self._st()), "rbnn_hmc_decide")
-        self.launches += 1
+        self._call("decide", _hip.ptr(self.ws_t["ce"]), self.B, C.c_uint64(self.key), int(transition), mode, int(adapt), int(window_end))
 
     def _commit(self, force=False, welford_n=0, sample_row=-1):
-        _hip.check(self.k.lib.rbnn_hmc_commit(C.byref(self.net), C.byref(self.chain), int(force), int(welford_n), int(sample_row), self._st()),
-                   "rbnn_hmc_commit")
-        self.launches += 1
+        self._call("commit", int(force), int(welford_n), int(sample_row))
 
     def _window_end(self, n):
-        _hip.check(self.k.lib.rbnn_hmc_window_end(C.byref(self.net), C.byref(self.chain), n, self._st()), "rbnn_hmc_window_end")
-        self.launches += 1
+        self._call("window_end", n)
 
     # -- the chain ------------------------------------------------------------------------------------------------------------------
     def stage(self, x, labels):
@@ -366,6 +351,36 @@ class HmcSampler(_Chains):
         self._run(num_samples, warmup, x, labels)
         self.L_log = self.L_log[0]
         return self.unflat(self.samples_t[:int(num_samples)])
+
+
+class HmcSampler(_OneChain):
+    """Device-resident state of one HMC chain over an fc / fc2 net: the trajectory's position / dCE/dW (an rbnn_svi_train_net's W / grad), the
+    chain's cached position and gradient, momentum, the diagonal inverse mass, Welford's mean / M2, the fp64 state block, the per-transition
+    log and the sample stack.  `launches` counts kernel launches by the entry points' documented launch counts."""
+
+    def __init__(self, arch, activation, input_shape, n_classes, q0, step_size, num_steps, device, key, adapt_step_size=True,
+                 adapt_mass_matrix=True, batch_size=128):
+        require_gpu_fc("HMC", arch, device)
+        super().__init__(arch, activation, input_shape, n_classes, [q0], float(step_size), num_steps, device, [key], adapt_step_size,
+                         adapt_mass_matrix, None)
+        self._one_chain(self.descriptor(_hip.SviTrainNet), batch_size)
+
+    def _ensure(self, B):
+        if B <= self.Bmax:
+            return
+        self.ws_t = train_workspace(self.arch, B, self.H, self.device)
+        self.ws = _hip.fill(_hip.SviTrainWs, self.ws_t)
+        self.X = torch.zeros(B, self.D, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.Bmax = B
+
+    def _gradient(self):
+        """dCE/dW and the per-point CE at self.W: the training forward (fc 2 launches, fc2 4) + the weight gradients (1)."""
+        lib, net = self.k.lib, C.byref(self.net)
+        _hip.check(lib.rbnn_svi_train_forward(net, _hip.ptr(self.X), self.D, self.B, _hip.ptr(self.labels), C.byref(self.ws), self._st()),
+                   "rbnn_svi_train_forward")
+        _hip.check(lib.rbnn_svi_weight_grads(net, _hip.ptr(self.X), self.D, self.B, C.byref(self.ws), self._st()), "rbnn_svi_weight_grads")
+        self.launches += self.fwd_launches + 1
 
 
 class LockstepHmc(_Chains):

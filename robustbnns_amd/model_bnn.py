@@ -16,10 +16,12 @@ Training: `train(train_loader, device, rel_path, filename)` runs the reference's
 (svi_train.SviTrainer: one weight draw, the training forward, the weight gradients and one Adam step per batch — csrc/rbnn_train.hip) and
 saves the param store.  `train_conv(train_loader, device, rel_path, filename)` runs the same algorithm for a conv net of the 1x28x28 geometry
 (conv_svi_train.ConvSviTrainer around the conv training forward and weight gradients, csrc/rbnn_conv_train.hip); `train()` itself keeps
-refusing conv.  CPU devices, conv HMC, conv in lockstep and the 3x32x32 geometry raise NotImplementedError.  `train()` refuses an HMC net
-too and names `train_hmc(train_loader, device, rel_path, filename, num_chains=1)`, which samples the chain of an fc / fc2 net on the GPU
-(hmc.HmcSampler, csrc/rbnn_hmc.hip; num_chains = K > 1: K chains in lockstep, hmc.LockstepHmc, pooled and judged by their split-R-hat) and
-writes the per-sample files `load()` reads.
+refusing conv.  CPU devices, conv SVI guides and conv HMC chains in lockstep and the 3x32x32 geometry raise NotImplementedError.  `train()`
+refuses an HMC net too and names `train_hmc(train_loader, device, rel_path, filename, num_chains=1)`, which samples the chain of an fc / fc2
+net on the GPU (hmc.HmcSampler, csrc/rbnn_hmc.hip; num_chains = K > 1: K chains in lockstep, hmc.LockstepHmc, pooled and judged by their
+split-R-hat) and writes the per-sample files `load()` reads.  `train_hmc_conv(train_loader, device, rel_path, filename)` is train_hmc with
+one chain for a conv net of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the same chain kernels around the conv training forward and
+weight gradients); `train_hmc()` itself keeps refusing conv.
 """
 import os
 import random
@@ -132,8 +134,8 @@ def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS,
         raise ValueError(f"train_svi_lockstep needs one n_inputs per net, not {len(n_inputs)} for {len(nets)} nets")
     for net in nets:
         if net.inference != "svi":
-            raise NotImplementedError("train() runs SVI only: sample an HMC posterior (fc / fc2) with BNN.train_hmc(train_loader, device), "
-                                      "or run it with the reference and load the chain here")
+            raise NotImplementedError("train() runs SVI only: sample an HMC posterior with BNN.train_hmc(train_loader, device) (fc / fc2) or "
+                                      "BNN.train_hmc_conv(train_loader, device) (conv, 1x28x28)")
         require_gpu_fc("SVI training", net.basenet.architecture)
     require_gpu_fc("SVI training", device=device)
     b0 = nets[0].basenet
@@ -432,8 +434,8 @@ class BNN(nn.Module):
         from the CPU generator first, as the reference's does — RandomSampler's order of draws recalled, not checked) unless the net
         already holds some (load() or an earlier train(): pyro's param store persists), which are then trained further."""
         if self.inference == "hmc":
-            raise NotImplementedError("train() runs SVI only: sample an HMC posterior (fc / fc2) with BNN.train_hmc(train_loader, device), "
-                                      "or run it with the reference and load the chain here")
+            raise NotImplementedError("train() runs SVI only: sample an HMC posterior with BNN.train_hmc(train_loader, device) (fc / fc2) or "
+                                      "BNN.train_hmc_conv(train_loader, device) (conv, 1x28x28)")
         require_gpu_fc("SVI training", self.basenet.architecture)
         require_gpu_fc("SVI training", device=device)
         from .svi_train import SviTrainer
@@ -446,8 +448,8 @@ class BNN(nn.Module):
         seeding, initialisation at the first batch, key, epoch lines, training_history, set_variational_params and save().  Every refusal
         comes before any state is changed, a generator touched or the library loaded."""
         if self.inference == "hmc":
-            raise NotImplementedError("train_conv() runs SVI only: an HMC posterior is sampled with BNN.train_hmc(train_loader, device), which "
-                                      "covers fc / fc2 (conv HMC is not built: run it with the reference and load the chain here)")
+            raise NotImplementedError("train_conv() runs SVI only: an HMC posterior is sampled with BNN.train_hmc(train_loader, device) for fc / "
+                                      "fc2 and with BNN.train_hmc_conv(train_loader, device) for a conv net of the 1x28x28 geometry")
         if self.basenet.architecture != "conv":
             raise ValueError(f"train_conv trains the conv architecture; a {self.basenet.architecture!r} net trains through train")
         from .conv_train import check_conv_trainable
@@ -538,6 +540,29 @@ class BNN(nn.Module):
             self.hmc_history = lockstep_history(sampler, 0, idx)
             self.hmc_history.update({"stack": stack, "chains": [lockstep_history(sampler, k) for k in range(K)],
                                      "r_hat_U": lockstep_r_hat(sampler, self.warmup)})
+        self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
+        self.save(rel_path=rel_path, filename=filename)
+
+    def train_hmc_conv(self, train_loader, device, rel_path=TESTS, filename=None):
+        """train_hmc with num_chains = 1 for the conv architecture of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the chain's kernels of
+        csrc/rbnn_hmc.hip around the conv training forward and weight gradients of csrc/rbnn_conv_train.hip): the same prologue, the chain on
+        the last batch, the resampling with torch.randint(0, batch_samples, (n_samples,)), set_posterior_samples, hmc_history and save().
+        Every refusal comes before any state is changed, a generator touched or the library loaded.  Conv chains in lockstep are not built."""
+        if self.inference != "hmc":
+            raise ValueError(f"train_hmc_conv() samples an HMC posterior; this net's inference is {self.inference!r} (use train_conv())")
+        if self.basenet.architecture != "conv":
+            raise ValueError(f"train_hmc_conv samples the conv architecture; a {self.basenet.architecture!r} net samples through train_hmc")
+        from .conv_train import check_conv_trainable
+        check_conv_trainable(self.basenet.input_shape, device)
+        from .conv_hmc import ConvHmcSampler
+        x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
+        b = self.basenet
+        sampler = ConvHmcSampler(b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, key,
+                                 batch_size=int(x_batch.shape[0]))
+        stack = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
+        idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
+        self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
+                            "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
         self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
         self.save(rel_path=rel_path, filename=filename)
 
