@@ -19,6 +19,63 @@ TIE = 2e-6
 # (Hc, act, B, C): a one-tile and a three-tile Hc, the four activations, B = 1, an odd B, a B past a 64-point boundary, fewer than 16 classes
 GRAD_CASES = [(16, "leaky", 8, 10), (16, "relu", 5, 3), (32, "tanh", 8, 10), (16, "sigm", 3, 10), (48, "leaky", 16, 10), (64, "leaky", 1, 10),
               (16, "leaky", 65, 2)]
+# ... and the cases named by the regime of the weight gradients' slice plan (slice_plan below) that they reach, which the seven above do not
+# (one point per slice of dK1, at most 5 of dK2, one 16-channel group per slice of dP1: no fold, no ragged slice):
+#   (144, tanh, 129, 10)  dP1: 291 tiles (the last one ragged), 5 slices of 2 groups, the last of 1 group; dK2: 15 slices of 9 points, the last
+#                         of 3, 36 stages (one fold), M = 144 leaves a ragged 64-row tile; dK1: 65 slices of 2 points, the last of 1, 72 stages
+#   (80, relu, 300, 10)   dP1: 3 slices of 2 groups, the last of 1; dK2: 16 slices of 19 points, the last of 15; dK1: 100 slices of 3 points
+#   (48, leaky, 500, 3)   dP1: ONE slice of 3 groups, 75 stages (two folds); dK2: 16 slices of 32 points, the last of 20, 128 stages (a fold on
+#                         the last stage); dK1: 125 slices of 4 points
+#   (16, sigm, 129, 2)    the fourth activation past B = 128, the fewest classes; dP1: one group; dK2 and dK1 as the first
+REGIME_CASES = [(144, "tanh", 129, 10), (80, "relu", 300, 10), (48, "leaky", 500, 3), (16, "sigm", 129, 2)]
+GRAD_CASES += REGIME_CASES
+
+# ------------------------------------------------------------------ the slice plan of the three conv GEMMs of the weight gradients
+# Restated from the comments of csrc/rbnn_conv_train.hip.  Every contraction is split across blocks and K is staged STAGE_K at a time; inside
+# a slice the running accumulator is folded into a second one every FOLD_STAGES stages.
+#   dK2: K = (point, 64 positions), split over the batch: never more than min(B, MAX_SPLITS2) slices
+#   dK1: K = (point, 576 positions), split over the batch: never more than min(B, MAX_SPLITS1) slices
+#   dP1: K = (conv2 channel, 25 taps), M = (point, 144 pooled positions) in tiles of TILE_M rows, split over groups of GROUP conv2 channels
+#        (GROUP_K = 400 products): as many slices as bring the grid to DP1_BLOCKS blocks, at most one per group and at least one
+MAX_SPLITS2, MAX_SPLITS1, DP1_BLOCKS = 16, 128, 2048
+TILE_M, GROUP, GROUP_K, STAGE_K, FOLD_STAGES = 64, 16, 400, 16, 32
+PP1, C1, N2, N1 = 144, 32, 801, 26                # pooled conv1 positions, conv1 channels, columns of a dK2 / dK1 partial (the taps | the bias)
+POINT_K = {"dK2": 64, "dK1": 576}                 # products one point adds to the contraction
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def slice_plan(B, Hc):
+    """{"dP1": (per, n), "dK2": (per, n), "dK1": (per, n)}: n slices of `per` units each (the last one: what remains) — a unit is one point
+    for dK2 and dK1 and one group of 16 conv2 channels for dP1."""
+    plan = {}
+    for name, cap in (("dK2", MAX_SPLITS2), ("dK1", MAX_SPLITS1)):
+        per = _cdiv(B, cap)
+        plan[name] = (per, _cdiv(B, per))
+    tiles, groups = _cdiv(B * PP1, TILE_M), Hc // GROUP
+    want = min(max(DP1_BLOCKS // tiles, 1), groups)
+    per = _cdiv(groups, want)
+    plan["dP1"] = (per, _cdiv(groups, per))
+    return plan
+
+
+def plan_units(B, Hc):
+    """The units each GEMM's slices share out: B points for dK2 and dK1, Hc / 16 groups for dP1."""
+    return {"dP1": Hc // GROUP, "dK2": B, "dK1": B}
+
+
+def plan_stages(B, Hc):
+    """Stages of a full slice per GEMM (the fold fires after every FOLD_STAGES of them)."""
+    p = slice_plan(B, Hc)
+    return {"dP1": p["dP1"][0] * GROUP_K // STAGE_K, "dK2": p["dK2"][0] * POINT_K["dK2"] // STAGE_K, "dK1": p["dK1"][0] * POINT_K["dK1"] // STAGE_K}
+
+
+def plan_floats(B, Hc):
+    """Floats of partP, part2 and part1 that a step on B points writes: slices x M x N of each GEMM."""
+    p = slice_plan(B, Hc)
+    return {"partP": p["dP1"][1] * B * PP1 * C1, "part2": p["dK2"][1] * Hc * N2, "part1": p["dK1"][1] * C1 * N1}
 
 
 def sequential(act, Hc, Cn, dtype=torch.float64):

@@ -127,8 +127,10 @@ def accuracy_forward(loc, raw, act, x, key, t, n_samples=ACC_SAMPLES):
 
 
 # ------------------------------------------------------------------ the gradient cases
-# (Hc, act, B, C): a one-tile and a three-tile Hc, B = 1, an odd B and a B past a 64-point boundary, 3 and 10 classes, the four activations
-GRAD_CASES = [(16, "leaky", 5, 10), (16, "relu", 65, 3), (48, "tanh", 1, 10), (48, "sigm", 65, 3), (48, "leaky", 5, 10)]
+# (Hc, act, B, C): a one-tile and a three-tile Hc, B = 1, an odd B and a B past a 64-point boundary, 3 and 10 classes, the four activations;
+# and conv_restate.REGIME_CASES[0], whose slice plan (conv_restate.slice_plan) has several units per slice, ragged last slices and a fold in
+# each of the three GEMMs of the weight gradients, through the SVI entry points
+GRAD_CASES = [(16, "leaky", 5, 10), (16, "relu", 65, 3), (48, "tanh", 1, 10), (48, "sigm", 65, 3), (48, "leaky", 5, 10), CR.REGIME_CASES[0]]
 GRAD_KEY, GRAD_DRAW = 0x0123456789ABCDEF, 5
 _CASES = {}
 

@@ -111,6 +111,73 @@ def test_restatement_holds_against_itself_and_the_case_stays_inside_its_caps(Hc,
     assert worst <= 1.0 and e <= 1.0 and abs(r32["loss"] - ref["loss"]) <= 1e-5 * abs(ref["loss"])
 
 
+def _regime(B, Hc, name):
+    """(several units per slice, a last slice shorter than the others, one slice) of one GEMM's plan."""
+    per, n = CR.slice_plan(B, Hc)[name]
+    units = CR.plan_units(B, Hc)[name]
+    assert n >= 1 and (n - 1) * per < units <= n * per, (B, Hc, name, per, n)       # the slices share out every unit, none is empty
+    return per > 1, units % per != 0, n == 1
+
+
+SHIPPED_SHAPES = [(128, 512), (100, 512), (100, 1024), (5000, 512), (5000, 1024)]   # (B, Hc) of the conv workloads: never run by a test
+
+
+def test_slice_plan_regimes_are_reached_and_the_buffers_cover_the_plan():
+    """1. The regime cases reach what conv_restate claims of them: the plans themselves, and for each of the three GEMMs a slice of several
+    units, a ragged last slice and a slice of at least 32 stages (the fold) somewhere; for dP1 the one-slice plan too.
+    2. The plan of every shipped shape lies in a regime some gradient case covers.  A regime is (several units per slice, one slice); a case
+    with a ragged last slice covers the plan without one as well (the same walk, the clamp at K idle), never the other way round.
+    3. rbnn_conv_train_sizes covers the plan of EVERY batch b <= B (the trainers reuse buffers sized for B at smaller batches, where dP1 takes
+    more slices), for B in 1..600, 1000, 5000, 65536 and six Hc: a running maximum over b makes the check exhaustive, not a spread."""
+    want = {(144, "tanh", 129, 10): {"dP1": (2, 5), "dK2": (9, 15), "dK1": (2, 65)}, (80, "relu", 300, 10): {"dP1": (2, 3), "dK2": (19, 16), "dK1": (3, 100)},
+            (48, "leaky", 500, 3): {"dP1": (3, 1), "dK2": (32, 16), "dK1": (4, 125)}, (16, "sigm", 129, 2): {"dP1": (1, 1), "dK2": (9, 15), "dK1": (2, 65)}}
+    assert list(want) == CR.REGIME_CASES and all(c in CR.GRAD_CASES for c in CR.REGIME_CASES)
+    for (Hc, act, B, Cn), plan in want.items():
+        assert CR.slice_plan(B, Hc) == plan, (Hc, B, CR.slice_plan(B, Hc))
+    assert CR.plan_stages(129, 144) == {"dP1": 50, "dK2": 36, "dK1": 72} and CR.plan_stages(500, 48) == {"dP1": 75, "dK2": 128, "dK1": 144}
+    assert -(-129 * CR.PP1 // CR.TILE_M) == 291 and (129 * CR.PP1) % CR.TILE_M and 144 % CR.TILE_M                   # ragged M tiles of dP1 and of dK2
+    assert CR.plan_floats(129, 144) == {"partP": 5 * 129 * 144 * 32, "part2": 15 * 144 * 801, "part1": 65 * 32 * 26}
+    for name in ("dP1", "dK2", "dK1"):
+        regs = [_regime(B, Hc, name) for Hc, _, B, _ in CR.REGIME_CASES]
+        assert any(r[0] for r in regs), f"{name}: no case with several units per slice"
+        assert any(r[0] and r[1] for r in regs), f"{name}: no case with a ragged last slice"
+        assert any(CR.plan_stages(B, Hc)[name] >= CR.FOLD_STAGES for Hc, _, B, _ in CR.REGIME_CASES), f"{name}: no case in which the fold fires"
+    assert any(_regime(B, Hc, "dP1")[2] and _regime(B, Hc, "dP1")[0] for Hc, _, B, _ in CR.REGIME_CASES), "dP1: no one-slice plan of several groups"
+    assert any(CR.plan_stages(B, Hc)["dP1"] >= 2 * CR.FOLD_STAGES for Hc, _, B, _ in CR.REGIME_CASES)                  # two folds in one slice
+    assert any(CR.plan_stages(B, Hc)["dK2"] % CR.FOLD_STAGES == 0 for Hc, _, B, _ in CR.REGIME_CASES)                  # a fold on the last stage
+    # 2. the shipped shapes
+    for name in ("dP1", "dK2", "dK1"):
+        covered = {(r[0], r[2]) for r in (_regime(B, Hc, name) for Hc, _, B, _ in CR.GRAD_CASES)}
+        ragged = {(r[0], r[2]) for r in (_regime(B, Hc, name) for Hc, _, B, _ in CR.GRAD_CASES) if r[1]}
+        for B, Hc in SHIPPED_SHAPES:
+            several, rag, one = _regime(B, Hc, name)
+            assert (several, one) in (ragged if rag else covered), f"{name} at B={B} Hc={Hc}: plan {CR.slice_plan(B, Hc)[name]} in a regime no case covers"
+            if name == "dP1":
+                assert one or several, (B, Hc)
+    assert CR.slice_plan(128, 512)["dP1"] == (5, 7) and CR.slice_plan(100, 512)["dP1"] == (4, 8) and CR.slice_plan(5000, 512)["dP1"] == (32, 1)
+    assert CR.slice_plan(5000, 512)["dK2"] == (313, 16) and CR.slice_plan(5000, 512)["dK1"] == (40, 125) and CR.slice_plan(128, 512)["dK2"] == (8, 16)
+    # 3. the buffers
+    lib, out = _hip.load(), _hip.ConvTrainBytes()
+    Bs = list(range(1, 601)) + [1000, 5000, 65536]
+    n_checked, tightest = 0, float("inf")
+    for Hc in (16, 48, 80, 144, 512, 1024):
+        need, b_at, run, b = {}, {"partP": 0, "part2": 0, "part1": 0}, {"partP": 0, "part2": 0, "part1": 0}, 0
+        for B in Bs:
+            while b < B:                                                   # the largest need of any batch up to B, and the batch that has it
+                b += 1
+                for k, v in CR.plan_floats(b, Hc).items():
+                    if 4 * v > run[k]:
+                        run[k], b_at[k] = 4 * v, b
+            need[B] = dict(run)
+            assert lib.rbnn_conv_train_sizes(C.byref(_net(Hc, 10)), B, C.byref(out)) == OK
+            for k in ("partP", "part2", "part1"):
+                assert getattr(out, k) >= need[B][k], f"{k} sized for B={B} at Hc={Hc} holds {getattr(out, k)} bytes; a batch of {b_at[k]} writes {need[B][k]}"
+                tightest = min(tightest, getattr(out, k) / need[B][k])
+                n_checked += 1
+    print(f"[conv-restate slice plan] {len(CR.REGIME_CASES)} regime cases reach their plans; {len(SHIPPED_SHAPES)} shipped shapes in covered regimes; "
+          f"{n_checked} buffer sizes cover every batch up to theirs (tightest: {tightest:.3f} x the need)")
+
+
 def test_trajectory_case_meets_no_pooling_tie_and_has_a_small_spread():
     """The condition of the end-to-end GPU test, on the fp64 run: no batch point of any step within TIE of a pooling tie (tanh: no kink).  The
     spread then is rounding alone: every one of the four summation orders stays below 2e-5, a third of the least spread (7e-5 .. 3e-4) of runs

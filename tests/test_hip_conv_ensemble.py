@@ -5,7 +5,8 @@ other and from data rows nobody names, two runs against each other, Ensemble_NN.
 device->host sync inside a step, and the guards.  Every check prints one line with its worst figure.
 
 Mutations these tests are written to catch: a member reading another member's weights or batch (any per-member base offset), rows not clamped
-or taken from member 0, slice counts that depend on M (another summation order), dZ scaled by 1 / (M B), stats of the wrong member."""
+or taken from member 0, slice counts that depend on M (another summation order), dZ scaled by 1 / (M B), stats of the wrong member, a
+per-member offset of the partial sums formed from the wrong slice count (visible only where a GEMM has several slices of several units)."""
 import os
 
 import pytest
@@ -72,11 +73,15 @@ def _rows(M, B, n, steps, seed):
     return out
 
 
-@pytest.mark.parametrize("Hc,act,B", [(16, "leaky", 5), (16, "leaky", 65), (16, "tanh", 5), (48, "leaky", 65)])
+@pytest.mark.parametrize("Hc,act,B", [(16, "leaky", 5), (16, "leaky", 65), (16, "tanh", 5), (48, "leaky", 65), (144, "tanh", 129)])
 def test_member_equals_the_net_trained_alone_bit_for_bit(Hc, act, B):
     """Four steps of M = 3 members on their own rows of 40 resident points; then P, m, v, grad and stats of member k, as int32, are those of a
     ConvNnTrainer stepped alone on data[rows[k]].  B = 65 crosses the 64-row tile of the GEMMs and gives dK1 and dK2 more than one slice;
-    Hc = 48 leaves a ragged 64-channel tile and gives dP1 three slices."""
+    Hc = 48 leaves a ragged 64-channel tile and gives dP1 three slices.  (144, tanh, 129) is conv_restate.REGIME_CASES[0]'s plan: the
+    per-member offsets of the partial sums (sP nP, s2 Hc N2, s1 C1 N1) carry 5 slices of 2 groups (the last of 1), 15 slices of 9 points (the
+    last of 3) and 65 slices of 2 points (the last of 1), with a fold inside the slices of dP1, dK2 and dK1."""
+    if (Hc, B) == (144, 129):
+        assert CR.slice_plan(B, Hc) == {"dP1": (2, 5), "dK2": (9, 15), "dK1": (2, 65)}
     Cn, M, steps = 10, 3, 4
     x, lab = _data(Cn)
     params = [CR.fresh_params(act, Hc, Cn, 50 + k) for k in range(M)]

@@ -378,11 +378,12 @@ def _canaried_step(Hc, act, B, Cn, canaries):
     return res, tails
 
 
-@pytest.mark.parametrize("Hc,act,B,Cn", [V.GRAD_CASES[0], V.GRAD_CASES[1]])
+@pytest.mark.parametrize("Hc,act,B,Cn", [V.GRAD_CASES[0], V.GRAD_CASES[1], V.GRAD_CASES[5]])
 def test_nothing_behind_the_bounds_is_read_or_written(Hc, act, B, Cn):
-    """B = 5 and B = 65, buffers sized for exactly B points.  Read: the results are bit-identical with and without NaN behind every buffer (NaN
-    is data: one that leaked into a sum would stay there).  Written: every canary element is still a canary after the step."""
-    assert B in (5, 65)
+    """B = 5, B = 65 and B = 129 (Hc = 144: partP holds 5 slices of 129 points, the last slice of dP1, dK2 and dK1 is ragged), buffers sized for
+    exactly B points.  Read: the results are bit-identical with and without NaN behind every buffer (NaN is data: one that leaked into a sum
+    would stay there).  Written: every canary element is still a canary after the step."""
+    assert B in (5, 65, 129)
     clean, _ = _canaried_step(Hc, act, B, Cn, False)
     dirty, tails = _canaried_step(Hc, act, B, Cn, True)
     for name in clean:

@@ -1,11 +1,22 @@
 """GPU tests (-m gpu) of deterministic conv training (model_nn.py:93-106, 175-219; csrc/rbnn_conv_train.hip, robustbnns_amd/conv_train.py): the
 weight gradients of all six tensors, per-point CE, step loss and correct count against fp64 autograd at the same parameters, the Adam kernel
-against torch.optim.Adam, the statistics kernel alone past one pass of its loop, two runs against each other, what must not be read (NaN behind every bound), NN.train_conv end to end against the
-fp64 restatement (tests/conv_restate.py), the files, no device->host sync inside a step, and the guards.  Every check prints one line with
-its worst figure in units of its bar.
+against torch.optim.Adam, the statistics kernel alone past one pass of its loop, two runs against each other, what must not be read (NaN behind
+every bound) or written (canaries behind every buffer of a trainer sized for exactly B), the slice plan that ran against the restated one
+(conv_restate.slice_plan), buffers sized for a large batch used by a small one, NN.train_conv end to end against the fp64 restatement
+(tests/conv_restate.py), the files, no device->host sync inside a step, and the guards.  Every check prints one line with its worst figure in
+units of its bar.
 
 Mutations these tests are written to catch: no `/ B` in dZ, a missing bias gradient, pool-2 routing that drops one of the overlapping windows,
-act' taken at the wrong element for sigm / tanh, dK2 in (tap, ci) instead of (ci, tap) order -> the gradient test."""
+act' taken at the wrong element for sigm / tanh, dK2 in (tap, ci) instead of (ci, tap) order -> the gradient test.
+With conv_restate.REGIME_CASES (slices of several groups / points, ragged last slices, the one-slice plan, more than 32 stages per slice):
+k_end not clamped to K in dP1's last slice (the K2w gather runs into model.3.bias and the head's weights, dO2 into the next point's) -> the
+gradient test (model.0.*) and, behind a canaried dO2, the bounds tests; kc formed from the slice count instead of the per-slice count (slice
+s starts at s kc, so any kc with slices x kc >= K still shares K out: only the one-slice plan of several groups, B = 500, leaves channels
+out) -> the gradient test at (48, leaky, 500, 3); the point index of dK1 / dK2 taken relative to the slice (every slice contracts the
+first points again), or dK1's staying at its slice's first point (right wherever a slice is one point, B <= 128) -> the gradient test
+(model.0.*, model.3.*); a fold that zeroes acc without adding it to tot (the first 512 products of a slice lost; dK1 folds at every B, dP1
+and dK2 only in these cases) -> the gradient test; a slice launched and not stored, or a plan other than the restated one -> the plan test; partP sized for the
+sizing batch's plan alone -> the large-small test and the host tier's sweep."""
 import ctypes as C
 import os
 
@@ -191,14 +202,124 @@ def _poisoned(Hc, act, B, Cn, poison):
     return res
 
 
-@pytest.mark.parametrize("Hc,act,B,Cn", [CR.GRAD_CASES[1], CR.GRAD_CASES[2], CR.GRAD_CASES[5]])
+@pytest.mark.parametrize("Hc,act,B,Cn", [CR.GRAD_CASES[1], CR.GRAD_CASES[2], CR.GRAD_CASES[5], CR.REGIME_CASES[0], CR.REGIME_CASES[2]])
 def test_nothing_behind_the_bounds_is_read(Hc, act, B, Cn):
-    """NaN is data: every index stays inside its allocation, and a NaN that leaked into a sum would stay there."""
+    """NaN is data: every index stays inside its allocation, and a NaN that leaked into a sum would stay there.  The two regime cases: slices of
+    several groups / points with a ragged last one (dP1's gather of K2w stops at its K; the point behind the batch is never fetched), and dP1's
+    one-slice plan."""
     clean, dirty = _poisoned(Hc, act, B, Cn, False), _poisoned(Hc, act, B, Cn, True)
     for name in clean:
         assert torch.equal(clean[name], dirty[name]), f"{name} depends on memory behind the bounds"
     print(f"[conv-train bounds Hc={Hc} {act} B={B} C={Cn}] {len(clean)} results bit-identical and finite with NaN behind [B, .] of every workspace, in rows >= {B} "
           f"and columns [784, 800) of the staged batch; excluded: nothing")
+
+
+CANARY = {torch.float32: float("nan"), torch.float64: float("nan"), torch.uint8: 255, torch.int32: 0x7FFFFFFF}
+PAD = 64                       # elements behind every buffer
+FLAT = ("P", "m", "v", "grad")
+
+
+def _padded(t):
+    """A copy of the contiguous tensor t at the front of an allocation with PAD canary elements behind it -> (view, tail)."""
+    big = torch.full((t.numel() + PAD,), CANARY[t.dtype], dtype=t.dtype, device=t.device)
+    big[:t.numel()].copy_(t.reshape(-1))
+    return big[:t.numel()].view(t.shape), big[t.numel():]
+
+
+def _canaried_step(Hc, act, B, Cn, canaries):
+    """One step of a trainer sized for exactly B points; canaries: the flat buffers, the staged batch, its labels, every workspace and stats are
+    moved to the front of allocations with PAD canary elements (NaN; 255 in the stash bytes; an impossible class in the labels) behind them.
+    -> (results' bit patterns, the tails)."""
+    from robustbnns_amd import _hip
+    c = CR.grad_case(Hc, act, B, Cn)
+    tr = _trainer(c["params"], act, Cn, B)
+    assert tr.Bmax == B
+    tails = {}
+    if canaries:
+        for name in FLAT + ("X", "labels", "stats"):
+            view, tails[name] = _padded(getattr(tr, name))
+            setattr(tr, name, view)
+        for k in list(tr.ws_t):
+            tr.ws_t[k], tails["ws_" + k] = _padded(tr.ws_t[k])
+        _hip.fill(tr.net, tr)
+        tr.ws = _hip.fill(_hip.ConvTrainWs, tr.ws_t)
+    tr.step(c["x"].to(DEV), c["lab"].to(DEV))
+    torch.cuda.synchronize()
+    res = _state(tr)
+    res["ce"], res["correct"], res["dZ"] = _bits(tr.ws_t["ce"][:B]), _bits(tr.ws_t["correct"][:B]), _bits(tr.ws_t["dZ"][:16 * B])
+    for name in FLAT + ("ce",):
+        assert bool(torch.isfinite(res[name].view(torch.float32)).all()), name
+    assert bool(torch.isfinite(tr.stats).all())
+    return res, tails
+
+
+@pytest.mark.parametrize("Hc,act,B,Cn", [CR.GRAD_CASES[1], CR.GRAD_CASES[6], CR.REGIME_CASES[0], CR.REGIME_CASES[2]])
+def test_nothing_behind_the_bounds_is_written(Hc, act, B, Cn):
+    """Buffers sized for exactly B points (B = 5, 65, 129 and 500: partP holds one, three, five and one slice).  Written: every canary element
+    behind every buffer is still a canary after the step.  Read: the results are bit-identical with and without the canaries."""
+    clean, _ = _canaried_step(Hc, act, B, Cn, False)
+    dirty, tails = _canaried_step(Hc, act, B, Cn, True)
+    for name in clean:
+        assert torch.equal(clean[name], dirty[name]), f"{name} depends on memory behind the bounds"
+    assert len(tails) == len(FLAT) + 3 + 13, sorted(tails)
+    for name, tail in tails.items():
+        intact = torch.isnan(tail).all() if tail.dtype.is_floating_point else (tail == CANARY[tail.dtype]).all()
+        assert bool(intact) and tail.numel() == PAD, f"the step wrote behind {name}"
+    print(f"[conv-train canaries Hc={Hc} {act} B={B} C={Cn}] {len(clean)} results bit-identical and finite with canaries behind {len(tails)} buffers sized for "
+          f"exactly {B} points, every canary intact; excluded: nothing")
+
+
+@pytest.mark.parametrize("Hc,act,B,Cn", [CR.GRAD_CASES[4], CR.GRAD_CASES[6]] + CR.REGIME_CASES)
+def test_the_plan_that_ran_is_the_restated_plan(Hc, act, B, Cn):
+    """part1, part2 and partP filled with NaN, then gradients(): the floats that are no longer NaN are the first slices x M x N of each buffer,
+    with conv_restate.slice_plan's slice count (NaN after them where the buffer is larger than this batch's plan).  A slice launched and not
+    written, written twice as wide, or a plan other than the restated one fails here; the gradients are finite."""
+    c = CR.grad_case(Hc, act, B, Cn)
+    tr = _trainer(c["params"], act, Cn, B)
+    for k in ("part1", "part2", "partP"):
+        tr.ws_t[k].fill_(float("nan"))
+    tr.gradients(c["x"].to(DEV), c["lab"].to(DEV))
+    torch.cuda.synchronize()
+    plan, want = CR.slice_plan(B, Hc), CR.plan_floats(B, Hc)
+    got = {k: int((~torch.isnan(tr.ws_t[k])).sum()) for k in want}
+    print(f"[conv-train plan Hc={Hc} {act} B={B} C={Cn}] plan (per, slices) {plan}; floats written / planned / allocated: "
+          + ", ".join(f"{k} {got[k]} / {want[k]} / {tr.ws_t[k].numel()}" for k in want))
+    for k in want:
+        assert got[k] == want[k] <= tr.ws_t[k].numel(), (k, got[k], want[k])
+        assert not bool(torch.isnan(tr.ws_t[k][:want[k]]).any()), f"{k}: a hole inside the planned slices"
+    assert bool(torch.isfinite(tr.grad).all())
+
+
+def test_buffers_sized_large_and_used_small_give_the_small_trainers_bits():
+    """A trainer grown to B = 129 at Hc = 144 (partP sized for that plan: 5 slices of 129 points), every workspace then filled with NaN (255 in
+    the stash bytes), stepped on the first 8 points of the case: dP1 now takes 9 slices of 8 points inside the same partP.  P, m, v, grad,
+    stats, the per-point CE and flags are bit-equal to those of a fresh trainer sized for 8."""
+    Hc, act, B, Cn = CR.REGIME_CASES[0]
+    c = CR.grad_case(Hc, act, B, Cn)
+    b = 8
+    x, lab = c["x"][:b].to(DEV), c["lab"][:b].to(DEV)
+    assert CR.slice_plan(B, Hc)["dP1"] == (2, 5) and CR.slice_plan(b, Hc)["dP1"] == (1, 9)
+    res = {}
+    for size in (B, b):
+        tr = _trainer(c["params"], act, Cn, size)
+        assert tr.Bmax == size and CR.plan_floats(b, Hc)["partP"] <= tr.ws_t["partP"].numel()
+        if size == B:
+            for v in tr.ws_t.values():
+                v.fill_({torch.float32: float("nan"), torch.uint8: 255, torch.int32: Cn}[v.dtype])
+            tr.X.fill_(float("nan"))
+            tr.labels.fill_(Cn)
+        tr.step(x, lab)
+        torch.cuda.synchronize()
+        res[size] = _state(tr)
+        res[size]["ce"], res[size]["correct"] = _bits(tr.ws_t["ce"][:b]), _bits(tr.ws_t["correct"][:b])
+        assert bool(torch.isfinite(tr.P).all()) and bool(torch.isfinite(tr.grad).all()) and bool(torch.isfinite(tr.stats).all())
+    n_diff = 0
+    for name in res[b]:
+        d = int((res[B][name] != res[b][name]).sum())
+        n_diff += d
+        assert d == 0, f"{name}: {d} elements differ between the trainer sized for {B} and the one sized for {b}"
+    print(f"[conv-train large-small Hc={Hc} {act}] a step on {b} points in buffers sized for {B} (dP1: 9 slices where the sizing batch has 5): {n_diff} "
+          f"differing elements over {len(res[b])} results (bar 0); excluded: nothing")
 
 
 def _nn():
