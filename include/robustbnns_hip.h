@@ -990,6 +990,97 @@ int rbnn_conv_ens_adam_step(const rbnn_conv_ens_net *net, int64_t step, double l
 /* One block per member: stats [M, 3] = rbnn_conv_train_finalize's three figures of every member. */
 int rbnn_conv_ens_finalize(const rbnn_conv_ens_net *net, const rbnn_conv_ens_ws *ws, int32_t n_points, double *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * K SVI guides of ONE conv net shape (1x28x28) trained in LOCKSTEP (csrc/rbnn_conv_train.hip; the Adam + KL step: csrc/rbnn_svi.hip; additive, ABI 10): the step of
+ * rbnn_conv_svi_train_net above for every guide in one set of launches whose count does not depend on K, the guide a grid dimension of each.
+ * Issued in this order on one stream:  conv_svi_guides_draw -> conv_svi_guides_gradient -> conv_svi_guides_adam_step -> [conv_svi_guides_accuracy]
+ * -> conv_svi_guides_finalize: 1 + (1 + 4 + 7) + 1 + [1 + 3 + 1] + 1 = 15 launches without the accuracy forward, 20 with it.  The nine flat
+ * buffers are TENSOR-MAJOR as rbnn_conv_ens_net's: six blocks [K, size of tensor t] in state_dict order, block t at K times the single
+ * guide's offset — the stacks of rbnn_conv_posterior, so the exact conv forward addresses guide k as sample k.  All guides of a step share its
+ * point count B: guide k's batch is rows[k, 0..B) of the resident data (indices clamped into [0, n_rows)), and the slice plans of the three
+ * conv GEMMs are the single guide's for B.  Guide k computes what the rbnn_conv_svi_train_* entry points, ConvStackedPosterior's redraw under
+ * keys[k] ^ key_xor, rbnn_conv_forward, rbnn_reduce_samples and rbnn_svi_train_finalize compute for that guide alone on those rows, bit for bit.
+ * active (device int32 [K]): a guide with active[k] == 0 has finished its epochs; the kernels that write its state (draw, Adam + KL, the
+ * accuracy draw and sum, finalize) return at once for it, so its loc, raw, sigma, moments, kl_part, stats, epoch_log rows, W and accuracy
+ * weight sets are never written again (its batch is still staged and the workspaces, packed by the call's B, are written: they hold nothing
+ * that outlives a step).
+ * No atomics, no sum across guides, no device->host synchronisation; a guide's blocks and tiles do not depend on K.
+ * Every entry point checks, before any launch: net NULL, then the descriptor (geometry / activation: RBNN_ERR_UNSUPPORTED; hidden, n_classes,
+ * n_guides outside [1, 65535 / RBNN_SVI_MULTI_ACC_SAMPLES]: RBNN_ERR_SHAPE), then NULL pointers, then shapes (n_points, K n_points <= 2^22,
+ * ldx, n_rows, part_stride, step), then 16-byte alignment.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_conv_svi_guides_net {
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_channels, in_width; /* 1, 28 (anything else: RBNN_ERR_UNSUPPORTED)                                  */
+    int32_t hidden;                /* Hc = conv2 output channels, a multiple of 16 in [16, 4096]                   */
+    int32_t n_classes;             /* C in [1, 16]                                                                 */
+    int32_t n_guides;              /* K in [1, 6553], K B <= 2^22                                                  */
+    float *loc, *raw, *sigma;      /* [K n_params] tensor-major: mean, raw scale, sigma = softplus(raw); 16-byte aligned */
+    float *m_loc, *v_loc, *m_raw, *v_raw;      /* [K n_params] Adam moments (zero before the first step)           */
+    float *W;                      /* [K n_params] the drawn weight samples (16-byte aligned)                      */
+    float *grad;                   /* [K n_params] dCE/dW of the step                                              */
+    float *kl_part;                /* [K, part_stride] KL partial sums of the update                               */
+    double *stats;                 /* [K, 3] step loss, running sum of the epoch's losses, running correct predictions */
+    const uint64_t *keys;          /* [K] on the device: guide k's key                                             */
+    int64_t part_stride;           /* >= n_partials of rbnn_conv_svi_guides_sizes                                   */
+} rbnn_conv_svi_guides_net;
+
+typedef struct rbnn_conv_svi_guides_ws {  /* caller-owned, for up to B points per guide; every buffer 16-byte aligned */
+    float   *Xs;                   /* the buffers of rbnn_conv_ens_ws, the guide in the member's place              */
+    int32_t *labels;
+    float   *logits;
+    float   *P1;
+    uint8_t *st1;
+    float   *Q2;
+    uint8_t *st2;
+    float   *dZ;                   /* [K, B, 16] softmax - e_y (the SUMMED cross-entropy)                          */
+    float   *ce;                   /* [K, B]                                                                       */
+    int32_t *correct;              /* [K, B] written by the head, not read by the step                             */
+    float   *dO2;
+    float   *dO1;
+    float   *part2;
+    float   *part1;
+    float   *partP;
+    float   *acc_W;                /* [K S n_params] the accuracy forward's weight sets, S = RBNN_SVI_MULTI_ACC_SAMPLES: tensor-major over K S sets, set k S + s */
+    float   *acc_P;                /* [K S, B, 16] their softmax probabilities                                     */
+    float   *acc_P1;               /* [K S, B, .] the buffers of rbnn_conv_workspace for K S samples of B points   */
+    uint8_t *acc_st1;
+    float   *acc_Q2;
+    uint8_t *acc_st2;
+    float   *Psum;                 /* [K, B, 16] sum over the S samples of the probabilities, s = 0, 1, ... in that order */
+} rbnn_conv_svi_guides_ws;
+
+typedef struct rbnn_conv_svi_guides_bytes {  /* of ONE guide: n_params, n_partials; the bytes of every rbnn_conv_svi_guides_ws buffer for B points per guide */
+    int64_t n_params, n_partials;
+    size_t Xs, labels, logits, P1, st1, Q2, st2, dZ, ce, correct, dO2, dO1, part2, part1, partP, acc_W, acc_P, acc_P1, acc_st1, acc_Q2, acc_st2, Psum;
+} rbnn_conv_svi_guides_bytes;
+
+/* [host] n_params and n_partials of one guide (rbnn_conv_svi_train_sizes'), and the workspace sizes: K times the single guide's, Xs and
+ * labels beside them as in rbnn_conv_ens_sizes, and the accuracy forward's (K S samples of B points: the large term).  Linear in K. */
+int rbnn_conv_svi_guides_sizes(const rbnn_conv_svi_guides_net *net, int32_t n_points, rbnn_conv_svi_guides_bytes *out);
+/* W[k] = loc[k] + sigma[k] * eps(keys[k], draw_id) for the six tensors of every active guide: exactly what rbnn_conv_svi_train_draw writes
+ * for (keys[k], draw_id).  One launch. */
+int rbnn_conv_svi_guides_draw(const rbnn_conv_svi_guides_net *net, const int32_t *active, uint32_t draw_id, void *stream);
+/* rbnn_conv_ens_stage of rows [K, n_points], the exact forward with the guide as sample and the head of the SUMMED cross-entropy (dZ =
+ * softmax - e_y), the seven weight-gradient launches of rbnn_conv_ens_weight_grads reading W and writing grad: 1 + 4 + 7 launches. */
+int rbnn_conv_svi_guides_gradient(const rbnn_conv_svi_guides_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *labels,
+                                 const int32_t *rows, int32_t n_points, const rbnn_conv_svi_guides_ws *ws, void *stream);
+/* rbnn_conv_svi_adam_step on every active guide, each with its own key and learning rate lr[k] (device, double [K]): step_size[k] =
+ * (float)(lr[k] / (1 - beta1^step)), an IEEE double division of the host's 1 - beta1^step, so bit for bit the single guide's.  One launch. */
+int rbnn_conv_svi_guides_adam_step(const rbnn_conv_svi_guides_net *net, const int32_t *active, uint32_t draw_id, int64_t step,
+                                  const double *lr, double beta1, double beta2, double adam_eps, void *stream);
+/* The accuracy forward of every active guide on the batch rbnn_conv_svi_guides_gradient staged: S weight sets per guide from the live loc /
+ * sigma with rbnn_svi_draw_flat's generator at (keys[k] ^ key_xor, draw_id, sample s) into acc_W, the exact conv forward of the K S nets
+ * (set k S + s reads guide k's n_points rows), Psum[k, b, :] = sum_s softmax(z_s).  1 + 3 + 1 launches. */
+int rbnn_conv_svi_guides_accuracy(const rbnn_conv_svi_guides_net *net, const int32_t *active, int32_t n_points, uint64_t key_xor,
+                                 uint32_t draw_id, const rbnn_conv_svi_guides_ws *ws, void *stream);
+/* One block per active guide, fixed order, fp64: rbnn_svi_train_finalize's sums over the guide's n_points points of ws->ce and (with_accuracy
+ * != 0) ws->Psum against ws->labels into stats[k].  epoch_slot (device int32 [K], nullable): a guide with epoch_slot[k] in [0, log_rows) ends
+ * an epoch with this step: epoch_log[k, slot] = (sum of the epoch's step losses, correct predictions) and both running sums restart at 0. */
+int rbnn_conv_svi_guides_finalize(const rbnn_conv_svi_guides_net *net, const int32_t *active, const rbnn_conv_svi_guides_ws *ws,
+                                 int32_t with_accuracy, int32_t n_points, const int32_t *epoch_slot, double *epoch_log, int32_t log_rows,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ STRUCTS = {
     "ConvTrainNet": "rbnn_conv_train_net", "ConvTrainWs": "rbnn_conv_train_ws", "ConvTrainBytes": "rbnn_conv_train_bytes",
     "ConvSviTrainNet": "rbnn_conv_svi_train_net",
     "ConvEnsNet": "rbnn_conv_ens_net", "ConvEnsWs": "rbnn_conv_ens_ws", "ConvEnsBytes": "rbnn_conv_ens_bytes",
+    "ConvSviLockstepNet": "rbnn_conv_svi_guides_net", "ConvSviLockstepWs": "rbnn_conv_svi_guides_ws", "ConvSviLockstepBytes": "rbnn_conv_svi_guides_bytes",
     "HmcChain": "rbnn_hmc_chain", "HmcLockstep": "rbnn_hmc_lockstep", "SviLockstep": "rbnn_svi_multi", "SviLockstepAcc": "rbnn_svi_multi_acc",
 }
 HEADER = _header.read(HEADER_PATH)
@@ -52,6 +53,7 @@ _keys = lambda cls: tuple(name for name, _ in cls._fields_)
 WS_KEYS, CONV_WS_KEYS, SPLIT_WS_KEYS, TRIPLE_WS_KEYS = _keys(Workspace), _keys(ConvWorkspace), _keys(SplitWorkspace), _keys(TripleWorkspace)
 SVI_TRAIN_WS_KEYS, NN_TRAIN_WS_KEYS, CONV_TRAIN_WS_KEYS = _keys(SviTrainWs), _keys(NnTrainWs), _keys(ConvTrainWs)
 CONV_ENS_WS_KEYS = _keys(ConvEnsWs)
+CONV_SVI_LOCKSTEP_WS_KEYS = _keys(ConvSviLockstepWs)
 SVI_LOCKSTEP_ACC_KEYS = _keys(SviLockstepAcc)
 
 _lib = None

@@ -31,7 +31,9 @@ namespace {
 // the FMA loop (0.52 -> see profiles/r03a/conv_small_kernels.txt).  Each output is still produced by one thread in the same order.
 // (3x32x32: 196 positions fill a 256-thread block well enough, and the two-halves form measured slower there: 2.45 -> 2.66 ms at c5)
 // The kernel's text is rbnn_conv1_pool_kernel.inc, included once per form: conv1_pool_kernel (X [N, ldx], every sample reads point n's row), and
-// conv1_pool_packed_kernel for the lockstep conv trainer (X [S * N, ldx], the block reads its own row s * N + n: every member has its own batch).
+// conv1_pool_packed_kernel for the lockstep conv trainer (X [S * N, ldx], the block reads its own row s * N + n: every member has its own batch),
+// and conv1_pool_grouped_kernel for the accuracy forward of conv SVI guides in lockstep (the samples of a group of RBNN_SVI_MULTI_ACC_SAMPLES
+// share their guide's batch: sample s reads row (s / that many) * N + n).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define RBNN_CONV1_KERNEL conv1_pool_kernel
 #define RBNN_CONV1_PACKED 0
@@ -40,6 +42,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #undef RBNN_CONV1_PACKED
 #define RBNN_CONV1_KERNEL conv1_pool_packed_kernel
 #define RBNN_CONV1_PACKED 1
+#include "rbnn_conv1_pool_kernel.inc"
+#undef RBNN_CONV1_KERNEL
+#undef RBNN_CONV1_PACKED
+#define RBNN_CONV1_KERNEL conv1_pool_grouped_kernel
+#define RBNN_CONV1_PACKED 2
 #include "rbnn_conv1_pool_kernel.inc"
 #undef RBNN_CONV1_KERNEL
 #undef RBNN_CONV1_PACKED
@@ -404,9 +411,11 @@ __global__ void __launch_bounds__(512, 2) conv2_pool_split_kernel(const ConvArgs
     }
 }
 
-template <int ACT, class G, bool PACKED = false>
+// ROWS: which row of X a (sample, point) block reads — 0: n, 1: s N + n (packed), 2: (s / RBNN_SVI_MULTI_ACC_SAMPLES) N + n (grouped)
+template <int ACT, class G, int ROWS = 0>
 int launch_conv_forward(const ConvArgs& a, hipStream_t st) {
-    if constexpr (PACKED) hipLaunchKernelGGL((conv1_pool_packed_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
+    if constexpr (ROWS == 2) hipLaunchKernelGGL((conv1_pool_grouped_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
+    else if constexpr (ROWS == 1) hipLaunchKernelGGL((conv1_pool_packed_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
     else hipLaunchKernelGGL((conv1_pool_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
     int rc = launch_status();
     if (rc) return rc;
@@ -1131,7 +1140,11 @@ int launch_conv1_pool(int act, int in_channels, const ConvArgs& a, hipStream_t s
 }
 int launch_conv_forward_packed(int act, ConvArgs a, hipStream_t st) {
     a.NP2 = GeoMnist::NP2;
-    return for_activation(act, [&](auto actc) { return launch_conv_forward<decltype(actc)::value, GeoMnist, true>(a, st); });
+    return for_activation(act, [&](auto actc) { return launch_conv_forward<decltype(actc)::value, GeoMnist, 1>(a, st); });
+}
+int launch_conv_forward_grouped(int act, ConvArgs a, hipStream_t st) {
+    a.NP2 = GeoMnist::NP2;
+    return for_activation(act, [&](auto actc) { return launch_conv_forward<decltype(actc)::value, GeoMnist, 2>(a, st); });
 }
 int launch_conv_fc(const ConvArgs& a, hipStream_t st) {
     const int items = ((a.N + 15) / 16) * a.S;

@@ -1,6 +1,8 @@
 // rbnn_conv1_pool_kernel.inc — the text of conv1_pool_kernel (described in rbnn_conv.hip, which includes it once per form).  RBNN_CONV1_KERNEL
 // names the kernel; RBNN_CONV1_PACKED: X is [S * N, ldx] and the block reads its own row s * N + n (every sample has its own batch: the lockstep
-// conv trainer), not row n.  Two kernels from one text, as rbnn_train_kernels.inc: the kernel of the attack path keeps its name and its code.
+// conv trainer), not row n; RBNN_CONV1_PACKED == 2: X is [S / RBNN_SVI_MULTI_ACC_SAMPLES * N, ldx] and the block reads row (s / RBNN_SVI_MULTI_ACC_SAMPLES) * N + n
+// (the samples come in groups of that many, every group has its own batch: the accuracy forward of the conv SVI guides in lockstep).  Three
+// kernels from one text, as rbnn_train_kernels.inc: the kernel of the attack path keeps its name and its code.
 
 template <int ACT, class G>
 __global__ void __launch_bounds__(conv1_threads<G>(), 1) RBNN_CONV1_KERNEL(const ConvArgs a) {
@@ -20,7 +22,9 @@ __global__ void __launch_bounds__(conv1_threads<G>(), 1) RBNN_CONV1_KERNEL(const
         const int c = e / G::K1, k = e - c * G::K1;
         wsh[((c >> 1) * G::CIN + k / 25) * WROW + 2 * (k % 25) + (c & 1)] = a.K1w[(long long)sw * C1 * G::K1 + e];
     }
-#if RBNN_CONV1_PACKED
+#if RBNN_CONV1_PACKED == 2
+    for (int e = tid; e < G::DIN; e += NTH) xsh[e] = a.X[((long long)(s / RBNN_SVI_MULTI_ACC_SAMPLES) * a.N + n) * a.ldx + e];
+#elif RBNN_CONV1_PACKED
     for (int e = tid; e < G::DIN; e += NTH) xsh[e] = a.X[sn * a.ldx + e];
 #else
     for (int e = tid; e < G::DIN; e += NTH) xsh[e] = a.X[(long long)n * a.ldx + e];

@@ -117,6 +117,9 @@ template <class G> constexpr int conv1_bwd_ts() { return G::O1 % 8 == 0 ? G::O1 
 RBNN_HIDDEN int launch_conv1_pool(int act, int in_channels, const ConvArgs& a, hipStream_t st);
 // the exact 1x28x28 forward (3 launches) on a PACKED batch: X [S * N, ldx], sample s reads rows s N .. s N + N - 1 (rbnn_conv_train.hip's members)
 RBNN_HIDDEN int launch_conv_forward_packed(int act, ConvArgs a, hipStream_t st);
+// the same on a GROUPED batch: X [S / RBNN_SVI_MULTI_ACC_SAMPLES * N, ldx], sample s reads the N rows of its group s / RBNN_SVI_MULTI_ACC_SAMPLES
+// (rbnn_conv_train.hip's accuracy forward of the SVI guides in lockstep: the ten weight sets of a guide on the guide's batch)
+RBNN_HIDDEN int launch_conv_forward_grouped(int act, ConvArgs a, hipStream_t st);
 RBNN_HIDDEN int launch_conv_fc(const ConvArgs& a, hipStream_t st);
 RBNN_HIDDEN int launch_conv_fc_bwd(int act, const ConvBwdArgs& a, hipStream_t st);
 RBNN_HIDDEN int launch_conv1_bwd_fp32(int act, int in_channels, const ConvBwdArgs& a, hipStream_t st);

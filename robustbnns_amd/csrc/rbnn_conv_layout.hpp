@@ -1,5 +1,6 @@
 // rbnn_conv_layout.hpp — the flat parameter layout of a conv net of the 1x28x28 geometry and its shape checks, each stated once for the units
-// that train or sample one (rbnn_conv_train.hip: the deterministic, SVI and ensemble trainers; rbnn_hmc.hip: the conv chain).  Host code only.
+// that train or sample one (rbnn_conv_train.hip: the deterministic, SVI and ensemble trainers; rbnn_svi.hip: the Adam + KL step of the conv SVI
+// guides in lockstep; rbnn_hmc.hip: the conv chain).  Host code only.
 #pragma once
 #include "rbnn_conv_common.hpp"
 #include "rbnn_train_core.hpp"
@@ -40,6 +41,16 @@ inline int check_conv_dims(int activation, int in_channels, int in_width, int hi
     if (in_channels != 1 || in_width != rbnn_conv_shared::GeoMnist::IW) return RBNN_ERR_UNSUPPORTED;
     if (hidden < 16 || (hidden & 15) || hidden > CONV_MAX_HIDDEN || n_classes < 1 || n_classes > RBNN_CPAD) return RBNN_ERR_SHAPE;
     return RBNN_OK;
+}
+
+// the descriptor of K SVI guides in lockstep (rbnn_conv_train.hip; rbnn_svi.hip: their Adam + KL step): the K * RBNN_SVI_MULTI_ACC_SAMPLES nets of
+// the accuracy forward are a grid dimension, so every entry point takes at most 65535 / RBNN_SVI_MULTI_ACC_SAMPLES guides
+constexpr int CONV_SVI_MAX_GUIDES = 65535 / RBNN_SVI_MULTI_ACC_SAMPLES;
+inline int check_conv_svils_net(const rbnn_conv_svi_guides_net* n) {
+    if (!n) return RBNN_ERR_NULL;
+    const int rc = check_conv_dims(n->activation, n->in_channels, n->in_width, n->hidden, n->n_classes);
+    if (rc) return rc;
+    return (n->n_guides < 1 || n->n_guides > CONV_SVI_MAX_GUIDES) ? RBNN_ERR_SHAPE : RBNN_OK;
 }
 
 }  // namespace

@@ -39,6 +39,21 @@
 //      in state_dict order: rbnn_conv_posterior's stacks, so the forward addresses member m as sample m).  conv_ens_do2 / _wgrad_gemm /
 //      _route1_kernel are the single net's text (rbnn_conv_wgrad_kernels.inc, included twice) on member views; the single net's kernels keep their code.
 //
+// and SVI training of K conv guides of one shape in LOCKSTEP (the SVI step above for every guide in one set of launches; the flat buffers are
+// tensor-major as the ensemble's, so the guides are the members of the staging, the forward and the weight gradients):
+//      rbnn_conv_svi_guides_draw      W[k] = loc[k] + sigma[k] * eps(keys[k], draw id): conv_svils_draw_kernel, the flat draw's bits.  1 launch
+//      rbnn_conv_svi_guides_gradient  rbnn_conv_ens_stage, the members' forward with the SUMMED cross-entropy (dZ scale 1), the members' 7
+//                                    weight-gradient launches on the view (P = W, grad = grad): 1 + 4 + 7 launches
+//      rbnn_conv_svi_guides_adam_step conv_svils_adam_kernel: rbnn_svi_adam_kernel.inc's text on tensor-major offsets, per-guide key and lr.  1 launch.
+//                                    Kernel and entry point stand in rbnn_svi.hip, not here: a second Adam kernel in THIS unit changes the
+//                                    code its adam_kernel<false> compiles to (profiles/conv_svi_lockstep/README.txt)
+//      rbnn_conv_svi_guides_accuracy  conv_svils_draw_kernel of the K * 10 weight sets under keys[k] ^ key_xor, the exact forward of those nets on
+//                                    the K staged batches (conv1_pool_grouped_kernel: set k * 10 + s reads guide k's rows; conv2_pool_kernel and
+//                                    conv_fc_kernel as they are), conv_svils_acc_sum_kernel: 1 + 3 + 1 launches
+//      rbnn_conv_svi_guides_finalize  conv_svils_finalize_kernel, one block per guide: the step's sums and the epoch's end on the device.  1 launch
+//      One lockstep SVI step = 1 + 12 + 1 + 1 = 15 launches without the accuracy forward, 20 with it, whatever K is.  A guide that has finished
+//      (active[k] == 0) is skipped by the four conv_svils_* kernels: nothing of its state is written again.
+//
 // Parameters, moments and gradients are flat fp32 buffers in state_dict order, unpadded (the convention of the fc trainers).  One stream, no
 // atomics, no device->host synchronisation: every output element is one lane's sum in one order, two runs are bit-identical.
 // The three conv GEMMs are one kernel text (conv_wgrad_gemm_kernel): 64 x 64 (G_DP1: 64 x 32) output tiles of the fp32 MFMA, K staged 16 at
@@ -300,6 +315,109 @@ inline int check_conv_ens_points(const rbnn_conv_ens_net* n, int B) {
     return (B < 1 || B > MAX_POINTS || (long long)n->n_members * B > MAX_ENS_POINTS) ? RBNN_ERR_SHAPE : RBNN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// K SVI guides in lockstep: the kernels that join the members' forward and weight gradients above to the SVI step.  Tensor-major buffers: guide
+// k's segment sg of a [K n_params] buffer starts at K sg.off + k sg.cols (every conv segment is one row of sg.cols columns).  Each returns at
+// once, the whole block, for a guide with active[k] == 0.  (conv_svils_adam_kernel, the fourth of them, stands in rbnn_svi.hip.)
+// ---------------------------------------------------------------------------------------------------
+constexpr int ACC_S = RBNN_SVI_MULTI_ACC_SAMPLES;
+
+// One thread per quad of weight set blockIdx.y = guide * per + sample of n_sets = K * per sets (per = 1: the training draw at sample 0; per =
+// ACC_S: the accuracy stack): draw_quad, i.e. rbnn_svi_draw_flat's fmaf(sigma, eps, loc) with the counter (e / 4, tensor id, sample, draw id).
+struct ConvSvilsDrawArgs {
+    Layout L;
+    const float *loc, *sigma;
+    float* W;
+    const unsigned long long* keys;
+    const int32_t* active;
+    unsigned long long key_xor;
+    uint32_t draw_id;
+    int per, n_guides;
+};
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_svils_draw_kernel(const ConvSvilsDrawArgs a) {
+    const int k = blockIdx.y / a.per, s = blockIdx.y % a.per;
+    if (a.active[k] == 0) return;
+    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (q >= a.L.n_quads) return;
+    const Seg sg = a.L.s[seg_of(a.L, q)];
+    const int c4 = (int)(q - sg.first_quad);
+    const unsigned long long key = a.keys[k] ^ a.key_xor;
+    const Rng rng = {(uint32_t)key, (uint32_t)(key >> 32), (uint32_t)s, a.draw_id};
+    const long long go = a.n_guides * sg.off + (long long)k * sg.cols;
+    float w[4];
+    draw_quad(rng, sg.tensor_id, a.loc + go, a.sigma + go, 0, c4, sg.cols, w);
+    float* const out = a.W + (long long)a.n_guides * a.per * sg.off + (long long)blockIdx.y * sg.cols + 4 * c4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (4 * c4 + j < sg.cols) out[j] = w[j];
+}
+
+// Psum[k, b, :] = sum_s P[k ACC_S + s, b, :], one thread per (point, 4-class quad) of guide blockIdx.y, s = 0, 1, ... in that order: the sum
+// reduce_samples_kernel (rbnn_kernels.hip) makes with scale 1.
+struct ConvSvilsAccSumArgs { const float* P; const int32_t* active; float* Psum; int B, C; };
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_svils_acc_sum_kernel(const ConvSvilsAccSumArgs a) {
+    const int k = blockIdx.y, i = blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (a.active[k] == 0 || i >= a.B * 4) return;
+    const int b = i >> 2, q = i & 3;
+    f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < ACC_S; ++s) sum += *(const f32x4*)(a.P + (((long long)k * ACC_S + s) * a.B + b) * RBNN_CPAD + 4 * q);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) if (4 * q + r < a.C) a.Psum[((long long)k * a.B + b) * RBNN_CPAD + 4 * q + r] = sum[r];
+}
+
+// One block per guide: finalize_kernel's sums (rbnn_train.hip; svi_step_sums) over the guide's B staged points, then the epoch's end as
+// svils_finalize_kernel (rbnn_svi_lockstep.hip) writes it: epoch_slot[k] in [0, log_rows) -> epoch_log[k, slot] = (sum of the step losses,
+// correct predictions) of the epoch that ends with this step, and both accumulators are zeroed.
+struct ConvSvilsFinalArgs {
+    const float *kl_part, *ce, *Psum;
+    const int32_t *labels, *active, *epoch_slot;
+    double *stats, *epoch_log;
+    long long part_stride;
+    int n_part, B, C, log_rows;
+};
+
+__global__ void __launch_bounds__(256) conv_svils_finalize_kernel(const ConvSvilsFinalArgs a) {
+    __shared__ double red[256];
+    __shared__ double cnt[256];
+    const int k = blockIdx.x;
+    if (a.active[k] == 0) return;
+    const long long pt = (long long)k * a.B;
+    svi::svi_step_sums<false>(a.kl_part + k * a.part_stride, a.n_part, a.ce + pt, a.B, a.Psum ? a.Psum + pt * RBNN_CPAD : nullptr, RBNN_CPAD, a.C,
+                              a.labels + pt, nullptr, 0, red, cnt);
+    if (threadIdx.x == 0) {
+        double* const st = a.stats + 3LL * k;
+        st[0] = red[0];
+        const double loss = st[1] + red[0], correct = st[2] + cnt[0];
+        const int slot = a.epoch_slot ? a.epoch_slot[k] : -1;
+        if (slot >= 0 && slot < a.log_rows) {
+            double* const row = a.epoch_log + ((long long)k * a.log_rows + slot) * 2;
+            row[0] = loss; row[1] = correct;
+            st[1] = 0.0; st[2] = 0.0;
+        } else {
+            st[1] = loss; st[2] = correct;
+        }
+    }
+}
+
+inline int check_conv_svils_points(const rbnn_conv_svi_guides_net* n, int B) {
+    return (B < 1 || B > MAX_POINTS || (long long)n->n_guides * B > MAX_ENS_POINTS) ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+
+// the guides as the members of rbnn_conv_ens_*: P = the drawn W, grad = dCE/dW, the first fifteen workspaces
+inline rbnn_conv_ens_net conv_svils_members(const rbnn_conv_svi_guides_net* n) {
+    rbnn_conv_ens_net e = {};
+    e.activation = n->activation; e.in_channels = n->in_channels; e.in_width = n->in_width; e.hidden = n->hidden; e.n_classes = n->n_classes;
+    e.n_members = n->n_guides; e.P = n->W; e.grad = n->grad;
+    return e;
+}
+inline rbnn_conv_ens_ws conv_svils_member_ws(const rbnn_conv_svi_guides_ws* w) {
+    rbnn_conv_ens_ws e = {};
+    e.Xs = w->Xs; e.labels = w->labels; e.logits = w->logits; e.P1 = w->P1; e.st1 = w->st1; e.Q2 = w->Q2; e.st2 = w->st2; e.dZ = w->dZ; e.ce = w->ce;
+    e.correct = w->correct; e.dO2 = w->dO2; e.dO1 = w->dO1; e.part2 = w->part2; e.part1 = w->part1; e.partP = w->partP;
+    return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,7 +583,9 @@ int rbnn_conv_ens_stage(const rbnn_conv_ens_net* net, const float* X, int32_t ld
     return launch_status();
 }
 
-int rbnn_conv_ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+// The members' training forward and the head.  dZ = (softmax - e_y) / B for the mean cross-entropy of the deterministic members, softmax - e_y
+// (summed) for the summed one of the SVI guides in lockstep.
+static int ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, bool summed, void* stream) {
     int rc = check_conv_ens_net(net);
     if (rc) return rc;
     if (!net->P || !ws || !ws->Xs || !ws->labels || !ws->logits || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->ce || !ws->correct)
@@ -485,9 +605,13 @@ int rbnn_conv_ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const 
     if ((rc = conv_forward_args(&p, p.K2w, true, ws->Xs, DIN, n_points, nullptr, M, RBNN_OUT_LOGITS, &w, a))) return rc;
     if ((rc = launch_conv_forward_packed(net->activation, a, (hipStream_t)stream))) return rc;
     const int n = M * n_points;
-    const ConvHeadArgs h = {ws->logits, ws->labels, ws->dZ, ws->ce, ws->correct, n, net->n_classes, 1.f / (float)n_points};
+    const ConvHeadArgs h = {ws->logits, ws->labels, ws->dZ, ws->ce, ws->correct, n, net->n_classes, summed ? 1.f : 1.f / (float)n_points};
     hipLaunchKernelGGL(conv_head_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
     return launch_status();
+}
+
+int rbnn_conv_ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+    return ens_forward(net, n_points, ws, false, stream);
 }
 
 int rbnn_conv_ens_weight_grads(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
@@ -631,6 +755,120 @@ int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net* net, uint64_t key, ui
     a.grad = net->grad; a.kl_part = kl_partials; a.key = key; a.draw_id = draw_id;
     a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
     hipLaunchKernelGGL(svi::adam_kernel<false>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The SVI step of K conv guides in lockstep: the members' stage / forward / weight gradients above on the view (P = W, grad = grad) with the
+// summed cross-entropy, around the kernels of the guides (the Adam + KL step: rbnn_svi.hip).  Every refusal comes before the first launch of an
+// entry point.
+// ---------------------------------------------------------------------------------------------------
+int rbnn_conv_svi_guides_sizes(const rbnn_conv_svi_guides_net* net, int32_t n_points, rbnn_conv_svi_guides_bytes* out) {
+    int rc = check_conv_svils_net(net);
+    if (rc) return rc;
+    if (!out) return RBNN_ERR_NULL;
+    if ((rc = check_conv_svils_points(net, n_points))) return rc;
+    const rbnn_conv_ens_net e = conv_svils_members(net);
+    rbnn_conv_ens_bytes s;
+    if ((rc = rbnn_conv_ens_sizes(&e, n_points, &s))) return rc;
+    const size_t KS = (size_t)net->n_guides * ACC_S, SN = KS * n_points, F = (size_t)net->hidden * NP2;
+    rbnn_conv_svi_guides_bytes z = {};
+    z.n_params = s.n_params;
+    z.n_partials = blocks_for(conv_svi_layout(net->hidden, net->n_classes).n_quads);
+    z.Xs = s.Xs; z.labels = s.labels; z.logits = s.logits; z.P1 = s.P1; z.st1 = s.st1; z.Q2 = s.Q2; z.st2 = s.st2; z.dZ = s.dZ; z.ce = s.ce;
+    z.correct = s.correct; z.dO2 = s.dO2; z.dO1 = s.dO1; z.part2 = s.part2; z.part1 = s.part1; z.partP = s.partP;
+    z.acc_W = KS * (size_t)s.n_params * sizeof(float);
+    z.acc_P = SN * RBNN_CPAD * sizeof(float);                     // the accuracy forward's buffers: rbnn_conv_workspace_query's for K S samples
+    z.acc_P1 = SN * (size_t)GeoMnist::P1STRIDE;
+    z.acc_st1 = SN * P1SZ;
+    z.acc_Q2 = SN * F * sizeof(float);
+    z.acc_st2 = SN * F;
+    z.Psum = (size_t)net->n_guides * n_points * RBNN_CPAD * sizeof(float);
+    *out = z;
+    return RBNN_OK;
+}
+
+int rbnn_conv_svi_guides_draw(const rbnn_conv_svi_guides_net* net, const int32_t* active, uint32_t draw_id, void* stream) {
+    const int rc = check_conv_svils_net(net);
+    if (rc) return rc;
+    if (!active || !net->loc || !net->sigma || !net->W || !net->keys) return RBNN_ERR_NULL;
+    ConvSvilsDrawArgs a = {};
+    a.L = conv_svi_layout(net->hidden, net->n_classes);
+    a.loc = net->loc; a.sigma = net->sigma; a.W = net->W; a.keys = (const unsigned long long*)net->keys; a.active = active;
+    a.key_xor = 0; a.draw_id = draw_id; a.per = 1; a.n_guides = net->n_guides;
+    hipLaunchKernelGGL(conv_svils_draw_kernel, dim3(blocks_for(a.L.n_quads), net->n_guides), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
+int rbnn_conv_svi_guides_gradient(const rbnn_conv_svi_guides_net* net, const float* X, int32_t ldx, int32_t n_rows, const int32_t* labels,
+                                 const int32_t* rows, int32_t n_points, const rbnn_conv_svi_guides_ws* ws, void* stream) {
+    int rc = check_conv_svils_net(net);
+    if (rc) return rc;
+    if (!X || !labels || !rows || !ws || !net->W || !net->grad) return RBNN_ERR_NULL;
+    const void* const bufs[] = {ws->Xs, ws->labels, ws->logits, ws->P1, ws->st1, ws->Q2, ws->st2, ws->dZ, ws->ce, ws->correct, ws->dO2, ws->dO1,
+                                ws->part2, ws->part1, ws->partP};
+    for (const void* b : bufs) if (!b) return RBNN_ERR_NULL;
+    if ((rc = check_conv_svils_points(net, n_points))) return rc;
+    if (n_rows < 1 || ldx < DIN || (ldx & 3)) return RBNN_ERR_SHAPE;
+    if (!aligned16(X) || !aligned16(net->W) || !aligned16(net->grad)) return RBNN_ERR_ALIGN;
+    for (const void* b : bufs) if (!aligned16(b)) return RBNN_ERR_ALIGN;
+    // nothing below can refuse: the three calls repeat these checks on the member view
+    const rbnn_conv_ens_net e = conv_svils_members(net);
+    const rbnn_conv_ens_ws w = conv_svils_member_ws(ws);
+    if ((rc = rbnn_conv_ens_stage(&e, X, ldx, n_rows, labels, rows, n_points, &w, stream))) return rc;
+    if ((rc = ens_forward(&e, n_points, &w, true, stream))) return rc;
+    return rbnn_conv_ens_weight_grads(&e, n_points, &w, stream);
+}
+
+int rbnn_conv_svi_guides_accuracy(const rbnn_conv_svi_guides_net* net, const int32_t* active, int32_t n_points, uint64_t key_xor, uint32_t draw_id,
+                                 const rbnn_conv_svi_guides_ws* ws, void* stream) {
+    int rc = check_conv_svils_net(net);
+    if (rc) return rc;
+    if (!active || !ws || !net->loc || !net->sigma || !net->keys) return RBNN_ERR_NULL;
+    const void* const bufs[] = {ws->Xs, ws->acc_W, ws->acc_P, ws->acc_P1, ws->acc_st1, ws->acc_Q2, ws->acc_st2, ws->Psum};
+    for (const void* b : bufs) if (!b) return RBNN_ERR_NULL;
+    if ((rc = check_conv_svils_points(net, n_points))) return rc;
+    for (const void* b : bufs) if (!aligned16(b)) return RBNN_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int K = net->n_guides, KS = K * ACC_S;
+    // the stack of the K S nets: tensor-major over the sets, so set k S + s is sample k S + s of an rbnn_conv_posterior
+    const ConvLayout L = conv_ens_layout(net->hidden, net->n_classes, KS);
+    rbnn_conv_posterior p = {};
+    p.activation = net->activation; p.hidden = net->hidden; p.n_classes = net->n_classes; p.n_stored = KS;
+    p.in_channels = net->in_channels; p.in_width = net->in_width;
+    float* const W = ws->acc_W;
+    p.K1w = W + L.K1w; p.K1b = W + L.K1b; p.K2w = W + L.K2w; p.K2b = W + L.K2b; p.Fw = W + L.Fw; p.Fb = W + L.Fb;
+    if ((rc = validate_conv(&p))) return rc;
+    rbnn_conv_workspace w = {};
+    w.P = ws->acc_P; w.P1 = ws->acc_P1; w.st1 = ws->acc_st1; w.Q2 = ws->acc_Q2; w.st2 = ws->acc_st2;
+    ConvArgs c = {};
+    if ((rc = conv_forward_args(&p, p.K2w, true, ws->Xs, DIN, n_points, nullptr, KS, RBNN_OUT_PROBS, &w, c))) return rc;
+    ConvSvilsDrawArgs d = {};
+    d.L = conv_svi_layout(net->hidden, net->n_classes);
+    d.loc = net->loc; d.sigma = net->sigma; d.W = W; d.keys = (const unsigned long long*)net->keys; d.active = active;
+    d.key_xor = key_xor; d.draw_id = draw_id; d.per = ACC_S; d.n_guides = K;
+    hipLaunchKernelGGL(conv_svils_draw_kernel, dim3(blocks_for(d.L.n_quads), KS), dim3(ELT_THREADS), 0, st, d);
+    if ((rc = launch_status())) return rc;
+    if ((rc = launch_conv_forward_grouped(net->activation, c, st))) return rc;
+    const ConvSvilsAccSumArgs r = {ws->acc_P, active, ws->Psum, n_points, net->n_classes};
+    hipLaunchKernelGGL(conv_svils_acc_sum_kernel, dim3(blocks_for(4LL * n_points), K), dim3(ELT_THREADS), 0, st, r);
+    return launch_status();
+}
+
+int rbnn_conv_svi_guides_finalize(const rbnn_conv_svi_guides_net* net, const int32_t* active, const rbnn_conv_svi_guides_ws* ws, int32_t with_accuracy,
+                                 int32_t n_points, const int32_t* epoch_slot, double* epoch_log, int32_t log_rows, void* stream) {
+    int rc = check_conv_svils_net(net);
+    if (rc) return rc;
+    if (!active || !ws || !ws->ce || !ws->labels || (with_accuracy && !ws->Psum) || !net->kl_part || !net->stats || (epoch_slot && !epoch_log))
+        return RBNN_ERR_NULL;
+    if ((rc = check_conv_svils_points(net, n_points))) return rc;
+    ConvSvilsFinalArgs a = {};
+    a.n_part = (int)blocks_for(conv_svi_layout(net->hidden, net->n_classes).n_quads);
+    if (net->part_stride < a.n_part || log_rows < 0) return RBNN_ERR_SHAPE;
+    a.kl_part = net->kl_part; a.ce = ws->ce; a.Psum = with_accuracy ? ws->Psum : nullptr; a.labels = ws->labels; a.active = active;
+    a.epoch_slot = epoch_slot; a.stats = net->stats; a.epoch_log = epoch_log; a.part_stride = net->part_stride;
+    a.B = n_points; a.C = net->n_classes; a.log_rows = log_rows;
+    hipLaunchKernelGGL(conv_svils_finalize_kernel, dim3(net->n_guides), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

@@ -16,7 +16,9 @@ Training: `train(train_loader, device, rel_path, filename)` runs the reference's
 (svi_train.SviTrainer: one weight draw, the training forward, the weight gradients and one Adam step per batch — csrc/rbnn_train.hip) and
 saves the param store.  `train_conv(train_loader, device, rel_path, filename)` runs the same algorithm for a conv net of the 1x28x28 geometry
 (conv_svi_train.ConvSviTrainer around the conv training forward and weight gradients, csrc/rbnn_conv_train.hip); `train()` itself keeps
-refusing conv.  CPU devices, conv SVI guides and conv HMC chains in lockstep and the 3x32x32 geometry raise NotImplementedError.  `train()`
+refusing conv.  `train_conv_svi_lockstep(nets, x_train, y_train, device)` is train_conv for several conv nets of one shape at once
+(conv_svi_train.ConvLockstepSvi: every launch covers all of them; each net's files and history are train_conv's bit for bit).  CPU devices,
+conv HMC chains in lockstep and the 3x32x32 geometry raise NotImplementedError.  `train()`
 refuses an HMC net too and names `train_hmc(train_loader, device, rel_path, filename, num_chains=1)`, which samples the chain of an fc / fc2
 net on the GPU (hmc.HmcSampler, csrc/rbnn_hmc.hip; num_chains = K > 1: K chains in lockstep, hmc.LockstepHmc, pooled and judged by their
 split-R-hat) and writes the per-sample files `load()` reads.  `train_hmc_conv(train_loader, device, rel_path, filename)` is train_hmc with
@@ -171,6 +173,73 @@ def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS,
         net.set_variational_params(loc, raw, device)
         net.save(rel_path=rel_path, filename=None)
     return trainer
+
+
+def train_conv_svi_lockstep(nets, x_train, y_train, device, rel_path=TESTS, batch_size=128, group=None):
+    """BNN.train_conv for several SVI conv nets of ONE net shape (1x28x28) at once, the counterpart of train_svi_lockstep
+    (conv_svi_train.ConvLockstepSvi: every kernel launch covers all of a group's nets).  The nets may differ in epochs and lr; every net
+    trains on all of x_train in order, unshuffled, in batches of batch_size with a short last batch.  Each net takes its initialisation and
+    key exactly as BNN.train_conv would (svi_lockstep_prologue) unless it already holds parameters, prints its epoch lines and gets
+    training_history, set_variational_params and save(): parameters, losses and accuracies are BNN.train_conv's on an unshuffled DataLoader of
+    the same data and batch size, bit for bit.  group: nets trained at a time — None: all of them when their workspaces fit the
+    RBNN_CONV_WS_GB budget, else the largest group that does (conv_svi_lockstep_group); the groups follow one another and no net's bits depend
+    on the grouping.  Every refusal comes before any state is changed, a generator touched or the library loaded."""
+    nets = list(nets)
+    if not nets:
+        raise ValueError("train_conv_svi_lockstep needs at least one net")
+    for net in nets:
+        if net.inference == "hmc":
+            raise NotImplementedError("train_conv_svi_lockstep() runs SVI only: an HMC posterior is sampled with BNN.train_hmc(train_loader, device) for "
+                                      "fc / fc2 and with BNN.train_hmc_conv(train_loader, device) for a conv net of the 1x28x28 geometry")
+        if net.basenet.architecture != "conv":
+            raise ValueError(f"train_conv_svi_lockstep trains the conv architecture; a {net.basenet.architecture!r} net trains through "
+                             "train_svi_lockstep")
+    from .conv_train import check_conv_trainable
+    for net in nets:
+        check_conv_trainable(net.basenet.input_shape, device)
+    b0 = nets[0].basenet
+    shape_of = lambda b: (b.architecture, b.activation, tuple(b.input_shape), int(b.output_size), int(b.hidden_size))
+    for net in nets[1:]:
+        if shape_of(net.basenet) != shape_of(b0):
+            raise ValueError(f"lockstep SVI nets share one net shape: {shape_of(net.basenet)} is not {shape_of(b0)}")
+    names = [net.name for net in nets]
+    for name in names:
+        if names.count(name) > 1:
+            raise ValueError(f"two nets are named {name!r}: their saved files would overwrite each other (give them different epochs or lr, or "
+                             "train them in separate calls under different rel_path)")
+    n = int(x_train.shape[0])
+    if n < 1 or int(batch_size) < 1 or (group is not None and int(group) < 1):
+        raise ValueError(f"train_conv_svi_lockstep needs at least one training point, batch_size >= 1 and group >= 1 (got {n}, {batch_size}, {group})")
+    from .conv_svi_train import ConvLockstepSvi, conv_svi_lockstep_group
+    B = min(int(batch_size), n)
+    if group is None:
+        group = conv_svi_lockstep_group(b0.activation, b0.hidden_size, b0.output_size, len(nets), B)
+    x_dev, lab_dev = x_train.to(device), y_train.argmax(-1).to(device)
+    for first in range(0, len(nets), int(group)):
+        members = nets[first:first + int(group)]
+        locs, raws, keys = [], [], []
+        for net in members:
+            net.device = device
+            net.basenet.device = device
+            loc, raw, key = svi_lockstep_prologue(net)
+            locs.append(loc); raws.append(raw); keys.append(key)
+        trainer = ConvLockstepSvi(b0.activation, b0.input_shape, b0.output_size, locs, raws, [net.lr for net in members], device, keys, batch_size=B)
+        trainer.set_data(x_dev, lab_dev)
+        trainer.run(ConvLockstepSvi.schedule(n, [net.epochs for net in members], B))
+        totals = trainer.epoch_totals()
+        for k, net in enumerate(members):
+            print("\n == SVI training ==")
+            loss_list, accuracy_list = [], []
+            for epoch in range(net.epochs):
+                loss, correct = totals[k][epoch]
+                print(f"\n[Epoch {epoch + 1}]\t loss: {loss / n:.2f} \t accuracy: {100 * correct / n:.2f}", end="\t")
+                loss_list.append(loss)
+                accuracy_list.append(100 * correct / n)
+            net.training_history = {"loss": loss_list, "accuracy": accuracy_list}
+            loc, raw = trainer.params(k)
+            net.set_variational_params(loc, raw, device)
+            net.save(rel_path=rel_path, filename=None)
+        del trainer
 
 
 class BNN(nn.Module):

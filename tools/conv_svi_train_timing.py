@@ -8,7 +8,14 @@ forward: 10 more weight sets and forwards under no_grad).  svi_train_timing.py's
 
 Every net is measured in a child process of its own, started through steps.Runner (one time limit each; after a fault, an abort or a time
 limit nothing more is started); the child's JSON line is printed and kept in its log under <OUT>/conv_svi_timing/.  --child: the measuring
-program itself (what to put behind `rocprofv3 --kernel-trace --stats --`, with --steps 5 --torch 0)."""
+program itself (what to put behind `rocprofv3 --kernel-trace --stats --`, with --steps 5 --torch 0).
+
+    python tools/conv_svi_train_timing.py --members 1,8,32 [--nets 512,1024] [--steps 40]
+
+times the lockstep step of K conv guides (ConvLockstepSvi, B = 128) at each K against that many ConvSviTrainers stepped one after the other on
+the same rows in the same process, in guide-steps per second, with and without the accuracy forward; every (net, K, accuracy) is measured
+in a child of its own through the same runner, its log under <OUT>/conv_svi_lockstep_timing/.  --child --members K --accuracy 0|1 --torch 0:
+the lockstep side alone (for a kernel trace)."""
 import argparse
 import json
 import os
@@ -93,13 +100,67 @@ def child(a):
         print(json.dumps(res), flush=True)
 
 
+def members_child(a):
+    """One net, one K, with or without the accuracy forward: ConvLockstepSvi's step at B = 128 on rows of 4096 resident points, against K
+    ConvSviTrainers stepped one after the other on the same rows in this process (the single guide's code: the baseline).  The figure is
+    guide-steps per second from the median block."""
+    from robustbnns_amd.conv_svi_train import ConvLockstepSvi, ConvSviTrainer
+    dev, B, Cn, steps, N = "cuda:0", 128, 10, a.steps, 4096
+    Hc, K, acc = int(a.nets), int(a.members), bool(a.accuracy)
+    g = torch.Generator().manual_seed(0)
+    X, Y = torch.rand(N, 1, 28, 28, generator=g), torch.randint(0, Cn, (N,), generator=g)
+    rows = torch.randint(0, N, (steps, K, B), generator=g, dtype=torch.int32).to(dev)
+    locs = [{k: 0.05 * torch.randn(*s, generator=g) for k, s in shapes_of(Hc, Cn)} for _ in range(K)]
+    raws = [{k: -3.0 + 0.5 * torch.randn(*s, generator=g) for k, s in shapes_of(Hc, Cn)} for _ in range(K)]
+    res = {"net": f"conv-{Hc}", "guides": K, "batch": B, "accuracy": acc, "steps_per_block": steps, "blocks": 7}
+    tr = ConvLockstepSvi("leaky", (1, 28, 28), Cn, locs, raws, 0.01, dev, [0x1234 + k for k in range(K)], batch_size=B)
+    tr.set_data(X, Y)
+
+    def block():
+        for i in range(steps):
+            tr.step(rows[i], accuracy=acc)
+    ms = _blocks(block)
+    res["lockstep"] = {"ms_per_step": ms[3] / steps, "spread": (ms[-1] - ms[0]) / ms[3], "guide_steps_per_s": 1e3 * K * steps / ms[3]}
+    res["launches_per_step"] = tr.launches // tr.t
+    del tr
+    torch.cuda.empty_cache()
+    if not a.torch:                                    # (--torch 0 skips the other side here too: the lockstep step alone, for a kernel trace)
+        return print(json.dumps(res), flush=True)
+    Xd, Yd = X.to(dev), Y.to(dev)
+    singles = [ConvSviTrainer("leaky", (1, 28, 28), Cn, locs[k], raws[k], 0.01, dev, 0x1234 + k, batch_size=B) for k in range(K)]
+    idx = rows.long()
+
+    def single_block():
+        for i in range(steps):
+            for k, one in enumerate(singles):
+                one.step(Xd[idx[i, k]], Yd[idx[i, k]], accuracy=acc)
+    sm = _blocks(single_block)
+    res["one_after_the_other"] = {"ms_per_step": sm[3] / steps, "spread": (sm[-1] - sm[0]) / sm[3], "guide_steps_per_s": 1e3 * K * steps / sm[3]}
+    res["lockstep_over_sequential"] = sm[3] / ms[3]
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nets", default="512,1024")
     ap.add_argument("--steps", type=int, default=40, help="steps per timed block")
     ap.add_argument("--torch", type=int, default=1, help="0: skip the torch-autograd side")
     ap.add_argument("--child", action="store_true", help="measure in this process (what the runner starts, one net at a time)")
+    ap.add_argument("--members", default="", help="e.g. 1,8,32: time ConvLockstepSvi at these guide counts instead")
+    ap.add_argument("--accuracy", type=int, default=1, help="with --members --child: 0 = without the accuracy forward")
     a = ap.parse_args()
+    if a.members and a.child:
+        return members_child(a)
+    if a.members:
+        # every (net, K, accuracy) in a child process of its own through the checked runner: one time limit each, nothing more started after a failure
+        runner = S.Runner("conv_svi_lockstep_timing")
+        for Hc in a.nets.split(","):
+            for K in a.members.split(","):
+                for acc in ("1", "0"):
+                    text = runner.gpu("timing", f"conv{Hc}_k{K}_acc{acc}", [S.PY, os.path.abspath(__file__), "--child", "--nets", Hc, "--members", K,
+                                                                            "--accuracy", acc, "--steps", str(a.steps), "--torch", str(a.torch)])
+                    print(json.dumps(S.last_json(text)), flush=True)
+        return
     if a.child:
         return child(a)
     runner = S.Runner("conv_svi_timing")
