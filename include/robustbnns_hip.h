@@ -716,7 +716,7 @@ int rbnn_hmc_window_end(const rbnn_svi_train_net *net, const rbnn_hmc_chain *cha
  * One transition on one stream:  momentum -> update(OPEN) -> { gradient -> update(step s) } x max_k steps[k] -> decide -> commit.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct rbnn_hmc_lockstep {
-    float *q_cur, *g_cur, *r, *m_inv, *w_mean, *w_m2;      /* [K, chain_stride], each as in rbnn_hmc_chain            */
+    float *q_cur, *g_cur, *r, *m_inv, *w_mean, *w_m2;      /* [K, chain_stride], each as in rbnn_hmc_chain; rbnn_conv_hmc_chains_*: tensor-major, chain_stride == n_params */
     float *k0_part;                /* [K, qpart_stride]                                                            */
     float *k1_part, *p_part;       /* [K, epart_stride]                                                            */
     double *state;                 /* [K, RBNN_HMC_STATE]                                                          */
@@ -914,7 +914,7 @@ int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net *net, uint64_t key, ui
  * chain's own: no atomics, one stream, no device->host synchronisation, two runs with the same key are bit-identical.  Every entry point
  * checks the net before any HIP call, as the conv SVI entry points do: a geometry other than 1 / 28 or an activation outside the four is
  * RBNN_ERR_UNSUPPORTED, hidden not a multiple of 16 in [16, 4096] or n_classes outside [1, 16] RBNN_ERR_SHAPE, a null pointer RBNN_ERR_NULL,
- * a phase or mode out of range RBNN_ERR_UNSUPPORTED.  Conv chains in lockstep are not built.
+ * a phase or mode out of range RBNN_ERR_UNSUPPORTED.  Several chains of one net shape: rbnn_conv_hmc_chains_* at the end of this header.
  * ------------------------------------------------------------------------------------------------------------ */
 /* [host] n_params; the lengths of k0_part and of k1_part / p_part (nullable).  < 0: rbnn_status. */
 int64_t rbnn_conv_hmc_sizes(const rbnn_conv_svi_train_net *net, int64_t *n_quad_partials, int64_t *n_elem_partials);
@@ -1080,6 +1080,71 @@ int rbnn_conv_svi_guides_accuracy(const rbnn_conv_svi_guides_net *net, const int
 int rbnn_conv_svi_guides_finalize(const rbnn_conv_svi_guides_net *net, const int32_t *active, const rbnn_conv_svi_guides_ws *ws,
                                  int32_t with_accuracy, int32_t n_points, const int32_t *epoch_slot, double *epoch_log, int32_t log_rows,
                                  void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K independent HMC chains over conv nets of ONE shape (1x28x28) with every launch covering all of them (the element-wise kernels:
+ * csrc/rbnn_hmc.hip; staging and gradient: csrc/rbnn_conv_train.hip; additive, ABI 10): the transition of rbnn_conv_hmc_* above for K chains,
+ * the chain a grid dimension of each launch, as rbnn_hmc_lockstep_* run K fc / fc2 chains.  One transition on one stream:
+ *   momentum -> update(OPEN) -> { gradient -> update(step s) } x max_k steps[k] -> decide -> commit
+ *   (a leapfrog step: 4 + 7 + 1 = 12 launches; a transition with L = max_k steps[k] steps: 1 + 1 + 12 L + 1 + 1, whatever K is)
+ * after ONE conv_hmc_chains_stage of the chains' batches (1 launch, once per batch, not per leapfrog step).
+ * Layout.  The chain block is an rbnn_hmc_lockstep with chain_stride == n_params REQUIRED, and its six per-parameter buffers (q_cur, g_cur,
+ * r, m_inv, w_mean, w_m2), like the net's W and grad, are TENSOR-MAJOR exactly as rbnn_conv_ens_net's P: six blocks [K, size of tensor t] in
+ * state_dict order, block t at K times the single net's offset of tensor t, chain k's tensor at + k * (size of tensor t) — the stacks of
+ * rbnn_conv_posterior, so the exact conv forward addresses chain k as sample k.  Everything else is chain-major as in rbnn_hmc_lockstep:
+ * the partial sums [K, qpart_stride] / [K, epart_stride], state [K, RBNN_HMC_STATE], log [K, log_rows, RBNN_HMC_LOG] and samples
+ * [K, sample_rows, n_params], each sample row FLAT in state_dict order: a row is the single chain's row.
+ * Per chain: its key (keys[k]), its step size (its state block), its number of leapfrog steps (steps[k]) and whether a launch touches it at
+ * all (active[k]).  All chains of a call share the point count B: chain k's batch is rows[k, 0..B) of the resident data (indices clamped into
+ * [0, n_rows)), and the slice plans of the three conv GEMMs are the single chain's for B (there is no counts argument).  The workspace is
+ * rbnn_conv_ens_ws, packed [K, B, .] for the call's B, with the sizes of rbnn_conv_ens_sizes.
+ * A block of the element-wise kernels covers the same quads (momentum) or the same 256 flat elements (update, commit, window end) of the
+ * single chain's layout as the single kernel's block of that index, writes the same partial sum in the same order, and draws from the same
+ * Philox counter (e / 4, tensor id, 0, draw id) under keys[k] ^ key_xor; no sum crosses chains, no atomics, no device->host synchronisation:
+ * chain k is bit-identical to rbnn_conv_hmc_* + rbnn_conv_svi_train_forward + rbnn_conv_svi_weight_grads running that chain alone on its rows.
+ * Every entry point checks, before any launch: net NULL, then the descriptor (geometry / activation: RBNN_ERR_UNSUPPORTED; hidden, n_classes,
+ * n_chains outside [1, 65535]: RBNN_ERR_SHAPE), then NULL pointers, then shapes (chain_stride != n_params, the strides of the partial sums,
+ * n_points, K n_points <= 2^22, ldx, n_rows, transition, welford_n, sample_row, n_window < 2), then a phase or mode out of range
+ * (RBNN_ERR_UNSUPPORTED) and step >= 0 without steps (RBNN_ERR_NULL), then 16-byte alignment of W, grad, X and the workspace buffers.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct rbnn_conv_hmc_chains_net {
+    int32_t activation;            /* rbnn_activation                                                              */
+    int32_t in_channels, in_width; /* 1, 28 (anything else: RBNN_ERR_UNSUPPORTED)                                  */
+    int32_t hidden;                /* Hc = conv2 output channels, a multiple of 16 in [16, 4096]                   */
+    int32_t n_classes;             /* C in [1, 16]                                                                 */
+    int32_t n_chains;              /* K in [1, 65535], K B <= 2^22                                                 */
+    float *W;                      /* [K n_params] the trajectory positions, tensor-major (16-byte aligned)        */
+    float *grad;                   /* [K n_params] dCE/dW there, tensor-major (16-byte aligned)                    */
+} rbnn_conv_hmc_chains_net;
+
+/* [host] n_params of one chain; the lengths of k0_part and of k1_part / p_part of one chain (rbnn_conv_hmc_sizes'); out: the workspace sizes
+ * for n_points points per chain (rbnn_conv_ens_sizes' for K members).  Every out-pointer is nullable; n_points is checked only when out is
+ * given.  < 0: rbnn_status. */
+int64_t rbnn_conv_hmc_chains_sizes(const rbnn_conv_hmc_chains_net *net, int32_t n_points, int64_t *n_quad_partials, int64_t *n_elem_partials,
+                                   rbnn_conv_ens_bytes *out);
+/* rbnn_conv_ens_stage of rows [K, n_points]: ws->Xs[k, b] = X[rows[k, b]], ws->labels[k, b] = labels[rows[k, b]].  1 launch. */
+int rbnn_conv_hmc_chains_stage(const rbnn_conv_hmc_chains_net *net, const float *X, int32_t ldx, int32_t n_rows, const int32_t *labels,
+                               const int32_t *rows, int32_t n_points, const rbnn_conv_ens_ws *ws, void *stream);
+/* dCE/dW (summed CE) into net->grad and ce [K, n_points] of every chain at net->W on the staged batches: the exact forward with the chain
+ * as the sample, the head with dZ = softmax - e_y, the seven weight-gradient launches of rbnn_conv_ens_weight_grads: 4 + 7 launches.
+ * active is NOT consulted: an inactive or finished chain's trajectory buffers are scratch. */
+int rbnn_conv_hmc_chains_gradient(const rbnn_conv_hmc_chains_net *net, int32_t n_points, const rbnn_conv_ens_ws *ws, void *stream);
+/* rbnn_hmc_lockstep_momentum: the momentum draw of every active chain under keys[k] ^ key_xor with draw id draw_ids[k] (device, nullable:
+ * draw_id for every chain).  1 launch. */
+int rbnn_conv_hmc_chains_momentum(const rbnn_conv_hmc_chains_net *net, const rbnn_hmc_lockstep *chains, uint64_t key_xor, uint32_t draw_id,
+                                  const uint32_t *draw_ids, void *stream);
+/* rbnn_hmc_lockstep_update: step < 0: the single chain's update `phase` on every active chain; step >= 0 (needs steps): MID for chains with
+ * step + 1 < steps[k], CLOSE at step + 1 == steps[k], nothing for step >= steps[k].  1 launch. */
+int rbnn_conv_hmc_chains_update(const rbnn_conv_hmc_chains_net *net, const rbnn_hmc_lockstep *chains, int32_t phase, int32_t step, void *stream);
+/* rbnn_hmc_lockstep_decide without counts: one fp64 block per active chain over ce [K, n_points] (ws->ce), the uniform under keys[k].  1 launch. */
+int rbnn_conv_hmc_chains_decide(const rbnn_conv_hmc_chains_net *net, const rbnn_hmc_lockstep *chains, const float *ce, int32_t n_points,
+                                int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void *stream);
+/* rbnn_hmc_lockstep_commit: the single chain's commit on every active chain, each by its own decision; sample_row >= 0: that row of every
+ * chain's stack.  1 launch. */
+int rbnn_conv_hmc_chains_commit(const rbnn_conv_hmc_chains_net *net, const rbnn_hmc_lockstep *chains, int32_t force, int32_t welford_n,
+                                int64_t sample_row, void *stream);
+/* rbnn_hmc_lockstep_window_end: the single chain's window end on every active chain.  1 launch. */
+int rbnn_conv_hmc_chains_window_end(const rbnn_conv_hmc_chains_net *net, const rbnn_hmc_lockstep *chains, int32_t n_window, void *stream);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,7 @@ STRUCTS = {
     "ConvSviTrainNet": "rbnn_conv_svi_train_net",
     "ConvEnsNet": "rbnn_conv_ens_net", "ConvEnsWs": "rbnn_conv_ens_ws", "ConvEnsBytes": "rbnn_conv_ens_bytes",
     "ConvSviLockstepNet": "rbnn_conv_svi_guides_net", "ConvSviLockstepWs": "rbnn_conv_svi_guides_ws", "ConvSviLockstepBytes": "rbnn_conv_svi_guides_bytes",
-    "HmcChain": "rbnn_hmc_chain", "HmcLockstep": "rbnn_hmc_lockstep", "SviLockstep": "rbnn_svi_multi", "SviLockstepAcc": "rbnn_svi_multi_acc",
+    "HmcChain": "rbnn_hmc_chain", "HmcLockstep": "rbnn_hmc_lockstep", "ConvHmcChainsNet": "rbnn_conv_hmc_chains_net", "SviLockstep": "rbnn_svi_multi", "SviLockstepAcc": "rbnn_svi_multi_acc",
 }
 HEADER = _header.read(HEADER_PATH)
 # name -> (restype, argtypes) of every prototype of the header.  The pointer rule: `T *` / `const T *` with T a struct of STRUCTS is

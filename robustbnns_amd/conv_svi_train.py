@@ -28,7 +28,7 @@ active is known on the host before the first step).  model_bnn.train_conv_svi_lo
 in groups when their workspaces exceed the RBNN_CONV_WS_GB budget (conv_svi_lockstep_group).
 
 What stays refused: the 3x32x32 geometry, CPU devices.  HMC posteriors of conv nets are sampled by conv_hmc.ConvHmcSampler
-(BNN.train_hmc_conv), on the forward and weight gradients this step runs; conv chains in lockstep stay refused.
+(BNN.train_hmc_conv), on the forward and weight gradients this step runs; several chains at once by conv_hmc.ConvLockstepHmc.
 """
 import ctypes as C
 import os

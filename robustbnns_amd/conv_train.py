@@ -15,9 +15,10 @@ bit-identical to that net trained alone by ConvNnTrainer.  The host loop is nn_t
 train in groups when their workspaces exceed the RBNN_CONV_WS_GB budget (conv_ensemble_group).
 
 What stays refused: every entry point of the fc trainers (NN.train, Ensemble_NN.train, NnTrainer, BNN.train, BNN.train_hmc, the lockstep
-forms) on a conv net, the 3x32x32 geometry, conv chains in lockstep.  SVI posteriors of conv nets are trained by
+forms) on a conv net, the 3x32x32 geometry.  SVI posteriors of conv nets are trained by
 conv_svi_train.ConvSviTrainer (BNN.train_conv; several guides in lockstep: conv_svi_train.ConvLockstepSvi, on the member kernels of the
-ensemble) and HMC posteriors sampled by conv_hmc.ConvHmcSampler (BNN.train_hmc_conv), on this module's forward and weight gradients.
+ensemble) and HMC posteriors sampled by conv_hmc.ConvHmcSampler (BNN.train_hmc_conv; several chains at once: conv_hmc.ConvLockstepHmc, on
+the member kernels too), on this module's forward and weight gradients.
 """
 import ctypes as C
 import os

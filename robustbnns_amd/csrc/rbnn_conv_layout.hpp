@@ -53,4 +53,19 @@ inline int check_conv_svils_net(const rbnn_conv_svi_guides_net* n) {
     return (n->n_guides < 1 || n->n_guides > CONV_SVI_MAX_GUIDES) ? RBNN_ERR_SHAPE : RBNN_OK;
 }
 
+// the descriptor and the point count of K HMC chains in one set of launches (rbnn_conv_train.hip: staging and gradient; rbnn_hmc.hip: the chain's
+// element-wise kernels): the chain is a grid dimension, and the packed batches obey the members' limits of rbnn_conv_train.hip
+constexpr int CONV_MAX_CHAINS = 65535;
+constexpr int CONV_CHAINS_MAX_POINTS = 65536;                        // rbnn_conv_train.hip's MAX_POINTS
+constexpr long long CONV_CHAINS_MAX_PACKED = 1LL << 22;              // its MAX_ENS_POINTS: K B
+inline int check_conv_chains_net(const rbnn_conv_hmc_chains_net* n) {
+    if (!n) return RBNN_ERR_NULL;
+    const int rc = check_conv_dims(n->activation, n->in_channels, n->in_width, n->hidden, n->n_classes);
+    if (rc) return rc;
+    return (n->n_chains < 1 || n->n_chains > CONV_MAX_CHAINS) ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+inline int check_conv_chains_points(const rbnn_conv_hmc_chains_net* n, int B) {
+    return (B < 1 || B > CONV_CHAINS_MAX_POINTS || (long long)n->n_chains * B > CONV_CHAINS_MAX_PACKED) ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+
 }  // namespace

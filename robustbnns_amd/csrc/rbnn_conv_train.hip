@@ -54,6 +54,11 @@
 //      One lockstep SVI step = 1 + 12 + 1 + 1 = 15 launches without the accuracy forward, 20 with it, whatever K is.  A guide that has finished
 //      (active[k] == 0) is skipped by the four conv_svils_* kernels: nothing of its state is written again.
 //
+// and the gradient of K HMC chains over conv nets of one shape (the chain's element-wise kernels: rbnn_hmc.hip), the chains as the members:
+//      rbnn_conv_hmc_chains_stage     rbnn_conv_ens_stage on the view: 1 launch, once per batch
+//      rbnn_conv_hmc_chains_gradient  the members' forward with the SUMMED cross-entropy and their 7 weight-gradient launches on the view
+//                                     (P = W, grad = grad): 4 + 7 launches per leapfrog step whatever K is.  No device code of its own.
+//
 // Parameters, moments and gradients are flat fp32 buffers in state_dict order, unpadded (the convention of the fc trainers).  One stream, no
 // atomics, no device->host synchronisation: every output element is one lane's sum in one order, two runs are bit-identical.
 // The three conv GEMMs are one kernel text (conv_wgrad_gemm_kernel): 64 x 64 (G_DP1: 64 x 32) output tiles of the fp32 MFMA, K staged 16 at
@@ -870,6 +875,59 @@ int rbnn_conv_svi_guides_finalize(const rbnn_conv_svi_guides_net* net, const int
     a.B = n_points; a.C = net->n_classes; a.log_rows = log_rows;
     hipLaunchKernelGGL(conv_svils_finalize_kernel, dim3(net->n_guides), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// dCE/dW of K HMC chains in one set of launches: the members' stage / forward / weight gradients above on the view (P = W, grad = grad) with
+// the summed cross-entropy.  No device code of its own; the chain's element-wise kernels are rbnn_hmc.hip's.  Every refusal comes before the
+// first launch of an entry point.
+// ---------------------------------------------------------------------------------------------------
+static_assert(MAX_MEMBERS == CONV_MAX_CHAINS && MAX_POINTS == CONV_CHAINS_MAX_POINTS && MAX_ENS_POINTS == CONV_CHAINS_MAX_PACKED,
+              "the chains are the members of the staging, the forward and the weight gradients");
+
+static rbnn_conv_ens_net conv_chains_members(const rbnn_conv_hmc_chains_net* n) {
+    rbnn_conv_ens_net e = {};
+    e.activation = n->activation; e.in_channels = n->in_channels; e.in_width = n->in_width; e.hidden = n->hidden; e.n_classes = n->n_classes;
+    e.n_members = n->n_chains; e.P = n->W; e.grad = n->grad;
+    return e;
+}
+
+int64_t rbnn_conv_hmc_chains_sizes(const rbnn_conv_hmc_chains_net* net, int32_t n_points, int64_t* n_quad_partials, int64_t* n_elem_partials,
+                                   rbnn_conv_ens_bytes* out) {
+    int rc = check_conv_chains_net(net);
+    if (rc) return rc;
+    const Layout L = conv_svi_layout(net->hidden, net->n_classes);
+    if (out) {
+        const rbnn_conv_ens_net e = conv_chains_members(net);
+        if ((rc = rbnn_conv_ens_sizes(&e, n_points, out))) return rc;
+    }
+    if (n_quad_partials) *n_quad_partials = blocks_for(L.n_quads);
+    if (n_elem_partials) *n_elem_partials = blocks_for(L.n_params);
+    return L.n_params;
+}
+
+int rbnn_conv_hmc_chains_stage(const rbnn_conv_hmc_chains_net* net, const float* X, int32_t ldx, int32_t n_rows, const int32_t* labels,
+                               const int32_t* rows, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+    const int rc = check_conv_chains_net(net);
+    if (rc) return rc;
+    const rbnn_conv_ens_net e = conv_chains_members(net);                  // rbnn_conv_ens_stage checks in the documented order and reads neither P nor grad
+    return rbnn_conv_ens_stage(&e, X, ldx, n_rows, labels, rows, n_points, ws, stream);
+}
+
+int rbnn_conv_hmc_chains_gradient(const rbnn_conv_hmc_chains_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
+    int rc = check_conv_chains_net(net);
+    if (rc) return rc;
+    if (!ws || !net->W || !net->grad) return RBNN_ERR_NULL;
+    const void* const bufs[] = {ws->Xs, ws->labels, ws->logits, ws->P1, ws->st1, ws->Q2, ws->st2, ws->dZ, ws->ce, ws->correct, ws->dO2, ws->dO1,
+                                ws->part2, ws->part1, ws->partP};
+    for (const void* b : bufs) if (!b) return RBNN_ERR_NULL;
+    if ((rc = check_conv_chains_points(net, n_points))) return rc;
+    if (!aligned16(net->W) || !aligned16(net->grad)) return RBNN_ERR_ALIGN;
+    for (const void* b : bufs) if (!aligned16(b)) return RBNN_ERR_ALIGN;
+    // nothing below can refuse: the two calls repeat these checks on the member view
+    const rbnn_conv_ens_net e = conv_chains_members(net);
+    if ((rc = ens_forward(&e, n_points, ws, true, stream))) return rc;
+    return rbnn_conv_ens_weight_grads(&e, n_points, ws, stream);
 }
 
 }  // extern "C"

@@ -30,6 +30,11 @@
 // rbnn_conv_layout.hpp — six tensors of one row each, so element e of tensor i draws component e % 4 of the Philox block with counter
 // (e / 4, i, 0, draw id), rbnn_conv_svi_*'s counter layout.  dCE/dW is rbnn_conv_svi_train_forward + rbnn_conv_svi_weight_grads on an
 // rbnn_conv_svi_train_net whose W is the trajectory's position and whose grad receives dCE/dW.  No device code of its own.
+//
+// K chains over conv nets of one shape (rbnn_conv_hmc_chains_*): the chain is grid dimension y, the per-parameter buffers are tensor-major (the
+// stacks the conv forward and weight gradients of K nets work on: rbnn_conv_hmc_chains_stage / _gradient in rbnn_conv_train.hip).  Four kernels
+// of their own (conv_chains_momentum / _update / _commit / _window_end_kernel) call the bodies below on a shifted view of chain k with the single
+// chain's flat index; the decision is lockstep_decide_kernel.  Chain k is bit-identical to the single conv chain.
 #define RBNN_TRAIN_LOCKSTEP
 #include "rbnn_train_gemm.hpp"
 #include "rbnn_conv_layout.hpp"
@@ -319,6 +324,75 @@ __global__ void __launch_bounds__(ELT_THREADS) lockstep_window_end_kernel(const 
     window_end_element(i, chain_of(a), scale, shift);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// K chains over CONV nets in one set of launches (rbnn_conv_hmc_chains_*): the chain is grid dimension y as above, but the per-parameter buffers
+// (and W / grad) are TENSOR-MAJOR — six blocks [K, size of tensor], block t at K times the single chain's offset of tensor t — as the conv forward
+// and weight gradients of K nets need them.  A thread finds the segment of its quad / element in the single chain's layout, shifts every
+// per-parameter pointer of chain k by  K off_t + k size_t - off_t  and calls the bodies above with the single chain's flat index: a block covers
+// the quads / elements of the single kernel's block of that index (a block that straddles two tensors has threads with different shifts) and
+// writes the same partial sum, so chain k is bit-identical to the single chain.  Partial sums, state, log and samples stay chain-major.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int seg_of_element(const Layout& L, long long i) {
+    int s = 0;
+#pragma unroll
+    for (int j = 1; j < 6; ++j) if (j < L.n && i >= L.s[j].off) s = j;
+    return s;
+}
+
+// chain blockIdx.y's view for flat indices inside segment sg (one row of sg.cols columns); shift: the same for W / grad
+__device__ __forceinline__ rbnn_hmc_chain conv_chain_of(const Chains& a, const Seg& sg, long long& shift) {
+    rbnn_hmc_chain c = chain_of(a);                                                  // the chain-major part: partial sums, state, log, samples
+    shift = ((long long)gridDim.y - 1) * sg.off + (long long)blockIdx.y * sg.cols;
+    c.q_cur = a.s.q_cur + shift; c.g_cur = a.s.g_cur + shift; c.r = a.s.r + shift; c.m_inv = a.s.m_inv + shift;
+    c.w_mean = a.s.w_mean + shift; c.w_m2 = a.s.w_m2 + shift;
+    return c;
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_chains_momentum_kernel(const Layout L, const Chains a, unsigned long long key_xor, uint32_t draw_id,
+                                                                           const uint32_t* __restrict__ draw_ids) {
+    __shared__ float red[ELT_THREADS];
+    if (!chain_active(a)) return;
+    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    long long shift;
+    const rbnn_hmc_chain c = conv_chain_of(a, L.s[seg_of(L, q)], shift);
+    const float k = momentum_quad(L, c, q, a.s.keys[blockIdx.y] ^ key_xor, draw_ids ? draw_ids[blockIdx.y] : draw_id);
+    block_sum_to(k, red, c.k0_part);
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_chains_update_kernel(const Layout L, const Chains a, int phase, int step) {
+    __shared__ float red[ELT_THREADS];
+    if (!chain_active(a)) return;
+    if (step >= 0) {
+        const int Lk = a.s.steps[blockIdx.y];
+        if (step >= Lk) return;
+        phase = step + 1 < Lk ? RBNN_HMC_MID : RBNN_HMC_CLOSE;
+    }
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    long long shift;
+    const rbnn_hmc_chain c = conv_chain_of(a, L.s[seg_of_element(L, i)], shift);
+    float kin = 0.f, pot = 0.f;
+    update_element(i, a.n_params, a.W + shift, a.grad + shift, c, phase, kin, pot);
+    if (phase == RBNN_HMC_CLOSE || phase == RBNN_HMC_ENERGY) {
+        block_sum_to(kin, red, c.k1_part);
+        block_sum_to(pot, red, c.p_part);
+    }
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_chains_commit_kernel(const Layout L, const Chains a, int force, float welford_n, long long sample_row) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= a.n_params || !chain_active(a)) return;
+    long long shift;
+    const rbnn_hmc_chain c = conv_chain_of(a, L.s[seg_of_element(L, i)], shift);
+    commit_element(i, a.W + shift, a.grad + shift, c, force, welford_n, sample_row >= 0 ? c.samples + sample_row * a.n_params : nullptr);
+}
+
+__global__ void __launch_bounds__(ELT_THREADS) conv_chains_window_end_kernel(const Layout L, const Chains a, float scale, float shift_m) {
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (i >= a.n_params || !chain_active(a)) return;
+    long long shift;
+    window_end_element(i, conv_chain_of(a, L.s[seg_of_element(L, i)], shift), scale, shift_m);
+}
+
 int check_chain(const rbnn_hmc_chain* c) {
     if (!c) return RBNN_ERR_NULL;
     if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state)
@@ -338,6 +412,24 @@ int check_chains(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* c, Chain
     if (c->qpart_stride < (long long)blocks_for(L.n_quads) || c->epart_stride < (long long)blocks_for(L.n_params)) return RBNN_ERR_SHAPE;
     if (c->log_rows < 0 || c->sample_rows < 0) return RBNN_ERR_SHAPE;
     out->s = *c; out->W = net->P; out->grad = net->grad; out->n_params = L.n_params;
+    return RBNN_OK;
+}
+
+// the chains of a conv call, in the order of the header's section: net NULL, the descriptor, NULL pointers (trajectory: the call reads net->W /
+// net->grad; more: one further pointer of the call, checked when `need_more`), then the shapes of the chain block
+int check_conv_chains(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* c, bool trajectory, bool need_more, const void* more, Layout* L,
+                      Chains* out) {
+    const int rc = check_conv_chains_net(net);
+    if (rc) return rc;
+    if (!c) return RBNN_ERR_NULL;
+    if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state || !c->keys)
+        return RBNN_ERR_NULL;
+    if ((trajectory && (!net->W || !net->grad)) || (need_more && !more)) return RBNN_ERR_NULL;
+    *L = conv_svi_layout(net->hidden, net->n_classes);
+    if (c->chain_stride != L->n_params) return RBNN_ERR_SHAPE;                         // tensor-major: there is no room between chains
+    if (c->qpart_stride < (long long)blocks_for(L->n_quads) || c->epart_stride < (long long)blocks_for(L->n_params)) return RBNN_ERR_SHAPE;
+    if (c->log_rows < 0 || c->sample_rows < 0) return RBNN_ERR_SHAPE;
+    out->s = *c; out->W = net->W; out->grad = net->grad; out->n_params = L->n_params;
     return RBNN_OK;
 }
 
@@ -551,6 +643,69 @@ int rbnn_hmc_lockstep_window_end(const rbnn_nn_train_net* net, const rbnn_hmc_lo
     if (n_window < 2) return RBNN_ERR_SHAPE;
     const double w = (double)n_window;                                               // the two scalars as rbnn_hmc_window_end forms them
     hipLaunchKernelGGL(lockstep_window_end_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a,
+                       (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
+    return launch_status();
+}
+
+// ---- K chains over conv nets: tensor-major buffers (staging and gradient: rbnn_conv_train.hip) ----
+int rbnn_conv_hmc_chains_momentum(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, uint64_t key_xor, uint32_t draw_id,
+                                  const uint32_t* draw_ids, void* stream) {
+    Layout L;
+    Chains a = {};
+    const int rc = check_conv_chains(net, chains, false, false, nullptr, &L, &a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(conv_chains_momentum_kernel, dim3(blocks_for(L.n_quads), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
+                       (unsigned long long)key_xor, draw_id, draw_ids);
+    return launch_status();
+}
+
+int rbnn_conv_hmc_chains_update(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, int32_t phase, int32_t step, void* stream) {
+    Layout L;
+    Chains a = {};
+    const int rc = check_conv_chains(net, chains, true, false, nullptr, &L, &a);
+    if (rc) return rc;
+    if (step < 0 && (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY)) return RBNN_ERR_UNSUPPORTED;
+    if (step >= 0 && !chains->steps) return RBNN_ERR_NULL;
+    hipLaunchKernelGGL(conv_chains_update_kernel, dim3(blocks_for(a.n_params), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
+                       (int)phase, (int)step);
+    return launch_status();
+}
+
+int rbnn_conv_hmc_chains_decide(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, const float* ce, int32_t n_points,
+                                int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    Layout L;
+    LockstepDecide d = {};
+    int rc = check_conv_chains(net, chains, false, true, ce, &L, &d.a);
+    if (rc || (rc = check_conv_chains_points(net, n_points))) return rc;
+    if (transition < 0) return RBNN_ERR_SHAPE;
+    if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
+    // the decision touches no per-parameter buffer: the chain-major kernel, every chain on all n_points points
+    d.ce = ce; d.counts = nullptr; d.n_points = n_points; d.n_qpart = blocks_for(L.n_quads); d.n_epart = blocks_for(L.n_params);
+    d.transition = transition; d.mode = mode; d.adapt = adapt; d.window_end = window_end;
+    hipLaunchKernelGGL(lockstep_decide_kernel, dim3(1, net->n_chains), dim3(256), 0, (hipStream_t)stream, d);
+    return launch_status();
+}
+
+int rbnn_conv_hmc_chains_commit(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, int32_t force, int32_t welford_n,
+                                int64_t sample_row, void* stream) {
+    Layout L;
+    Chains a = {};
+    const int rc = check_conv_chains(net, chains, true, sample_row >= 0, chains ? chains->samples : nullptr, &L, &a);
+    if (rc) return rc;
+    if (welford_n < 0 || sample_row >= chains->sample_rows) return RBNN_ERR_SHAPE;
+    hipLaunchKernelGGL(conv_chains_commit_kernel, dim3(blocks_for(a.n_params), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
+                       (int)force, (float)welford_n, (long long)sample_row);
+    return launch_status();
+}
+
+int rbnn_conv_hmc_chains_window_end(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, int32_t n_window, void* stream) {
+    Layout L;
+    Chains a = {};
+    const int rc = check_conv_chains(net, chains, false, false, nullptr, &L, &a);
+    if (rc) return rc;
+    if (n_window < 2) return RBNN_ERR_SHAPE;
+    const double w = (double)n_window;                                               // the two scalars as rbnn_hmc_window_end forms them
+    hipLaunchKernelGGL(conv_chains_window_end_kernel, dim3(blocks_for(a.n_params), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
                        (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
     return launch_status();
 }

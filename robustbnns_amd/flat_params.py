@@ -1,4 +1,4 @@
-"""What SviTrainer, LockstepSvi, NnTrainer, ConvNnTrainer, ConvSviTrainer, HmcSampler, ConvHmcSampler and LockstepHmc share: the refusals (require_gpu_fc), the constructor
+"""What SviTrainer, LockstepSvi, NnTrainer, ConvNnTrainer, ConvSviTrainer, HmcSampler, ConvHmcSampler, LockstepHmc and ConvLockstepHmc share: the refusals (require_gpu_fc), the constructor
 state of a trainer of nets of one shape (FlatNets: shapes, sizes, the net descriptors, zeroed buffers, the parameter views; set_data: the resident data
 of the lockstep classes), the flat parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
 import ctypes as C
@@ -17,8 +17,8 @@ def require_gpu_fc(what, arch=None, device=None):
         raise NotImplementedError(f"{what} runs on the MI355X kernels only (device {device!r}): there is no CPU compute path")
     if arch is not None and arch not in LAYER_KEYS:
         raise NotImplementedError(f"{what} covers fc and fc2, not {arch!r} (a conv net trains through NN.train_conv / BNN.train_conv, a conv "
-                                  "ensemble through Ensemble_NN.train_conv, a conv HMC chain is sampled by BNN.train_hmc_conv; conv SVI guides "
-                                  "and conv HMC chains in lockstep are not built)")
+                                  "ensemble through Ensemble_NN.train_conv, conv HMC chains are sampled by BNN.train_hmc_conv (num_chains of "
+                                  "them at once) and several conv SVI guides at once train through train_conv_svi_lockstep)")
 
 
 def state_keys(arch):

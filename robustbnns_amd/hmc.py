@@ -16,9 +16,12 @@ LockstepHmc runs K chains of one net shape with every launch covering all of the
 chain bit-identical to HmcSampler running it alone; split_r_hat is the convergence figure that goes with several chains.
 
 The chain algorithm (transition, step-size search, warmup windows, sampling, logs) is written once, in _Chains, over K chains with per-chain
-host lists; _OneChain (K = 1, the single-chain entry points, scalar / flat public values) and LockstepHmc supply the launches, the staging of
-the batch and the shape of what they return.  HmcSampler is _OneChain on rbnn_hmc_* with the fc / fc2 gradient; conv_hmc.ConvHmcSampler is
-_OneChain on rbnn_conv_hmc_* with the conv gradient (BNN.train_hmc_conv).  HmcSampler and LockstepHmc refuse a conv net.
+host lists; _OneChain (K = 1, the single-chain entry points, scalar / flat public values) and _LockstepChains (K chains behind every launch:
+the per-chain device values, the state block's accessors, the element-wise launches) supply the launches, and their subclasses the gradient,
+the staging of the batch and the shape of what they return.  HmcSampler is _OneChain on rbnn_hmc_* with the fc / fc2 gradient,
+conv_hmc.ConvHmcSampler _OneChain on rbnn_conv_hmc_* with the conv gradient; LockstepHmc is _LockstepChains on rbnn_hmc_lockstep_*,
+conv_hmc.ConvLockstepHmc _LockstepChains on rbnn_conv_hmc_chains_* (BNN.train_hmc_conv runs both conv classes).  HmcSampler and LockstepHmc
+refuse a conv net.
 """
 import ctypes as C
 import math
@@ -383,30 +386,27 @@ class HmcSampler(_OneChain):
         self.launches += self.fwd_launches + 1
 
 
-class LockstepHmc(_Chains):
-    """K independent chains over nets of ONE shape in lockstep: every launch covers all chains, so a transition costs the launches of a single
-    chain whatever K is.  Each chain has its own key, start position, step size, mass matrix, state block, log and sample stack, and may have
-    its own batch (rows / counts into resident data); warmup, the number of samples, num_steps and the adapt flags are shared.  Chain k is
-    bit-identical to HmcSampler(…, q0s[k], …, keys[k]) alone on its batch: sample stack, log, m_inv, q_cur, g_cur, state, L_log, search tries.
-
-    Adapted step sizes differ, so the chains' trajectory lengths L_k do: the host issues max_k L_k leapfrog steps and the update launch of
-    step s closes the chains with L_k == s + 1 and skips those behind it (their forward / gradient launches still run, on a position that
-    no longer moves).  The step-size search probes all chains together and freezes a chain whose direction has flipped (`active`).
-    `launches` counts kernel launches as HmcSampler does."""
+class _LockstepChains(_Chains):
+    """What the classes that run K chains behind every launch share (LockstepHmc; conv_hmc.ConvLockstepHmc): one rbnn_hmc_lockstep chain block
+    with the per-chain keys, lengths, draw ids and activity on the device, the state block's accessors, and the momentum / update / commit /
+    window-end launches through the entry points ENTRY + their names.  A subclass checks its own arguments (refuse_bad_chains among them),
+    calls _Chains' constructor with members = K and then _lockstep(batch_size), and supplies _bind (self.net, then _bind_chain), _ensure,
+    _gradient, _decide, stage() and run()."""
+    ENTRY = "rbnn_hmc_lockstep_"
     eps_host, searches, search_log, trajectory_length = (_view(n) for n in ("_eps", "_searches", "_search_log", "_traj"))
     set_data = set_data
     length = _Chains._length
 
-    def __init__(self, arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size=True,
-                 adapt_mass_matrix=True, batch_size=128):
-        require_gpu_fc("HMC", arch, device)
-        q0s, keys = list(q0s), list(keys)
+    @staticmethod
+    def refuse_bad_chains(who, q0s, keys):
+        """The refusals of a chain count, before the library is loaded."""
         if len(q0s) < 1 or len(keys) != len(q0s):
-            raise ValueError(f"LockstepHmc needs one key per chain and at least one chain: {len(q0s)} start positions, {len(keys)} keys")
+            raise ValueError(f"{who} needs one key per chain and at least one chain: {len(q0s)} start positions, {len(keys)} keys")
         if len(q0s) > 65535:
             raise ValueError(f"at most 65535 chains run in lockstep (the chain is a grid dimension), not {len(q0s)}")
-        super().__init__(arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size, adapt_mass_matrix,
-                         len(q0s))
+
+    def _lockstep(self, batch_size):
+        """The end of a subclass's constructor: the per-chain device values, then _Chains._start."""
         K, dev = self.K, self.device
         self.keys_t = keys_tensor(self.chain_keys, dev)
         self.steps_t = torch.ones(K, dtype=torch.int32, device=dev)
@@ -414,27 +414,19 @@ class LockstepHmc(_Chains):
         self.active_t = torch.ones(K, dtype=torch.int32, device=dev)
         self.active = None                                               # None: every chain; else the host's copy of active_t
         self._steps_host = [1] * K
-        self.cap = 0
-        self.X = self.labels = self.rows_t = self.counts_t = None
+        self.X = self.labels = self.rows_t = None
         self._start(batch_size)
 
-    # -- buffers --------------------------------------------------------------------------------------------------------------------
-    def _bind(self):
-        net = self.descriptor(_hip.NnTrainNet, self.K)
-        net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), self.n_params
-        self.net = net
-        ch = self._chain_struct(_hip.HmcLockstep, 1, keys=self.keys_t, steps=self.steps_t, active=None if self.active is None else self.active_t)
+    def _bind_chain(self, **more):
+        """self.chain: the rbnn_hmc_lockstep of the chain buffers (more: buffers that are not attributes of their field's name)."""
+        ch = self._chain_struct(_hip.HmcLockstep, 1, keys=self.keys_t, steps=self.steps_t, active=None if self.active is None else self.active_t,
+                                **more)
         ch.chain_stride, ch.qpart_stride, ch.epart_stride = self.n_params, self.n_qpart, self.n_epart
         self.chain = ch
 
-    def _ensure(self, B):
-        """Workspaces for K x B points (packed [K, B, .] for the call's B)."""
-        if self.K * B <= self.cap:
-            return
-        self.ws_t = train_workspace(self.arch, self.K * B, self.H, self.device)
-        self.ws_t["correct"] = torch.zeros(self.K * B, dtype=torch.int32, device=self.device)
-        self.ws = _hip.fill(_hip.NnTrainWs, self.ws_t)
-        self.cap = self.K * B
+    def _call(self, name, *args):
+        _hip.check(getattr(self.k.lib, self.ENTRY + name)(C.byref(self.net), C.byref(self.chain), *args, self._st()), self.ENTRY + name)
+        self.launches += 1
 
     def _set_state(self, **kv):
         """Host -> device writes of state-block entries (warmup / set-up only): one value for every chain, or one per chain."""
@@ -464,20 +456,11 @@ class LockstepHmc(_Chains):
             self._steps_host = list(Ls)
 
     # -- launches -------------------------------------------------------------------------------------------------------------------
-    def _gradient(self):
-        _hip.check(self.k.lib.rbnn_hmc_lockstep_gradient(C.byref(self.net), _hip.ptr(self.X), self.D, int(self.X.shape[0]), _hip.ptr(self.labels),
-                                                         _hip.ptr(self.rows_t), _hip.ptr(self.counts_t), self.B, C.byref(self.ws), self._st()),
-                   "rbnn_hmc_lockstep_gradient")
-        self.launches += self.fwd_launches + 1
-
     def _update(self, phase, step=-1):
-        _hip.check(self.k.lib.rbnn_hmc_lockstep_update(C.byref(self.net), C.byref(self.chain), phase, step, self._st()), "rbnn_hmc_lockstep_update")
-        self.launches += 1
+        self._call("update", phase, step)
 
     def _momentum(self, key_xor, draw_id, per_chain=False):
-        _hip.check(self.k.lib.rbnn_hmc_lockstep_momentum(C.byref(self.net), C.byref(self.chain), C.c_uint64(key_xor), C.c_uint32(draw_id & 0xFFFFFFFF),
-                                                         _hip.ptr(self.draw_ids_t) if per_chain else None, self._st()), "rbnn_hmc_lockstep_momentum")
-        self.launches += 1
+        self._call("momentum", C.c_uint64(key_xor), C.c_uint32(draw_id & 0xFFFFFFFF), _hip.ptr(self.draw_ids_t) if per_chain else None)
 
     def _draw(self, i):
         """The momenta of transition i, or (None) of the search's next probe: every chain's try counter goes to the device first."""
@@ -487,20 +470,11 @@ class LockstepHmc(_Chains):
         else:
             self._momentum(0, i)
 
-    def _decide(self, mode, transition=0, adapt=False, window_end=False):
-        _hip.check(self.k.lib.rbnn_hmc_lockstep_decide(C.byref(self.net), C.byref(self.chain), _hip.ptr(self.ws_t["ce"]), _hip.ptr(self.counts_t),
-                                                       self.B, int(transition), mode, int(adapt), int(window_end), self._st()),
-                   "rbnn_hmc_lockstep_decide")
-        self.launches += 1
-
     def _commit(self, force=False, welford_n=0, sample_row=-1):
-        _hip.check(self.k.lib.rbnn_hmc_lockstep_commit(C.byref(self.net), C.byref(self.chain), int(force), int(welford_n), int(sample_row), self._st()),
-                   "rbnn_hmc_lockstep_commit")
-        self.launches += 1
+        self._call("commit", int(force), int(welford_n), int(sample_row))
 
     def _window_end(self, n):
-        _hip.check(self.k.lib.rbnn_hmc_lockstep_window_end(C.byref(self.net), C.byref(self.chain), n, self._st()), "rbnn_hmc_lockstep_window_end")
-        self.launches += 1
+        self._call("window_end", n)
 
     def leapfrog(self, Ls):
         """Chain k takes Ls[k] leapfrog steps (an int: every chain) from (q_cur, r) at its own step size: max(Ls) gradient + update launches,
@@ -512,6 +486,55 @@ class LockstepHmc(_Chains):
             self._gradient()
             self._update(_hip.HMC_MID, s)
         return Ls
+
+
+class LockstepHmc(_LockstepChains):
+    """K independent chains over nets of ONE shape in lockstep: every launch covers all chains, so a transition costs the launches of a single
+    chain whatever K is.  Each chain has its own key, start position, step size, mass matrix, state block, log and sample stack, and may have
+    its own batch (rows / counts into resident data); warmup, the number of samples, num_steps and the adapt flags are shared.  Chain k is
+    bit-identical to HmcSampler(…, q0s[k], …, keys[k]) alone on its batch: sample stack, log, m_inv, q_cur, g_cur, state, L_log, search tries.
+
+    Adapted step sizes differ, so the chains' trajectory lengths L_k do: the host issues max_k L_k leapfrog steps and the update launch of
+    step s closes the chains with L_k == s + 1 and skips those behind it (their forward / gradient launches still run, on a position that
+    no longer moves).  The step-size search probes all chains together and freezes a chain whose direction has flipped (`active`).
+    `launches` counts kernel launches as HmcSampler does."""
+
+    def __init__(self, arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size=True,
+                 adapt_mass_matrix=True, batch_size=128):
+        require_gpu_fc("HMC", arch, device)
+        q0s, keys = list(q0s), list(keys)
+        self.refuse_bad_chains("LockstepHmc", q0s, keys)
+        super().__init__(arch, activation, input_shape, n_classes, q0s, step_size, num_steps, device, keys, adapt_step_size, adapt_mass_matrix,
+                         len(q0s))
+        self.cap = 0
+        self.counts_t = None
+        self._lockstep(batch_size)
+
+    # -- buffers --------------------------------------------------------------------------------------------------------------------
+    def _bind(self):
+        net = self.descriptor(_hip.NnTrainNet, self.K)
+        net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), self.n_params
+        self.net = net
+        self._bind_chain()
+
+    def _ensure(self, B):
+        """Workspaces for K x B points (packed [K, B, .] for the call's B)."""
+        if self.K * B <= self.cap:
+            return
+        self.ws_t = train_workspace(self.arch, self.K * B, self.H, self.device)
+        self.ws_t["correct"] = torch.zeros(self.K * B, dtype=torch.int32, device=self.device)
+        self.ws = _hip.fill(_hip.NnTrainWs, self.ws_t)
+        self.cap = self.K * B
+
+    # -- launches -------------------------------------------------------------------------------------------------------------------
+    def _gradient(self):
+        _hip.check(self.k.lib.rbnn_hmc_lockstep_gradient(C.byref(self.net), _hip.ptr(self.X), self.D, int(self.X.shape[0]), _hip.ptr(self.labels),
+                                                         _hip.ptr(self.rows_t), _hip.ptr(self.counts_t), self.B, C.byref(self.ws), self._st()),
+                   "rbnn_hmc_lockstep_gradient")
+        self.launches += self.fwd_launches + 1
+
+    def _decide(self, mode, transition=0, adapt=False, window_end=False):
+        self._call("decide", _hip.ptr(self.ws_t["ce"]), _hip.ptr(self.counts_t), self.B, int(transition), mode, int(adapt), int(window_end))
 
     # -- data -----------------------------------------------------------------------------------------------------------------------
     def stage(self, rows=None, counts=None):

@@ -17,13 +17,14 @@ Training: `train(train_loader, device, rel_path, filename)` runs the reference's
 saves the param store.  `train_conv(train_loader, device, rel_path, filename)` runs the same algorithm for a conv net of the 1x28x28 geometry
 (conv_svi_train.ConvSviTrainer around the conv training forward and weight gradients, csrc/rbnn_conv_train.hip); `train()` itself keeps
 refusing conv.  `train_conv_svi_lockstep(nets, x_train, y_train, device)` is train_conv for several conv nets of one shape at once
-(conv_svi_train.ConvLockstepSvi: every launch covers all of them; each net's files and history are train_conv's bit for bit).  CPU devices,
-conv HMC chains in lockstep and the 3x32x32 geometry raise NotImplementedError.  `train()`
+(conv_svi_train.ConvLockstepSvi: every launch covers all of them; each net's files and history are train_conv's bit for bit).  CPU devices
+and the 3x32x32 geometry raise NotImplementedError.  `train()`
 refuses an HMC net too and names `train_hmc(train_loader, device, rel_path, filename, num_chains=1)`, which samples the chain of an fc / fc2
 net on the GPU (hmc.HmcSampler, csrc/rbnn_hmc.hip; num_chains = K > 1: K chains in lockstep, hmc.LockstepHmc, pooled and judged by their
-split-R-hat) and writes the per-sample files `load()` reads.  `train_hmc_conv(train_loader, device, rel_path, filename)` is train_hmc with
-one chain for a conv net of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the same chain kernels around the conv training forward and
-weight gradients); `train_hmc()` itself keeps refusing conv.
+split-R-hat) and writes the per-sample files `load()` reads.  `train_hmc_conv(train_loader, device, rel_path, filename, num_chains=1,
+group=None)` is train_hmc for a conv net of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the same chain kernels around the conv training
+forward and weight gradients; num_chains = K > 1: conv_hmc.ConvLockstepHmc, K chains behind every launch in groups that fit the conv
+workspace budget, pooled and judged by their split-R-hat); `train_hmc()` itself keeps refusing conv.
 """
 import os
 import random
@@ -612,26 +613,62 @@ class BNN(nn.Module):
         self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
         self.save(rel_path=rel_path, filename=filename)
 
-    def train_hmc_conv(self, train_loader, device, rel_path=TESTS, filename=None):
-        """train_hmc with num_chains = 1 for the conv architecture of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the chain's kernels of
-        csrc/rbnn_hmc.hip around the conv training forward and weight gradients of csrc/rbnn_conv_train.hip): the same prologue, the chain on
-        the last batch, the resampling with torch.randint(0, batch_samples, (n_samples,)), set_posterior_samples, hmc_history and save().
-        Every refusal comes before any state is changed, a generator touched or the library loaded.  Conv chains in lockstep are not built."""
+    def train_hmc_conv(self, train_loader, device, rel_path=TESTS, filename=None, num_chains=1, group=None):
+        """train_hmc for the conv architecture of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the chain's kernels of csrc/rbnn_hmc.hip
+        around the conv training forward and weight gradients of csrc/rbnn_conv_train.hip): the same prologue, the chain on the last batch,
+        the resampling with torch.randint(0, batch_samples, (n_samples,)), set_posterior_samples, hmc_history and save().
+
+        num_chains = K > 1: K chains with every launch covering all of them (conv_hmc.ConvLockstepHmc), exactly as train_hmc runs K fc
+        chains.  Chain 0 takes its start position and key where the single chain does (it IS the num_chains = 1 chain, bit for bit); chains
+        1..K-1 draw theirs afterwards, all before any chain runs.  All run batch_samples samples on the last batch; the pooled stack is
+        chain-major [K * batch_samples, ...] (hmc_history["stack"]) and is resampled with torch.randint(0, K * batch_samples, (n_samples,)).
+        hmc_history's logs are chain 0's, "chains" holds every chain's, "r_hat_U" the split-R-hat of the chains' potential over the sampling
+        phase.  The chains run in consecutive groups of `group` (None: as many as fit the RBNN_CONV_WS_GB budget,
+        conv_hmc.conv_hmc_chains_group; else an int in [1, K]), one group after the other; the chains are independent and every host draw is
+        made before the first group, so the grouping changes no bit.
+        Every refusal comes before any state is changed, a generator touched or the library loaded."""
         if self.inference != "hmc":
             raise ValueError(f"train_hmc_conv() samples an HMC posterior; this net's inference is {self.inference!r} (use train_conv())")
         if self.basenet.architecture != "conv":
             raise ValueError(f"train_hmc_conv samples the conv architecture; a {self.basenet.architecture!r} net samples through train_hmc")
+        K = int(num_chains)
+        if K < 1:
+            raise ValueError(f"train_hmc_conv() needs num_chains >= 1, not {num_chains}")
+        if group is not None and not 1 <= int(group) <= K:
+            raise ValueError(f"train_hmc_conv() runs its chains in groups of 1 .. num_chains = {K}, not group = {group}")
         from .conv_train import check_conv_trainable
         check_conv_trainable(self.basenet.input_shape, device)
-        from .conv_hmc import ConvHmcSampler
+        from .conv_hmc import ConvHmcSampler, ConvLockstepHmc, conv_hmc_chains_group
         x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
         b = self.basenet
-        sampler = ConvHmcSampler(b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, key,
-                                 batch_size=int(x_batch.shape[0]))
-        stack = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
-        idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
-        self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
-                            "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
+        x, labels, B = x_batch.to(device), y_batch.to(device).argmax(-1), int(x_batch.shape[0])
+        if K == 1:
+            sampler = ConvHmcSampler(b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, key, batch_size=B)
+            stack = sampler.run(x, labels, batch_samples, self.warmup)
+            idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
+            self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
+                                "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
+        else:
+            from types import SimpleNamespace
+            from .hmc import initial_position
+            from .svi_train import draw_key
+            q0s, keys = [q0], [key]
+            for _ in range(1, K):
+                q0s.append(initial_position(state_shapes(b)))
+                keys.append(draw_key())
+            group = conv_hmc_chains_group(b.activation, b.hidden_size, b.output_size, K, B) if group is None else int(group)
+            stacks, chains, logs = [], [], []
+            for a in range(0, K, group):
+                sampler = ConvLockstepHmc(b.activation, b.input_shape, b.output_size, q0s[a:a + group], self.step_size, self.num_steps, device,
+                                          keys[a:a + group], batch_size=B)
+                stacks += [{k: v.clone() for k, v in s.items()} for s in sampler.run(x, labels, batch_samples, self.warmup)]
+                chains += [lockstep_history(sampler, k) for k in range(sampler.K)]
+                logs.append(sampler.log)
+                del sampler                                                               # the next group's workspaces take its place
+            stack = {k: torch.cat([s[k] for s in stacks], 0) for k in stacks[0]}          # chain-major [K * batch_samples, ...]
+            idx = torch.randint(0, K * batch_samples, (self.n_samples,)).to(device)
+            self.hmc_history = {**chains[0], "resampled": idx.cpu(), "stack": stack, "chains": chains,
+                                "r_hat_U": lockstep_r_hat(SimpleNamespace(log=torch.cat(logs, 0)), self.warmup)}
         self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
         self.save(rel_path=rel_path, filename=filename)
 

@@ -5,11 +5,15 @@ six layers by torch.nn.functional, sum CE + 1/2 sum q^2, torch.autograd.grad, ea
 conv_svi_train_timing.py's protocol: device events; after one warm-up block, 7 blocks of --n transitions each: the figure is the median
 block, its noise the spread (max - min) / median.
 
-    python tools/conv_hmc_timing.py [--nets 512,1024] [--n 2] [--batch 5000] [--torch 1]
+    python tools/conv_hmc_timing.py [--nets 512,1024] [--n 2] [--batch 5000] [--torch 1] [--chains 1,8]
 
-Every net is measured in a child process of its own, started through steps.Runner (one time limit each; after a fault, an abort or a time
-limit nothing more is started); the child's JSON line is printed and kept in its log under <OUT>/conv_hmc_timing/.  --child: the measuring
-program itself (what to put behind `rocprofv3 --kernel-trace --stats --`, with --n 1 --torch 0)."""
+--chains 1,8: instead, K chains behind every launch (robustbnns_amd.conv_hmc.ConvLockstepHmc) against K ConvHmcSamplers stepped one after the
+other in the same process, the same protocol, in chain-transitions per second (K transitions a launch set).  K is cut to what
+conv_hmc_chains_group allows for the batch (the RBNN_CONV_WS_GB budget); the line says which K was measured.
+
+Every net (with --chains: every net and K) is measured in a child process of its own, started through steps.Runner (one time limit each;
+after a fault, an abort or a time limit nothing more is started); the child's JSON line is printed and kept in its log under
+<OUT>/conv_hmc_timing/.  --child: the measuring program itself (what to put behind `rocprofv3 --kernel-trace --stats --`, with --n 1 --torch 0)."""
 import argparse
 import json
 import os
@@ -102,6 +106,51 @@ def child(a):
         print(json.dumps(res), flush=True)
 
 
+def chains_child(a):
+    """One (net, K): K ConvHmcSamplers stepped one after the other, then (their memory freed) one ConvLockstepHmc of the same K chains."""
+    from robustbnns_amd.conv_hmc import ConvHmcSampler, ConvLockstepHmc, conv_hmc_chains_group
+    dev, B, Cn, n, asked = "cuda:0", a.batch, 10, a.n, int(a.chains)
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.rand(B, 1, 28, 28, device=dev, generator=g)
+    y = torch.randint(0, Cn, (B,), device=dev, generator=g)
+    for Hc in (int(v) for v in a.nets.split(",")):
+        K = conv_hmc_chains_group("leaky", Hc, Cn, asked, B)
+        g = torch.Generator().manual_seed(0)
+        q0s = [{k: 0.05 * torch.randn(*s, generator=g) for k, s in shapes_of(Hc, Cn)} for _ in range(K)]
+        keys = [0x1234 + k for k in range(K)]
+        state = {"i": 0}
+        singles = [ConvHmcSampler("leaky", (1, 28, 28), Cn, q0s[k], EPS, L, dev, keys[k], adapt_step_size=False, batch_size=B) for k in range(K)]
+        for s in singles:
+            s.stage(x, y)
+
+        def one_after_the_other():
+            for _ in range(n):
+                for s in singles:
+                    s.transition(state["i"], L)
+                state["i"] += 1
+        apart = figures(_blocks(one_after_the_other), n * K)
+        n_params = singles[0].n_params
+        del singles
+        torch.cuda.empty_cache()
+        ls = ConvLockstepHmc("leaky", (1, 28, 28), Cn, q0s, EPS, L, dev, keys, adapt_step_size=False, batch_size=B)
+        ls.set_data(x, y)
+        ls.stage()
+        state["i"] = 0
+
+        def together():
+            for _ in range(n):
+                ls.transition(state["i"], L)
+                state["i"] += 1
+        n0 = ls.launches
+        ms = _blocks(together)
+        res = {"net": f"conv-{Hc}", "batch": B, "L": L, "n_params": n_params, "chains_asked": asked, "chains": K, "transitions_per_block": n,
+               "blocks": 7, "launches_per_transition": (ls.launches - n0) // (8 * n), "lockstep": figures(ms, n * K), "one_after_the_other": apart}
+        res["lockstep_over_apart"] = res["lockstep"]["chain_transitions_per_s"] / apart["chain_transitions_per_s"]
+        del ls
+        torch.cuda.empty_cache()
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nets", default="512,1024")
@@ -109,11 +158,18 @@ def main():
     ap.add_argument("--batch", type=int, default=5000)
     ap.add_argument("--torch", type=int, default=1, help="0: skip the torch-autograd side")
     ap.add_argument("--child", action="store_true", help="measure in this process (what the runner starts, one net at a time)")
+    ap.add_argument("--chains", default="", help="e.g. 1,8: time K chains behind every launch against K single chains one after the other")
     a = ap.parse_args()
     if a.child:
-        return child(a)
+        return chains_child(a) if a.chains else child(a)
     runner = S.Runner("conv_hmc_timing")
     for Hc in a.nets.split(","):
+        for K in (a.chains.split(",") if a.chains else ()):
+            text = runner.gpu("timing", f"conv{Hc}_k{K}", [S.PY, os.path.abspath(__file__), "--child", "--nets", Hc, "--n", str(a.n), "--batch",
+                                                         str(a.batch), "--chains", K])
+            print(json.dumps(S.last_json(text)), flush=True)
+        if a.chains:
+            continue
         text = runner.gpu("timing", f"conv{Hc}", [S.PY, os.path.abspath(__file__), "--child", "--nets", Hc, "--n", str(a.n), "--batch", str(a.batch),
                                                   "--torch", str(a.torch)])
         print(json.dumps(S.last_json(text)), flush=True)
