@@ -337,15 +337,48 @@ class ConvEngine(AttackEngine):
     # Activations cost 148 KB per (point, sample) at Hc=512 on 1x28x28 (P1 18 KB, Q2 100 KB, two byte stashes, per-sample
     # gradients), and the mean-probability loss needs every sample's forward before any backward — so large jobs are
     # split over POINTS (independent), never over samples.  Budget: RBNN_CONV_WS_GB (default 48 GB of the 288 GB).
-    def point_block(self, S):
+    # Sample-sharded, every block all-reduces [n, 16] and [n, D] tensors (AttackEngine._loss_backward / _step), so the cut is ONE PLAN PER
+    # GROUP: sized by the group's LARGEST shard (c5: 500 samples over 8 ranks are 62 / 63 — 3296 vs 3248 points by the local count), which
+    # keeps every rank inside the budget.  With one rank the plan is point_block(n_samples).
+    def __init__(self, posterior, kernels=None, group=None, total_samples=None, precision=None):
+        super().__init__(posterior, kernels=kernels, group=group, total_samples=total_samples, precision=precision)
+        self._S_plan = self._group_max(self.post.S)                        # the one exchange, when the engine is built
+
+    def bytes_per_sample(self):
+        """Workspace bytes per (point, sample) — rbnn_conv_workspace_query's buffers (P, dZ, P1, st1, Q2, st2, G); Psum (64 B) and Gsum
+        (4 D B) per point do not grow with S and are not counted."""
         p = self.post
         p1 = 32 * p.P1W * p.P1W
-        per_point = S * (max(24576, (p1 + 255) // 256 * 1024) + p1 + p.H * p.NP2 * 5 + p.D * 4 + 2 * 64)
+        return max(24576, (p1 + 255) // 256 * 1024) + p1 + p.H * p.NP2 * 5 + p.D * 4 + 2 * 64
+
+    def point_block(self, S):
+        """Points per block that S samples fit into the budget with: the pure formula, of this rank's quantities only."""
         budget = float(os.environ.get("RBNN_CONV_WS_GB", "48")) * 2 ** 30
-        return max(16, int(budget // per_point) // 16 * 16)
+        return max(16, int(budget // (S * self.bytes_per_sample())) // 16 * 16)
+
+    def _group_max(self, S):
+        """max over the group's ranks of S (a 1-rank group, collectives forced or not: S itself, nothing is exchanged)."""
+        if self.group is None or self._fake_comm:
+            return S
+        import torch.distributed as dist
+        if dist.get_world_size(self.group) == 1:
+            return S
+        t = torch.tensor([float(S)], device=self.device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        return int(round(t.item()))
+
+    def group_point_block(self, n_samples):
+        """point_block of the largest per-rank sample count of this call — the same number on every rank of the group.  A call on each rank's
+        whole shard (n_samples == post.S) takes the count learnt at construction; any other count is exchanged, where total_samples()
+        exchanges too when the engine was built without it."""
+        if self.world == 1:
+            return self.point_block(n_samples)
+        if self._S_total is not None and n_samples == self.post.S:
+            return self.point_block(self._S_plan)
+        return self.point_block(self._group_max(n_samples))
 
     def _blocked(self, fn, x, *rest, n_samples, cat=True):
-        nb = self.point_block(n_samples)
+        nb = self.group_point_block(n_samples)
         if x.shape[0] <= nb:
             return fn(x, *rest)
         outs = [fn(x[i:i + nb], *[r[i:i + nb] if torch.is_tensor(r) and r.shape[:1] == x.shape[:1] else r for r in rest])

@@ -787,6 +787,8 @@ class AttackEngine:
         kind = OUT_LOGITS if logits else OUT_PROBS
         labels = to_labels(y, self.device)
         prep = self._flat if self.precision == "lowdim" else self.pad_inputs
+        if clean is not None and clean.shape[0] != x.shape[0]:                  # rbnn_eval_metrics takes its row count from the clean outputs
+            raise ValueError(f"clean holds {clean.shape[0]} rows, the inputs {x.shape[0]}")
         o = clean if clean is not None else self.forward_padded(prep(x), sidx, S, kind)
         a = self.forward_padded(prep(x_attack), sidx, S, kind)
         counts = torch.zeros(2, dtype=torch.int32, device=self.device)

@@ -112,6 +112,66 @@ def test_unequal_sample_shards_world2(arch, comm_blocks):
     assert errs["fgsm_bad"] == 0 and errs["pgd_frac"] < 0.02, errs
 
 
+def _worker_conv_plan(rank, world, port, q):
+    """Unequal conv shards (S = 5 as 2 + 3) at a 4 MB budget: the block lengths each rank's ConvEngine._blocked cuts a call into, recorded
+    by a callable that runs no kernel and no collective (a mismatch cannot hang), then exchanged."""
+    sys.path.insert(0, ROOT); sys.path.insert(0, HERE)
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    os.environ["RBNN_CONV_WS_GB"] = "0.004"
+    torch.set_num_threads(1)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from fake_kernels import FakeKernels
+        from oracle import bnn_oracle as O
+        from robustbnns_amd.conv import ConvEngine, ConvStackedPosterior
+        S, Hc, C = 5, 32, 10
+        out = {}
+        for shape, N, pure in (((1, 28, 28), 80, (48, 32)), ((3, 32, 32), 40, (32, 16))):
+            D = shape[0] * shape[1] * shape[2]
+            q2 = (shape[1] - 4) // 2 - 5
+            post = O.synthetic_posterior("conv", D, Hc, C, S, 0.05, in_ch=shape[0], head=q2 * q2 * Hc)
+            lo, hi = S * rank // world, S * (rank + 1) // world
+            part = ConvStackedPosterior("leaky", shape, C, Hc, {k: v[lo:hi] for k, v in post.items()}, "cpu")
+            eng = ConvEngine(part, kernels=FakeKernels(), group=dist.group.WORLD, total_samples=S)
+            assert eng.world == 2 and eng.post.S == (2, 3)[rank]
+            assert eng.point_block(eng.post.S) == pure[rank]                 # the pure formula: the two shards get different plans
+            seen = []
+            got = eng._blocked(lambda xb, yb: (seen.append((len(xb), len(yb))), xb + 1)[1], torch.arange(float(N)).reshape(N, 1), torch.arange(N),
+                               n_samples=eng.post.S)
+            assert torch.equal(got, torch.arange(float(N)).reshape(N, 1) + 1) and all(a == b for a, b in seen)
+            out[shape] = [a for a, _ in seen]
+        plans = [None] * world
+        dist.all_gather_object(plans, out)
+        if rank == 0:
+            q.put(plans)
+    except Exception as exc:                                     # report instead of leaving the parent on q.get
+        q.put([{"error": f"rank {rank}: {exc!r}"}])
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+def test_conv_block_plan_agrees_across_unequal_shards_world2():
+    """Two ranks holding 2 and 3 conv samples cut the same call at the same points — the plan of the LARGER shard: 80 points at 1x28x28 as
+    32 + 32 + 16 (by their own counts: 48 + 32 on rank 0, 32 + 32 + 16 on rank 1), 40 points at 3x32x32 as 16 + 16 + 8 (32 + 8 / 16 + 16 + 8).
+    Inside a block the sharded step all-reduces [n, 16] and [n, D] tensors: other lengths on the two ranks are mismatched collectives."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_conv_plan, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        plans = q.get(timeout=300)
+    finally:
+        for p in procs:
+            p.join(timeout=120)
+    assert not any("error" in rank_plan for rank_plan in plans), plans
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    for rank_plan in plans:
+        assert rank_plan[(1, 28, 28)] == [32, 32, 16] and rank_plan[(3, 32, 32)] == [16, 16, 8], plans
+
+
 def test_sample_sharded_world8_c4_split_on_tiny_dims():
     """BASELINE config 4's layout — the posterior sharded 8 ways, `loss_gradients` (per-sample loss) + FGSM (mean-probability loss) over
     all points — and config 5's uneven split (here S = 20 over 8 ranks: 2 / 3 samples each, as 500 -> 62 / 63) with EIGHT processes over

@@ -41,6 +41,13 @@ def _problem(arch, dev, S_fc=6):
         x, y = O.synthetic_inputs(N, shape, C, seed=7)
         part = lambda r, w: ConvStackedPosterior("leaky", shape, C, Hc, {k: v[r * S // w:(r + 1) * S // w] for k, v in post.items()}, dev)
         return full, part, x, y, D, S, N, 8
+    if arch == "convblk":                                        # UNEQUAL conv shards (2 + 3) at a 4 MB budget (_worker): 80 points in blocks of 32 + 32 + 16
+        D, Hc, C, S, N = 784, 32, 10, 5, 80
+        post = O.synthetic_posterior("conv", D, Hc, C, S, 0.05)
+        full = ConvStackedPosterior("leaky", (1, 28, 28), C, Hc, post, dev)
+        x, y = O.synthetic_inputs(N, (1, 28, 28), C, seed=8)
+        part = lambda r, w: ConvStackedPosterior("leaky", (1, 28, 28), C, Hc, {k: v[r * S // w:(r + 1) * S // w] for k, v in post.items()}, dev)
+        return full, part, x, y, D, S, N, 40
     D, Hc, C, S, N = 784, 32, 10, 4, 48
     post = O.synthetic_posterior("conv", D, Hc, C, S, 0.05)
     full = ConvStackedPosterior("leaky", (1, 28, 28), C, Hc, post, dev)
@@ -53,6 +60,8 @@ def _worker(rank, world, port, precision, q, arch="fc", S_fc=6):
     sys.path.insert(0, ROOT); sys.path.insert(0, HERE)
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ["RBNN_COMM_BLOCKS"], os.environ["RBNN_COMM_MIN_POINTS"] = "2", "256"
+    if arch == "convblk":
+        os.environ["RBNN_CONV_WS_GB"] = "0.004"
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         from robustbnns_amd import _hip
@@ -63,6 +72,13 @@ def _worker(rank, world, port, precision, q, arch="fc", S_fc=6):
         assert eng.world == 2 and eng.post.S == S * (rank + 1) // world - S * rank // world      # shards may be unequal (S = 7: 3 + 4)
         if arch == "fc":
             assert eng._comm_blocks(N) == 2                     # pipelined over two point blocks; ConvEngine keeps the plain sequence
+        if arch == "convblk":
+            # by its own sample count rank 0 (2 samples) would cut 48 + 32 and rank 1 (3 samples) 32 + 32 + 16 — all-reduces of other sizes on
+            # the two ranks; the plan is the group's, that of the largest shard.  Checked BEFORE anything is exchanged: a mismatch raises here
+            assert eng.point_block(eng.post.S) == (48, 32)[rank] and eng.group_point_block(eng.post.S) == 32, "the ranks' block plans differ"
+            cut = []
+            eng._blocked(lambda xb, yb: (cut.append((len(xb), len(yb))), xb)[1], x, y, n_samples=eng.post.S)
+            assert cut == [(32, 32), (32, 32), (16, 16)], cut
         lab = y.argmax(-1).int().to(dev)
         out = {"probs": eng.forward(x, eng.post.S).cpu(), "lg": eng.loss_gradients(x, y, eng.post.S).cpu(),
                "gm": eng.gradient(eng.pad_inputs(x), lab, None, eng.post.S, _hip.LOSS_MEAN_PROB)[:, :D].cpu().clone(),
@@ -79,6 +95,7 @@ def _worker(rank, world, port, precision, q, arch="fc", S_fc=6):
         dist.broadcast(t, src=0)
         assert torch.equal(t, out["fgsm"])
         if rank == 0:
+            os.environ.pop("RBNN_CONV_WS_GB", None)              # the yardstick runs every call in one piece (this rank has exchanged all it will)
             single = make_engine(full, precision=precision)
             ref = {"probs": single.forward(x, S).cpu(), "lg": single.loss_gradients(x, y, S).cpu(),
                    "gm": single.gradient(single.pad_inputs(x), lab, None, S, _hip.LOSS_MEAN_PROB)[:, :D].cpu().clone(),
@@ -102,6 +119,18 @@ def _worker(rank, world, port, precision, q, arch="fc", S_fc=6):
 @pytest.mark.parametrize("arch,precision,S_fc", [("fc", "auto", 6), ("fc", "exact", 6), ("conv", "auto", 6), ("fc", "auto", 7)])
 def test_two_ranks_real_kernels_match_single_process(arch, precision, S_fc):
     """S_fc = 7: UNEQUAL sample shards (3 + 4) — BASELINE config 5's n_samples = 500 over 8 GPUs is 62 / 63 per rank."""
+    _two_ranks_match_single_process(arch, precision, S_fc)
+
+
+def test_two_ranks_unequal_conv_shards_in_point_blocks_match_single_process():
+    """BASELINE config 5's layout in small: conv samples sharded UNEQUALLY (5 as 2 + 3) and a job larger than the point block (80 points at
+    a 4 MB budget).  Both ranks cut it 32 + 32 + 16 — the plan of the larger shard (ConvEngine.group_point_block), asserted in the workers
+    before anything is exchanged — so every block's all-reduces have the same sizes on both ranks; the results equal the single-process
+    engine's on the full posterior, run in one piece."""
+    _two_ranks_match_single_process("convblk", "auto", 5)
+
+
+def _two_ranks_match_single_process(arch, precision, S_fc):
     assert torch.cuda.is_available(), "this test needs the MI355X"
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

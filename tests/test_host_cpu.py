@@ -558,6 +558,144 @@ def test_conv_engine_point_blocking(monkeypatch, golden):
     assert eng.point_block(100) >= 2048
 
 
+class _ConvStub:
+    """What ConvEngine's block plan reads of a posterior: the geometry, Hc and this rank's sample count."""
+    arch = "conv"
+
+    def __init__(self, shape, Hc, S):
+        from robustbnns_amd.conv import conv_geometry
+        self.P1W, p2w = conv_geometry(shape)
+        self.NP2, self.H, self.S, self.C = p2w * p2w, Hc, S, 10
+        self.D = self.Dp = shape[0] * shape[1] * shape[2]
+        self.device = torch.device("cpu")
+
+
+def _blocks_of(eng, N, n_samples):
+    """Block lengths _blocked cuts N points into (a recording callable: no kernel, no collective)."""
+    seen = []
+    eng._blocked(lambda xb, yb: (seen.append((len(xb), len(yb))), xb)[1], torch.zeros(N, 1), torch.zeros(N), n_samples=n_samples)
+    assert all(a == b for a, b in seen)
+    return [a for a, _ in seen]
+
+
+def test_conv_block_plan_is_one_per_group_at_config_5(monkeypatch):
+    """BASELINE config 5 shards n_samples = 500 over 8 ranks as 62 / 63 samples.  The pure formula gives those shards DIFFERENT blocks (3296 /
+    3248 points at 3x32x32, Hc = 512, the default budget), and inside a block the sharded step all-reduces [n, 16] and [n, D] tensors: cut by
+    its own count, a 62-sample rank would issue collectives of other sizes than a 63-sample rank.  The plan _blocked cuts by is therefore that
+    of the group's largest shard, on both kinds of rank: 10 000 points as 3248 + 3248 + 3248 + 256.  (The group is simulated: world size 2,
+    and a MAX all-reduce that answers as a peer holding 63 samples would.)"""
+    import torch.distributed as dist
+    from robustbnns_amd.conv import ConvEngine
+    monkeypatch.delenv("RBNN_CONV_WS_GB", raising=False)
+    monkeypatch.delenv("RBNN_FORCE_COLLECTIVES", raising=False)
+    monkeypatch.delenv("RBNN_FAKE_COLLECTIVES", raising=False)
+    shape, Hc = (3, 32, 32), 512
+    alone = ConvEngine(_ConvStub(shape, Hc, 62), kernels=FakeKernels())
+    assert alone.point_block(62) == 3296 and alone.point_block(63) == 3248          # shards of one group do get different pure plans
+    assert _blocks_of(alone, 10000, 62) == [3296, 3296, 3296, 112]                  # one rank: today's blocks, unchanged
+
+    reduced = []
+
+    def all_reduce(t, op=None, group=None, async_op=False):
+        assert op == dist.ReduceOp.MAX
+        reduced.append(float(t))
+        t.clamp_(min=63.0)                                                           # the other rank holds 63 samples
+
+    monkeypatch.setattr(dist, "get_world_size", lambda g=None: 2)
+    monkeypatch.setattr(dist, "all_reduce", all_reduce)
+    for S_local in (62, 63):
+        eng = ConvEngine(_ConvStub(shape, Hc, S_local), kernels=FakeKernels(), group=object(), total_samples=500)
+        assert _blocks_of(eng, 10000, S_local) == [3248, 3248, 3248, 256]
+        assert eng.group_point_block(S_local) == 3248
+        assert reduced == [float(S_local)]                                           # learnt once, when the engine is built: no exchange in a call on the whole shard
+        # a call on fewer samples than the shard: its largest count is exchanged (total_samples() exchanges there as well)
+        assert eng.group_point_block(10) == eng.point_block(63) and reduced == [float(S_local), 10.0]
+        reduced.clear()
+    # a 1-rank group with the collectives forced (the diagnostic world of 2): today's value, nothing exchanged
+    monkeypatch.setattr(dist, "get_world_size", lambda g=None: 1)
+    monkeypatch.setenv("RBNN_FORCE_COLLECTIVES", "1")
+    eng = ConvEngine(_ConvStub(shape, Hc, 62), kernels=FakeKernels(), group=object(), total_samples=62)
+    assert eng.world == 2 and _blocks_of(eng, 10000, 62) == [3296, 3296, 3296, 112] and reduced == []
+
+
+def test_conv_blocked_calls_slice_every_per_point_argument(monkeypatch):
+    """ConvEngine's public calls over three blocks (16 + 16 + 8), with the inherited AttackEngine calls replaced by row-wise stand-ins
+    that refuse arguments of unequal length: every per-point argument (y, x_attack, clean) is cut at the block's own rows, the parts are
+    joined in order (the norms=True tuple too), evaluate's accuracies are weighted by the block lengths, and before_step reaches every
+    block.  tests/test_hip_conv_blocking.py holds the same calls to the real kernels."""
+    from robustbnns_amd.conv import ConvEngine
+    monkeypatch.setenv("RBNN_CONV_WS_GB", "0.001")
+    eng = ConvEngine(_ConvStub((1, 28, 28), 32, 3), kernels=FakeKernels())
+    assert eng.point_block(3) == 16
+    N = 40
+    x, xa = torch.arange(float(N)).reshape(N, 1) + 0.25, torch.arange(float(N)).reshape(N, 1) * 7
+    y = torch.arange(N) * 3
+    clean = torch.arange(float(N)).reshape(N, 1) * 11 + torch.arange(16.)
+    lens = []
+
+    def same(*ts):
+        assert len({len(t) for t in ts}) == 1, [len(t) for t in ts]
+        lens.append(len(ts[0]))
+
+    def grads(self, xb, yb, n_samples, seeds=None, norms=False):
+        same(xb, yb)
+        g = xb * 2 + yb.reshape(-1, 1)
+        return (g, g[:, 0] + 1, g[:, 0] + 2) if norms else g
+
+    def attack(self, xb, yb, n_samples, epsilon=0.3, *a, before_step=None, **kw):
+        same(xb, yb)
+        if before_step is not None:
+            before_step()
+        return xb + epsilon * yb.reshape(-1, 1)
+
+    def pgd(self, xb, yb, n_samples, epsilon, alpha=None, iters=40, seeds=None, mode=_hip.LOSS_MEAN_PROB, before_step=None):
+        return attack(self, xb, yb, n_samples, epsilon, before_step=before_step)
+
+    def evaluate(self, xb, ab, yb, n_samples, logits=False, clean=None):
+        same(xb, ab, yb, *(() if clean is None else (clean,)))
+        o = clean if clean is not None else xb * 5
+        ok_o, ok_a = (yb < 60).double(), (yb < 30).double()                     # 20 / 10 of the 40 points, all in the first blocks
+        return 100 * float(ok_o.mean()), 100 * float(ok_a.mean()), xb[:, 0] + yb, o, ab * 2
+
+    for name, fn in (("loss_gradients", grads), ("fgsm", attack), ("pgd", pgd), ("evaluate", evaluate)):
+        monkeypatch.setattr(AttackEngine, name, fn)
+    g = x * 2 + y.reshape(-1, 1)
+    assert torch.equal(eng.loss_gradients(x, y, 3), g)
+    got = eng.loss_gradients(x, y, 3, norms=True)
+    assert isinstance(got, tuple) and all(torch.equal(a, b) for a, b in zip(got, (g, g[:, 0] + 1, g[:, 0] + 2)))
+    assert torch.equal(eng.fgsm(x, y, 3, 0.5), x + 0.5 * y.reshape(-1, 1))
+    ran = []
+    assert torch.equal(eng.pgd(x, y, 3, 0.25, iters=3, before_step=lambda: ran.append(1)), x + 0.25 * y.reshape(-1, 1)) and len(ran) == 3
+    for cl in (None, clean):
+        oa, aa, rob, o, a = eng.evaluate(x, xa, y, 3, clean=cl)
+        assert (oa, aa) == (50.0, 25.0)                                         # per block 100 / 25 / 0 and 62.5 / 0 / 0: the plain means are 41.7 and 20.8
+        assert torch.equal(rob, x[:, 0] + y) and torch.equal(o, x * 5 if cl is None else clean) and torch.equal(a, xa * 2)
+    assert lens == [16, 16, 8] * 6
+
+
+@pytest.mark.parametrize("shape", [(1, 28, 28), (3, 32, 32)])
+def test_conv_block_formula_restates_the_workspace_query(shape, monkeypatch):
+    """ConvEngine.point_block divides the budget by S x (bytes per (point, sample)); that figure restates rbnn_conv_workspace_query, the
+    sizes the workspace is allocated by.  The sum of every buffer the query reports must equal S x N x that figure exactly.  Two buffers of
+    ConvEngine.workspace are NOT proportional to S and stand outside the formula (and outside the query): Psum, 64 N bytes, and Gsum, 4 D N
+    bytes — 12 KB per point at 3x32x32 against 251 KB per (point, sample); the block sizes are left as they are."""
+    from robustbnns_amd.conv import ConvEngine
+    monkeypatch.delenv("RBNN_CONV_WS_GB", raising=False)
+    lib = _hip.load()
+    out = _hip.ConvWorkspaceSizes()
+    for Hc in (16, 32, 512, 1024):
+        eng = ConvEngine(_ConvStub(shape, Hc, 1), kernels=FakeKernels())
+        d = _hip.ConvPosterior()
+        d.activation, d.hidden, d.n_classes, d.n_stored, d.in_channels, d.in_width = 1, Hc, 10, 63, shape[0], shape[1]
+        for S in (1, 16, 62, 63):
+            for N in (16, 3296):
+                assert lib.rbnn_conv_workspace_query(C.byref(d), N, S, C.byref(out)) == 0
+                total = sum(getattr(out, f[0]) for f in out._fields_)                # every buffer the query knows
+                assert total == S * N * eng.bytes_per_sample(), (Hc, S, N)
+                budget = 48 * 2 ** 30
+                assert eng.point_block(S) == max(16, budget // (S * eng.bytes_per_sample()) // 16 * 16)
+
+
 # ----------------------------------------------------------------------------- f2: Pyro param-store files
 def test_pyro_param_store_layout_roundtrip(tmp_path):
     """BNN.load(inference="svi") reads a file in pyro 1.3.0's ParamStoreDict layout ({"params": unconstrained leaf tensors,
