@@ -22,6 +22,12 @@ _U8 = {"st1", "st2"}
 GEOMETRIES = {(1, 28, 28), (3, 32, 32)}
 
 
+def conv_ws_budget(budget_gb=None):
+    """Bytes of the conv workspace budget — budget_gb, or RBNN_CONV_WS_GB (default 48 GB of the 288 GB): what ConvEngine's point blocks and
+    the groups of the lockstep trainers and samplers (conv_train.conv_group) are cut to."""
+    return float(os.environ.get("RBNN_CONV_WS_GB", "48") if budget_gb is None else budget_gb) * 2 ** 30
+
+
 def conv_geometry(input_shape):
     """(pooled conv1 width, pooled conv2 width) of model_nn.py:98-106 on a Cin x W x W input: 5x5 convs, pool 2, pool 2 stride 1."""
     p1 = (int(input_shape[1]) - 4) // 2
@@ -353,8 +359,7 @@ class ConvEngine(AttackEngine):
 
     def point_block(self, S):
         """Points per block that S samples fit into the budget with: the pure formula, of this rank's quantities only."""
-        budget = float(os.environ.get("RBNN_CONV_WS_GB", "48")) * 2 ** 30
-        return max(16, int(budget // (S * self.bytes_per_sample())) // 16 * 16)
+        return max(16, int(conv_ws_budget() // (S * self.bytes_per_sample())) // 16 * 16)
 
     def _group_max(self, S):
         """max over the group's ranks of S (a 1-rank group, collectives forced or not: S itself, nothing is exchanged)."""

@@ -26,20 +26,12 @@ the conv workspace budget.
 What stays refused: the 3x32x32 geometry, CPU devices.
 """
 import ctypes as C
-import os
 
 import torch
 
 from . import _hip
-from .conv_train import _WS_DTYPES, CONV_KEYS, check_conv_trainable
+from .conv_train import CONV_KEYS, check_conv_trainable, conv_group, conv_net, conv_workspace, flat_of as chain_flat, tensor_major
 from .hmc import _LockstepChains, _OneChain
-
-
-def _conv_net(activation, hidden, n_classes):
-    net = _hip.ConvSviTrainNet()
-    net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-    net.hidden, net.n_classes = int(hidden), int(n_classes)
-    return net
 
 
 class ConvHmcSampler(_OneChain):
@@ -55,11 +47,11 @@ class ConvHmcSampler(_OneChain):
         check_conv_trainable(input_shape, device)
         super().__init__("conv", activation, input_shape, n_classes, [q0], float(step_size), num_steps, device, [key], adapt_step_size,
                          adapt_mass_matrix, None)
-        self._one_chain(_conv_net(activation, self.H, self.C), batch_size)
+        self._one_chain(conv_net(_hip.ConvSviTrainNet, activation, self.H, self.C), batch_size)
 
     def _hmc_sizes(self):
         nq, ne = C.c_int64(0), C.c_int64(0)
-        n = self.sizes("rbnn_conv_hmc_sizes", _conv_net(self.activation, self.H, self.C), nq, ne)
+        n = self.sizes("rbnn_conv_hmc_sizes", conv_net(_hip.ConvSviTrainNet, self.activation, self.H, self.C), nq, ne)
         return n, int(nq.value), int(ne.value)
 
     def _ensure(self, B):
@@ -67,14 +59,8 @@ class ConvHmcSampler(_OneChain):
             return
         sz = _hip.ConvTrainBytes()
         _hip.check(self.k.lib.rbnn_conv_svi_train_sizes(C.byref(self.net), B, None, C.byref(sz)), "rbnn_conv_svi_train_sizes")
-        self.ws_t = {}
-        for k in _hip.CONV_TRAIN_WS_KEYS:
-            dt = _WS_DTYPES.get(k, torch.float32)
-            self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
-        self.ws = _hip.fill(_hip.ConvTrainWs, self.ws_t)
-        self.X = torch.zeros(B, self.D, dtype=torch.float32, device=self.device)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.Bmax = B
+        self.ws_t, self.ws = conv_workspace(sz, _hip.CONV_TRAIN_WS_KEYS, _hip.ConvTrainWs, self.device)
+        self.staging(B)
 
     def _gradient(self):
         """dCE/dW and the per-point CE at self.W: the conv training forward (3 + 1 launches) + the conv weight gradients (7)."""
@@ -89,28 +75,9 @@ class ConvHmcSampler(_OneChain):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # K chains behind every launch
 # ---------------------------------------------------------------------------------------------------------------------------------------
-TENSOR_MAJOR = ("W", "grad", "q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2")      # the per-parameter buffers of K chains, [K * n_params]
-
-
-def tensor_major(flat, blocks):
-    """[K, n_params] chain-major (each row flat in state_dict order) -> [K * n_params] tensor-major: six blocks [K, size of tensor]."""
-    return torch.cat([t.reshape(-1) for t in flat.split(list(blocks), dim=1)])
-
-
-def chain_flat(buf, k, blocks, n_chains):
-    """Chain k's values of a tensor-major per-parameter buffer as a flat [n_params] tensor in state_dict order."""
-    out, off = [], 0
-    for size in blocks:
-        out.append(buf[off + k * size:off + (k + 1) * size])
-        off += n_chains * size
-    return torch.cat(out)
-
-
-def _chains_net(activation, hidden, n_classes, n_chains):
-    net = _hip.ConvHmcChainsNet()
-    net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-    net.hidden, net.n_classes, net.n_chains = int(hidden), int(n_classes), int(n_chains)
-    return net
+# The per-parameter buffers of K chains, [K * n_params] in conv_train's tensor-major layout: tensor_major(flat [K, n_params], blocks) makes one,
+# chain_flat(buf, k, blocks, K) (conv_train.flat_of) gives chain k's values back as a flat [n_params] tensor in state_dict order.
+TENSOR_MAJOR = ("W", "grad", "q_cur", "g_cur", "r", "m_inv", "w_mean", "w_m2")
 
 
 class ConvLockstepHmc(_LockstepChains):
@@ -143,11 +110,6 @@ class ConvLockstepHmc(_LockstepChains):
         self._lockstep(batch_size)
 
     @property
-    def blocks(self):
-        """The sizes of the six tensors in state_dict order."""
-        return [int(torch.Size(self.shapes[k]).numel()) for k in self.keys]
-
-    @property
     def m_inv(self):
         """The diagonal inverse masses, [K, n_params] chain-major (a copy)."""
         return torch.stack([chain_flat(self._m_inv, k, self.blocks, self.K) for k in range(self.K)])
@@ -164,16 +126,20 @@ class ConvLockstepHmc(_LockstepChains):
         """Chain k's values of one of the tensor-major buffers ("m_inv": self._m_inv) as a flat [n_params] tensor in state_dict order."""
         return chain_flat(buf, k, self.blocks, self.K)
 
+    def _net(self):
+        """A fresh descriptor of the K chains' nets, every pointer NULL (the sizes queries run before self.net is bound)."""
+        return conv_net(_hip.ConvHmcChainsNet, self.activation, self.H, self.C, n_chains=self.K)
+
     def _hmc_sizes(self):
         nq, ne = C.c_int64(0), C.c_int64(0)
-        net = _chains_net(self.activation, self.H, self.C, self.K)
+        net = self._net()
         n = int(self.k.lib.rbnn_conv_hmc_chains_sizes(C.byref(net), 0, C.byref(nq), C.byref(ne), None))     # no workspace sizes: no point count
         _hip.check(min(n, 0), "rbnn_conv_hmc_chains_sizes")
         return n, int(nq.value), int(ne.value)
 
     # -- buffers --------------------------------------------------------------------------------------------------------------------
     def _bind(self):
-        net = _chains_net(self.activation, self.H, self.C, self.K)
+        net = self._net()
         net.W, net.grad = self.W.data_ptr(), self.grad.data_ptr()
         self.net = net
         self._bind_chain(m_inv=self._m_inv)
@@ -183,13 +149,8 @@ class ConvLockstepHmc(_LockstepChains):
         if B <= self.Bmax:
             return
         sz = _hip.ConvEnsBytes()
-        net = _chains_net(self.activation, self.H, self.C, self.K)
-        _hip.check(min(int(self.k.lib.rbnn_conv_hmc_chains_sizes(C.byref(net), B, None, None, C.byref(sz))), 0), "rbnn_conv_hmc_chains_sizes")
-        self.ws_t = {}
-        for k in _hip.CONV_ENS_WS_KEYS:
-            dt = _WS_DTYPES.get(k, torch.float32)
-            self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
-        self.ws = _hip.fill(_hip.ConvEnsWs, self.ws_t)
+        _hip.check(min(int(self.k.lib.rbnn_conv_hmc_chains_sizes(C.byref(self._net()), B, None, None, C.byref(sz))), 0), "rbnn_conv_hmc_chains_sizes")
+        self.ws_t, self.ws = conv_workspace(sz, _hip.CONV_ENS_WS_KEYS, _hip.ConvEnsWs, self.device)
         self.Bmax = B
 
     # -- launches -------------------------------------------------------------------------------------------------------------------
@@ -237,12 +198,11 @@ class ConvLockstepHmc(_LockstepChains):
 
 def conv_hmc_chains_group(activation, hidden, n_classes, n_chains, batch_size, budget_gb=None):
     """The largest number of chains (<= n_chains, >= 1) whose packed workspaces for batch_size points and eight per-parameter buffers fit the
-    conv workspace budget, RBNN_CONV_WS_GB (default 48 GB of the 288 GB), following conv_train.conv_ensemble_group: the sizes are linear in
-    K, so one chain's figure decides.  Never more than a launch takes: 65535 chains, 2^22 packed points.  (The logs and the sample stacks
-    are not counted: [warmup + samples, 8] doubles and [samples, n_params] floats per chain.)"""
+    conv workspace budget (conv_train.conv_group), by rbnn_conv_hmc_chains_sizes for one chain.  Never more than a launch takes: 65535
+    chains, 2^22 packed points.  (The logs and the sample stacks are not counted: [warmup + samples, 8] doubles and [samples, n_params]
+    floats per chain.)"""
     out = _hip.ConvEnsBytes()
-    rc = int(_hip.load().rbnn_conv_hmc_chains_sizes(C.byref(_chains_net(activation, hidden, n_classes, 1)), int(batch_size), None, None, C.byref(out)))
-    _hip.check(min(rc, 0), "rbnn_conv_hmc_chains_sizes")
+    net = conv_net(_hip.ConvHmcChainsNet, activation, hidden, n_classes, n_chains=1)
+    _hip.check(min(int(_hip.load().rbnn_conv_hmc_chains_sizes(C.byref(net), int(batch_size), None, None, C.byref(out))), 0), "rbnn_conv_hmc_chains_sizes")
     per_chain = sum(getattr(out, k) for k in _hip.CONV_ENS_WS_KEYS) + len(TENSOR_MAJOR) * 4 * out.n_params
-    budget = float(os.environ.get("RBNN_CONV_WS_GB", "48") if budget_gb is None else budget_gb) * 2 ** 30
-    return max(1, min(int(n_chains), int(budget // per_chain), 65535, (1 << 22) // int(batch_size)))
+    return conv_group(per_chain, n_chains, budget_gb, 65535, (1 << 22) // int(batch_size))

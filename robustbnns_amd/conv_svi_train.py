@@ -31,16 +31,15 @@ What stays refused: the 3x32x32 geometry, CPU devices.  HMC posteriors of conv n
 (BNN.train_hmc_conv), on the forward and weight gradients this step runs; several chains at once by conv_hmc.ConvLockstepHmc.
 """
 import ctypes as C
-import os
 
 import torch
 import torch.nn.functional as F
 
 from . import _hip
 from .conv import ConvStackedPosterior, ConvSviGuide
-from .conv_train import _WS_DTYPES, CONV_KEYS, check_conv_trainable
-from .flat_params import FlatNets, flatten, keys_tensor, set_data
-from .svi_train import ACC_KEY, ACC_SAMPLES, ADAM_EPS, BETAS, LockstepSvi
+from .conv_train import CONV_KEYS, check_conv_trainable, conv_group, conv_net, conv_workspace, tensor_major, views
+from .flat_params import FlatNets, flatten
+from .svi_train import ACC_KEY, ACC_SAMPLES, ADAM_EPS, BETAS, LockstepGuides, LockstepSvi
 
 
 class _LiveConvGuide:
@@ -62,11 +61,7 @@ class ConvSviTrainer(FlatNets):
         check_conv_trainable(input_shape, device)
         super().__init__("conv", activation, input_shape, n_classes, loc, device, keys=CONV_KEYS)
         dev, z = self.device, self.zeros
-        self.Dp = self.D
-        net = _hip.ConvSviTrainNet()
-        net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-        net.hidden, net.n_classes = self.H, self.C
-        self.net = net
+        self.net = net = conv_net(_hip.ConvSviTrainNet, activation, self.H, self.C)
         sz, self.n_partials = self._sizes(1)
         n = self.n_params = int(sz.n_params)
         self.loc, self.raw = flatten(loc, self.keys).to(dev), flatten(raw, self.keys).to(dev)
@@ -92,31 +87,18 @@ class ConvSviTrainer(FlatNets):
         """Workspaces for batches of up to B points (grown, never shrunk: a short last batch reuses them)."""
         if B <= self.Bmax:
             return
-        dev, sz = self.device, self._sizes(B)[0]
-        self.ws_t = {}
-        for k in _hip.CONV_TRAIN_WS_KEYS:
-            dt = _WS_DTYPES.get(k, torch.float32)
-            self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=dev)
-        self.ws = _hip.fill(_hip.ConvTrainWs, self.ws_t)
-        self.X = torch.zeros(B, self.Dp, dtype=torch.float32, device=dev)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
+        dev = self.device
+        self.ws_t, self.ws = conv_workspace(self._sizes(B)[0], _hip.CONV_TRAIN_WS_KEYS, _hip.ConvTrainWs, dev)
         self.Psum = torch.zeros(B, _hip.CPAD, dtype=torch.float32, device=dev)
         sizes = self.k.conv_workspace_sizes(self.acc_post, B, ACC_SAMPLES)
         self.acc_ws = {k: torch.zeros(sizes[k] // (1 if k in ("st1", "st2") else 4), dtype=torch.uint8 if k in ("st1", "st2") else torch.float32,
                                       device=dev) for k in ("P", "P1", "st1", "Q2", "st2")}           # the forward's buffers: no dZ, no input gradients
-        self.Bmax = B
-
-    def _stage(self, x, labels):
-        B = int(x.shape[0])
-        self._ensure(B)
-        self.X[:B].copy_(x.reshape(B, -1))
-        self.labels[:B].copy_(labels.reshape(B))
-        return B
+        self.staging(B)
 
     def gradients(self, x, labels):
         """Draw + training forward + weight gradients of the NEXT step (no update): self.W holds the drawn weights, self.grad dCE/dW,
         ws_t["ce"] the per-point CE of the B points."""
-        B = self._stage(x, labels)
+        B = self.stage(x, labels)
         lib, st, net, ws = self.k.lib, _hip.stream_of(self.X), C.byref(self.net), C.byref(self.ws)
         _hip.check(lib.rbnn_conv_svi_train_draw(net, C.c_uint64(self.key), C.c_uint32(self.t & 0xFFFFFFFF), st), "rbnn_conv_svi_train_draw")
         _hip.check(lib.rbnn_conv_svi_train_forward(net, _hip.ptr(self.X), self.Dp, _hip.ptr(self.labels), B, ws, st), "rbnn_conv_svi_train_forward")
@@ -153,18 +135,10 @@ class ConvSviTrainer(FlatNets):
         return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
 
 
-_LOCKSTEP_WS_DTYPES = {**_WS_DTYPES, "acc_st1": torch.uint8, "acc_st2": torch.uint8}
 FLAT_BUFFERS = ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "W", "grad")
 
 
-def _lockstep_net(activation, hidden, n_classes, n_guides):
-    net = _hip.ConvSviLockstepNet()
-    net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-    net.hidden, net.n_classes, net.n_guides = int(hidden), int(n_classes), int(n_guides)
-    return net
-
-
-class ConvLockstepSvi(FlatNets):
+class ConvLockstepSvi(LockstepGuides):
     """K SVI guides of ONE conv net shape (activation, hidden size, classes; the 1x28x28 geometry) trained in lockstep: every launch of a step
     covers all K guides (csrc/rbnn_conv_train.hip, the rbnn_conv_svi_guides_* entry points).  The nine flat buffers are [K * n_params],
     TENSOR-MAJOR (six blocks [K, size of tensor] in state_dict order: unflat(buf, k) gives guide k's views), the workspaces packed [K, B, .] for
@@ -186,32 +160,15 @@ class ConvLockstepSvi(FlatNets):
     def __init__(self, activation, input_shape, n_classes, locs, raws, lrs, device, keys, batch_size=128):
         check_conv_trainable(input_shape, device)
         K = len(locs)
-        if K < 1:
-            raise ValueError("ConvLockstepSvi needs at least one guide")
-        if len(raws) != K or len(keys) != K:
-            raise ValueError(f"{K} guides need one raw-scale dict and one key per guide, not {len(raws)} and {len(keys)}")
-        lrs = [float(v) for v in lrs] if isinstance(lrs, (list, tuple)) else [float(lrs)] * K
-        if len(lrs) != K:
-            raise ValueError(f"{len(lrs)} learning rates for {K} guides")
-        if K * ACC_SAMPLES > 65535:
-            raise ValueError(f"{K} guides x {ACC_SAMPLES} accuracy samples exceed the 65535 nets of one launch")
-        if int(batch_size) < 1:
-            raise ValueError(f"batch_size must be at least 1, not {batch_size}")
-        shapes = {k: tuple(locs[0][k].shape) for k in CONV_KEYS}
-        for i in range(K):
-            for d in (locs[i], raws[i]):
-                if {k: tuple(d[k].shape) for k in shapes} != shapes:
-                    raise ValueError(f"guide {i} has another net shape than guide 0: lockstep guides share one (hidden, classes, input)")
+        lrs = self.refuse_bad_guides("ConvLockstepSvi", "(hidden, classes, input)", CONV_KEYS, locs, raws, lrs, keys, batch_size)
         super().__init__("conv", activation, input_shape, n_classes, locs[0], device, keys=CONV_KEYS)
         self.K = K
-        self.net = _lockstep_net(activation, self.H, self.C, K)
+        self.net = conv_net(_hip.ConvSviLockstepNet, activation, self.H, self.C, n_guides=K)
         sz = self._sizes(1)
         n = self.n_params = int(sz.n_params)
         self.n_partials = int(sz.n_partials)
-        self.blocks = [int(torch.Size(self.shapes[k]).numel()) for k in self.keys]
         assert sum(self.blocks) == n, (self.blocks, n)
-        # [K, n] guide-major -> six blocks [K, size]
-        major = lambda ds: torch.cat([t.reshape(-1) for t in torch.stack([flatten(d, self.keys) for d in ds]).split(self.blocks, dim=1)])
+        major = lambda ds: tensor_major(torch.stack([flatten(d, self.keys) for d in ds]), self.blocks)     # [K, n] guide-major -> six blocks [K, size]
         self.loc = major(locs).to(self.device)
         self.device = dev = self.loc.device                  # "cuda" names the current card: step() compares against where the buffers are
         self.raw = major(raws).to(dev)
@@ -220,10 +177,7 @@ class ConvLockstepSvi(FlatNets):
         self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = (z(K * n) for _ in range(6))
         self.kl_part = z(K * self.n_partials)
         self.stats = torch.zeros(K, 3, dtype=torch.float64, device=dev)
-        self.keys_list = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
-        self.keys_t = keys_tensor(self.keys_list, dev)
-        self.lrs = lrs
-        self.lr_t = torch.tensor(lrs, dtype=torch.float64).to(dev)
+        self.guide_values(lrs, keys)
         _hip.fill(self.net, {**vars(self), "keys": self.keys_t})
         self.net.part_stride = self.n_partials
         self.all_active = torch.ones(K, dtype=torch.int32, device=dev)
@@ -232,8 +186,6 @@ class ConvLockstepSvi(FlatNets):
         self.t = self.launches = self.Bmax = 0
         self._rows = {}
         self._ensure(int(batch_size))
-
-    set_data = set_data
 
     def _sizes(self, B):
         out = _hip.ConvSviLockstepBytes()
@@ -244,13 +196,8 @@ class ConvLockstepSvi(FlatNets):
         """Workspaces for batches of up to B points per guide (grown, never shrunk; a call packs them [K, its own B, .])."""
         if B <= self.Bmax:
             return
-        sz = self._sizes(B)
-        self.ws_t = {"acc_W": self.acc_W}
-        for k in _hip.CONV_SVI_LOCKSTEP_WS_KEYS:
-            if k != "acc_W":
-                dt = _LOCKSTEP_WS_DTYPES.get(k, torch.float32)
-                self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
-        self.ws = _hip.fill(_hip.ConvSviLockstepWs, self.ws_t)
+        self.ws_t, self.ws = conv_workspace(self._sizes(B), _hip.CONV_SVI_LOCKSTEP_WS_KEYS, _hip.ConvSviLockstepWs, self.device,
+                                            given={"acc_W": self.acc_W})
         self.Psum = self.ws_t["Psum"]
         self._arange = torch.arange(B, dtype=torch.int32, device=self.device).unsqueeze(0)
         self.Bmax = B
@@ -258,20 +205,11 @@ class ConvLockstepSvi(FlatNets):
     def unflat(self, buf, k=0):
         """state_dict key -> view of guide k's tensor inside its block of `buf` (one of the flat buffers), in that tensor's shape:
         ConvEnsembleTrainer.unflat."""
-        out, off = {}, 0
-        for key, size in zip(self.keys, self.blocks):
-            out[key] = buf[off + k * size:off + (k + 1) * size].reshape(self.shapes[key])
-            off += self.K * size
-        return out
+        return views(buf, k, self.K, self)
 
     def acc_sample(self, k, s):
         """state_dict key -> view of weight set s of guide k in the accuracy forward's stack (tensor-major over the K * 10 sets)."""
-        out, off, KS = {}, 0, self.K * ACC_SAMPLES
-        for key, size in zip(self.keys, self.blocks):
-            i = k * ACC_SAMPLES + s
-            out[key] = self.acc_W[off + i * size:off + (i + 1) * size].reshape(self.shapes[key])
-            off += KS * size
-        return out
+        return views(self.acc_W, k * ACC_SAMPLES + s, self.K * ACC_SAMPLES, self)
 
     def _checked(self, rows, active, epoch_slot=None):
         """(B, active) of a call, its arguments checked and the workspaces grown to B; nothing is launched before this."""
@@ -328,10 +266,6 @@ class ConvLockstepSvi(FlatNets):
         self.launches += 1
         self.t += 1
 
-    def begin_log(self, n_epochs):
-        """A zeroed device log [K, n_epochs, 2] for the epoch sums (loss, correct predictions)."""
-        self.epoch_log = torch.zeros(self.K, max(1, int(n_epochs)), 2, dtype=torch.float64, device=self.device)
-
     @staticmethod
     def schedule(n_points, epochs, batch_size, first_rows=None):
         """LockstepSvi.schedule for guides that share their point count (n_points: one number, or K equal ones): the unshuffled epochs as host
@@ -364,15 +298,6 @@ class ConvLockstepSvi(FlatNets):
         self.launches += 2
         self.step(rows, accuracy, s["slot"][t], s["active"][t])
 
-    def run(self, schedule, accuracy=True):
-        """Every step of a schedule(), the epoch sums into the device log (epoch_totals() reads it)."""
-        for t in range(self.load_schedule(schedule)):
-            self.scheduled_step(t, accuracy)
-
-    def epoch_totals(self):
-        """Per guide the list of (sum of the step losses, correct predictions) of its epochs: the one device->host read of a run."""
-        return [[(row[0], row[1]) for row in guide] for guide in self.epoch_log.tolist()]
-
     def params(self, k):
         """(loc, raw scale) of guide k as dicts state_dict key -> fresh device tensor."""
         return ({n: v.clone() for n, v in self.unflat(self.loc, k).items()}, {n: v.clone() for n, v in self.unflat(self.raw, k).items()})
@@ -380,11 +305,10 @@ class ConvLockstepSvi(FlatNets):
 
 def conv_svi_lockstep_group(activation, hidden, n_classes, n_guides, batch_size, budget_gb=None):
     """The largest number of guides (<= n_guides, >= 1) whose packed workspaces for batch_size points and nine flat buffers fit the conv
-    workspace budget, RBNN_CONV_WS_GB (default 48 GB of the 288 GB), following conv_train.conv_ensemble_group: rbnn_conv_svi_guides_sizes is
-    linear in K, so one guide's figure decides.  The accuracy forward's 10 x batch_size activations per guide are its large term."""
+    workspace budget (conv_train.conv_group), by rbnn_conv_svi_guides_sizes for one guide, and never more than a launch takes
+    (65535 // 10).  The accuracy forward's 10 x batch_size activations per guide are its large term."""
     out = _hip.ConvSviLockstepBytes()
-    _hip.check(_hip.load().rbnn_conv_svi_guides_sizes(C.byref(_lockstep_net(activation, hidden, n_classes, 1)), int(batch_size), C.byref(out)),
-               "rbnn_conv_svi_guides_sizes")
+    _hip.check(_hip.load().rbnn_conv_svi_guides_sizes(C.byref(conv_net(_hip.ConvSviLockstepNet, activation, hidden, n_classes, n_guides=1)),
+                                                      int(batch_size), C.byref(out)), "rbnn_conv_svi_guides_sizes")
     per_guide = sum(getattr(out, k) for k in _hip.CONV_SVI_LOCKSTEP_WS_KEYS) + len(FLAT_BUFFERS) * 4 * out.n_params
-    budget = float(os.environ.get("RBNN_CONV_WS_GB", "48") if budget_gb is None else budget_gb) * 2 ** 30
-    return max(1, min(int(n_guides), int(budget // per_guide), 65535 // ACC_SAMPLES))
+    return conv_group(per_guide, n_guides, budget_gb, 65535 // ACC_SAMPLES)

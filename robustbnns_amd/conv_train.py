@@ -14,6 +14,11 @@ rbnn_conv_ens_* entry points: 14 launches whatever M is).  Its flat buffers are 
 bit-identical to that net trained alone by ConvNnTrainer.  The host loop is nn_train.train_members, the one Ensemble_NN.train runs; members
 train in groups when their workspaces exceed the RBNN_CONV_WS_GB budget (conv_ensemble_group).
 
+What the six conv classes (these two, conv_svi_train's ConvSviTrainer / ConvLockstepSvi, conv_hmc's ConvHmcSampler / ConvLockstepHmc) share
+beyond flat_params.FlatNets stands here once: the net descriptor of the geometry (conv_net), the workspace allocator and its dtype table
+(conv_workspace), the tensor-major layout of the lockstep forms' flat buffers (tensor_major, views, flat_of) and the group budget
+(conv_group on conv.conv_ws_budget).  gradients() / step() / _gradient() stay written out in each class: they are the per-step path.
+
 What stays refused: every entry point of the fc trainers (NN.train, Ensemble_NN.train, NnTrainer, BNN.train, BNN.train_hmc, the lockstep
 forms) on a conv net, the 3x32x32 geometry.  SVI posteriors of conv nets are trained by
 conv_svi_train.ConvSviTrainer (BNN.train_conv; several guides in lockstep: conv_svi_train.ConvLockstepSvi, on the member kernels of the
@@ -21,18 +26,18 @@ ensemble) and HMC posteriors sampled by conv_hmc.ConvHmcSampler (BNN.train_hmc_c
 the member kernels too), on this module's forward and weight gradients.
 """
 import ctypes as C
-import os
 
 import torch
 
 from . import _hip
+from .conv import conv_ws_budget
 from .flat_params import flatten, require_gpu_fc
 from .nn_train import ENSEMBLE_BATCH, AdamNets, train_members, train_on_loader
 from .svi_train import ADAM_EPS, BETAS
 
 CONV_KEYS = [k + sfx for k in ("model.0", "model.3", "model.7") for sfx in (".weight", ".bias")]
 GEOMETRY = (1, 28, 28)
-_WS_DTYPES = {"st1": torch.uint8, "st2": torch.uint8, "correct": torch.int32, "labels": torch.int32}
+_WS_DTYPES = {"st1": torch.uint8, "st2": torch.uint8, "acc_st1": torch.uint8, "acc_st2": torch.uint8, "correct": torch.int32, "labels": torch.int32}
 
 
 def check_conv_trainable(input_shape, device):
@@ -42,6 +47,61 @@ def check_conv_trainable(input_shape, device):
         raise NotImplementedError(f"conv training covers the 1x28x28 geometry, not {tuple(input_shape)!r}")
 
 
+def conv_net(cls, activation, hidden, n_classes, **count):
+    """A net descriptor `cls` of _hip for a conv net of GEOMETRY with every pointer NULL; count: n_members / n_guides / n_chains = how many
+    nets the descriptor of a lockstep form covers."""
+    net = cls()
+    net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], GEOMETRY[0], GEOMETRY[1]
+    net.hidden, net.n_classes = int(hidden), int(n_classes)
+    for name, v in count.items():
+        setattr(net, name, int(v))
+    return net
+
+
+def conv_workspace(sizes, keys, struct_cls, device, given=None):
+    """(ws_t, ws): the zeroed workspace buffers named `keys`, of the byte counts a `*_sizes` entry point wrote into `sizes` (fp32 unless
+    _WS_DTYPES says otherwise), and the `struct_cls` of _hip that points at them.  given: key -> buffer that exists already."""
+    ws_t = dict(given or {})
+    for k in keys:
+        if k not in ws_t:
+            dt = _WS_DTYPES.get(k, torch.float32)
+            ws_t[k] = torch.zeros(getattr(sizes, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=device)
+    return ws_t, _hip.fill(struct_cls, ws_t)
+
+
+# The TENSOR-MAJOR layout of the lockstep forms' flat buffers, a device contract (the rbnn_conv_ens_* kernels address it): for n nets of one
+# shape, six blocks [n, size of tensor] in state_dict order, so net i's tensor t starts at n * (the single net's offset of t) + i * size.
+def tensor_major(flat, blocks):
+    """[n, n_params] net-major (each row flat in state_dict order) -> [n * n_params] tensor-major."""
+    return torch.cat([t.reshape(-1) for t in flat.split(list(blocks), dim=1)])
+
+
+def _slices(buf, i, n, blocks):
+    """Net i's slice of every block of a tensor-major buffer of n nets: views, in state_dict order."""
+    out, off = [], 0
+    for size in blocks:
+        out.append(buf[off + i * size:off + (i + 1) * size])
+        off += n * size
+    return out
+
+
+def views(buf, i, n, nets):
+    """state_dict key -> view of net i's tensor inside its block of `buf`, tensor-major over n nets, in that tensor's shape; nets: the
+    FlatNets whose state_keys / shapes / blocks describe one net."""
+    return {k: t.reshape(nets.shapes[k]) for k, t in zip(nets.state_keys, _slices(buf, i, n, nets.blocks))}
+
+
+def flat_of(buf, i, blocks, n):
+    """Net i's values of a tensor-major buffer of n nets as a flat [n_params] tensor in state_dict order (a copy)."""
+    return torch.cat(_slices(buf, i, n, blocks))
+
+
+def conv_group(per_net_bytes, n, budget_gb, *caps):
+    """The largest number of nets (<= n and the caps, >= 1) of per_net_bytes each that fit the conv workspace budget (conv.conv_ws_budget:
+    budget_gb, or RBNN_CONV_WS_GB, default 48 GB of the 288 GB).  The lockstep sizes are linear in the count, so one net's figure decides."""
+    return max(1, min(int(n), int(conv_ws_budget(budget_gb) // per_net_bytes), *caps))
+
+
 class ConvNnTrainer(AdamNets):
     """Device-resident training state of one conv net: flat parameters, Adam moments and gradients [n_params], the workspaces for up to Bmax
     points and a device-side accumulator stats [3] = [step loss, sum of step losses, correct predictions]."""
@@ -49,12 +109,8 @@ class ConvNnTrainer(AdamNets):
     def __init__(self, activation, input_shape, n_classes, params, lr, device, batch_size=ENSEMBLE_BATCH):
         check_conv_trainable(input_shape, device)
         super().__init__("conv", activation, input_shape, n_classes, params, device, keys=CONV_KEYS)
-        self.Dp = self.D
-        net = _hip.ConvTrainNet()
-        net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-        net.hidden, net.n_classes = self.H, self.C
-        self.net = net
-        self.adam_state(net, self._sizes(1).n_params, flatten(params, self.keys), lr)
+        self.net = conv_net(_hip.ConvTrainNet, activation, self.H, self.C)
+        self.adam_state(self.net, self._sizes(1).n_params, flatten(params, self.keys), lr)
         self._ensure(int(batch_size))
 
     def _sizes(self, B):
@@ -66,12 +122,7 @@ class ConvNnTrainer(AdamNets):
         """Workspaces for batches of up to B points (grown, never shrunk; a call packs them [its own B, .])."""
         if B <= self.Bmax:
             return
-        sz = self._sizes(B)
-        self.ws_t = {}
-        for k in _hip.CONV_TRAIN_WS_KEYS:
-            dt = _WS_DTYPES.get(k, torch.float32)
-            self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
-        self.ws = _hip.fill(_hip.ConvTrainWs, self.ws_t)
+        self.ws_t, self.ws = conv_workspace(self._sizes(B), _hip.CONV_TRAIN_WS_KEYS, _hip.ConvTrainWs, self.device)
         self.staging(B)
 
     def gradients(self, x, labels):
@@ -113,15 +164,10 @@ class ConvEnsembleTrainer(AdamNets):
             params_list = [params_list]
         super().__init__("conv", activation, input_shape, n_classes, params_list[0], device, keys=CONV_KEYS)
         self.M = len(params_list)
-        net = _hip.ConvEnsNet()
-        net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-        net.hidden, net.n_classes, net.n_members = self.H, self.C, self.M
-        self.net = net
+        self.net = conv_net(_hip.ConvEnsNet, activation, self.H, self.C, n_members=self.M)
         n = self._sizes(1).n_params
-        flat = torch.stack([flatten(p, self.keys) for p in params_list])                       # [M, n] member-major ...
-        sizes = [int(torch.Size(self.shapes[k]).numel()) for k in self.keys]
-        self.adam_state(net, self.M * n, torch.cat([t.reshape(-1) for t in flat.split(sizes, dim=1)]), lr)      # ... -> six blocks [M, size]
-        self.n_params, self.blocks = n, sizes
+        self.adam_state(self.net, self.M * n, tensor_major(torch.stack([flatten(p, self.keys) for p in params_list]), self.blocks), lr)
+        self.n_params = n
         self.stats = torch.zeros(self.M, 3, dtype=torch.float64, device=self.device)
         self.data = self.data_labels = None
         self._ensure(int(batch_size))
@@ -135,21 +181,12 @@ class ConvEnsembleTrainer(AdamNets):
         """Workspaces for batches of up to B points per member (grown, never shrunk; a call packs them [M, its own B, .])."""
         if B <= self.Bmax:
             return
-        sz = self._sizes(B)
-        self.ws_t = {}
-        for k in _hip.CONV_ENS_WS_KEYS:
-            dt = _WS_DTYPES.get(k, torch.float32)
-            self.ws_t[k] = torch.zeros(getattr(sz, k) // torch.empty(0, dtype=dt).element_size(), dtype=dt, device=self.device)
-        self.ws = _hip.fill(_hip.ConvEnsWs, self.ws_t)
+        self.ws_t, self.ws = conv_workspace(self._sizes(B), _hip.CONV_ENS_WS_KEYS, _hip.ConvEnsWs, self.device)
         self.Bmax = B
 
     def unflat(self, buf, member=0):
         """state_dict key -> view of member `member`'s tensor inside its block of `buf` (one of the flat buffers), in that tensor's shape."""
-        out, off = {}, 0
-        for k, size in zip(self.keys, self.blocks):
-            out[k] = buf[off + member * size:off + (member + 1) * size].reshape(self.shapes[k])
-            off += self.M * size
-        return out
+        return views(buf, member, self.M, self)
 
     def set_data(self, x, labels):
         """The resident data set the row indices of step(rows=...) refer to: x [N, ...] and integer labels [N], copied to the device once."""
@@ -199,15 +236,11 @@ class ConvEnsembleTrainer(AdamNets):
 
 def conv_ensemble_group(activation, hidden, n_classes, n_members, batch_size, budget_gb=None):
     """The largest number of members (<= n_members, >= 1) whose packed workspaces for batch_size points and four flat buffers fit the conv
-    workspace budget, RBNN_CONV_WS_GB (default 48 GB of the 288 GB): rbnn_conv_ens_sizes is linear in M, so one member's figure decides."""
-    net = _hip.ConvEnsNet()
-    net.activation, net.in_channels, net.in_width = _hip.ACTIVATIONS[activation], 1, 28
-    net.hidden, net.n_classes, net.n_members = int(hidden), int(n_classes), 1
+    workspace budget (conv_group), by rbnn_conv_ens_sizes for one member."""
     out = _hip.ConvEnsBytes()
-    _hip.check(_hip.load().rbnn_conv_ens_sizes(C.byref(net), int(batch_size), C.byref(out)), "rbnn_conv_ens_sizes")
-    per_member = sum(getattr(out, k) for k in _hip.CONV_ENS_WS_KEYS) + 4 * 4 * out.n_params
-    budget = float(os.environ.get("RBNN_CONV_WS_GB", "48") if budget_gb is None else budget_gb) * 2 ** 30
-    return max(1, min(int(n_members), int(budget // per_member)))
+    _hip.check(_hip.load().rbnn_conv_ens_sizes(C.byref(conv_net(_hip.ConvEnsNet, activation, hidden, n_classes, n_members=1)), int(batch_size),
+                                               C.byref(out)), "rbnn_conv_ens_sizes")
+    return conv_group(sum(getattr(out, k) for k in _hip.CONV_ENS_WS_KEYS) + 4 * 4 * out.n_params, n_members, budget_gb)
 
 
 def train_conv_ensemble(ens, x_train, y_train, device, group=None):

@@ -1,6 +1,9 @@
-"""What SviTrainer, LockstepSvi, NnTrainer, ConvNnTrainer, ConvSviTrainer, HmcSampler, ConvHmcSampler, LockstepHmc and ConvLockstepHmc share: the refusals (require_gpu_fc), the constructor
-state of a trainer of nets of one shape (FlatNets: shapes, sizes, the net descriptors, zeroed buffers, the parameter views; set_data: the resident data
-of the lockstep classes), the flat parameter buffers (state_dict order, unpadded, row-major) and the workspaces."""
+"""What SviTrainer, LockstepSvi, NnTrainer, HmcSampler, LockstepHmc and the six conv classes (ConvNnTrainer, ConvEnsembleTrainer, ConvSviTrainer,
+ConvLockstepSvi, ConvHmcSampler, ConvLockstepHmc) share: the refusals (require_gpu_fc), the constructor state of a trainer of nets of one shape
+(FlatNets: shapes, the tensors' sizes `blocks`, the net descriptors, zeroed buffers, the parameter views, the staged batch; set_data: the resident
+data of the lockstep classes), the flat parameter buffers (state_dict order, unpadded, row-major) and the workspaces.  What only the conv classes
+share is in conv_train.py (the 1x28x28 descriptor, the workspace allocator, the tensor-major layout, the group budget); what only the lockstep
+guides share is svi_train.LockstepGuides."""
 import ctypes as C
 
 import numpy as np
@@ -62,7 +65,8 @@ class FlatNets:
     """The constructor state of a trainer or sampler of nets of one shape, a single net (members None: buffers [n]) or `members` of them in
     lockstep (buffers [members, n]): the kernels' handle, arch / activation / device / input_shape, the state_dict keys (`state_keys`, and
     `keys` until a class puts something else there; those of fc / fc2 unless `keys` names them, as conv does) and `shapes` (taken from
-    `like`, a dict key -> tensor), D / H / C and fwd_launches."""
+    `like`, a dict key -> tensor) with their element counts `blocks`, D / H / C, Dp (the row stride of a staged batch: D until a class pads
+    it) and fwd_launches."""
 
     def __init__(self, arch, activation, input_shape, n_classes, like, device, members=None, keys=None):
         self.k = _hip.HipKernels()
@@ -70,7 +74,8 @@ class FlatNets:
         self.input_shape = tuple(int(v) for v in input_shape)
         self.state_keys = self.keys = state_keys(arch) if keys is None else list(keys)
         self.shapes = {k: tuple(like[k].shape) for k in self.state_keys}
-        self.D = int(np.prod(self.input_shape))
+        self.blocks = [int(np.prod(self.shapes[k])) for k in self.state_keys]
+        self.D = self.Dp = int(np.prod(self.input_shape))
         self.H, self.C = int(self.shapes[self.state_keys[-3]][0]), int(n_classes)      # the bias in front of the output layer: fc model.1, fc2 / conv model.3
         self.lead = () if members is None else (int(members),)
         self.fwd_launches = 2 if arch == "fc" else 4
@@ -97,6 +102,20 @@ class FlatNets:
     def unflat(self, buf):
         """state_dict key -> view of `buf` ([n_params] or [..., n_params]) in that tensor's shape."""
         return unflat(buf, self.state_keys, self.shapes)
+
+    def staging(self, B):
+        """The buffers of a staged batch of up to B points (X [B, Dp], labels [B]); the end of a class's _ensure(B)."""
+        self.X = torch.zeros(B, self.Dp, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.Bmax = B
+
+    def stage(self, x, labels):
+        """x [B, ...] and integer labels [B] into X / labels (the workspaces grown to B points first) -> B."""
+        B = int(x.shape[0])
+        self._ensure(B)
+        self.X[:B, :self.D].copy_(x.reshape(B, -1))
+        self.labels[:B].copy_(labels.reshape(B))
+        return B
 
 
 def set_data(self, x, labels):

@@ -373,9 +373,7 @@ class HmcSampler(_OneChain):
             return
         self.ws_t = train_workspace(self.arch, B, self.H, self.device)
         self.ws = _hip.fill(_hip.SviTrainWs, self.ws_t)
-        self.X = torch.zeros(B, self.D, dtype=torch.float32, device=self.device)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.Bmax = B
+        self.staging(B)
 
     def _gradient(self):
         """dCE/dW and the per-point CE at self.W: the training forward (fc 2 launches, fc2 4) + the weight gradients (1)."""

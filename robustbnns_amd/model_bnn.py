@@ -125,6 +125,35 @@ def svi_lockstep_prologue(net):
     return loc, raw, draw_key()
 
 
+def svi_lockstep_prologues(nets, device):
+    """svi_lockstep_prologue of every net in order, each put on `device` first -> (locs, raws, keys)."""
+    locs, raws, keys = [], [], []
+    for net in nets:
+        net.device = device
+        net.basenet.device = device
+        loc, raw, key = svi_lockstep_prologue(net)
+        locs.append(loc); raws.append(raw); keys.append(key)
+    return locs, raws, keys
+
+
+def record_svi_lockstep(trainer, nets, n_points, device, rel_path):
+    """The end of a lockstep run, net by net as BNN.train prints and saves: the epoch lines from the trainer's epoch_totals() (net k saw
+    n_points[k] points an epoch), training_history, set_variational_params from trainer.params(k), and save()."""
+    totals = trainer.epoch_totals()
+    for k, net in enumerate(nets):
+        print("\n == SVI training ==")
+        n, loss_list, accuracy_list = n_points[k], [], []
+        for epoch in range(net.epochs):
+            loss, correct = totals[k][epoch]
+            print(f"\n[Epoch {epoch + 1}]\t loss: {loss / n:.2f} \t accuracy: {100 * correct / n:.2f}", end="\t")
+            loss_list.append(loss)
+            accuracy_list.append(100 * correct / n)
+        net.training_history = {"loss": loss_list, "accuracy": accuracy_list}
+        loc, raw = trainer.params(k)
+        net.set_variational_params(loc, raw, device)
+        net.save(rel_path=rel_path, filename=None)
+
+
 def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS, batch_size=64):
     """BNN.train for several SVI nets of ONE net shape at once (svi_train.LockstepSvi: every kernel launch covers all of them).  The nets may
     differ in epochs, lr and training-set size: member k trains on x_train[:n_inputs[k]] in order, unshuffled, in batches of batch_size (what
@@ -150,29 +179,12 @@ def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS,
     if min(n_inputs) < 1:
         raise ValueError("every member needs at least one training point")
     from .svi_train import LockstepSvi
-    locs, raws, keys = [], [], []
-    for net in nets:
-        net.device = device
-        net.basenet.device = device
-        loc, raw, key = svi_lockstep_prologue(net)
-        locs.append(loc); raws.append(raw); keys.append(key)
+    locs, raws, keys = svi_lockstep_prologues(nets, device)
     trainer = LockstepSvi(b0.architecture, b0.activation, b0.input_shape, b0.output_size, locs, raws, [net.lr for net in nets], device, keys,
                           batch_size=int(batch_size))
     trainer.set_data(x_train, y_train.argmax(-1))
     trainer.run(LockstepSvi.schedule(n_inputs, [net.epochs for net in nets], int(batch_size)))
-    totals = trainer.epoch_totals()
-    for k, net in enumerate(nets):
-        print("\n == SVI training ==")
-        n, loss_list, accuracy_list = n_inputs[k], [], []
-        for epoch in range(net.epochs):
-            loss, correct = totals[k][epoch]
-            print(f"\n[Epoch {epoch + 1}]\t loss: {loss / n:.2f} \t accuracy: {100 * correct / n:.2f}", end="\t")
-            loss_list.append(loss)
-            accuracy_list.append(100 * correct / n)
-        net.training_history = {"loss": loss_list, "accuracy": accuracy_list}
-        loc, raw = trainer.params(k)
-        net.set_variational_params(loc, raw, device)
-        net.save(rel_path=rel_path, filename=None)
+    record_svi_lockstep(trainer, nets, n_inputs, device, rel_path)
     return trainer
 
 
@@ -218,28 +230,11 @@ def train_conv_svi_lockstep(nets, x_train, y_train, device, rel_path=TESTS, batc
     x_dev, lab_dev = x_train.to(device), y_train.argmax(-1).to(device)
     for first in range(0, len(nets), int(group)):
         members = nets[first:first + int(group)]
-        locs, raws, keys = [], [], []
-        for net in members:
-            net.device = device
-            net.basenet.device = device
-            loc, raw, key = svi_lockstep_prologue(net)
-            locs.append(loc); raws.append(raw); keys.append(key)
+        locs, raws, keys = svi_lockstep_prologues(members, device)
         trainer = ConvLockstepSvi(b0.activation, b0.input_shape, b0.output_size, locs, raws, [net.lr for net in members], device, keys, batch_size=B)
         trainer.set_data(x_dev, lab_dev)
         trainer.run(ConvLockstepSvi.schedule(n, [net.epochs for net in members], B))
-        totals = trainer.epoch_totals()
-        for k, net in enumerate(members):
-            print("\n == SVI training ==")
-            loss_list, accuracy_list = [], []
-            for epoch in range(net.epochs):
-                loss, correct = totals[k][epoch]
-                print(f"\n[Epoch {epoch + 1}]\t loss: {loss / n:.2f} \t accuracy: {100 * correct / n:.2f}", end="\t")
-                loss_list.append(loss)
-                accuracy_list.append(100 * correct / n)
-            net.training_history = {"loss": loss_list, "accuracy": accuracy_list}
-            loc, raw = trainer.params(k)
-            net.set_variational_params(loc, raw, device)
-            net.save(rel_path=rel_path, filename=None)
+        record_svi_lockstep(trainer, members, [n] * len(members), device, rel_path)
         del trainer
 
 

@@ -57,7 +57,6 @@ class NN(nn.Module):
     def set_model(self, architecture, activation, input_shape, output_size, hidden_size):
         """Same layer list as model_nn.py:60-124 (parameter container only)."""
         input_size = input_shape[0] * input_shape[1] * input_shape[2]
-        in_channels = input_shape[0]
         if activation not in _ACTIV:
             raise AssertionError("\nWrong activation name.")
         activ = _ACTIV[activation]
@@ -77,7 +76,7 @@ class NN(nn.Module):
             head = int(hidden_size / (4 * 4)) * input_size
             if self.dataset_name not in ["mnist", "fashion_mnist"]:
                 head = (((input_shape[1] - 4) // 2) - 5) ** 2 * hidden_size
-            self.model = nn.Sequential(nn.Conv2d(in_channels, 32, kernel_size=5), activ(), nn.MaxPool2d(kernel_size=2),
+            self.model = nn.Sequential(nn.Conv2d(input_shape[0], 32, kernel_size=5), activ(), nn.MaxPool2d(kernel_size=2),
                                        nn.Conv2d(32, hidden_size, kernel_size=5), activ(),
                                        nn.MaxPool2d(kernel_size=2, stride=1), nn.Flatten(),
                                        nn.Linear(head, output_size))

@@ -27,8 +27,8 @@ ENSEMBLE_BATCH = 100                    # model_ensemble.py:73
 
 
 class AdamNets(FlatNets):
-    """What NnTrainer and ConvNnTrainer (conv_train.py) share beyond FlatNets: the Adam buffers and their pointers in the net descriptor, the
-    statistics, lr / t, the staged batch and begin_epoch.  gradients() and step() are written out in each class (they are the per-step path)."""
+    """What NnTrainer, ConvNnTrainer and ConvEnsembleTrainer (conv_train.py) share beyond FlatNets: the Adam buffers and their pointers in the
+    net descriptor, the statistics, lr / t and begin_epoch.  gradients() and step() are written out in each class (they are the per-step path)."""
 
     def adam_state(self, net, n, P, lr):
         """P (CPU, [n] or [M, n]) onto the device beside zeroed m / v / grad, their addresses into `net`; stats [3] or [M, 3]; nothing staged."""
@@ -40,20 +40,6 @@ class AdamNets(FlatNets):
         self.lr, self.t = float(lr), 0
         self.Bmax = 0
         self.X = self.labels = None
-
-    def staging(self, B):
-        """The buffers of a staged batch of up to B points (step(x, labels)); the end of a class's _ensure(B)."""
-        self.X = torch.zeros(B, self.Dp, dtype=torch.float32, device=self.device)
-        self.labels = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.Bmax = B
-
-    def stage(self, x, labels):
-        """x [B, ...] and integer labels [B] into X / labels (the workspaces grown to B points first) -> B."""
-        B = int(x.shape[0])
-        self._ensure(B)
-        self.X[:B, :self.D].copy_(x.reshape(B, -1))
-        self.labels[:B].copy_(labels.reshape(B))
-        return B
 
     def begin_epoch(self):
         self.stats[..., 1:].zero_()

@@ -108,28 +108,18 @@ class SviTrainer(FlatNets):
         if B <= self.Bmax:
             return
         dev = self.device
-        e = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         self.ws_t = train_workspace(self.arch, B, self.H, dev)
         self.ws = _hip.fill(_hip.SviTrainWs, self.ws_t)
-        self.X = e(B, self.Dp)                                  # rows of Dp floats, zero columns [D, Dp): what rbnn_fc_forward reads
-        self.labels = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.Psum = e(B, _hip.CPAD)
+        self.Psum = torch.zeros(B, _hip.CPAD, dtype=torch.float32, device=dev)
         sizes = self.k.workspace_sizes(self.acc_post, B, ACC_SAMPLES)
         self.acc_ws = {k: torch.empty(max(1, sizes[k] // 4), dtype=torch.float32, device=dev) for k in _hip.WS_KEYS
                        if sizes[k] and k not in ("dZ", "slabs")}
-        self.Bmax = B
-
-    def _stage(self, x, labels):
-        B = int(x.shape[0])
-        self._ensure(B)
-        self.X[:B, :self.D].copy_(x.reshape(B, -1))
-        self.labels[:B].copy_(labels.reshape(B))
-        return B
+        self.staging(B)                                         # X: rows of Dp floats, zero columns [D, Dp): what rbnn_fc_forward reads
 
     def gradients(self, x, labels):
         """Draw + training forward + weight gradients of the NEXT step (no update): self.W holds the drawn weights, self.grad dCE/dW,
         ws_t["ce"] the per-point CE."""
-        B = self._stage(x, labels)
+        B = self.stage(x, labels)
         lib, st, net = self.k.lib, _hip.stream_of(self.X), C.byref(self.net)
         _hip.check(lib.rbnn_svi_train_draw(net, C.c_uint64(self.key), C.c_uint32(self.t & 0xFFFFFFFF), st), "rbnn_svi_train_draw")
         _hip.check(lib.rbnn_svi_train_forward(net, _hip.ptr(self.X), self.Dp, B, _hip.ptr(self.labels), C.byref(self.ws), st),
@@ -169,7 +159,56 @@ class SviTrainer(FlatNets):
         return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
 
 
-class LockstepSvi(FlatNets):
+class LockstepGuides(FlatNets):
+    """The host surface LockstepSvi and conv_svi_train.ConvLockstepSvi share: the refusals of a list of guides, the per-guide key and
+    learning-rate tensors, the resident data, the device log of the epoch sums and the run over a schedule.  schedule, load_schedule,
+    scheduled_step and step differ for real (counts against `active`, a fixed B against each step's own) and are each class's own."""
+    set_data = set_data
+
+    @staticmethod
+    def refuse_bad_guides(who, shape_words, state_keys, locs, raws, lrs, keys, batch_size):
+        """The refusals of K guides, before the library is loaded; shape_words: what lockstep guides share, in words.  -> the K learning rates."""
+        K = len(locs)
+        if K < 1:
+            raise ValueError(f"{who} needs at least one guide")
+        if len(raws) != K or len(keys) != K:
+            raise ValueError(f"{K} guides need one raw-scale dict and one key per guide, not {len(raws)} and {len(keys)}")
+        lrs = [float(v) for v in lrs] if isinstance(lrs, (list, tuple)) else [float(lrs)] * K
+        if len(lrs) != K:
+            raise ValueError(f"{len(lrs)} learning rates for {K} guides")
+        if K * ACC_SAMPLES > 65535:
+            raise ValueError(f"{K} guides x {ACC_SAMPLES} accuracy samples exceed the 65535 nets of one launch")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be at least 1, not {batch_size}")
+        shapes = {k: tuple(locs[0][k].shape) for k in state_keys}
+        for i in range(K):
+            for d in (locs[i], raws[i]):
+                if {k: tuple(d[k].shape) for k in shapes} != shapes:
+                    raise ValueError(f"guide {i} has another net shape than guide 0: lockstep guides share one {shape_words}")
+        return lrs
+
+    def guide_values(self, lrs, keys):
+        """The guides' Philox keys and learning rates on the host (keys_list, lrs) and on the device (keys_t, lr_t)."""
+        self.keys_list = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
+        self.keys_t = keys_tensor(self.keys_list, self.device)
+        self.lrs = lrs
+        self.lr_t = torch.tensor(lrs, dtype=torch.float64).to(self.device)
+
+    def begin_log(self, n_epochs):
+        """A zeroed device log [K, n_epochs, 2] for the epoch sums (loss, correct predictions)."""
+        self.epoch_log = torch.zeros(self.K, max(1, int(n_epochs)), 2, dtype=torch.float64, device=self.device)
+
+    def run(self, schedule, accuracy=True):
+        """Every step of a schedule(), the epoch sums into the device log (epoch_totals() reads it)."""
+        for t in range(self.load_schedule(schedule)):
+            self.scheduled_step(t, accuracy)
+
+    def epoch_totals(self):
+        """Per guide the list of (sum of the step losses, correct predictions) of its epochs: the one device->host read of a run."""
+        return [[(row[0], row[1]) for row in guide] for guide in self.epoch_log.tolist()]
+
+
+class LockstepSvi(LockstepGuides):
     """K SVI guides of ONE net shape (arch, activation, input shape, hidden size, classes) trained in lockstep: every launch of a step covers
     all K guides (csrc/rbnn_svi_lockstep.hip; the guide is grid dimension y).  Guide k has its own parameters, key, learning rate and batches —
     rows[k, :counts[k]] of the resident data (set_data) — and is bit-identical to an SviTrainer stepped alone on the same batches, except for the
@@ -184,20 +223,7 @@ class LockstepSvi(FlatNets):
     def __init__(self, arch, activation, input_shape, n_classes, locs, raws, lrs, device, keys, batch_size=64):
         require_gpu_fc("SVI training", arch, device)
         K = len(locs)
-        if K < 1:
-            raise ValueError("LockstepSvi needs at least one guide")
-        if len(raws) != K or len(keys) != K:
-            raise ValueError(f"{K} guides need one raw-scale dict and one key per guide, not {len(raws)} and {len(keys)}")
-        lrs = [float(v) for v in lrs] if isinstance(lrs, (list, tuple)) else [float(lrs)] * K
-        if len(lrs) != K:
-            raise ValueError(f"{len(lrs)} learning rates for {K} guides")
-        if K * ACC_SAMPLES > 65535:
-            raise ValueError(f"{K} guides x {ACC_SAMPLES} accuracy samples exceed the 65535 nets of one launch")
-        shapes = {k: tuple(locs[0][k].shape) for k in state_keys(arch)}
-        for i in range(K):
-            for d in (locs[i], raws[i]):
-                if {k: tuple(d[k].shape) for k in shapes} != shapes:
-                    raise ValueError(f"guide {i} has another net shape than guide 0: lockstep guides share one (arch, hidden, classes, input)")
+        lrs = self.refuse_bad_guides("LockstepSvi", "(arch, hidden, classes, input)", state_keys(arch), locs, raws, lrs, keys, batch_size)
         super().__init__(arch, activation, input_shape, n_classes, locs[0], device, members=K)
         self.K, n_part = K, C.c_int64(0)
         n = self.sizes("rbnn_svi_train_sizes", self.descriptor(_hip.SviTrainNet), n_part)
@@ -216,10 +242,8 @@ class LockstepSvi(FlatNets):
         self.m_loc, self.v_loc, self.m_raw, self.v_raw, self.W, self.grad = z(n), z(n), z(n), z(n), z(n), z(n)
         self.kl_part = z(self.n_partials)
         self.stats = torch.zeros(K, 3, dtype=torch.float64, device=dev)
-        self.keys = [int(k) & 0xFFFFFFFFFFFFFFFF for k in keys]
-        self.keys_t = keys_tensor(self.keys, dev)
-        self.lrs = lrs
-        self.lr_t = torch.tensor(lrs, dtype=torch.float64).to(dev)
+        self.guide_values(lrs, keys)
+        self.keys = self.keys_list
         self.t = 0
         net = self.descriptor(_hip.NnTrainNet, K)
         net.P, net.grad, net.member_stride = self.W.data_ptr(), self.grad.data_ptr(), n
@@ -229,8 +253,6 @@ class LockstepSvi(FlatNets):
         self.X = self.labels = None
         self.epoch_log = None
         self.B = int(batch_size)
-        if self.B < 1:
-            raise ValueError(f"batch_size must be at least 1, not {batch_size}")
         S = ACC_SAMPLES
         self.ws_t = train_workspace(arch, K * self.B, self.H, dev)
         self.ws_t["correct"] = torch.zeros(K * self.B, dtype=torch.int32, device=dev)
@@ -244,8 +266,6 @@ class LockstepSvi(FlatNets):
         self.rows_t = torch.zeros(K, self.B, dtype=torch.int32, device=dev)
         self._arange = torch.arange(self.B, dtype=torch.int32, device=dev).unsqueeze(0)
         self.launches = 0
-
-    set_data = set_data
 
     def step(self, rows, counts, accuracy=True, epoch_slot=None):
         """One SVI step of every guide with counts[k] > 0 on rows[k, :counts[k]] of the resident data.  rows: int32 device tensor [K, batch_size]
@@ -283,10 +303,6 @@ class LockstepSvi(FlatNets):
         self.launches += 1
         self.t += 1
 
-    def begin_log(self, n_epochs):
-        """A zeroed device log [K, n_epochs, 2] for the epoch sums (loss, correct predictions)."""
-        self.epoch_log = torch.zeros(self.K, max(1, int(n_epochs)), 2, dtype=torch.float64, device=self.device)
-
     @staticmethod
     def schedule(n_points, epochs, batch_size, first_rows=None):
         """The unshuffled epochs of K members as host tensors [T, K] (T = the longest member's number of steps): member k walks rows
@@ -321,15 +337,6 @@ class LockstepSvi(FlatNets):
         torch.minimum(self.rows_t, s["last"][t].unsqueeze(1), out=self.rows_t)
         self.launches += 2
         self.step(self.rows_t, s["count"][t], accuracy, s["slot"][t])
-
-    def run(self, schedule, accuracy=True):
-        """Every step of a schedule(), the epoch sums into the device log (epoch_totals() reads it)."""
-        for t in range(self.load_schedule(schedule)):
-            self.scheduled_step(t, accuracy)
-
-    def epoch_totals(self):
-        """Per member the list of (sum of the step losses, correct predictions) of its epochs: the one device->host read of a run."""
-        return [[(row[0], row[1]) for row in member] for member in self.epoch_log.tolist()]
 
     def params(self, k):
         """(loc, raw scale) of guide k as dicts state_dict key -> fresh device tensor."""
