@@ -1146,6 +1146,51 @@ int rbnn_conv_hmc_chains_commit(const rbnn_conv_hmc_chains_net *net, const rbnn_
 /* rbnn_hmc_lockstep_window_end: the single chain's window end on every active chain.  1 launch. */
 int rbnn_conv_hmc_chains_window_end(const rbnn_conv_hmc_chains_net *net, const rbnn_hmc_lockstep *chains, int32_t n_window, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * fp64 precision mode of the fc / fc2 forward and expected input gradient (csrc/rbnn_fp64.inc): the checker at workload size.
+ * The DATA stay fp32 — the posterior exactly as rbnn_posterior holds it, X, the attack iterates — and are widened on load, which
+ * is exact; every operation from the first product to the written result is fp64: the contractions over D and H on
+ * v_mfma_f64_16x16x4_f64 with fp64 accumulators, bias and activation (leaky slope 0.01 as a double), softmax with the maximum
+ * subtracted, the three label losses, act', the sum over samples, the norms.  No atomics and one fixed accumulation order per result
+ * element (K ascending, samples ascending): two runs are bit-identical, and a point's result depends neither on n_points nor on the
+ * 16-point tile or point block it ran in.  All four activations, n_classes <= 16, hidden a multiple of 4 (RBNN_ERR_SHAPE otherwise;
+ * none of the 32 / 64 / k*128 rule of the fp32 kernels), n_samples <= 65535.  No counterpart in the reference (it computes in fp32).
+ * Every buffer below is fp64, caller-owned, 16-byte aligned; per-sample buffers are indexed by POSITION in the call (0 .. n_samples-1),
+ * the weights by sample_idx.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_F64_WS_BUFFERS 6
+/* bytes[0 .. 5] <- sizes of P [S,N,16], dZ [S,N,16], Psum [N,16], dact1 [S,N,H], hid1 [S,N,H] (fc2, else 0), dact2 [S,N,H] (fc2, else 0)
+ * for N points x S used samples. [host; bytes: host array of RBNN_F64_WS_BUFFERS] */
+int rbnn_f64_workspace_query(const rbnn_posterior *net, int32_t n_points, int32_t n_samples, size_t *bytes);
+
+/* rbnn_fc_forward in fp64: P[s] = softmax(NN_s(X)) (or logits; columns >= C are 0) and the stash act'(pre-activation) of every hidden
+ * layer: dact1 (and, fc2, dact2; hid1 takes the first hidden activations between the two launches).  X: fp32 [N, ldx], ldx >= D_pad,
+ * multiple of 4, columns [D, D_pad) zero.  fc: 1 launch, fc2: 2. */
+int rbnn_fc_forward_f64(const rbnn_posterior *net, const float *X, int32_t ldx, int32_t n_points, const int32_t *sample_idx,
+                        int32_t n_samples, int32_t out_kind, double *P, double *dact1, double *hid1, double *dact2, void *stream);
+
+/* rbnn_reduce_samples in fp64: out[n,c] = scale * sum_s P[s,n,c], s = 0, 1, ... in that order (c < C; out row stride ldo doubles). */
+int rbnn_reduce_samples_f64(const double *P, int32_t n_samples, int32_t n_points, int32_t n_classes, double scale, double *out,
+                            int32_t ldo, void *stream);
+
+/* rbnn_loss_dlogits in fp64 for the three label losses (RBNN_LOSS_MEAN_PROB — the double softmax —, RBNN_LOSS_PER_SAMPLE,
+ * RBNN_LOSS_MEAN_LOGIT; the upstream modes of the autograd hook: RBNN_ERR_UNSUPPORTED).  inv_S multiplies every dZ, the per-sample
+ * loss included (the 1/S of lossGradients.py:40 is folded in here).  Psum [N,ldp]: sum_s P[s], not needed for RBNN_LOSS_PER_SAMPLE. */
+int rbnn_loss_dlogits_f64(int32_t mode, const double *P, const double *Psum, int32_t ldp, const int32_t *labels, int32_t n_samples,
+                          double inv_S, int32_t n_points, int32_t n_classes, double *dZ, void *stream);
+
+/* rbnn_fc_input_grad + rbnn_sum_slabs_norms in fp64: G[n,d] = scale * sum_s (dA_s[n,:] . W1_s)[d] for d < D_pad (row stride ldg
+ * doubles), the samples summed in ascending order inside one accumulator: no slabs.  linf / l2 (nullable, [N]): the norms of every
+ * row over d < D.  CONSUMES the stash: dact1 (and dact2) of rbnn_fc_forward_f64 are overwritten with dL/d(pre-activation) — one
+ * backward per forward.  fc: 2 launches, fc2: 3; + 1 with norms. */
+int rbnn_fc_input_grad_f64(const rbnn_posterior *net, const int32_t *sample_idx, int32_t n_samples, int32_t n_points, const double *dZ,
+                           double *dact1, double *dact2, double scale, double *G, int32_t ldg, double *linf, double *l2, void *stream);
+
+/* rbnn_attack_step with the SIGN read from an fp64 gradient G [N, ldg]: X, X0, alpha, eps and the arithmetic on X are that call's
+ * (fp32, both the FGSM and the PGD form) — given equal signs the images are bit-equal to its. */
+int rbnn_attack_step_f64(float *X, const float *X0, int32_t ldx, const double *G, int32_t ldg, const float *alpha, float alpha_scalar,
+                         float eps, int32_t project, int32_t n_points, int32_t in_features, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,8 @@ SVI_TRAIN_WS_KEYS, NN_TRAIN_WS_KEYS, CONV_TRAIN_WS_KEYS = _keys(SviTrainWs), _ke
 CONV_ENS_WS_KEYS = _keys(ConvEnsWs)
 CONV_SVI_LOCKSTEP_WS_KEYS = _keys(ConvSviLockstepWs)
 SVI_LOCKSTEP_ACC_KEYS = _keys(SviLockstepAcc)
+F64_WS_KEYS = ("P", "dZ", "Psum", "dact1", "hid1", "dact2")        # rbnn_f64_workspace_query's order (plain fp64 pointers: no struct)
+assert len(F64_WS_KEYS) == F64_WS_BUFFERS
 
 _lib = None
 
@@ -290,6 +292,35 @@ class HipKernels:
             w.dZ = None
         return self._fc_input_grad_pieces("rbnn_fc_input_grad_triple", net.descriptor(lazy_ok=True), images, sidx, S, N, chunk, w,
                                           fill(TripleWorkspace, tws), stream_of(ws["slabs"]))
+
+    # -- fp64 mode (rbnn_fp64.inc): fp32 data widened on load, every operation in fp64 --------------------
+    def f64_workspace_sizes(self, net, N, S):
+        out = (C.c_size_t * F64_WS_BUFFERS)()
+        check(self.lib.rbnn_f64_workspace_query(C.byref(net.descriptor(lazy_ok=True)), N, S, out), "rbnn_f64_workspace_query")
+        return dict(zip(F64_WS_KEYS, out))
+
+    def fc_forward_f64(self, net, X, sidx, S, out_kind, ws):
+        """ws: dict of float64 tensors keyed like F64_WS_KEYS.  (descriptor(): a pending images-only SVI draw is completed — this mode
+        reads the fp32 weight stack.)"""
+        require_gpu(X, "X")
+        check(self.lib.rbnn_fc_forward_f64(C.byref(net.descriptor()), ptr(X), X.stride(0), X.shape[0], ptr(sidx), S, out_kind, ptr(ws["P"]),
+                                           ptr(ws["dact1"]), ptr(ws.get("hid1")), ptr(ws.get("dact2")), stream_of(X)), "rbnn_fc_forward_f64")
+
+    def reduce_samples_f64(self, P, S, N, Cn, scale, out):
+        check(self.lib.rbnn_reduce_samples_f64(ptr(P), S, N, Cn, scale, ptr(out), out.stride(0), stream_of(P)), "rbnn_reduce_samples_f64")
+
+    def loss_dlogits_f64(self, mode, P, Psum, labels, S, inv_S, N, Cn, dZ):
+        check(self.lib.rbnn_loss_dlogits_f64(mode, ptr(P), ptr(Psum), CPAD, ptr(labels), S, inv_S, N, Cn, ptr(dZ), stream_of(P)),
+              "rbnn_loss_dlogits_f64")
+
+    def fc_input_grad_f64(self, net, sidx, S, N, ws, scale, G, linf=None, l2=None):
+        check(self.lib.rbnn_fc_input_grad_f64(C.byref(net.descriptor()), ptr(sidx), S, N, ptr(ws["dZ"]), ptr(ws["dact1"]), ptr(ws.get("dact2")),
+                                              scale, ptr(G), G.stride(0), ptr(linf), ptr(l2), stream_of(G)), "rbnn_fc_input_grad_f64")
+
+    def attack_step_f64(self, X, X0, G, alpha, alpha_scalar, eps, project, D):
+        require_gpu(X, "X")
+        check(self.lib.rbnn_attack_step_f64(ptr(X), ptr(X0), X.stride(0), ptr(G), G.stride(0), ptr(alpha), alpha_scalar, eps, int(project),
+                                            X.shape[0], D, stream_of(X)), "rbnn_attack_step_f64")
 
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):

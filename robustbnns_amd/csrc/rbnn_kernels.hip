@@ -967,3 +967,6 @@ int rbnn_svi_materialize(const float* loc, const float* scale_raw, const float* 
 }
 
 }  // extern "C"
+
+// the fp64 precision mode (fc / fc2 forward and expected input gradient on the f64 MFMA): kernels and C-ABI
+#include "rbnn_fp64.inc"

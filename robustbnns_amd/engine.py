@@ -23,6 +23,9 @@ gradient or a whole T-iteration attack is ONE launch of rbnn_lowdim_run (rbnn_lo
 torch supplies device memory, the current HIP stream and torch.distributed (RCCL); all arithmetic is
 in the HIP kernels behind `kernels` (robustbnns_amd._hip.HipKernels — there is no other backend in
 this package; tests inject a CPU fake to exercise the multi-process orchestration under gloo).
+"fp64" (opt-in, never picked by auto / fast): fc / fc2 on one GPU with the fp32 data widened on load and every operation in fp64, the
+contractions on the f64 MFMA (rbnn_fc_forward_f64 / rbnn_fc_input_grad_f64, rbnn_fp64.inc): forward, the three label-loss gradients and their
+norms come back as float64, fgsm / pgd images stay fp32 (only the gradient's sign is read).  The device-side checker of the other modes.
 """
 import os
 
@@ -126,8 +129,21 @@ class AttackEngine:
         same 1e-5 parity bar, and the same adversarial accuracy in the split-vs-exact tests) — OPT-IN, raises where the split
         kernels do not cover the posterior.  fast: split where it applies, else exact.  RBNN_PRECISION sets the default."""
         want = (precision or os.environ.get("RBNN_PRECISION") or "auto").lower()
-        if want not in ("auto", "exact", "triple", "split", "fast", "lowdim"):
-            raise ValueError(f"precision={want!r}: expected 'auto', 'exact', 'triple', 'split', 'fast' or 'lowdim'")
+        if want not in ("auto", "exact", "triple", "split", "fast", "lowdim", "fp64"):
+            raise ValueError(f"precision={want!r}: expected 'auto', 'exact', 'triple', 'split', 'fast', 'lowdim' or 'fp64'")
+        # fp64 (OPT-IN; auto and fast never pick it): the fp32 data widened on load, every operation from the first product to the written
+        # result in fp64, the contractions on the f64 MFMA (rbnn_fp64.inc) — the checker at workload size.  fc / fc2 on ONE GPU; everything it
+        # does not cover is refused here, before anything is launched: an answer computed in fp32 under this name would be a lie.
+        if want == "fp64":
+            if getattr(self.post, "arch", None) not in ("fc", "fc2"):
+                raise _hip.HipError("precision='fp64' covers fc and fc2 posteriors: there are no fp64 conv kernels")
+            if self.world > 1:
+                raise _hip.HipError("precision='fp64' runs on one GPU: fp64 under sample- or point-sharding (a process group of more than "
+                                    "one rank) is not built")
+            if not isinstance(self.k, _hip.HipKernels) or self.device.type != "cuda":
+                raise _hip.HipError("precision='fp64' needs the HIP kernels and a posterior on the GPU: there is no fp64 path on a CPU device "
+                                    "or through substitute kernels")
+            return "fp64"
         # lowdim: in_features <= 16 (half-moons).  The contractions are then a few FMAs per hidden unit and a pass is bound by the launch
         # floor of the 7 kernels above: one kernel does the forward / the expected gradient / ALL iterations of an attack in fp32 FMA
         # arithmetic (rbnn_lowdim.hip).  Single process only (the sample-sharded step needs its all-reduces between the phases); calls it
@@ -377,9 +393,67 @@ class AttackEngine:
         out = torch.empty(8, dtype=torch.int32, device=self.device)
         return self.k.input_scales(X, self.post.D, 1.0 if iterates else 0.0, mul, add, cap, out)
 
+    # ------------------------------------------------------------------ fp64 mode (rbnn_fp64.inc)
+    def _fp64_block(self, S):
+        """Points per block of the fp64 path: the fp64 workspaces of a block (probabilities, dZ and the act' stash of every hidden layer:
+        8 S (32 + H) bytes per point, fc2 8 S (32 + 3 H)) stay within RBNN_FP64_WS_GB (default 4).  A multiple of the kernels' 16-point tile,
+        at least one tile; every result element is one accumulation chain that does not know its block, so blocking changes no bits."""
+        per_point = sum(self.k.f64_workspace_sizes(self.post, 1, S).values())
+        budget = float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
+        return max(16, int(budget // per_point) // 16 * 16)
+
+    def _fp64_buffer(self, n_bytes):
+        return torch.empty(n_bytes // 8, dtype=torch.float64, device=self.device)
+
+    def _fp64_workspace(self, N, S):
+        key = ("fp64", N, S)
+        ws = self._ws_cache.pop(key, None)
+        if ws is None:
+            ws = {k: self._fp64_buffer(v) for k, v in self.k.f64_workspace_sizes(self.post, N, S).items() if v}
+            while len(self._ws_cache) > 6:
+                self._ws_cache.pop(next(iter(self._ws_cache)))
+        self._ws_cache[key] = ws
+        return ws
+
+    def _fp64_blocks(self, N, S):
+        nb = self._fp64_block(S)
+        return [(lo, min(N, lo + nb)) for lo in range(0, N, nb)]
+
+    def _fp64_forward(self, Xp, sidx, S, out_kind, out=None):
+        """forward_padded in fp64: float64 [N, 16]."""
+        N = Xp.shape[0]
+        if out is None:
+            out = torch.zeros(N, _hip.CPAD, dtype=torch.float64, device=self.device)
+        for lo, hi in self._fp64_blocks(N, S):
+            ws = self._fp64_workspace(hi - lo, S)
+            self.k.fc_forward_f64(self.post, Xp[lo:hi], sidx, S, out_kind, ws)
+            self.k.reduce_samples_f64(ws["P"], S, hi - lo, self.post.C, 1.0 / S, out[lo:hi])
+        return out
+
+    def _fp64_gradient(self, Xp, labels, sidx, S, mode, norms=None):
+        """gradient() in fp64: the summed expected input gradient, float64 [N, D_pad] (a fresh tensor), from forward + sum over samples +
+        loss + backward per point block.  The 1/S of every loss is inside dZ, as in the fp64 oracle."""
+        if mode not in (LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT):
+            raise _hip.HipError("precision='fp64' differentiates the three label losses; the autograd hook's upstream gradient is not built in fp64")
+        N, p = Xp.shape[0], self.post
+        G = torch.empty(N, p.Dp, dtype=torch.float64, device=self.device)
+        for lo, hi in self._fp64_blocks(N, S):
+            n, ws = hi - lo, self._fp64_workspace(hi - lo, S)
+            self.k.fc_forward_f64(p, Xp[lo:hi], sidx, S, OUT_LOGITS if mode == LOSS_MEAN_LOGIT else OUT_PROBS, ws)
+            Psum = None
+            if mode != LOSS_PER_SAMPLE:
+                Psum = ws["Psum"].view(n, _hip.CPAD)
+                self.k.reduce_samples_f64(ws["P"], S, n, p.C, 1.0, Psum)
+            self.k.loss_dlogits_f64(mode, ws["P"], Psum, labels[lo:hi], S, 1.0 / S, n, p.C, ws["dZ"])
+            self.k.fc_input_grad_f64(p, sidx, S, n, ws, 1.0, G[lo:hi], None if norms is None else norms[0][lo:hi],
+                                     None if norms is None else norms[1][lo:hi])
+        return G
+
     # ------------------------------------------------------------------ forward
     def forward_padded(self, Xp, sidx, S, out_kind=OUT_PROBS, out=None):
-        """mean over samples of P (probabilities or logits) -> [N, 16] buffer (columns >= C are zero)."""
+        """mean over samples of P (probabilities or logits) -> [N, 16] buffer (columns >= C are zero); precision fp64: float64."""
+        if self.precision == "fp64":
+            return self._fp64_forward(Xp, sidx, S, out_kind, out)
         N = Xp.shape[0]
         if out is None:
             out = torch.zeros(N, _hip.CPAD, dtype=torch.float32, device=self.device)
@@ -398,6 +472,9 @@ class AttackEngine:
 
     def forward(self, x, n_samples, seeds=None, logits=False):
         sidx, S = self.sample_index(n_samples, seeds)
+        if self.precision == "fp64" and torch.is_grad_enabled() and x.requires_grad:
+            raise _hip.HipError("precision='fp64': the autograd hook (an input with requires_grad) is not built in fp64, and its fp32 backward "
+                                "must not answer under this name; detach the input, or use loss_gradients / fgsm / pgd")
         if torch.is_grad_enabled() and x.requires_grad:
             # callers that differentiate the forward themselves (the reference's own fgsm_attack does:
             # adversarialAttacks.py:73-79): the backward is the HIP input-gradient path with the upstream dL/dout
@@ -463,7 +540,12 @@ class AttackEngine:
 
     def gradient(self, Xp, labels, sidx, S, mode, G_up=None, norms=None):
         """Summed (and, sample-sharded, all-reduced) expected input gradient [N, D_pad].  norms = (linf [N], l2 [N]) device
-        buffers: filled with the per-point norms of that gradient in the same pass as the slab sum (rbnn_sum_slabs_norms)."""
+        buffers: filled with the per-point norms of that gradient in the same pass as the slab sum (rbnn_sum_slabs_norms).
+        precision fp64: float64, gradient and norms."""
+        if self.precision == "fp64":
+            if G_up is not None:
+                raise _hip.HipError("precision='fp64': an upstream gradient (the autograd hook) is not built in fp64")
+            return self._fp64_gradient(Xp, labels, sidx, S, mode, norms)
         if self.precision == "lowdim" and G_up is None and mode in (LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT):
             per = mode == LOSS_PER_SAMPLE
             G = self._low_out(Xp.shape[0])
@@ -492,8 +574,8 @@ class AttackEngine:
         sidx, S = self.sample_index(n_samples, seeds)
         nb = None
         if norms:
-            nb = (torch.empty(x.shape[0], dtype=torch.float32, device=self.device),
-                  torch.empty(x.shape[0], dtype=torch.float32, device=self.device))
+            dt = torch.float64 if self.precision == "fp64" else torch.float32
+            nb = (torch.empty(x.shape[0], dtype=dt, device=self.device), torch.empty(x.shape[0], dtype=dt, device=self.device))
         xin = self._flat(x) if self.precision == "lowdim" else self.pad_inputs(x)
         G = self.gradient(xin, to_labels(y, self.device), sidx, S, LOSS_PER_SAMPLE, norms=nb)
         return (self.unpad(G, x), nb[0], nb[1]) if norms else self.unpad(G, x)
@@ -501,6 +583,9 @@ class AttackEngine:
     # ------------------------------------------------------------------ attacks
     def _step(self, X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project):
         p = self.post
+        if self.precision == "fp64":            # X stays fp32 (the reference's iterates are); only the SIGN of the fp64 gradient is read
+            G = self._fp64_gradient(X, labels, sidx, S, mode)
+            return self.k.attack_step_f64(X, X0, G, alpha, alpha_scalar, eps, project, p.D)
         if self.world > 1 and self.pipelined_comm:
             return self._step_sharded(X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project)
         ws, n_slabs, _ = self.gradient_slabs(X, labels, sidx, S, mode)
@@ -597,6 +682,9 @@ class AttackEngine:
         gradient of attack_gradient(): no forward, no backward."""
         p = self.post
         X = self.pad_inputs(x, clone=True)
+        if G.dtype == torch.float64:            # a gradient of the fp64 mode: its sign, the same fp32 arithmetic on x
+            self.k.attack_step_f64(X, None, G, None, float(epsilon), 0.0, False, p.D)
+            return self.unpad(X, x)
         self.k.attack_step(X, None, G, 1, 0, p.Dp, None, float(epsilon), 0.0, False, p.D)
         return self.unpad(X, x)
 
@@ -610,7 +698,8 @@ class AttackEngine:
         its order of operations are those of the two separate calls: both results are BIT-IDENTICAL to them (tests/test_hip_round5.py).
         Returns (expected loss gradients, adversarial inputs), both of x's shape.  Sample-sharded: the three exchanges of the separate
         calls (summed per-sample-loss gradients — overlapped with the second backward; sum_s p_s; summed mean-loss gradients)."""
-        if not self.shared_forward or self.precision == "lowdim" or mode != LOSS_MEAN_PROB:
+        if not self.shared_forward or self.precision in ("lowdim", "fp64") or mode != LOSS_MEAN_PROB:
+            # (the fp64 backward consumes the forward's stash: one backward per forward)
             # (an ensemble's / a deterministic net's attack differentiates the mean LOGITS: its forward leaves logits, the per-sample loss needs
             # probabilities — nothing to share; the lowdim kernels recompute the forward inside their one launch)
             return self.loss_gradients(x, y, n_samples, seeds), self.fgsm(x, y, n_samples, epsilon, seeds, mode)
@@ -741,6 +830,7 @@ class AttackEngine:
 
     def _graph_capturable(self):
         return (self.graph_safe and self.world == 1 and self.device.type == "cuda" and isinstance(self.k, _hip.HipKernels)
+                and self.precision != "fp64"        # (its step allocates the gradient it returns and cuts the points into blocks)
                 and os.environ.get("RBNN_HIPGRAPH", "0") == "1")
 
     def _capture(self, fn):
@@ -793,7 +883,10 @@ class AttackEngine:
         a = self.forward_padded(prep(x_attack), sidx, S, kind)
         counts = torch.zeros(2, dtype=torch.int32, device=self.device)
         rob = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
-        self.k.eval_metrics(o, a, labels, self.post.C, counts, rob)
+        if self.precision == "fp64":            # the outputs are returned in fp64; the reductions (argmax counts, softmax difference) read them rounded to fp32
+            self.k.eval_metrics(o.float(), a.float(), labels, self.post.C, counts, rob)
+        else:
+            self.k.eval_metrics(o, a, labels, self.post.C, counts, rob)
         c = counts.cpu()
         n = x.shape[0]
         return 100 * float(c[0]) / n, 100 * float(c[1]) / n, rob, o[:, :self.post.C], a[:, :self.post.C]
