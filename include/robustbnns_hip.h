@@ -1191,6 +1191,42 @@ int rbnn_fc_input_grad_f64(const rbnn_posterior *net, const int32_t *sample_idx,
 int rbnn_attack_step_f64(float *X, const float *X0, int32_t ldx, const double *G, int32_t ldg, const float *alpha, float alpha_scalar,
                          float eps, int32_t project, int32_t n_points, int32_t in_features, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * fp64 checker of the conv forward and expected input gradient (csrc/rbnn_conv_fp64.inc): the conv half of the section above, behind
+ * entry points of its own (the precision switch keeps refusing conv posteriors).  The DATA stay fp32 — the posterior exactly as
+ * rbnn_conv_posterior holds it (K2w_ci is not read), X, the attack iterates — and are widened on load; every operation from the first
+ * product to the written result is fp64: conv2 and conv2^T (implicit GEMMs, K = 800 and K = 25 Hc) on v_mfma_f64_16x16x4_f64 with fp64
+ * accumulators, conv1, conv1^T and the head in fp64 FMAs, bias, activation (leaky slope 0.01 as a double), softmax with the maximum
+ * subtracted.  Pooling compares the activated values and takes the FIRST maximum in row-major window order (torch's rule); act' is
+ * taken from the pooled value.  No atomics, one fixed accumulation order per result element, one block per (sample, point): two runs
+ * are bit-identical, and a point's result depends neither on n_points nor on the point block it ran in.  Both geometries, all four
+ * activations, hidden a multiple of 16, n_classes <= 16, n_points * n_samples < 2^31.  No counterpart in the reference.
+ * P, dZ, Psum have the layout of the fc section, so rbnn_reduce_samples_f64, rbnn_loss_dlogits_f64 and rbnn_attack_step_f64 serve
+ * unchanged.  Buffers are caller-owned; the fp64 ones 16-byte aligned; per-sample buffers are indexed by POSITION in the call, the
+ * weights by sample_idx.  Every argument is checked on the host before any launch: a null pointer RBNN_ERR_NULL; a geometry other
+ * than 28 / 1 or 32 / 3, an activation or an out_kind outside the enums RBNN_ERR_UNSUPPORTED; hidden, n_classes, the counts, ldx
+ * below Cin*W*W or not a multiple of 4, ldg below Cin*W*W RBNN_ERR_SHAPE; a misaligned X or fp64 buffer RBNN_ERR_ALIGN.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_CONV_FP64_WS_BUFFERS 8
+/* bytes[0 .. 7] <- sizes of P [S,N,16], dZ [S,N,16], Psum [N,16], P1 [S,N,32*P1W*P1W] (fp64), arg1 [S,N,32*P1W*P1W] (bytes),
+ * Q2 [S,N,Hc*NP2] (fp64), arg2 [S,N,Hc*NP2] (bytes), Gs [S,N,Cin*W*W] (fp64, per-sample input gradients) for N points x S used
+ * samples. [host; bytes: host array of RBNN_CONV_FP64_WS_BUFFERS] */
+int rbnn_conv_fp64_workspace_query(const rbnn_conv_posterior *net, int32_t n_points, int32_t n_samples, size_t *bytes);
+
+/* rbnn_conv_forward in fp64: P[s] = softmax(NN_s(X)) (or logits; columns >= C are 0), the pooled activations P1 and Q2 and the
+ * argmax byte (0..3, row-major in the window) of every pooled output.  X: fp32 [N, ldx].  3 launches. */
+int rbnn_conv_forward_fp64(const rbnn_conv_posterior *net, const float *X, int32_t ldx, int32_t n_points, const int32_t *sample_idx,
+                           int32_t n_samples, int32_t out_kind, double *P, double *P1, uint8_t *arg1, double *Q2, uint8_t *arg2,
+                           void *stream);
+
+/* rbnn_conv_input_grad + the sum over samples + the norms in fp64, from the dZ that rbnn_loss_dlogits_f64 left and the forward's
+ * P1 / arg1 / Q2 / arg2 (read only: several backwards may follow one forward): Gs[s,n,:] = dL_s/dx_n, then
+ * G[n,d] = scale * sum_s Gs[s,n,d] with s ascending (row stride ldg doubles), linf / l2 (nullable, [N]) the norms of every row.
+ * 2 launches; + 1 with norms. */
+int rbnn_conv_input_grad_fp64(const rbnn_conv_posterior *net, const int32_t *sample_idx, int32_t n_samples, int32_t n_points,
+                              const double *dZ, const double *P1, const uint8_t *arg1, const double *Q2, const uint8_t *arg2,
+                              double *Gs, double scale, double *G, int32_t ldg, double *linf, double *l2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

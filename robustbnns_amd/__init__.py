@@ -7,6 +7,7 @@ gfx950 HIP kernels behind the C-ABI of include/robustbnns_hip.h.  See DESIGN.md.
 """
 from . import adversarialAttacks, grid_search_halfMoons, lossGradients, model_bnn, model_ensemble, model_nn, plot_baseline_attacks, plot_eps_attacks, plot_gradients_components   # noqa: F401
 from .conv import ConvEngine, ConvStackedPosterior                                      # noqa: F401
+from .conv_fp64 import ConvFp64Engine                                                  # noqa: F401
 from .engine import AttackEngine                                                        # noqa: F401
 from .posterior import StackedPosterior                                                 # noqa: F401
 

@@ -57,6 +57,8 @@ CONV_SVI_LOCKSTEP_WS_KEYS = _keys(ConvSviLockstepWs)
 SVI_LOCKSTEP_ACC_KEYS = _keys(SviLockstepAcc)
 F64_WS_KEYS = ("P", "dZ", "Psum", "dact1", "hid1", "dact2")        # rbnn_f64_workspace_query's order (plain fp64 pointers: no struct)
 assert len(F64_WS_KEYS) == F64_WS_BUFFERS
+CONV_FP64_WS_KEYS = ("P", "dZ", "Psum", "P1", "arg1", "Q2", "arg2", "Gs")     # rbnn_conv_fp64_workspace_query's order; arg1 / arg2 are bytes
+assert len(CONV_FP64_WS_KEYS) == CONV_FP64_WS_BUFFERS
 
 _lib = None
 
@@ -321,6 +323,23 @@ class HipKernels:
         require_gpu(X, "X")
         check(self.lib.rbnn_attack_step_f64(ptr(X), ptr(X0), X.stride(0), ptr(G), G.stride(0), ptr(alpha), alpha_scalar, eps, int(project),
                                             X.shape[0], D, stream_of(X)), "rbnn_attack_step_f64")
+
+    # -- fp64 checker of the conv nets (rbnn_conv_fp64.inc); reduce_samples_f64 / loss_dlogits_f64 / attack_step_f64 above serve it too ----
+    def conv_fp64_workspace_sizes(self, net, N, S):
+        out = (C.c_size_t * CONV_FP64_WS_BUFFERS)()
+        check(self.lib.rbnn_conv_fp64_workspace_query(C.byref(net.descriptor()), N, S, out), "rbnn_conv_fp64_workspace_query")
+        return dict(zip(CONV_FP64_WS_KEYS, out))
+
+    def conv_forward_fp64(self, net, X, sidx, S, out_kind, ws):
+        """ws: dict keyed like CONV_FP64_WS_KEYS (float64 tensors; arg1 / arg2 uint8)."""
+        require_gpu(X, "X")
+        check(self.lib.rbnn_conv_forward_fp64(C.byref(net.descriptor()), ptr(X), X.stride(0), X.shape[0], ptr(sidx), S, out_kind, ptr(ws["P"]),
+                                              ptr(ws["P1"]), ptr(ws["arg1"]), ptr(ws["Q2"]), ptr(ws["arg2"]), stream_of(X)), "rbnn_conv_forward_fp64")
+
+    def conv_input_grad_fp64(self, net, sidx, S, N, ws, scale, G, linf=None, l2=None):
+        check(self.lib.rbnn_conv_input_grad_fp64(C.byref(net.descriptor()), ptr(sidx), S, N, ptr(ws["dZ"]), ptr(ws["P1"]), ptr(ws["arg1"]),
+                                                 ptr(ws["Q2"]), ptr(ws["arg2"]), ptr(ws["Gs"]), scale, ptr(G), G.stride(0), ptr(linf), ptr(l2),
+                                                 stream_of(G)), "rbnn_conv_input_grad_fp64")
 
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):

@@ -1,0 +1,192 @@
+"""The fp64 checker of the conv nets on the GPU (csrc/rbnn_conv_fp64.inc): forward, the three label-loss gradients with their norms,
+FGSM / PGD from the fp64 gradient's sign.
+
+The conv half of AttackEngine's precision='fp64' — which keeps refusing conv posteriors: this is an entry point of its own, as
+conv training is (train_conv).  The posterior stays the fp32 ConvStackedPosterior (K1w .. Fb as they stand: a stored stack or a
+redrawable SVI stack alike) and is widened on load; every operation from the first product on is fp64, conv2 and conv2^T on the f64
+MFMA.  One kernel block is one (sample, point), every result element has one fixed accumulation order and nothing is atomic, so runs
+are bit-identical and a point's result depends neither on N nor on the point block it ran in.
+
+One GPU, the HIP kernels, the label losses: everything else is refused with HipError before anything is launched.  Point blocks are
+cut so that the fp64 workspaces stay under RBNN_FP64_WS_GB (default 4); the unit is one point."""
+import os
+
+import torch
+
+from . import _hip
+from ._hip import LOSS_MEAN_LOGIT, LOSS_MEAN_PROB, LOSS_PER_SAMPLE, OUT_LOGITS, OUT_PROBS
+from .engine import AttackEngine, to_labels
+
+_U8 = ("arg1", "arg2")
+
+
+def kink_margin(post, x, n_samples, block=512):
+    """Per point, over the first n_samples samples: how far the conv net is from a discontinuity of its gradient — the smallest, over every
+    pooling window of both layers, of the gap between the window's two largest pre-activations and of |the largest| (oracle.kink_margin's
+    conv rule; relu / leaky, else +inf).  float64 [N] on the posterior's device.  A DIAGNOSTIC of the checker's users (which rows a
+    comparison of fp32 results may keep), not a kernel: fp64 torch contractions on the device over the fp32 weights, `block` points at a time."""
+    dev = post.device
+    out = torch.full((x.shape[0],), float("inf"), dtype=torch.float64, device=dev)
+    if post.activation not in ("relu", "leaky"):
+        return out
+    slope = 0.0 if post.activation == "relu" else 0.01
+    conv = lambda h, w, b: torch.einsum("ncyxij,ocij->noyx", h.unfold(2, 5, 1).unfold(3, 5, 1), w) + b.view(1, -1, 1, 1)
+    for lo in range(0, x.shape[0], block):
+        xd = x[lo:lo + block].to(dev, torch.float64).reshape(-1, post.Cin, post.W, post.W)
+        for s in range(n_samples):
+            a = conv(xd, post.K1w[s].double().view(32, post.Cin, 5, 5), post.K1b[s].double())
+            for layer, stride in ((1, 2), (2, 1)):
+                win = a.unfold(2, 2, stride).unfold(3, 2, stride).reshape(a.shape[0], a.shape[1], -1, 4)
+                top2 = win.topk(2, dim=-1)[0]
+                m = torch.minimum(top2[..., 0] - top2[..., 1], top2[..., 0].abs()).reshape(a.shape[0], -1).amin(1)
+                out[lo:lo + block] = torch.minimum(out[lo:lo + block], m)
+                if layer == 1:
+                    top = top2[..., 0].reshape(a.shape[0], 32, post.P1W, post.P1W)
+                    a = conv(torch.where(top > 0, top, top * slope), post.K2w[s].double().view(post.H, 32, 5, 5), post.K2b[s].double())
+    return out
+
+
+class ConvFp64Engine:
+    def __init__(self, posterior, kernels=None, group=None):
+        self.post = posterior
+        if getattr(posterior, "arch", None) != "conv":
+            raise _hip.HipError("ConvFp64Engine is the fp64 checker of conv posteriors; fc / fc2: AttackEngine(..., precision='fp64')")
+        if group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(group) > 1:
+                raise _hip.HipError("the fp64 conv checker runs on one GPU: fp64 under a process group of more than one rank is not built")
+        self.k = kernels if kernels is not None else _hip.HipKernels()
+        if not isinstance(self.k, _hip.HipKernels) or self.device.type != "cuda":
+            raise _hip.HipError("the fp64 conv checker needs the HIP kernels and a posterior on the GPU: there is no fp64 path on a CPU device "
+                                "or through substitute kernels")
+        self._ws_cache = {}
+
+    @property
+    def device(self):
+        return self.post.device
+
+    # ------------------------------------------------------------------ workspaces and point blocks
+    def point_block(self, S):
+        """Points per block: the fp64 workspaces of a block (rbnn_conv_fp64_workspace_query: P, dZ, Psum, P1, Q2, the two argmax byte
+        images, the per-sample gradients) stay within RBNN_FP64_WS_GB (default 4).  The unit is one point, at least one."""
+        per_point = sum(self.k.conv_fp64_workspace_sizes(self.post, 1, S).values())
+        budget = float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
+        return max(1, int(budget // per_point))
+
+    def point_blocks(self, N, S):
+        nb = self.point_block(S)
+        return [(lo, min(N, lo + nb)) for lo in range(0, N, nb)]
+
+    def _fp64_buffer(self, n_bytes, dtype=torch.float64):
+        """Every workspace buffer is allocated here (n_bytes of `dtype`: float64, or uint8 for the argmax images)."""
+        return torch.empty(n_bytes // torch.empty((), dtype=dtype).element_size(), dtype=dtype, device=self.device)
+
+    def _workspace(self, N, S):
+        key = (N, S)
+        ws = self._ws_cache.pop(key, None)
+        if ws is None:
+            sizes = self.k.conv_fp64_workspace_sizes(self.post, N, S)
+            ws = {k: self._fp64_buffer(v, torch.uint8 if k in _U8 else torch.float64) for k, v in sizes.items()}
+            while len(self._ws_cache) > 1:          # the full block and a ragged tail block stay cached
+                self._ws_cache.pop(next(iter(self._ws_cache)))
+        self._ws_cache[key] = ws
+        return ws
+
+    # ------------------------------------------------------------------ inputs
+    def _inputs(self, x, clone=False):
+        """[N, Cin, W, W] -> contiguous fp32 [N, D] on the device, 16-byte aligned."""
+        if torch.is_tensor(x) and x.requires_grad:
+            raise _hip.HipError("the fp64 conv checker takes no input with requires_grad: the autograd hook is not built in fp64, and an fp32 "
+                                "backward under this name would be a lie")
+        x = torch.as_tensor(x)
+        xf = x.detach().reshape(x.shape[0], -1).to(self.device, torch.float32).contiguous()
+        if xf.shape[1] != self.post.D:
+            raise ValueError(f"inputs flatten to {xf.shape[1]} features, posterior expects {self.post.D}")
+        return xf.clone() if (clone or xf.data_ptr() % 16) else xf
+
+    def _samples(self, n_samples, seeds):
+        """model_bnn.py:200-202,246-252: the first n_samples stored samples, or `seeds` as indices -> (int32 index buffer or None, count)."""
+        return AttackEngine.sample_index(self, n_samples, seeds)
+
+    @staticmethod
+    def _check_mode(mode):
+        if mode not in (LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT):
+            raise _hip.HipError("the fp64 conv checker differentiates the three label losses; the autograd hook's upstream modes are not built in fp64")
+
+    # ------------------------------------------------------------------ forward and gradient
+    def forward(self, x, n_samples, seeds=None, logits=False):
+        """Mean over the samples of the probabilities (or logits): float64 [N, C]."""
+        X = self._inputs(x)
+        sidx, S = self._samples(n_samples, seeds)
+        N, p = X.shape[0], self.post
+        out = torch.zeros(N, _hip.CPAD, dtype=torch.float64, device=self.device)
+        for lo, hi in self.point_blocks(N, S):
+            ws = self._workspace(hi - lo, S)
+            self.k.conv_forward_fp64(p, X[lo:hi], sidx, S, OUT_LOGITS if logits else OUT_PROBS, ws)
+            self.k.reduce_samples_f64(ws["P"], S, hi - lo, p.C, 1.0 / S, out[lo:hi])
+        return out[:, :p.C].clone()
+
+    def _gradient(self, X, labels, sidx, S, mode, norms=None):
+        """The summed expected input gradient, float64 [N, D] (a fresh tensor): forward + sum over samples + loss + backward per point
+        block.  The 1/S of every loss is inside dZ, as in the fp64 oracle."""
+        self._check_mode(mode)
+        N, p = X.shape[0], self.post
+        G = torch.empty(N, p.D, dtype=torch.float64, device=self.device)
+        for lo, hi in self.point_blocks(N, S):
+            n, ws = hi - lo, self._workspace(hi - lo, S)
+            self.k.conv_forward_fp64(p, X[lo:hi], sidx, S, OUT_LOGITS if mode == LOSS_MEAN_LOGIT else OUT_PROBS, ws)
+            Psum = None
+            if mode != LOSS_PER_SAMPLE:
+                Psum = ws["Psum"].view(n, _hip.CPAD)
+                self.k.reduce_samples_f64(ws["P"], S, n, p.C, 1.0, Psum)
+            self.k.loss_dlogits_f64(mode, ws["P"], Psum, labels[lo:hi], S, 1.0 / S, n, p.C, ws["dZ"])
+            self.k.conv_input_grad_fp64(p, sidx, S, n, ws, 1.0, G[lo:hi], None if norms is None else norms[0][lo:hi],
+                                        None if norms is None else norms[1][lo:hi])
+        return G
+
+    def loss_gradients(self, x, y, n_samples, seeds=None, norms=False):
+        """lossGradients.loss_gradient for every row of x (lossGradients.py:20-40): float64 in x's shape; norms=True: also the per-point
+        Linf and L2 norms of those gradients (float64 [N] each)."""
+        X = self._inputs(x)
+        sidx, S = self._samples(n_samples, seeds)
+        nb = None
+        if norms:
+            nb = (torch.empty(X.shape[0], dtype=torch.float64, device=self.device), torch.empty(X.shape[0], dtype=torch.float64, device=self.device))
+        G = self._gradient(X, to_labels(y, self.device), sidx, S, LOSS_PER_SAMPLE, nb).reshape(x.shape)
+        return (G, nb[0], nb[1]) if norms else G
+
+    def attack_gradient(self, x, y, n_samples, seeds=None, mode=LOSS_MEAN_PROB):
+        """The gradient whose SIGN fgsm / pgd take (adversarialAttacks.py:74-79): float64 [N, D]."""
+        self._check_mode(mode)
+        X = self._inputs(x)
+        sidx, S = self._samples(n_samples, seeds)
+        return self._gradient(X, to_labels(y, self.device), sidx, S, mode)
+
+    # ------------------------------------------------------------------ attacks: fp32 images from the sign of the fp64 gradient
+    def _step(self, X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project):
+        G = self._gradient(X, labels, sidx, S, mode)
+        self.k.attack_step_f64(X, X0, G, alpha, alpha_scalar, eps, project, self.post.D)
+
+    def fgsm(self, x, y, n_samples, epsilon=0.3, seeds=None, mode=LOSS_MEAN_PROB):
+        """adversarialAttacks.fgsm_attack on every row of x (adversarialAttacks.py:69-83): fp32 images."""
+        self._check_mode(mode)
+        X = self._inputs(x, clone=True)
+        sidx, S = self._samples(n_samples, seeds)
+        self._step(X, None, to_labels(y, self.device), sidx, S, mode, None, float(epsilon), 0.0, False)
+        return X.reshape(x.shape)
+
+    def pgd(self, x, y, n_samples, epsilon, alpha=None, iters=40, seeds=None, mode=LOSS_MEAN_PROB):
+        """adversarialAttacks.pgd_attack on every row of x (adversarialAttacks.py:86-108): fp32 images.
+        alpha=None: 2/max(image) per image (:89); a float: the same step for all (2/225, :91)."""
+        self._check_mode(mode)
+        X0 = self._inputs(x, clone=True)
+        sidx, S = self._samples(n_samples, seeds)
+        labels = to_labels(y, self.device)
+        X = X0.clone()
+        alpha_t = None
+        if alpha is None:
+            alpha_t = torch.empty(X.shape[0], dtype=torch.float32, device=self.device)
+            self.k.pgd_alpha(X0, self.post.D, alpha_t)
+        for _ in range(iters):
+            self._step(X, X0, labels, sidx, S, mode, alpha_t, 0.0 if alpha is None else float(alpha), float(epsilon), True)
+        return X.reshape(x.shape)

@@ -1161,3 +1161,6 @@ int launch_conv1_bwd_fp32(int act, int in_channels, const ConvBwdArgs& a, hipStr
     return in_channels == 1 ? go(GeoMnist{}) : go(GeoCifar{});
 }
 }  // namespace rbnn_conv_shared
+
+// the fp64 checker of the conv forward and expected input gradient (conv2 and conv2^T on the f64 MFMA): kernels and C-ABI
+#include "rbnn_conv_fp64.inc"

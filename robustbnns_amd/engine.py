@@ -136,7 +136,8 @@ class AttackEngine:
         # does not cover is refused here, before anything is launched: an answer computed in fp32 under this name would be a lie.
         if want == "fp64":
             if getattr(self.post, "arch", None) not in ("fc", "fc2"):
-                raise _hip.HipError("precision='fp64' covers fc and fc2 posteriors: there are no fp64 conv kernels")
+                raise _hip.HipError("precision='fp64' covers fc and fc2 posteriors: the fp64 conv checker is a class of its own, "
+                                    "conv_fp64.ConvFp64Engine, and is not reached through the precision switch")
             if self.world > 1:
                 raise _hip.HipError("precision='fp64' runs on one GPU: fp64 under sample- or point-sharding (a process group of more than "
                                     "one rank) is not built")

@@ -1,0 +1,200 @@
+"""Host side of the fp64 conv checker (no GPU): the three C-ABI additions and their argument checks, what ConvFp64Engine refuses before
+anything is launched, its point blocks, and the resources of its kernels read from the built library.  Everything here fails on a tree
+without the checker (the module, the class and the three C names do not exist there)."""
+import ctypes as C
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+from robustbnns_amd import _hip
+
+pytestmark = pytest.mark.usefixtures("built_library")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"rbnn_conv_fp64_workspace_query", "rbnn_conv_forward_fp64", "rbnn_conv_input_grad_fp64"}
+FC_NAMES = {"rbnn_f64_workspace_query", "rbnn_fc_forward_f64", "rbnn_reduce_samples_f64", "rbnn_loss_dlogits_f64", "rbnn_fc_input_grad_f64",
+            "rbnn_attack_step_f64"}
+
+
+class Recorder:
+    """Stands where the kernels stand and records every call made through it: `calls` stays empty while nothing is launched."""
+    calls = []
+
+    def __getattr__(self, name):
+        return lambda *a, **k: Recorder.calls.append(name)
+
+
+class OtherKernels:
+    """Kernels that are not _hip.HipKernels; records into the same list."""
+    __getattr__ = Recorder.__getattr__
+
+
+class Post:
+    """As much of a ConvStackedPosterior as the engines' constructors and the refusals read."""
+
+    def __init__(self, arch="conv", device="cuda"):
+        self.arch, self.device, self.S, self.C, self.D, self.Dp, self.H = arch, torch.device(device), 4, 10, 784, 784, 64
+        self.triple_supported, self.split_supported = (lambda: False), (lambda: False)
+
+
+@pytest.fixture
+def recorder(monkeypatch):
+    Recorder.calls = []
+    monkeypatch.setattr(_hip, "HipKernels", Recorder)
+    monkeypatch.delenv("RBNN_PRECISION", raising=False)
+    return Recorder
+
+
+def test_header_declares_the_three_entry_points_and_the_abi_is_unchanged():
+    import __graft_entry__ as G
+    hdr = open(_hip.HEADER_PATH).read()
+    declared = set(re.findall(r"\b(rbnn_\w+)\s*\(", hdr))
+    assert NAMES <= declared and NAMES <= set(_hip.SIGNATURES)
+    assert {n for n in declared if "conv" in n and "fp64" in n} == NAMES
+    assert {n for n in declared if "f64" in n} == FC_NAMES                      # no declared name containing f64 was added
+    assert "#define RBNN_ABI_VERSION 10" in hdr and _hip.ABI_VERSION == 10 and _hip.load().rbnn_abi_version() == 10
+    assert len(G.SOURCES) == 12 and any(d.endswith("rbnn_conv_fp64.inc") for d in G.DEPS) and any(d.endswith("rbnn_fp64.inc") for d in G.DEPS)
+    assert _hip.F64_WS_BUFFERS == 6 and _hip.CONV_FP64_WS_BUFFERS == len(_hip.CONV_FP64_WS_KEYS) == 8
+    assert _hip.SIGNATURES["rbnn_conv_fp64_workspace_query"] == (C.c_int32, [C.POINTER(_hip.ConvPosterior), C.c_int32, C.c_int32, C.c_void_p])
+    assert _hip.SIGNATURES["rbnn_conv_input_grad_fp64"][1][10] is C.c_double
+
+
+def _net(cin, w, hc=48, c=10):
+    net = _hip.ConvPosterior()
+    net.activation, net.hidden, net.n_classes, net.n_stored, net.in_channels, net.in_width = 1, hc, c, 5, cin, w
+    return net
+
+
+@pytest.mark.parametrize("cin,w", [(1, 28), (3, 32)])
+def test_workspace_query_follows_the_formula(cin, w):
+    """N points x S samples: P, dZ [S,N,16] and Psum [N,16] in fp64; per (s, n) the pooled conv1 image 32 P1W^2 and the pooled conv2 image
+    Hc NP2, each as fp64 values + one argmax byte per value; the per-sample input gradient Cin W^2 in fp64.
+    P1W = (W - 4) / 2, NP2 = (P1W - 5)^2."""
+    lib, N, S, hc = _hip.load(), 7, 3, 48
+    p1 = 32 * ((w - 4) // 2) ** 2
+    q2 = hc * ((w - 4) // 2 - 5) ** 2
+    out = (C.c_size_t * 8)()
+    assert lib.rbnn_conv_fp64_workspace_query(C.byref(_net(cin, w, hc)), N, S, out) == 0
+    assert list(out) == [S * N * 16 * 8, S * N * 16 * 8, N * 16 * 8, S * N * p1 * 8, S * N * p1, S * N * q2 * 8, S * N * q2, S * N * cin * w * w * 8]
+    assert (p1, q2) == ((4608, 49 * hc) if w == 28 else (6272, 81 * hc))
+
+
+def test_every_argument_error_returns_its_code_before_any_launch():
+    """Fake pointers: a call that got past the checks would fault."""
+    lib, p = _hip.load(), 4096
+    out = (C.c_size_t * 8)()
+    q = lib.rbnn_conv_fp64_workspace_query
+    assert q(None, 4, 2, out) == _hip.ERR_NULL and q(C.byref(_net(1, 28)), 4, 2, None) == _hip.ERR_NULL
+    assert q(C.byref(_net(1, 32)), 4, 2, out) == _hip.ERR_UNSUPPORTED and q(C.byref(_net(3, 28)), 4, 2, out) == _hip.ERR_UNSUPPORTED
+    assert q(C.byref(_net(1, 28, hc=40)), 4, 2, out) == _hip.ERR_SHAPE and q(C.byref(_net(1, 28)), 0, 2, out) == _hip.ERR_SHAPE
+
+    def fwd(net, X=p, ldx=784, N=4, S=2, kind=0, P=p, P1=p, a1=p, Q2=p, a2=p):
+        return lib.rbnn_conv_forward_fp64(C.byref(net), X, ldx, N, None, S, kind, P, P1, a1, Q2, a2, None)
+
+    def bwd(net, N=4, S=2, dZ=p, P1=p, a1=p, Q2=p, a2=p, Gs=p, G=p, ldg=784):
+        return lib.rbnn_conv_input_grad_fp64(C.byref(net), None, S, N, dZ, P1, a1, Q2, a2, Gs, 1.0, G, ldg, None, None, None)
+
+    bare = _net(1, 28)
+    assert fwd(bare) == _hip.ERR_NULL and bwd(bare) == _hip.ERR_NULL             # no weights
+
+    def full(cin=1, w=28, hc=48, c=10):
+        net = _net(cin, w, hc, c)
+        for k in ("K1w", "K1b", "K2w", "K2b", "Fw", "Fb"):
+            setattr(net, k, p)
+        return net
+    for call in (fwd, bwd):
+        assert call(full(1, 32)) == _hip.ERR_UNSUPPORTED and call(full(3, 28)) == _hip.ERR_UNSUPPORTED      # a geometry other than 28 / 1 or 32 / 3
+        assert call(full(hc=40)) == _hip.ERR_SHAPE and call(full(hc=8)) == _hip.ERR_SHAPE                   # hidden not a multiple of 16
+        assert call(full(c=17)) == _hip.ERR_SHAPE                                                           # C > 16
+        assert call(full(), N=0) == _hip.ERR_SHAPE and call(full(), N=1 << 20, S=1 << 12) == _hip.ERR_SHAPE
+        net = full()
+        net.activation = 9
+        assert call(net) == _hip.ERR_UNSUPPORTED
+    net = full()
+    for k in ("X", "P", "P1", "a1", "Q2", "a2"):
+        assert fwd(net, **{k: None}) == _hip.ERR_NULL, k
+    assert fwd(net, ldx=780) == _hip.ERR_SHAPE and fwd(net, ldx=786) == _hip.ERR_SHAPE                       # below Cin*W*W; not a multiple of 4
+    assert fwd(full(3, 32), ldx=3068) == _hip.ERR_SHAPE
+    assert fwd(net, X=p + 4) == _hip.ERR_ALIGN and fwd(net, Q2=p + 8) == _hip.ERR_ALIGN                      # a misaligned X, a misaligned fp64 buffer
+    assert fwd(net, kind=7) == _hip.ERR_UNSUPPORTED                                                          # an unknown out_kind
+    for k in ("dZ", "P1", "a1", "Q2", "a2", "Gs", "G"):
+        assert bwd(net, **{k: None}) == _hip.ERR_NULL, k
+    assert bwd(net, ldg=780) == _hip.ERR_SHAPE and bwd(net, Gs=p + 8) == _hip.ERR_ALIGN
+
+
+def test_the_engine_refuses_before_anything_is_launched(recorder, monkeypatch):
+    from robustbnns_amd.conv_fp64 import ConvFp64Engine
+    import torch.distributed as dist
+    with monkeypatch.context() as m:
+        m.setattr(dist, "get_world_size", lambda group=None: 2)
+        with pytest.raises(_hip.HipError, match=r"fp64.*one GPU"):                              # a process group of more than one rank
+            ConvFp64Engine(Post(), kernels=recorder(), group=object())
+    with pytest.raises(_hip.HipError, match=r"fp64.*CPU device"):                               # a CPU device ...
+        ConvFp64Engine(Post(device="cpu"), kernels=recorder())
+    with pytest.raises(_hip.HipError, match=r"fp64.*substitute kernels"):                       # ... or kernels that are not the HIP kernels
+        ConvFp64Engine(Post(), kernels=OtherKernels())
+    with pytest.raises(_hip.HipError, match=r"fp64.*conv posteriors"):                          # fc / fc2 have the precision switch
+        ConvFp64Engine(Post("fc"), kernels=recorder())
+    eng = ConvFp64Engine(Post(), kernels=recorder())
+    x, y = torch.rand(3, 1, 28, 28), torch.zeros(3, dtype=torch.long)
+    xg = x.clone().requires_grad_(True)
+    for call in (lambda: eng.forward(xg, 4), lambda: eng.loss_gradients(xg, y, 4), lambda: eng.attack_gradient(xg, y, 4),
+                 lambda: eng.fgsm(xg, y, 4), lambda: eng.pgd(xg, y, 4, 0.3, iters=2)):
+        with pytest.raises(_hip.HipError, match=r"fp64.*requires_grad"):                        # the autograd hook: never answered in fp32
+            call()
+    for mode in (_hip.LOSS_UPSTREAM, _hip.LOSS_UPSTREAM_LOGIT):
+        for call in (lambda: eng.attack_gradient(x, y, 4, mode=mode), lambda: eng.fgsm(x, y, 4, mode=mode),
+                     lambda: eng.pgd(x, y, 4, 0.3, iters=2, mode=mode)):
+            with pytest.raises(_hip.HipError, match=r"fp64.*upstream"):
+                call()
+    assert recorder.calls == []
+
+
+def test_precision_fp64_still_refuses_conv_and_names_the_checker(recorder):
+    from robustbnns_amd.conv import ConvEngine
+    from robustbnns_amd.engine import AttackEngine
+    for cls in (AttackEngine, ConvEngine):
+        with pytest.raises(_hip.HipError, match=r"fp64.*conv.*ConvFp64Engine"):
+            cls(Post(), kernels=recorder(), precision="fp64")
+    assert recorder.calls == []
+
+
+def test_point_blocks_follow_the_workspace_budget(recorder, monkeypatch):
+    """RBNN_FP64_WS_GB bounds the fp64 workspaces of a block; the unit is one point, never less than one."""
+    from robustbnns_amd.conv_fp64 import ConvFp64Engine
+    eng = ConvFp64Engine(Post(), kernels=recorder())
+    per_point = 100 * (2 * 16 * 8 + 9 * (4608 + 49 * 512) + 784 * 8) + 16 * 8                   # conv-512, S = 100 (the formula of the query test)
+    eng.k = type("K", (), {"conv_fp64_workspace_sizes": staticmethod(lambda post, N, S: {"all": N * per_point})})()
+    monkeypatch.delenv("RBNN_FP64_WS_GB", raising=False)
+    assert eng.point_block(100) == 4 * 2 ** 30 // per_point == 156
+    assert eng.point_blocks(400, 100) == [(0, 156), (156, 312), (312, 400)]
+    monkeypatch.setenv("RBNN_FP64_WS_GB", "1")
+    assert eng.point_block(100) == 39
+    monkeypatch.setenv("RBNN_FP64_WS_GB", "1e-6")
+    assert eng.point_block(100) == 1 and eng.point_blocks(3, 100) == [(0, 1), (1, 2), (2, 3)]
+
+
+def test_conv_fp64_kernels_use_no_scratch_and_fit_the_lds():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources as KR
+    if not os.path.exists(KR.READELF):
+        pytest.skip("llvm-readelf not in this image")
+    res = KR.kernel_resources()
+    new = {n: r for n, r in res.items() if "conv" in n and "fp64" in n}
+    kinds = {re.search(r"(\w+_fp64_kernel)", n).group(1) for n in new}
+    assert kinds == {"conv1_pool_fp64_kernel", "conv2_pool_fp64_kernel", "conv_head_fp64_kernel", "conv_input_grad_fp64_kernel",
+                     "conv_sum_samples_fp64_kernel", "conv_norms_fp64_kernel"}, kinds
+    assert len(new) == 3 * 4 * 2 + 3, sorted(new)             # conv1, conv2, backward: 4 activations x 2 geometries; head, sum, norms
+    assert not [n for n in new if "f64_kernel" in n]          # the fc set's fence (test_fp64_cpu.py) does not see them
+    for n, r in new.items():
+        assert r["scratch"] == 0 and r["spill_vgpr"] == 0 and r["lds"] <= 160 * 1024, (n, r)
+    # conv2 and the backward take their LDS at launch (dynamic): the sizes the launchers ask for, restated from rbnn_conv_fp64.inc
+    for w in (28, 32):
+        cin, p1w = (1 if w == 28 else 3), (w - 4) // 2
+        o2w, np2, p1sz = p1w - 4, (p1w - 5) ** 2, 32 * p1w * p1w
+        fwd = (p1sz + 4 * 16 * o2w * o2w) * 8 + 800 * 4
+        bwd = (16 * (o2w + 8) ** 2 + 16 * np2 + 16 + p1sz + 32 * cin * 25) * 8 + 2 * 400 * 4 + p1sz
+        assert max(fwd, bwd) <= 160 * 1024, (w, fwd, bwd)

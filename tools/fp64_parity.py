@@ -2,6 +2,7 @@
 """The fp32 precision modes against the DEVICE fp64 result at workload size, and what an fp64 pass costs.
 
     python tools/fp64_parity.py [--nets c2,fc2] [--reps 7]
+    python tools/fp64_parity.py --nets conv [--points N]          # bench.py's conv-512 (S = 16, N = 2048) against conv_fp64.ConvFp64Engine
 
 At BASELINE C2's size (fc-512, S = 100, N = 10 000) and at fc2-512, S = 100 (bench.py's workloads of those names, same inputs and posterior), for
 each of `auto`, `exact` and `split`:
@@ -12,6 +13,9 @@ each of `auto`, `exact` and `split`:
     hidden unit's whole contribution; at this size, 5e8 pre-activations, about a tenth of the rows have one that close).  The margin is a
     diagnostic of this tool: fp64 torch matmuls on the device over the fp32 weights;
   - the number of adversarial pixels (fgsm, eps = 0.3) that differ from the fp64 mode's, i.e. whose gradient sign differs (all rows / kept rows);
+A conv net (--nets conv; any conv workload of bench.py is taken, only `conv` was measured: ConvEngine's modes against ConvFp64Engine) keeps the rows whose conv margin exceeds KINK: the smallest, over
+the pooling windows of both layers, of the gap between a window's two largest pre-activations and of |the largest| (oracle.kink_margin's conv
+rule; conv_fp64.kink_margin, fp64 torch contractions on the device).
 and the time of a loss_gradients pass in fp64 next to `exact`, each the median of --reps passes (device synchronised around every pass).
 Every net is measured in a child process of its own, started through steps.Runner (kind bench_full: one time limit each; after a fault, an
 abort or a time limit nothing more is started); the child's JSON line is printed and kept in its log under <OUT>/fp64_parity/.  --child: the
@@ -69,25 +73,35 @@ def timed(fn, reps):
     return statistics.median(out), out
 
 
-def child(name, reps):
+def child(name, reps, points=0):
     import torch
     import bench
     from robustbnns_amd import AttackEngine, StackedPosterior, _hip
     w = bench.WORKLOADS[name]
+    if points:
+        w = dict(w, N=points)
     x, y, post = bench.make_problem(w, 0, "cuda:0")
     n, D = w["S"], x[0].numel()
-    sp = StackedPosterior(w["arch"], w["act"], w["shape"], w["C"], w["H"], post, "cuda:0")
-    e64 = AttackEngine(sp, precision="fp64")
+    if w["arch"] == "conv":
+        from robustbnns_amd import conv_fp64
+        from robustbnns_amd.conv import ConvEngine, ConvStackedPosterior
+        sp = ConvStackedPosterior(w["act"], w["shape"], w["C"], w["H"], post, "cuda:0")
+        e64, engine = conv_fp64.ConvFp64Engine(sp), (lambda mode: ConvEngine(sp, precision=mode))
+        margin, block = (lambda: conv_fp64.kink_margin(sp, x, n)), e64.point_block(n)
+    else:
+        sp = StackedPosterior(w["arch"], w["act"], w["shape"], w["C"], w["H"], post, "cuda:0")
+        e64, engine = AttackEngine(sp, precision="fp64"), (lambda mode: AttackEngine(sp, precision=mode))
+        margin, block = (lambda: kink_margin(sp, x, n)), e64._fp64_block(n)
     g64 = e64.loss_gradients(x, y, n)
     a64 = e64.attack_gradient(x, y, n)[:, :D]
     adv64 = e64.fgsm(x, y, n, 0.3)
-    keep = kink_margin(sp, x, n) > KINK
-    rec = {"net": name, "arch": w["arch"], "H": w["H"], "S": n, "N": w["N"], "act": w["act"], "bar": BAR, "fp64_point_block": e64._fp64_block(n),
+    keep = margin() > KINK
+    rec = {"net": name, "arch": w["arch"], "H": w["H"], "S": n, "N": w["N"], "act": w["act"], "bar": BAR, "fp64_point_block": block,
            "kink": KINK, "rows_kept": int(keep.sum()), "modes": {}}
     keep_px = keep.reshape((-1,) + (1,) * (x.dim() - 1))
     for mode in MODES:
         try:
-            e = AttackEngine(sp, precision=mode)
+            e = engine(mode)
         except _hip.HipError as exc:                # a mode that does not cover the posterior says so; nothing was launched
             rec["modes"][mode] = {"refused": str(exc)}
             continue
@@ -95,15 +109,17 @@ def child(name, reps):
         a = e.attack_gradient(x, y, n)[:, :D]
         adv = e.fgsm(x, y, n, 0.3)
         eg, ea = row_err(g, g64) / BAR, row_err(a, a64) / BAR
+        worst = lambda e: float(e.max()) if e.numel() else float("nan")      # (a conv net at workload size may keep no row at all)
         rec["modes"][mode] = {"resolved": e.precision, "loss_gradients_worst_row_over_bar": float(eg.max()),
-                              "loss_gradients_worst_kept_row_over_bar": float(eg[keep].max()), "loss_gradients_kept_rows_beyond_bar": int((eg[keep] > 1).sum()),
-                              "loss_gradients_rows_beyond_bar": int((eg > 1).sum()),
-                              "fgsm_gradient_worst_row_over_bar": float(ea.max()), "fgsm_gradient_worst_kept_row_over_bar": float(ea[keep].max()),
+                              "loss_gradients_worst_kept_row_over_bar": worst(eg[keep]), "loss_gradients_kept_rows_beyond_bar": int((eg[keep] > 1).sum()),
+                              "loss_gradients_rows_beyond_bar": int((eg > 1).sum()), "loss_gradients_median_row_over_bar": float(eg.median()),
+                              "fgsm_gradient_median_row_over_bar": float(ea.median()),
+                              "fgsm_gradient_worst_row_over_bar": float(ea.max()), "fgsm_gradient_worst_kept_row_over_bar": worst(ea[keep]),
                               "fgsm_gradient_kept_rows_beyond_bar": int((ea[keep] > 1).sum()), "fgsm_gradient_rows_beyond_bar": int((ea > 1).sum()),
                               "adversarial_pixels_that_differ": int((adv != adv64).sum()),
                               "adversarial_pixels_that_differ_in_kept_rows": int(((adv != adv64) & keep_px).sum()), "pixels": adv.numel()}
         del e, g, a, adv
-    exact = AttackEngine(sp, precision="exact")
+    exact = engine("exact")
     rec["fp64_pass_ms_median"], rec["fp64_pass_ms"] = timed(lambda: e64.loss_gradients(x, y, n), reps)
     rec["exact_pass_ms_median"], rec["exact_pass_ms"] = timed(lambda: exact.loss_gradients(x, y, n), reps)
     rec["device"] = torch.cuda.get_device_name(0)
@@ -112,7 +128,7 @@ def child(name, reps):
 
 def line(rec):
     out = ["%s (%s-%d, S = %d, N = %d, %s) on %s: fp64 pass %.1f ms, exact pass %.2f ms (medians of %d; fp64 point block %d); "
-           "%d of %d rows kept (every hidden |pre-activation| > %g)"
+           "%d of %d rows kept (kink margin > %g)"
            % (rec["net"], rec["arch"], rec["H"], rec["S"], rec["N"], rec["act"], rec["device"], rec["fp64_pass_ms_median"], rec["exact_pass_ms_median"],
               len(rec["fp64_pass_ms"]), rec["fp64_point_block"], rec["rows_kept"], rec["N"], rec["kink"])]
     for mode, m in rec["modes"].items():
@@ -120,10 +136,11 @@ def line(rec):
             out.append("    %-5s refused: %s" % (mode, m["refused"]))
             continue
         out.append("    %-5s (-> %-6s) worst row, kept rows: loss_gradients %.3f x 1e-5 (%d beyond), FGSM gradient %.3f x 1e-5 (%d beyond); all rows: "
-                   "%.1f x 1e-5 (%d beyond), %.1f x 1e-5 (%d beyond); adversarial pixels that differ: %d in kept rows, %d in all, of %d"
+                   "%.1f x 1e-5 (%d beyond, median %.3f), %.1f x 1e-5 (%d beyond, median %.3f); adversarial pixels that differ: %d in kept rows, %d in all, of %d"
                    % (mode, m["resolved"], m["loss_gradients_worst_kept_row_over_bar"], m["loss_gradients_kept_rows_beyond_bar"],
                       m["fgsm_gradient_worst_kept_row_over_bar"], m["fgsm_gradient_kept_rows_beyond_bar"], m["loss_gradients_worst_row_over_bar"],
-                      m["loss_gradients_rows_beyond_bar"], m["fgsm_gradient_worst_row_over_bar"], m["fgsm_gradient_rows_beyond_bar"],
+                      m["loss_gradients_rows_beyond_bar"], m.get("loss_gradients_median_row_over_bar", float("nan")), m["fgsm_gradient_worst_row_over_bar"],
+                      m["fgsm_gradient_rows_beyond_bar"], m.get("fgsm_gradient_median_row_over_bar", float("nan")),
                       m["adversarial_pixels_that_differ_in_kept_rows"], m["adversarial_pixels_that_differ"], m["pixels"]))
     return "\n".join(out)
 
@@ -132,14 +149,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nets", default="c2,fc2")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--points", type=int, default=0, help="override the workload's point count (conv-512, S = 16: an fp64 pass is 240 ms per 2048 points)")
     ap.add_argument("--child", action="store_true", help="measure in this process (what the runner starts, one net at a time)")
     a = ap.parse_args()
     if a.child:
-        return child(a.nets, a.reps)
+        return child(a.nets, a.reps, a.points)
     runner = S.Runner("fp64_parity")
     with open(os.path.join(runner.out, "summary.txt"), "w") as f:
         for name in a.nets.split(","):
-            text = runner.gpu("bench_full", name, [S.PY, os.path.abspath(__file__), "--child", "--nets", name, "--reps", str(a.reps)])
+            text = runner.gpu("bench_full", name, [S.PY, os.path.abspath(__file__), "--child", "--nets", name, "--reps", str(a.reps), "--points", str(a.points)])
             rec = S.last_json(text)
             print(line(rec), flush=True)
             f.write(line(rec) + "\n" + json.dumps(rec) + "\n")
