@@ -1227,6 +1227,39 @@ int rbnn_conv_input_grad_fp64(const rbnn_conv_posterior *net, const int32_t *sam
                               const double *dZ, const double *P1, const uint8_t *arg1, const double *Q2, const uint8_t *arg2,
                               double *Gs, double scale, double *G, int32_t ldg, double *linf, double *l2, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Weight gradients of the conv nets in double precision (csrc/rbnn_conv_wgrad_dp.inc): the checker of the conv trainers' gradients,
+ * behind the forward of the section above.  The loss is the trainers' cross-entropy ON THE LOGITS, ce = logsumexp(z) - z_y (not the
+ * attack path's loss on probabilities).  After the section's forward with RBNN_OUT_LOGITS: the head below turns the logits into
+ * per-point CE and dZ = scale (softmax - e_y); the weight-gradient call runs dZ -> dQ2 -> dO2 -> conv2^T -> dO1 with one block per
+ * (sample, point) as the input-gradient call does, writes dO2 and dO1 (dL/d(pre-activation) of both convolutions), and contracts over
+ * the points:  dFw | dFb = dZ^T [Q2 | 1],  dK2w | dK2b = sum_{n,pos} dO2 x [P1 patch | 1],  dK1w | dK1b = sum_{n,pos} dO1 x [x patch | 1],
+ * all three on v_mfma_f64_16x16x4_f64.  No atomics.  Every output tile of 16 x 16 belongs to one wave, which LOADS its accumulator
+ * from the output buffer, walks the call's points in ascending order and stores it back: the six outputs ACCUMULATE, the caller zeroes
+ * them before the first point block, and an output element is the same chain of operations wherever the borders of the point blocks
+ * fall — bit-identical between runs and between any two point-block sizes.  (An MFMA of dK2 / dK1 takes 4 positions of ONE point,
+ * one of dFw takes ONE point.)  Both geometries, all four activations, hidden a multiple of 16, n_classes <= 16,
+ * n_points * n_samples < 2^31.  The outputs are indexed by POSITION in the call and have the state_dict's layouts:
+ * dK1w [S,32,Cin*25], dK1b [S,32], dK2w [S,Hc,800], dK2b [S,Hc], dFw [S,C,Hc*NP2], dFb [S,C].  Argument checks as in the section above.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_CONV_WGRAD_DP_WS_BUFFERS 3
+/* bytes[0 .. 2] <- sizes of ce [S,N], dO2 [S,N,Hc,NPOS], dO1 [S,N,32,O1*O1] (all doubles; NPOS = conv2's output positions, O1 = conv1's
+ * output width) for N points x S used samples. [host; bytes: host array of RBNN_CONV_WGRAD_DP_WS_BUFFERS] */
+int rbnn_conv_wgrad_dp_workspace_query(const rbnn_conv_posterior *net, int32_t n_points, int32_t n_samples, size_t *bytes);
+
+/* The training head: Z [S,N,16] logits (columns >= C ignored) -> ce[s,n] = logsumexp(z) - z_y (unscaled) and
+ * dZ[s,n,c] = scale * (softmax(z)_c - [c = y]) with the maximum subtracted and the label class formed as -(sum of the others) / den
+ * (columns >= C are 0).  labels [N], each in [0, C): the caller's to check.  dZ may not alias Z.  1 launch. */
+int rbnn_conv_head_ce_dp(const double *Z, const int32_t *labels, int32_t n_samples, int32_t n_points, int32_t n_classes, double scale,
+                         double *dZ, double *ce, void *stream);
+
+/* The weight gradients of n_points points, ADDED to the six outputs (see above).  X: fp32 [N, ldx] as in the forward; dZ of the head;
+ * P1 / arg1 / Q2 / arg2 of the forward (read only); dO2, dO1: workspaces of the query, written.  4 launches. */
+int rbnn_conv_weight_grads_dp(const rbnn_conv_posterior *net, const float *X, int32_t ldx, const int32_t *sample_idx, int32_t n_samples,
+                              int32_t n_points, const double *dZ, const double *P1, const uint8_t *arg1, const double *Q2,
+                              const uint8_t *arg2, double *dO2, double *dO1, double *dK1w, double *dK1b, double *dK2w, double *dK2b,
+                              double *dFw, double *dFb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,9 @@ F64_WS_KEYS = ("P", "dZ", "Psum", "dact1", "hid1", "dact2")        # rbnn_f64_wo
 assert len(F64_WS_KEYS) == F64_WS_BUFFERS
 CONV_FP64_WS_KEYS = ("P", "dZ", "Psum", "P1", "arg1", "Q2", "arg2", "Gs")     # rbnn_conv_fp64_workspace_query's order; arg1 / arg2 are bytes
 assert len(CONV_FP64_WS_KEYS) == CONV_FP64_WS_BUFFERS
+CONV_WGRAD_DP_WS_KEYS = ("ce", "dO2", "dO1")                       # rbnn_conv_wgrad_dp_workspace_query's order: the weight-gradient checker's own buffers
+assert len(CONV_WGRAD_DP_WS_KEYS) == CONV_WGRAD_DP_WS_BUFFERS
+CONV_WGRAD_DP_OUT_KEYS = ("dK1w", "dK1b", "dK2w", "dK2b", "dFw", "dFb")     # rbnn_conv_weight_grads_dp's six outputs, in its order
 
 _lib = None
 
@@ -340,6 +343,24 @@ class HipKernels:
         check(self.lib.rbnn_conv_input_grad_fp64(C.byref(net.descriptor()), ptr(sidx), S, N, ptr(ws["dZ"]), ptr(ws["P1"]), ptr(ws["arg1"]),
                                                  ptr(ws["Q2"]), ptr(ws["arg2"]), ptr(ws["Gs"]), scale, ptr(G), G.stride(0), ptr(linf), ptr(l2),
                                                  stream_of(G)), "rbnn_conv_input_grad_fp64")
+
+    # -- ... and of the conv weight gradients (rbnn_conv_wgrad_dp.inc): behind conv_forward_fp64 with logits out ---------------------------
+    def conv_wgrad_dp_workspace_sizes(self, net, N, S):
+        out = (C.c_size_t * CONV_WGRAD_DP_WS_BUFFERS)()
+        check(self.lib.rbnn_conv_wgrad_dp_workspace_query(C.byref(net.descriptor()), N, S, out), "rbnn_conv_wgrad_dp_workspace_query")
+        return dict(zip(CONV_WGRAD_DP_WS_KEYS, out))
+
+    def conv_head_ce_dp(self, Z, labels, S, N, Cn, scale, dZ, ce):
+        """Z, dZ [S, N, 16] float64, labels int32 [N] in [0, Cn), ce [S, N] float64."""
+        check(self.lib.rbnn_conv_head_ce_dp(ptr(Z), ptr(labels), S, N, Cn, scale, ptr(dZ), ptr(ce), stream_of(Z)), "rbnn_conv_head_ce_dp")
+
+    def conv_weight_grads_dp(self, net, X, sidx, S, ws, out):
+        """ws: the forward's workspace and the three buffers of CONV_WGRAD_DP_WS_KEYS in one dict; out: float64 tensors keyed like
+        CONV_WGRAD_DP_OUT_KEYS, which the call ADDS to."""
+        require_gpu(X, "X")
+        check(self.lib.rbnn_conv_weight_grads_dp(C.byref(net.descriptor()), ptr(X), X.stride(0), ptr(sidx), S, X.shape[0], ptr(ws["dZ"]),
+                                                 ptr(ws["P1"]), ptr(ws["arg1"]), ptr(ws["Q2"]), ptr(ws["arg2"]), ptr(ws["dO2"]), ptr(ws["dO1"]),
+                                                 *(ptr(out[k]) for k in CONV_WGRAD_DP_OUT_KEYS), stream_of(X)), "rbnn_conv_weight_grads_dp")
 
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):

@@ -1,5 +1,6 @@
 """The fp64 checker of the conv nets on the GPU (csrc/rbnn_conv_fp64.inc): forward, the three label-loss gradients with their norms,
-FGSM / PGD from the fp64 gradient's sign.
+FGSM / PGD from the fp64 gradient's sign; and, for the conv trainers, the per-sample WEIGHT gradients of the cross-entropy on the logits
+(csrc/rbnn_conv_wgrad_dp.inc: weight_gradients).
 
 The conv half of AttackEngine's precision='fp64' — which keeps refusing conv posteriors: this is an entry point of its own, as
 conv training is (train_conv).  The posterior stays the fp32 ConvStackedPosterior (K1w .. Fb as they stand: a stored stack or a
@@ -60,6 +61,7 @@ class ConvFp64Engine:
             raise _hip.HipError("the fp64 conv checker needs the HIP kernels and a posterior on the GPU: there is no fp64 path on a CPU device "
                                 "or through substitute kernels")
         self._ws_cache = {}
+        self._wgrad_ws_cache = {}
 
     @property
     def device(self):
@@ -161,6 +163,66 @@ class ConvFp64Engine:
         X = self._inputs(x)
         sidx, S = self._samples(n_samples, seeds)
         return self._gradient(X, to_labels(y, self.device), sidx, S, mode)
+
+    # ------------------------------------------------------------------ weight gradients (csrc/rbnn_conv_wgrad_dp.inc)
+    def wgrad_point_block(self, S):
+        """Points per block of weight_gradients: the forward's workspaces and dO2, dO1, ce together stay within RBNN_FP64_WS_GB."""
+        per_point = sum(self.k.conv_fp64_workspace_sizes(self.post, 1, S).values()) + sum(self.k.conv_wgrad_dp_workspace_sizes(self.post, 1, S).values())
+        budget = float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
+        return max(1, int(budget // per_point))
+
+    def _wgrad_workspace(self, N, S):
+        """The forward's workspace of (N, S) and the three buffers of the weight gradients in one dict (cached like _workspace, on its own)."""
+        cache = self._wgrad_ws_cache
+        own = cache.pop((N, S), None)
+        if own is None:
+            own = {k: self._fp64_buffer(v) for k, v in self.k.conv_wgrad_dp_workspace_sizes(self.post, N, S).items()}
+            while len(cache) > 1:
+                cache.pop(next(iter(cache)))
+        cache[(N, S)] = own
+        return {**self._workspace(N, S), **own}
+
+    def weight_gradients(self, x, y, n_samples, seeds=None, reduction="sum"):
+        """The weight gradients of the trainers' loss in fp64, per sample: ({state_dict key: float64 [S, *state_dict shape]}, ce float64
+        [S, N]).  Row s is d/dW_s of sum_n CE(W_s; x_n, y_n) ('sum': the data term of the SVI / HMC step) or of the mean over the N points
+        ('mean': ConvNnTrainer's loss, the 1/N inside dZ as in its head); CE = logsumexp(z) - z_y on the LOGITS (nn.CrossEntropyLoss), and
+        `ce` is the per-point CE, unscaled in both.  The points run in blocks under RBNN_FP64_WS_GB and every gradient element is one
+        accumulation chain over the points in ascending order, carried from block to block: the result is bit-identical between runs and
+        between point-block budgets."""
+        if reduction not in ("sum", "mean"):
+            raise _hip.HipError(f"the fp64 conv checker's weight gradients take reduction 'sum' or 'mean', not {reduction!r}")
+        if torch.is_tensor(x) and x.requires_grad:
+            raise _hip.HipError("the fp64 conv checker takes no input with requires_grad: the autograd hook is not built in fp64, and an fp32 "
+                                "backward under this name would be a lie")
+        x, yl = torch.as_tensor(x), torch.as_tensor(y)
+        N, p = int(x.shape[0]), self.post
+        if N < 1:
+            raise _hip.HipError("the fp64 conv checker's weight gradients need at least one point")
+        if yl.dim() >= 2:
+            yl = yl.argmax(-1)
+        if yl.numel() != N:
+            raise ValueError(f"{yl.numel()} labels for {N} points")
+        if int(yl.min()) < 0 or int(yl.max()) >= p.C:
+            raise _hip.HipError(f"the fp64 conv checker's weight gradients take labels in [0, {p.C}): got {int(yl.min())} .. {int(yl.max())}")
+        X = self._inputs(x)
+        labels = to_labels(yl, self.device)
+        sidx, S = self._samples(n_samples, seeds)
+        shapes = {"dK1w": (32, p.Cin, 5, 5), "dK1b": (32,), "dK2w": (p.H, 32, 5, 5), "dK2b": (p.H,), "dFw": (p.C, p.NP2 * p.H), "dFb": (p.C,)}
+        out = {}
+        for k, shp in shapes.items():               # the kernels add to these: zero before the first block
+            n = S * int(torch.Size(shp).numel())
+            out[k] = self._fp64_buffer(-(-n // 2) * 16)[:n].view((S,) + shp).zero_()
+        ce = self._fp64_buffer(-(-S * N // 2) * 16)[:S * N].view(S, N)
+        nb = self.wgrad_point_block(S)
+        for lo in range(0, N, nb):
+            hi = min(N, lo + nb)
+            n, ws = hi - lo, self._wgrad_workspace(hi - lo, S)
+            self.k.conv_forward_fp64(p, X[lo:hi], sidx, S, OUT_LOGITS, ws)
+            self.k.conv_head_ce_dp(ws["P"], labels[lo:hi], S, n, p.C, 1.0 / N if reduction == "mean" else 1.0, ws["dZ"], ws["ce"])
+            self.k.conv_weight_grads_dp(p, X[lo:hi], sidx, S, ws, out)
+            ce[:, lo:hi] = ws["ce"].view(S, n)
+        keys = ("model.0.weight", "model.0.bias", "model.3.weight", "model.3.bias", "model.7.weight", "model.7.bias")
+        return dict(zip(keys, (out[k] for k in _hip.CONV_WGRAD_DP_OUT_KEYS))), ce
 
     # ------------------------------------------------------------------ attacks: fp32 images from the sign of the fp64 gradient
     def _step(self, X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project):

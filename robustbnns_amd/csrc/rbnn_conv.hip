@@ -1164,3 +1164,5 @@ int launch_conv1_bwd_fp32(int act, int in_channels, const ConvBwdArgs& a, hipStr
 
 // the fp64 checker of the conv forward and expected input gradient (conv2 and conv2^T on the f64 MFMA): kernels and C-ABI
 #include "rbnn_conv_fp64.inc"
+// ... and of the conv weight gradients (the three contractions over the batch on the f64 MFMA): kernels and C-ABI
+#include "rbnn_conv_wgrad_dp.inc"
