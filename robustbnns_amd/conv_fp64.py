@@ -10,15 +10,12 @@ are bit-identical and a point's result depends neither on N nor on the point blo
 
 One GPU, the HIP kernels, the label losses: everything else is refused with HipError before anything is launched.  Point blocks are
 cut so that the fp64 workspaces stay under RBNN_FP64_WS_GB (default 4); the unit is one point."""
-import os
-
 import torch
 
 from . import _hip
-from ._hip import LOSS_MEAN_LOGIT, LOSS_MEAN_PROB, LOSS_PER_SAMPLE, OUT_LOGITS, OUT_PROBS
+from ._hip import LOSS_MEAN_PROB, LOSS_PER_SAMPLE, OUT_LOGITS, OUT_PROBS
 from .engine import AttackEngine, to_labels
-
-_U8 = ("arg1", "arg2")
+from .fp64_core import Fp64Core
 
 
 def kink_margin(post, x, n_samples, block=512):
@@ -60,39 +57,27 @@ class ConvFp64Engine:
         if not isinstance(self.k, _hip.HipKernels) or self.device.type != "cuda":
             raise _hip.HipError("the fp64 conv checker needs the HIP kernels and a posterior on the GPU: there is no fp64 path on a CPU device "
                                 "or through substitute kernels")
-        self._ws_cache = {}
-        self._wgrad_ws_cache = {}
+        # blocks of whole points; the second size query is weight_gradients' (dO2, dO1, ce)
+        self.fp64 = Fp64Core(self.k, posterior, self.device, [self.k.conv_fp64_workspace_sizes, self.k.conv_wgrad_dp_workspace_sizes],
+                             self.k.conv_forward_fp64, self.k.conv_input_grad_fp64, 1, posterior.D,
+                             "the fp64 conv checker differentiates the three label losses; the autograd hook's upstream modes are not built in fp64")
 
     @property
     def device(self):
         return self.post.device
 
-    # ------------------------------------------------------------------ workspaces and point blocks
+    # ------------------------------------------------------------------ point blocks (fp64_core: RBNN_FP64_WS_GB, default 4; the unit is one point)
     def point_block(self, S):
         """Points per block: the fp64 workspaces of a block (rbnn_conv_fp64_workspace_query: P, dZ, Psum, P1, Q2, the two argmax byte
-        images, the per-sample gradients) stay within RBNN_FP64_WS_GB (default 4).  The unit is one point, at least one."""
-        per_point = sum(self.k.conv_fp64_workspace_sizes(self.post, 1, S).values())
-        budget = float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
-        return max(1, int(budget // per_point))
+        images, the per-sample gradients) stay within the budget."""
+        return self.fp64.point_block(S)
 
     def point_blocks(self, N, S):
-        nb = self.point_block(S)
-        return [(lo, min(N, lo + nb)) for lo in range(0, N, nb)]
+        return self.fp64.point_blocks(N, S)
 
-    def _fp64_buffer(self, n_bytes, dtype=torch.float64):
-        """Every workspace buffer is allocated here (n_bytes of `dtype`: float64, or uint8 for the argmax images)."""
-        return torch.empty(n_bytes // torch.empty((), dtype=dtype).element_size(), dtype=dtype, device=self.device)
-
-    def _workspace(self, N, S):
-        key = (N, S)
-        ws = self._ws_cache.pop(key, None)
-        if ws is None:
-            sizes = self.k.conv_fp64_workspace_sizes(self.post, N, S)
-            ws = {k: self._fp64_buffer(v, torch.uint8 if k in _U8 else torch.float64) for k, v in sizes.items()}
-            while len(self._ws_cache) > 1:          # the full block and a ragged tail block stay cached
-                self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = ws
-        return ws
+    def wgrad_point_block(self, S):
+        """Points per block of weight_gradients: the forward's workspaces and dO2, dO1, ce together stay within the budget."""
+        return self.fp64.point_block(S, 2)
 
     # ------------------------------------------------------------------ inputs
     def _inputs(self, x, clone=False):
@@ -110,41 +95,12 @@ class ConvFp64Engine:
         """model_bnn.py:200-202,246-252: the first n_samples stored samples, or `seeds` as indices -> (int32 index buffer or None, count)."""
         return AttackEngine.sample_index(self, n_samples, seeds)
 
-    @staticmethod
-    def _check_mode(mode):
-        if mode not in (LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT):
-            raise _hip.HipError("the fp64 conv checker differentiates the three label losses; the autograd hook's upstream modes are not built in fp64")
-
     # ------------------------------------------------------------------ forward and gradient
     def forward(self, x, n_samples, seeds=None, logits=False):
         """Mean over the samples of the probabilities (or logits): float64 [N, C]."""
         X = self._inputs(x)
         sidx, S = self._samples(n_samples, seeds)
-        N, p = X.shape[0], self.post
-        out = torch.zeros(N, _hip.CPAD, dtype=torch.float64, device=self.device)
-        for lo, hi in self.point_blocks(N, S):
-            ws = self._workspace(hi - lo, S)
-            self.k.conv_forward_fp64(p, X[lo:hi], sidx, S, OUT_LOGITS if logits else OUT_PROBS, ws)
-            self.k.reduce_samples_f64(ws["P"], S, hi - lo, p.C, 1.0 / S, out[lo:hi])
-        return out[:, :p.C].clone()
-
-    def _gradient(self, X, labels, sidx, S, mode, norms=None):
-        """The summed expected input gradient, float64 [N, D] (a fresh tensor): forward + sum over samples + loss + backward per point
-        block.  The 1/S of every loss is inside dZ, as in the fp64 oracle."""
-        self._check_mode(mode)
-        N, p = X.shape[0], self.post
-        G = torch.empty(N, p.D, dtype=torch.float64, device=self.device)
-        for lo, hi in self.point_blocks(N, S):
-            n, ws = hi - lo, self._workspace(hi - lo, S)
-            self.k.conv_forward_fp64(p, X[lo:hi], sidx, S, OUT_LOGITS if mode == LOSS_MEAN_LOGIT else OUT_PROBS, ws)
-            Psum = None
-            if mode != LOSS_PER_SAMPLE:
-                Psum = ws["Psum"].view(n, _hip.CPAD)
-                self.k.reduce_samples_f64(ws["P"], S, n, p.C, 1.0, Psum)
-            self.k.loss_dlogits_f64(mode, ws["P"], Psum, labels[lo:hi], S, 1.0 / S, n, p.C, ws["dZ"])
-            self.k.conv_input_grad_fp64(p, sidx, S, n, ws, 1.0, G[lo:hi], None if norms is None else norms[0][lo:hi],
-                                        None if norms is None else norms[1][lo:hi])
-        return G
+        return self.fp64.forward(X, sidx, S, OUT_LOGITS if logits else OUT_PROBS)[:, :self.post.C].clone()
 
     def loss_gradients(self, x, y, n_samples, seeds=None, norms=False):
         """lossGradients.loss_gradient for every row of x (lossGradients.py:20-40): float64 in x's shape; norms=True: also the per-point
@@ -154,34 +110,17 @@ class ConvFp64Engine:
         nb = None
         if norms:
             nb = (torch.empty(X.shape[0], dtype=torch.float64, device=self.device), torch.empty(X.shape[0], dtype=torch.float64, device=self.device))
-        G = self._gradient(X, to_labels(y, self.device), sidx, S, LOSS_PER_SAMPLE, nb).reshape(x.shape)
+        G = self.fp64.gradient(X, to_labels(y, self.device), sidx, S, LOSS_PER_SAMPLE, nb).reshape(x.shape)
         return (G, nb[0], nb[1]) if norms else G
 
     def attack_gradient(self, x, y, n_samples, seeds=None, mode=LOSS_MEAN_PROB):
         """The gradient whose SIGN fgsm / pgd take (adversarialAttacks.py:74-79): float64 [N, D]."""
-        self._check_mode(mode)
+        self.fp64.check_mode(mode)
         X = self._inputs(x)
         sidx, S = self._samples(n_samples, seeds)
-        return self._gradient(X, to_labels(y, self.device), sidx, S, mode)
+        return self.fp64.gradient(X, to_labels(y, self.device), sidx, S, mode)
 
     # ------------------------------------------------------------------ weight gradients (csrc/rbnn_conv_wgrad_dp.inc)
-    def wgrad_point_block(self, S):
-        """Points per block of weight_gradients: the forward's workspaces and dO2, dO1, ce together stay within RBNN_FP64_WS_GB."""
-        per_point = sum(self.k.conv_fp64_workspace_sizes(self.post, 1, S).values()) + sum(self.k.conv_wgrad_dp_workspace_sizes(self.post, 1, S).values())
-        budget = float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
-        return max(1, int(budget // per_point))
-
-    def _wgrad_workspace(self, N, S):
-        """The forward's workspace of (N, S) and the three buffers of the weight gradients in one dict (cached like _workspace, on its own)."""
-        cache = self._wgrad_ws_cache
-        own = cache.pop((N, S), None)
-        if own is None:
-            own = {k: self._fp64_buffer(v) for k, v in self.k.conv_wgrad_dp_workspace_sizes(self.post, N, S).items()}
-            while len(cache) > 1:
-                cache.pop(next(iter(cache)))
-        cache[(N, S)] = own
-        return {**self._workspace(N, S), **own}
-
     def weight_gradients(self, x, y, n_samples, seeds=None, reduction="sum"):
         """The weight gradients of the trainers' loss in fp64, per sample: ({state_dict key: float64 [S, *state_dict shape]}, ce float64
         [S, N]).  Row s is d/dW_s of sum_n CE(W_s; x_n, y_n) ('sum': the data term of the SVI / HMC step) or of the mean over the N points
@@ -191,9 +130,6 @@ class ConvFp64Engine:
         between point-block budgets."""
         if reduction not in ("sum", "mean"):
             raise _hip.HipError(f"the fp64 conv checker's weight gradients take reduction 'sum' or 'mean', not {reduction!r}")
-        if torch.is_tensor(x) and x.requires_grad:
-            raise _hip.HipError("the fp64 conv checker takes no input with requires_grad: the autograd hook is not built in fp64, and an fp32 "
-                                "backward under this name would be a lie")
         x, yl = torch.as_tensor(x), torch.as_tensor(y)
         N, p = int(x.shape[0]), self.post
         if N < 1:
@@ -211,12 +147,11 @@ class ConvFp64Engine:
         out = {}
         for k, shp in shapes.items():               # the kernels add to these: zero before the first block
             n = S * int(torch.Size(shp).numel())
-            out[k] = self._fp64_buffer(-(-n // 2) * 16)[:n].view((S,) + shp).zero_()
-        ce = self._fp64_buffer(-(-S * N // 2) * 16)[:S * N].view(S, N)
-        nb = self.wgrad_point_block(S)
-        for lo in range(0, N, nb):
-            hi = min(N, lo + nb)
-            n, ws = hi - lo, self._wgrad_workspace(hi - lo, S)
+            out[k] = self.fp64.buffer(-(-n // 2) * 16)[:n].view((S,) + shp).zero_()
+        ce = self.fp64.buffer(-(-S * N // 2) * 16)[:S * N].view(S, N)
+        for lo, hi in self.fp64.point_blocks(N, S, 2):
+            n, own = hi - lo, self.fp64.workspace(hi - lo, S, 1)
+            ws = {**self.fp64.workspace(n, S), **own}
             self.k.conv_forward_fp64(p, X[lo:hi], sidx, S, OUT_LOGITS, ws)
             self.k.conv_head_ce_dp(ws["P"], labels[lo:hi], S, n, p.C, 1.0 / N if reduction == "mean" else 1.0, ws["dZ"], ws["ce"])
             self.k.conv_weight_grads_dp(p, X[lo:hi], sidx, S, ws, out)
@@ -225,22 +160,18 @@ class ConvFp64Engine:
         return dict(zip(keys, (out[k] for k in _hip.CONV_WGRAD_DP_OUT_KEYS))), ce
 
     # ------------------------------------------------------------------ attacks: fp32 images from the sign of the fp64 gradient
-    def _step(self, X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project):
-        G = self._gradient(X, labels, sidx, S, mode)
-        self.k.attack_step_f64(X, X0, G, alpha, alpha_scalar, eps, project, self.post.D)
-
     def fgsm(self, x, y, n_samples, epsilon=0.3, seeds=None, mode=LOSS_MEAN_PROB):
         """adversarialAttacks.fgsm_attack on every row of x (adversarialAttacks.py:69-83): fp32 images."""
-        self._check_mode(mode)
+        self.fp64.check_mode(mode)
         X = self._inputs(x, clone=True)
         sidx, S = self._samples(n_samples, seeds)
-        self._step(X, None, to_labels(y, self.device), sidx, S, mode, None, float(epsilon), 0.0, False)
+        self.fp64.step(X, None, to_labels(y, self.device), sidx, S, mode, None, float(epsilon), 0.0, False)
         return X.reshape(x.shape)
 
     def pgd(self, x, y, n_samples, epsilon, alpha=None, iters=40, seeds=None, mode=LOSS_MEAN_PROB):
         """adversarialAttacks.pgd_attack on every row of x (adversarialAttacks.py:86-108): fp32 images.
         alpha=None: 2/max(image) per image (:89); a float: the same step for all (2/225, :91)."""
-        self._check_mode(mode)
+        self.fp64.check_mode(mode)
         X0 = self._inputs(x, clone=True)
         sidx, S = self._samples(n_samples, seeds)
         labels = to_labels(y, self.device)
@@ -250,5 +181,5 @@ class ConvFp64Engine:
             alpha_t = torch.empty(X.shape[0], dtype=torch.float32, device=self.device)
             self.k.pgd_alpha(X0, self.post.D, alpha_t)
         for _ in range(iters):
-            self._step(X, X0, labels, sidx, S, mode, alpha_t, 0.0 if alpha is None else float(alpha), float(epsilon), True)
+            self.fp64.step(X, X0, labels, sidx, S, mode, alpha_t, 0.0 if alpha is None else float(alpha), float(epsilon), True)
         return X.reshape(x.shape)

@@ -16,12 +16,14 @@
 //                               + bias, act, MaxPool 2 stride 1                                                  -> Q2 [S][N][Hc*NP2], arg2
 //   conv_head_fp64_kernel       z[c] = sum_f Q2[f] * Fw[c][f] + Fb[c]: 16 interleaved chains (f = j, j + 16, ...) added in ascending j;
 //                               softmax with the maximum subtracted, or logits                                  -> P [S][N][16]
-//   conv_input_grad_fp64_kernel dQ2 = Fw^T dZ (c ascending) * act'(Q2), routed through pool-2 in GATHER form (a conv2 output adds the <= 4
+//   conv_backward_fp64_body     the backward of both checkers, written once (a __device__ function; WGRAD picks the tail):
+//                               dQ2 = Fw^T dZ (c ascending) * act'(Q2), routed through pool-2 in GATHER form (a conv2 output adds the <= 4
 //                               windows that chose it, rows then columns ascending) into a zero-bordered image per 16 channels;
 //                               conv2^T as  dP1[pos][ci] = sum_{k = (hc, tap)} dO2pad[hc][Y - ky + 4][X - kx + 4] * W2[hc][ci][tap]
-//                               with all accumulators resident over K = Hc*25;  * act'(P1), pool-1 routing, conv1^T as a gather over
-//                               (ci, ky, kx ascending)                                                           -> Gs [S][N][Cin*W*W]
-//   conv_sum_samples_fp64_kernel  G[n][d] = scale * sum_s Gs[s][n][d], s ascending;   conv_norms_fp64_kernel: linf / l2 per row
+//                               with all accumulators resident over K = Hc*25;  * act'(P1); then
+//   conv_input_grad_fp64_kernel   (WGRAD off) pool-1 routing, conv1^T as a gather over (ci, ky, kx ascending)  -> Gs [S][N][Cin*W*W]
+//   cwg_backward_dp_kernel        (WGRAD on, rbnn_conv_wgrad_dp.inc) the routed images themselves              -> dO2, dO1
+//   conv_sum_samples_fp64_kernel  G[n][d] = scale * sum_s Gs[s][n][d], s ascending;   conv_norms_fp64_kernel: linf / l2 per row (row_norms64)
 #include "rbnn_fp64_common.hpp"
 
 namespace {
@@ -200,29 +202,32 @@ __global__ void __launch_bounds__(256) conv_head_fp64_kernel(const ConvFp64Args 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Backward to the input: one block (4 waves) = one (sample, point).  Wave w owns the P1-position tiles w, w + 4, ... (<= MT) x both
-// ci tiles: <= 8 accumulator tiles that live through the whole K = Hc*25 loop.  Per chunk of 16 conv2 channels the block builds
-// dQ2 * act' (stage 1), routes it through pool-2 into the interior of the zero-bordered image (stage 2) and runs 25 K blocks of 16.
-// Rows past P1W*P1W of the ragged last tile repeat the last position and are never stored.
-// Dynamic LDS: 88 KiB at 1x28x28, 128 KiB at 3x32x32.
+// The backward, one text for both of its kernels: one block (4 waves) = one (sample, point).  Wave w owns the P1-position tiles w, w + 4, ...
+// (<= MT) x both ci tiles: <= 8 accumulator tiles that live through the whole K = Hc*25 loop.  Per chunk of 16 conv2 channels the block
+// builds dQ2 * act' (stage 1), routes it through pool-2 into the interior of the zero-bordered image (stage 2) and runs 25 K blocks of 16.
+// Rows past P1W*P1W of the ragged last tile repeat the last position and are never stored.  Behind the K loop dP1 * act'(P1) goes to LDS and
+//   WGRAD = false (conv_input_grad_fp64_kernel, ConvFp64Args): pool-1 routing + conv1^T as a gather over the sample's K1 in LDS -> Gs;
+//   WGRAD = true  (cwg_backward_dp_kernel of rbnn_conv_wgrad_dp.inc, CwgDpArgs): stage 2 also writes the chunk's routed image to dO2, and the
+//                 tail routes dP1 through pool-1 into dO1; K1 is neither loaded nor given room.
+// Dynamic LDS: 88 KiB at 1x28x28, 128 KiB at 3x32x32; with WGRAD 82 KiB and 109 KiB.
 // ---------------------------------------------------------------------------------------------------
-template <class G> struct BwdFp64Lds {
+template <class G, bool WGRAD = false> struct BwdFp64Lds {
     static constexpr int PB = G::O2W + 8;                                   // pitch of the image: the gradients with a border of 4
-    static constexpr int IMG = 16 * PB * PB, DQ = 16 * G::NP2, K1N = C1 * G::K1;
+    static constexpr int IMG = 16 * PB * PB, DQ = 16 * G::NP2, K1N = WGRAD ? 0 : C1 * G::K1;
     static constexpr int DOUBLES = IMG + DQ + 16 + G::P1SZ + K1N;
     static constexpr int BYTES = DOUBLES * 8 + 2 * 400 * 4 + G::P1SZ;
 };
 
-template <int ACT, class G>
-__global__ void __launch_bounds__(256) conv_input_grad_fp64_kernel(const ConvFp64Args a) {
+template <int ACT, class G, bool WGRAD, class Args>
+__device__ __forceinline__ void conv_backward_fp64_body(const Args a) {
     extern __shared__ double lds64[];
-    using L = BwdFp64Lds<G>;
-    constexpr int PB = L::PB, PP = G::P1W * G::P1W, II = G::IW * G::IW, MT = (G::NPT1 + 3) / 4;
+    using L = BwdFp64Lds<G, WGRAD>;
+    constexpr int PB = L::PB, PP = G::P1W * G::P1W, MT = (G::NPT1 + 3) / 4;
     double* const dpad = lds64;                                 // [16 hc][PB][PB]
     double* const dq = dpad + L::IMG;                           // [16 hc][NP2]
     double* const dzs = dq + L::DQ;                             // [16]
     double* const dp1 = dzs + 16;                               // [32][P1W][P1W]: dL/d(conv1 pre-activation at the window's argmax)
-    double* const k1 = dp1 + G::P1SZ;                           // [32][Cin*25]
+    double* const k1 = dp1 + G::P1SZ;                           // [32][Cin*25]  (no room with WGRAD)
     int* const tab_a = (int*)(k1 + L::K1N);                     // [400] k = hl*25 + tap -> offset into the image relative to (Y + 4, X + 4)
     int* const tab_w = tab_a + 400;                             // [400] -> offset into W2 relative to [hc0][ci]
     uint8_t* const a1s = (uint8_t*)(tab_w + 400);               // [32][P1W][P1W]
@@ -234,7 +239,8 @@ __global__ void __launch_bounds__(256) conv_input_grad_fp64_kernel(const ConvFp6
 
     if (tid < 16) dzs[tid] = (tid < a.C) ? a.dZ[sn * RBNN_CPAD + tid] : 0.;
     for (int i = tid; i < L::IMG; i += 256) dpad[i] = 0.;
-    for (int i = tid; i < L::K1N; i += 256) k1[i] = (double)a.K1w[(long long)sw * L::K1N + i];
+    if constexpr (!WGRAD)
+        for (int i = tid; i < L::K1N; i += 256) k1[i] = (double)a.K1w[(long long)sw * L::K1N + i];
     for (int i = tid; i < G::P1SZ; i += 256) a1s[i] = a.arg1[sn * G::P1SZ + i];
     for (int k = tid; k < 400; k += 256) {
         const int hl = k / 25, tap = k - hl * 25, ky = tap / 5, kx = tap - ky * 5;
@@ -261,7 +267,8 @@ __global__ void __launch_bounds__(256) conv_input_grad_fp64_kernel(const ConvFp6
             dq[o] = g * act_deriv_value64<ACT>(a.Q2[sn * F + f]);
         }
         __syncthreads();
-        // stage 2: every conv2 output adds the windows that chose it (window rows, then columns, ascending)
+        // stage 2: every conv2 output adds the windows that chose it (window rows, then columns, ascending); the chunk's 16 x NPOS values are
+        // contiguous in dO2
         for (int o = tid; o < 16 * G::NPOS; o += 256) {
             const int h = o / G::NPOS, pos = o - h * G::NPOS, y = pos / G::O2W, x = pos - y * G::O2W;
             const uint8_t* const ar = a.arg2 + sn * F + (long long)(hc0 + h) * G::NP2;
@@ -275,6 +282,7 @@ __global__ void __launch_bounds__(256) conv_input_grad_fp64_kernel(const ConvFp6
                 }
             }
             dpad[h * PB * PB + (y + 4) * PB + x + 4] = g;
+            if constexpr (WGRAD) a.dO2[(sn * a.Hc + hc0) * G::NPOS + o] = g;
         }
         __syncthreads();
         // conv2^T over the chunk: K = 16 channels x 25 taps
@@ -317,24 +325,38 @@ __global__ void __launch_bounds__(256) conv_input_grad_fp64_kernel(const ConvFp6
                 }
             }
     __syncthreads();
-    // pool-1 routing + conv1^T, gather form: an input pixel adds the conv1 outputs it fed that were their window's argmax
-    for (int o = tid; o < G::DIN; o += 256) {
-        const int cin = o / II, rem = o - cin * II, Y = rem / G::IW, X = rem - Y * G::IW;
-        double g = 0.;
-        for (int ci = 0; ci < C1; ++ci)
-            for (int ky = 0; ky < 5; ++ky) {
-                const int oy = Y - ky;
-                if (oy < 0 || oy >= G::O1) continue;
-                for (int kx = 0; kx < 5; ++kx) {
-                    const int ox = X - kx;
-                    if (ox < 0 || ox >= G::O1) continue;
-                    const int pidx = ci * PP + (oy >> 1) * G::P1W + (ox >> 1);
-                    if (a1s[pidx] == (oy & 1) * 2 + (ox & 1)) g = fma(k1[ci * G::K1 + cin * 25 + ky * 5 + kx], dp1[pidx], g);
+    if constexpr (WGRAD) {
+        // pool-1 routing: a conv1 output takes its window's gradient where it was the window's argmax, zero elsewhere
+        constexpr int OO = G::O1 * G::O1;
+        for (int o = tid; o < C1 * OO; o += 256) {
+            const int ci = o / OO, rem = o - ci * OO, oy = rem / G::O1, ox = rem - oy * G::O1;
+            const int pidx = ci * PP + (oy >> 1) * G::P1W + (ox >> 1);
+            a.dO1[sn * (C1 * OO) + o] = (a1s[pidx] == (oy & 1) * 2 + (ox & 1)) ? dp1[pidx] : 0.;
+        }
+    } else {
+        // pool-1 routing + conv1^T, gather form: an input pixel adds the conv1 outputs it fed that were their window's argmax
+        constexpr int II = G::IW * G::IW;
+        for (int o = tid; o < G::DIN; o += 256) {
+            const int cin = o / II, rem = o - cin * II, Y = rem / G::IW, X = rem - Y * G::IW;
+            double g = 0.;
+            for (int ci = 0; ci < C1; ++ci)
+                for (int ky = 0; ky < 5; ++ky) {
+                    const int oy = Y - ky;
+                    if (oy < 0 || oy >= G::O1) continue;
+                    for (int kx = 0; kx < 5; ++kx) {
+                        const int ox = X - kx;
+                        if (ox < 0 || ox >= G::O1) continue;
+                        const int pidx = ci * PP + (oy >> 1) * G::P1W + (ox >> 1);
+                        if (a1s[pidx] == (oy & 1) * 2 + (ox & 1)) g = fma(k1[ci * G::K1 + cin * 25 + ky * 5 + kx], dp1[pidx], g);
+                    }
                 }
-            }
-        a.Gs[sn * G::DIN + o] = g;
+            a.Gs[sn * G::DIN + o] = g;
+        }
     }
 }
+
+template <int ACT, class G>
+__global__ void __launch_bounds__(256) conv_input_grad_fp64_kernel(const ConvFp64Args a) { conv_backward_fp64_body<ACT, G, false>(a); }
 
 __global__ void conv_sum_samples_fp64_kernel(const double* __restrict__ Gs, int S, int N, int D, double scale, double* __restrict__ G, int ldg) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (n, d); s = 0, 1, ... in order
@@ -346,24 +368,8 @@ __global__ void conv_sum_samples_fp64_kernel(const double* __restrict__ Gs, int 
     G[n * ldg + d] = sum * scale;
 }
 
-// per-point norms of the finished gradient: one wave per row, a fixed butterfly (norms_f64_kernel of rbnn_fp64.inc)
 __global__ void __launch_bounds__(256) conv_norms_fp64_kernel(const double* __restrict__ G, int ldg, int N, int D, double* __restrict__ linf,
-                                                              double* __restrict__ l2) {
-    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (n >= N) return;
-    double m = 0., ss = 0.;
-    for (int d = lane; d < D; d += 64) {
-        const double g = G[(long long)n * ldg + d];
-        m = fmax(m, fabs(g));
-        ss = fma(g, g, ss);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o)); ss += __shfl_xor(ss, o); }
-    if (lane == 0) {
-        if (linf) linf[n] = m;
-        if (l2) l2[n] = sqrt(ss);
-    }
-}
+                                                              double* __restrict__ l2) { row_norms64(G, ldg, N, D, linf, l2); }
 
 // what the two device entry points check in common: the descriptor (validate_conv), then the block count (one block per (s, n))
 int validate_conv_fp64(const rbnn_conv_posterior* net, int32_t N, int32_t S) {

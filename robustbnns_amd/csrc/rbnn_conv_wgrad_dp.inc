@@ -4,9 +4,8 @@
 // The loss is the trainers': cross-entropy on the logits.  After that file's forward with logits out:
 //   cwg_head_dp_kernel          per (s, n): ce = logsumexp(z) - z_y and dZ = scale (softmax - e_y), the maximum subtracted, the label class
 //                               formed as -(sum of the others) / den                                             -> ce [S][N], dZ [S][N][16]
-//   cwg_backward_dp_kernel      the text of conv_input_grad_fp64_kernel up to dP1, a second time under this name (that kernel keeps its
-//                               device code): dQ2 = Fw^T dZ * act'(Q2), pool-2 routing in gather form, conv2^T on the f64 MFMA,
-//                               * act'(P1); it WRITES the routed images instead of running conv1^T           -> dO2 [S][N][Hc][NPOS], dO1 [S][N][32][O1^2]
+//   cwg_backward_dp_kernel      that file's conv_backward_fp64_body with WGRAD = true: the input gradient's stages up to dP1 * act'(P1), and it
+//                               WRITES the routed images instead of running conv1^T                         -> dO2 [S][N][Hc][NPOS], dO1 [S][N][32][O1^2]
 //   cwg_dfw_dp_kernel           dFw | dFb = dZ^T [Q2 | 1]                 M = C,  N = Hc NP2 | 1,  K = points
 //   cwg_dk2_dp_kernel           dK2 | dK2b = sum dO2 x [P1 patch | 1]     M = Hc, N = 800 | 1,     K = (point, conv2 position), gathered from P1 as
 //                               conv2_pool_fp64_kernel gathers
@@ -60,129 +59,9 @@ __global__ void cwg_head_dp_kernel(const double* __restrict__ Z, const int* __re
     for (int c = 0; c < 16; ++c) dZ[i * RBNN_CPAD + c] = (c < C) ? ((c == y ? -rest : e[c]) / den) * scale : 0.;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Backward to dO2 and dO1: one block (4 waves) = one (sample, point); conv_input_grad_fp64_kernel's stages (see there) with the chunk's
-// routed image also written to dO2, and dP1 * act'(P1) routed through pool-1 into dO1 in place of conv1^T.
-// Dynamic LDS: 82 KiB at 1x28x28, 109 KiB at 3x32x32.
-// ---------------------------------------------------------------------------------------------------
-template <class G> struct CwgBwdLds {
-    static constexpr int PB = G::O2W + 8;
-    static constexpr int IMG = 16 * PB * PB, DQ = 16 * G::NP2;
-    static constexpr int DOUBLES = IMG + DQ + 16 + G::P1SZ;
-    static constexpr int BYTES = DOUBLES * 8 + 2 * 400 * 4 + G::P1SZ;
-};
-
+// Backward to dO2 and dO1: the backward body of rbnn_conv_fp64.inc with its WGRAD switch on (see there).
 template <int ACT, class G>
-__global__ void __launch_bounds__(256) cwg_backward_dp_kernel(const CwgDpArgs a) {
-    extern __shared__ double lds64[];
-    using L = CwgBwdLds<G>;
-    constexpr int PB = L::PB, PP = G::P1W * G::P1W, OO = G::O1 * G::O1, MT = (G::NPT1 + 3) / 4;
-    double* const dpad = lds64;                                 // [16 hc][PB][PB]
-    double* const dq = dpad + L::IMG;                           // [16 hc][NP2]
-    double* const dzs = dq + L::DQ;                             // [16]
-    double* const dp1 = dzs + 16;                               // [32][P1W][P1W]: dL/d(conv1 pre-activation at the window's argmax)
-    int* const tab_a = (int*)(dp1 + G::P1SZ);                   // [400] k = hl*25 + tap -> offset into the image relative to (Y + 4, X + 4)
-    int* const tab_w = tab_a + 400;                             // [400] -> offset into W2 relative to [hc0][ci]
-    uint8_t* const a1s = (uint8_t*)(tab_w + 400);               // [32][P1W][P1W]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
-    const long long sn = blockIdx.x;
-    const int s = (int)(sn / a.N);
-    const int sw = a.sidx ? a.sidx[s] : s;
-    const long long F = (long long)a.Hc * G::NP2;
-
-    if (tid < 16) dzs[tid] = (tid < a.C) ? a.dZ[sn * RBNN_CPAD + tid] : 0.;
-    for (int i = tid; i < L::IMG; i += 256) dpad[i] = 0.;
-    for (int i = tid; i < G::P1SZ; i += 256) a1s[i] = a.arg1[sn * G::P1SZ + i];
-    for (int k = tid; k < 400; k += 256) {
-        const int hl = k / 25, tap = k - hl * 25, ky = tap / 5, kx = tap - ky * 5;
-        tab_a[k] = hl * PB * PB - ky * PB - kx;
-        tab_w[k] = hl * 800 + tap;
-    }
-    int abase[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const int pos = min((wave + 4 * m) * 16 + li, PP - 1), Y = pos / G::P1W, X = pos - Y * G::P1W;
-        abase[m] = (Y + 4) * PB + X + 4;
-    }
-    f64x4 acc[MT * 2];
-#pragma unroll
-    for (int t = 0; t < MT * 2; ++t) acc[t] = (f64x4){0., 0., 0., 0.};
-    __syncthreads();
-
-    for (int hc0 = 0; hc0 < a.Hc; hc0 += 16) {
-        // stage 1: dL/d(conv2 pre-activation at the window's argmax) of the chunk's 16*NP2 pooled outputs (contiguous features)
-        for (int o = tid; o < L::DQ; o += 256) {
-            const long long f = (long long)hc0 * G::NP2 + o;
-            double g = 0.;
-            for (int c = 0; c < a.C; ++c) g = fma(dzs[c], (double)a.Fw[((long long)sw * a.C + c) * F + f], g);
-            dq[o] = g * act_deriv_value64<ACT>(a.Q2[sn * F + f]);
-        }
-        __syncthreads();
-        // stage 2: every conv2 output adds the windows that chose it (window rows, then columns, ascending); the chunk's 16 x NPOS values are
-        // contiguous in dO2
-        for (int o = tid; o < 16 * G::NPOS; o += 256) {
-            const int h = o / G::NPOS, pos = o - h * G::NPOS, y = pos / G::O2W, x = pos - y * G::O2W;
-            const uint8_t* const ar = a.arg2 + sn * F + (long long)(hc0 + h) * G::NP2;
-            double g = 0.;
-            for (int py = y - 1; py <= y; ++py) {
-                if (py < 0 || py >= G::P2W) continue;
-                for (int px = x - 1; px <= x; ++px) {
-                    if (px < 0 || px >= G::P2W) continue;
-                    const int p = py * G::P2W + px;
-                    if (ar[p] == (y - py) * 2 + (x - px)) g += dq[h * G::NP2 + p];
-                }
-            }
-            dpad[h * PB * PB + (y + 4) * PB + x + 4] = g;
-            a.dO2[(sn * a.Hc + hc0) * G::NPOS + o] = g;
-        }
-        __syncthreads();
-        // conv2^T over the chunk: K = 16 channels x 25 taps
-        const float* const wb = a.K2w + ((long long)sw * a.Hc + hc0) * 800 + li * 25;
-        for (int k0 = 0; k0 < 400; k0 += 16) {
-            int ao[4];
-            double b0[4], b1[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = k0 + 4 * lg + r, wo = tab_w[k];
-                ao[r] = tab_a[k];
-                b0[r] = (double)wb[wo];                                     // ci = li
-                b1[r] = (double)wb[wo + 16 * 25];                           // ci = 16 + li
-            }
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                if (wave + 4 * m >= G::NPT1) continue;                      // (wave-uniform) a tile past the last position tile
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double av = dpad[abase[m] + ao[r]];
-                    acc[2 * m] = MFMA64(av, b0[r], acc[2 * m]);
-                    acc[2 * m + 1] = MFMA64(av, b1[r], acc[2 * m + 1]);
-                }
-            }
-        }
-        // (the next chunk's stage 1 writes dq only; its barrier stands between these reads of the image and stage 2's writes)
-    }
-    mfma64_drain(acc);
-    // acc[2 m + jt][r] = dL/dP1 at position (wave + 4 m)*16 + lg + 4 r, channel jt*16 + li
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int tile = wave + 4 * m, pos = tile * 16 + lg + 4 * r;
-                if (tile < G::NPT1 && pos < PP) {
-                    const int idx = (jt * 16 + li) * PP + pos;
-                    dp1[idx] = acc[2 * m + jt][r] * act_deriv_value64<ACT>(a.P1[sn * G::P1SZ + idx]);
-                }
-            }
-    __syncthreads();
-    // pool-1 routing: a conv1 output takes its window's gradient where it was the window's argmax, zero elsewhere
-    for (int o = tid; o < C1 * OO; o += 256) {
-        const int ci = o / OO, rem = o - ci * OO, oy = rem / G::O1, ox = rem - oy * G::O1;
-        const int pidx = ci * PP + (oy >> 1) * G::P1W + (ox >> 1);
-        a.dO1[sn * (C1 * OO) + o] = (a1s[pidx] == (oy & 1) * 2 + (ox & 1)) ? dp1[pidx] : 0.;
-    }
-}
+__global__ void __launch_bounds__(256) cwg_backward_dp_kernel(const CwgDpArgs a) { conv_backward_fp64_body<ACT, G, true>(a); }
 
 // ---------------------------------------------------------------------------------------------------
 // dFw | dFb: wave = (sample, 16 head features f0 .. f0 + 15), or the sample's bias tile (column 0 = the ones).  D[i = class][j = feature].
@@ -334,7 +213,7 @@ __global__ void __launch_bounds__(64) cwg_dk1_dp_kernel(const CwgDpArgs a) {
 
 template <int ACT, class G>
 int launch_cwg_backward_dp(const CwgDpArgs& a, hipStream_t st) {
-    constexpr int LDSB = CwgBwdLds<G>::BYTES;
+    constexpr int LDSB = BwdFp64Lds<G, true>::BYTES;
     static unsigned long long attr = 0;                                   // per instantiation, one bit per device
     if (!ensure_dynamic_lds((const void*)cwg_backward_dp_kernel<ACT, G>, LDSB, attr)) return RBNN_ERR_LAUNCH;
     hipLaunchKernelGGL((cwg_backward_dp_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(256), LDSB, st, a);

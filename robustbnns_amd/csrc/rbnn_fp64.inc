@@ -197,24 +197,9 @@ __global__ void __launch_bounds__(64) fc_grad_f64_kernel(const Grad64Args a) {
     }
 }
 
-// per-point norms of the finished gradient over its D real columns: one wave per row, a fixed butterfly (deterministic)
+// per-point norms of the finished gradient over its D real columns (row_norms64 of rbnn_fp64_common.hpp)
 __global__ void __launch_bounds__(256) norms_f64_kernel(const double* __restrict__ G, int ldg, int N, int D, double* __restrict__ linf,
-                                                        double* __restrict__ l2) {
-    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (n >= N) return;
-    double m = 0., ss = 0.;
-    for (int d = lane; d < D; d += 64) {
-        const double g = G[(long long)n * ldg + d];
-        m = fmax(m, fabs(g));
-        ss = fma(g, g, ss);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o)); ss += __shfl_xor(ss, o); }
-    if (lane == 0) {
-        if (linf) linf[n] = m;
-        if (l2) l2[n] = sqrt(ss);
-    }
-}
+                                                        double* __restrict__ l2) { row_norms64(G, ldg, N, D, linf, l2); }
 
 // ===================================================================================================
 // Element-wise kernels.

@@ -52,4 +52,24 @@ template <int T> __device__ __forceinline__ void mfma64_drain(f64x4 (&acc)[T]) {
     for (int t = 0; t < T; ++t) asm volatile("" : "+v"(acc[t]));
 }
 
+// per-point norms of a finished gradient G [N][ldg], the body of norms_f64_kernel and conv_norms_fp64_kernel: one wave per row (blocks of
+// whole waves), a fixed butterfly; linf / l2 may each be null
+__device__ __forceinline__ void row_norms64(const double* __restrict__ G, int ldg, int N, int D, double* __restrict__ linf,
+                                            double* __restrict__ l2) {
+    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n >= N) return;
+    double m = 0., ss = 0.;
+    for (int d = lane; d < D; d += 64) {
+        const double g = G[(long long)n * ldg + d];
+        m = fmax(m, fabs(g));
+        ss = fma(g, g, ss);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o)); ss += __shfl_xor(ss, o); }
+    if (lane == 0) {
+        if (linf) linf[n] = m;
+        if (l2) l2[n] = sqrt(ss);
+    }
+}
+
 }  // namespace

@@ -33,6 +33,7 @@ import torch
 
 from . import _hip
 from ._hip import (LOSS_MEAN_LOGIT, LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_UPSTREAM, LOSS_UPSTREAM_LOGIT, OUT_LOGITS, OUT_PROBS)
+from .fp64_core import Fp64Core
 
 _WS_DTYPE = {"mask1": torch.int32, "mask2": torch.int32}
 
@@ -120,6 +121,10 @@ class AttackEngine:
                                     "(with RBNN_FORCE_COLLECTIVES=1), never valid with more than one rank")
         self._ws_cache = {}
         self.precision = self._resolve_precision(precision)
+        if self.precision == "fp64":            # blocks of whole 16-point tiles under the workspace budget; the gradient is [N, D_pad]
+            self.fp64 = Fp64Core(self.k, posterior, self.device, [self.k.f64_workspace_sizes], self.k.fc_forward_f64, self.k.fc_input_grad_f64, 16,
+                                 posterior.Dp, "precision='fp64' differentiates the three label losses; the autograd hook's upstream gradient "
+                                 "is not built in fp64")
         self._scales = None                     # device-resident operand scales of an attack's iterates (split mode), set by the attack loops
         self._carry_image = False               # inside pgd(): attack steps also write the next iterate's triple image
 
@@ -394,67 +399,11 @@ class AttackEngine:
         out = torch.empty(8, dtype=torch.int32, device=self.device)
         return self.k.input_scales(X, self.post.D, 1.0 if iterates else 0.0, mul, add, cap, out)
 
-    # ------------------------------------------------------------------ fp64 mode (rbnn_fp64.inc)
-    def _fp64_block(self, S):
-        """Points per block of the fp64 path: the fp64 workspaces of a block (probabilities, dZ and the act' stash of every hidden layer:
-        8 S (32 + H) bytes per point, fc2 8 S (32 + 3 H)) stay within RBNN_FP64_WS_GB (default 4).  A multiple of the kernels' 16-point tile,
-        at least one tile; every result element is one accumulation chain that does not know its block, so blocking changes no bits."""
-        per_point = sum(self.k.f64_workspace_sizes(self.post, 1, S).values())
-        budget = float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
-        return max(16, int(budget // per_point) // 16 * 16)
-
-    def _fp64_buffer(self, n_bytes):
-        return torch.empty(n_bytes // 8, dtype=torch.float64, device=self.device)
-
-    def _fp64_workspace(self, N, S):
-        key = ("fp64", N, S)
-        ws = self._ws_cache.pop(key, None)
-        if ws is None:
-            ws = {k: self._fp64_buffer(v) for k, v in self.k.f64_workspace_sizes(self.post, N, S).items() if v}
-            while len(self._ws_cache) > 6:
-                self._ws_cache.pop(next(iter(self._ws_cache)))
-        self._ws_cache[key] = ws
-        return ws
-
-    def _fp64_blocks(self, N, S):
-        nb = self._fp64_block(S)
-        return [(lo, min(N, lo + nb)) for lo in range(0, N, nb)]
-
-    def _fp64_forward(self, Xp, sidx, S, out_kind, out=None):
-        """forward_padded in fp64: float64 [N, 16]."""
-        N = Xp.shape[0]
-        if out is None:
-            out = torch.zeros(N, _hip.CPAD, dtype=torch.float64, device=self.device)
-        for lo, hi in self._fp64_blocks(N, S):
-            ws = self._fp64_workspace(hi - lo, S)
-            self.k.fc_forward_f64(self.post, Xp[lo:hi], sidx, S, out_kind, ws)
-            self.k.reduce_samples_f64(ws["P"], S, hi - lo, self.post.C, 1.0 / S, out[lo:hi])
-        return out
-
-    def _fp64_gradient(self, Xp, labels, sidx, S, mode, norms=None):
-        """gradient() in fp64: the summed expected input gradient, float64 [N, D_pad] (a fresh tensor), from forward + sum over samples +
-        loss + backward per point block.  The 1/S of every loss is inside dZ, as in the fp64 oracle."""
-        if mode not in (LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT):
-            raise _hip.HipError("precision='fp64' differentiates the three label losses; the autograd hook's upstream gradient is not built in fp64")
-        N, p = Xp.shape[0], self.post
-        G = torch.empty(N, p.Dp, dtype=torch.float64, device=self.device)
-        for lo, hi in self._fp64_blocks(N, S):
-            n, ws = hi - lo, self._fp64_workspace(hi - lo, S)
-            self.k.fc_forward_f64(p, Xp[lo:hi], sidx, S, OUT_LOGITS if mode == LOSS_MEAN_LOGIT else OUT_PROBS, ws)
-            Psum = None
-            if mode != LOSS_PER_SAMPLE:
-                Psum = ws["Psum"].view(n, _hip.CPAD)
-                self.k.reduce_samples_f64(ws["P"], S, n, p.C, 1.0, Psum)
-            self.k.loss_dlogits_f64(mode, ws["P"], Psum, labels[lo:hi], S, 1.0 / S, n, p.C, ws["dZ"])
-            self.k.fc_input_grad_f64(p, sidx, S, n, ws, 1.0, G[lo:hi], None if norms is None else norms[0][lo:hi],
-                                     None if norms is None else norms[1][lo:hi])
-        return G
-
     # ------------------------------------------------------------------ forward
     def forward_padded(self, Xp, sidx, S, out_kind=OUT_PROBS, out=None):
         """mean over samples of P (probabilities or logits) -> [N, 16] buffer (columns >= C are zero); precision fp64: float64."""
         if self.precision == "fp64":
-            return self._fp64_forward(Xp, sidx, S, out_kind, out)
+            return self.fp64.forward(Xp, sidx, S, out_kind, out)
         N = Xp.shape[0]
         if out is None:
             out = torch.zeros(N, _hip.CPAD, dtype=torch.float32, device=self.device)
@@ -546,7 +495,7 @@ class AttackEngine:
         if self.precision == "fp64":
             if G_up is not None:
                 raise _hip.HipError("precision='fp64': an upstream gradient (the autograd hook) is not built in fp64")
-            return self._fp64_gradient(Xp, labels, sidx, S, mode, norms)
+            return self.fp64.gradient(Xp, labels, sidx, S, mode, norms)
         if self.precision == "lowdim" and G_up is None and mode in (LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_MEAN_LOGIT):
             per = mode == LOSS_PER_SAMPLE
             G = self._low_out(Xp.shape[0])
@@ -585,8 +534,7 @@ class AttackEngine:
     def _step(self, X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project):
         p = self.post
         if self.precision == "fp64":            # X stays fp32 (the reference's iterates are); only the SIGN of the fp64 gradient is read
-            G = self._fp64_gradient(X, labels, sidx, S, mode)
-            return self.k.attack_step_f64(X, X0, G, alpha, alpha_scalar, eps, project, p.D)
+            return self.fp64.step(X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project)
         if self.world > 1 and self.pipelined_comm:
             return self._step_sharded(X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project)
         ws, n_slabs, _ = self.gradient_slabs(X, labels, sidx, S, mode)

@@ -167,7 +167,7 @@ def test_point_blocks_follow_the_workspace_budget(recorder, monkeypatch):
     from robustbnns_amd.conv_fp64 import ConvFp64Engine
     eng = ConvFp64Engine(Post(), kernels=recorder())
     per_point = 100 * (2 * 16 * 8 + 9 * (4608 + 49 * 512) + 784 * 8) + 16 * 8                   # conv-512, S = 100 (the formula of the query test)
-    eng.k = type("K", (), {"conv_fp64_workspace_sizes": staticmethod(lambda post, N, S: {"all": N * per_point})})()
+    eng.fp64.sizes[0] = lambda post, N, S: {"all": N * per_point}
     monkeypatch.delenv("RBNN_FP64_WS_GB", raising=False)
     assert eng.point_block(100) == 4 * 2 ** 30 // per_point == 156
     assert eng.point_blocks(400, 100) == [(0, 156), (156, 312), (312, 400)]

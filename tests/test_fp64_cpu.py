@@ -140,7 +140,7 @@ def test_the_four_refusals_name_fp64_and_launch_nothing(recorder, monkeypatch):
     with pytest.raises(_hip.HipError, match=r"fp64.*upstream"):
         eng.gradient(None, None, None, 4, _hip.LOSS_UPSTREAM, G_up=torch.zeros(3, 16))
     with pytest.raises(_hip.HipError, match=r"fp64.*label losses"):
-        eng._fp64_gradient(None, None, None, 4, _hip.LOSS_UPSTREAM)
+        eng.fp64.gradient(None, None, None, 4, _hip.LOSS_UPSTREAM)
     assert recorder.calls == []
 
 
@@ -148,12 +148,28 @@ def test_point_blocks_follow_the_workspace_budget(recorder, monkeypatch):
     """RBNN_FP64_WS_GB bounds the fp64 workspaces of a block; blocks are whole 16-point tiles, never less than one."""
     eng = AttackEngine(Post(), kernels=recorder(), precision="fp64")
     per_point = 100 * (2 * 16 + 512) * 8 + 16 * 8
-    eng.k = type("K", (), {"f64_workspace_sizes": staticmethod(lambda post, N, S: {"all": N * per_point})})()
+    eng.fp64.sizes = [lambda post, N, S: {"all": N * per_point}]
     monkeypatch.delenv("RBNN_FP64_WS_GB", raising=False)
-    assert eng._fp64_block(100) == 4 * 2 ** 30 // per_point // 16 * 16 == 9856
-    assert eng._fp64_blocks(10000, 100) == [(0, 9856), (9856, 10000)]
+    assert eng.fp64.point_block(100) == 4 * 2 ** 30 // per_point // 16 * 16 == 9856
+    assert eng.fp64.point_blocks(10000, 100) == [(0, 9856), (9856, 10000)]
     monkeypatch.setenv("RBNN_FP64_WS_GB", "1e-6")
-    assert eng._fp64_block(100) == 16 and eng._fp64_blocks(33, 100) == [(0, 16), (16, 32), (32, 33)]
+    assert eng.fp64.point_block(100) == 16 and eng.fp64.point_blocks(33, 100) == [(0, 16), (16, 32), (32, 33)]
+
+
+def test_the_shared_fp64_rules_have_one_definition_each():
+    """One definition each: os.environ.get("RBNN_FP64_WS_GB" occurs once over robustbnns_amd/*.py, in fp64_core.ws_budget; the conv backward's
+    stage-2 routing line occurs once over robustbnns_amd/csrc/, in rbnn_conv_fp64.inc's conv_backward_fp64_body."""
+    import glob
+    pkg = os.path.join(ROOT, "robustbnns_amd")
+
+    def holders(patterns, needle):
+        files = sorted(f for p in patterns for f in glob.glob(os.path.join(pkg, p)))
+        return {os.path.basename(f): n for f in files if (n := open(f).read().count(needle))}
+    csrc = ("csrc/*.hip", "csrc/*.hpp", "csrc/*.inc")
+    assert holders(("*.py",), 'os.environ.get("RBNN_FP64_WS_GB"') == {"fp64_core.py": 1}
+    assert holders(csrc, "if (ar[p] == (y - py) * 2 + (x - px))") == {"rbnn_conv_fp64.inc": 1}
+    assert holders(csrc, "conv_backward_fp64_body<") == {"rbnn_conv_fp64.inc": 1, "rbnn_conv_wgrad_dp.inc": 1}      # the two one-line kernels
+    assert holders(csrc, "ss = fma(g, g, ss)") == {"rbnn_fp64_common.hpp": 1}                                        # the row norms
 
 
 def test_fp64_kernels_use_no_scratch_and_fit_the_lds():

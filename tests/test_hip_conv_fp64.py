@@ -25,7 +25,13 @@ CASES = {1: ("leaky", (1, 28, 28), 16, 10, 3, 5, 5, 0.05),          # one channe
          3: ("sigm", (1, 28, 28), 32, 2, 2, 2, 3, 0.05),            # C = 2
          4: ("relu", (3, 32, 32), 32, 10, 2, 2, 3, 0.03),           # ragged position tiles: 100 and 196
          5: ("relu", (1, 28, 28), 80, 16, 1, 1, 1, 0.05),           # S = N = 1, C = 16
-         6: ("tanh", (1, 28, 28), 16, 10, 2, 2, 3, 0.3)}            # saturated, max prob 0.99
+         6: ("tanh", (1, 28, 28), 16, 10, 2, 2, 3, 0.3),            # saturated, max prob 0.99
+         # with 1 .. 6 every (activation, geometry) instantiation of the backward runs: the three that 4 leaves out at 3x32x32
+         7: ("leaky", (3, 32, 32), 16, 10, 1, 1, 2, 0.03),
+         8: ("tanh", (3, 32, 32), 16, 10, 1, 1, 2, 0.03),
+         9: ("sigm", (3, 32, 32), 16, 10, 1, 1, 2, 0.03),
+         10: ("relu", (3, 32, 32), 80, 10, 1, 1, 2, 0.03)}          # as 5 at the other geometry: five channel tiles on four waves (a second, ragged
+                                                                    # round of the forward), six chunks of the backward
 _cache = {}
 
 
@@ -182,7 +188,7 @@ def test_exact_integers_catch_a_wrong_fragment_map_or_tap_order(shape, N):
     assert torch.equal(both * 2, (zs[0] + zs[1]).double())
     # backward
     k, Xd = eng.k, X.float().reshape(N, -1).to("cuda:0").contiguous()
-    ws = eng._workspace(N, S)
+    ws = eng.fp64.workspace(N, S)
     k.conv_forward_fp64(post, Xd, None, S, _hip.OUT_LOGITS, ws)
     dZ = torch.zeros(S, N, 16, dtype=torch.float64)
     dZ[:, :, :C] = torch.randint(-3, 4, (S, N, C), generator=g).double()
@@ -218,7 +224,7 @@ def test_bit_identical_runs_rows_and_point_blocks(monkeypatch):
         t = torch.full((n + guard,), 123, dtype=dtype, device="cuda:0")
         held.append((t, n))
         return t[:n]
-    monkeypatch.setattr(eng, "_fp64_buffer", with_canary)
+    monkeypatch.setattr(eng.fp64, "buffer", with_canary)
     c = device_results(eng, x, y, S)
     gn = eng.loss_gradients(x, y, S, norms=True)
     torch.cuda.synchronize()

@@ -17,8 +17,10 @@ pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("built_library")]
 
 DEV = "cuda:0"
 BAR = 1e-12
-MNIST_CASES = CR.GRAD_CASES[:7] + [(144, "tanh", 129, 10), (48, "leaky", 500, 3)]
-CIFAR_CASES = [(16, "leaky", 5, 10), (32, "tanh", 3, 7), (48, "relu", 17, 10)]
+# (80, ...): five channel tiles on four waves, a second, ragged round of the forward and six chunks of the backward; (16, "sigm", 2, 10): with it
+# every (activation, geometry) instantiation of the backward runs
+MNIST_CASES = CR.GRAD_CASES[:7] + [(144, "tanh", 129, 10), (48, "leaky", 500, 3), (80, "relu", 2, 10)]
+CIFAR_CASES = [(16, "leaky", 5, 10), (32, "tanh", 3, 7), (48, "relu", 17, 10), (16, "sigm", 2, 10), (80, "leaky", 2, 10)]
 _cache = {}
 
 
@@ -175,7 +177,7 @@ def test_nothing_is_written_or_read_behind_the_buffers(monkeypatch):
         t = torch.full((n + guard,), float("nan") if dtype == torch.float64 else 123, dtype=dtype, device=DEV)
         held.append((t, n))
         return t[:n]
-    monkeypatch.setattr(eng, "_fp64_buffer", with_canary)
+    monkeypatch.setattr(eng.fp64, "buffer", with_canary)
     got = eng.weight_gradients(x, lab, 1)
     torch.cuda.synchronize()
     assert _equal(want, got)

@@ -176,14 +176,14 @@ def test_bit_identical_runs_rows_and_point_blocks(monkeypatch):
         assert torch.equal(part[name], a[name][16:33]), name
     monkeypatch.setenv("RBNN_FP64_WS_GB", "1e-6")
     eng = engine(1)
-    assert eng._fp64_block(S) == 16 and eng._fp64_blocks(33, S) == [(0, 16), (16, 32), (32, 33)]
+    assert eng.fp64.point_block(S) == 16 and eng.fp64.point_blocks(33, S) == [(0, 16), (16, 32), (32, 33)]
     guard, held = 64, []
 
-    def with_canary(n_bytes):
+    def with_canary(n_bytes, dtype=torch.float64):
         t = torch.full((n_bytes // 8 + guard,), 12345.678, dtype=torch.float64, device="cuda:0")
         held.append((t, n_bytes // 8))
         return t[:n_bytes // 8]
-    monkeypatch.setattr(eng, "_fp64_buffer", with_canary)
+    monkeypatch.setattr(eng.fp64, "buffer", with_canary)
     c = device_results(eng, x, y, S)
     gn = eng.loss_gradients(x, y, S, norms=True)
     torch.cuda.synchronize()

@@ -91,7 +91,7 @@ def child(name, reps, points=0):
     else:
         sp = StackedPosterior(w["arch"], w["act"], w["shape"], w["C"], w["H"], post, "cuda:0")
         e64, engine = AttackEngine(sp, precision="fp64"), (lambda mode: AttackEngine(sp, precision=mode))
-        margin, block = (lambda: kink_margin(sp, x, n)), e64._fp64_block(n)
+        margin, block = (lambda: kink_margin(sp, x, n)), e64.fp64.point_block(n)
     g64 = e64.loss_gradients(x, y, n)
     a64 = e64.attack_gradient(x, y, n)[:, :D]
     adv64 = e64.fgsm(x, y, n, 0.3)
