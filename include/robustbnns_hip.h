@@ -1260,6 +1260,42 @@ int rbnn_conv_weight_grads_dp(const rbnn_conv_posterior *net, const float *X, in
                               const uint8_t *arg2, double *dO2, double *dO1, double *dK1w, double *dK1b, double *dK2w, double *dK2b,
                               double *dFw, double *dFb, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Weight gradients of the fc / fc2 nets in double precision (csrc/rbnn_fc_wgrad_dp.inc): the checker of the gradients of the SVI, Adam
+ * and HMC trainers, behind the forward and input gradient of the fc section above.  The loss is the trainers' cross-entropy ON THE
+ * LOGITS.  The sequence per point block: rbnn_fc_forward_f64 with RBNN_OUT_LOGITS; rbnn_conv_head_ce_dp (it knows no geometry) turns
+ * the logits into per-point CE and dZ = scale (softmax - e_y); rbnn_fc_hidden_dp writes the activations of the LAST hidden layer,
+ * which the forward keeps on the chip; rbnn_fc_input_grad_f64 turns the act' stashes into dL/d(pre-activation) of every hidden layer
+ * (its G is a by-product); rbnn_fc_weight_grads_dp contracts over the points on v_mfma_f64_16x16x4_f64:
+ *   dW2 | db2 = dZ^T [hidL | 1],   fc2: dWm | dbm = dact2^T [hid1 | 1],   dW1 | db1 = dact1^T [X | 1].
+ * No atomics.  Every output tile of 16 x 16 belongs to one wave, which LOADS its accumulator from the output buffer, walks the call's
+ * points in ascending order (an MFMA takes 4 points of one 16-point tile, points past the last contribute zeros) and stores it back:
+ * the six outputs ACCUMULATE, the caller zeroes them before the first point block, and with point blocks that are multiples of 16
+ * points an output element is the same chain of operations wherever the borders of the blocks fall — bit-identical between runs and
+ * between point-block sizes.  All four activations, n_classes <= 16, hidden a multiple of 4, n_samples <= 65535,
+ * n_points * n_samples < 2^31.  The outputs are indexed by POSITION in the call and have the state_dict's layouts with the
+ * descriptor's hidden and the UNPADDED in_features: dW1 [S,H,D], db1 [S,H], dWm [S,H,H], dbm [S,H] (fc2, else not read), dW2 [S,C,H],
+ * db2 [S,C].  A hidden unit the caller padded the net with has act(0) != 0 under the sigmoid: its columns of dWm and dW2 are not zero,
+ * the caller's to drop.  Every argument is checked on the host before any launch: a null pointer RBNN_ERR_NULL; ldx below in_stride
+ * or not a multiple of 4 and the counts RBNN_ERR_SHAPE; a misaligned X or fp64 input RBNN_ERR_ALIGN; the net as in the fc section.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_FC_WGRAD_DP_WS_BUFFERS 2
+/* bytes[0 .. 1] <- sizes of ce [S,N] and hidL [S,N,H] (doubles) for N points x S used samples.
+ * [host; bytes: host array of RBNN_FC_WGRAD_DP_WS_BUFFERS] */
+int rbnn_fc_wgrad_dp_workspace_query(const rbnn_posterior *net, int32_t n_points, int32_t n_samples, size_t *bytes);
+
+/* hidL[s,n,h] = act(A[s,n,:] . W_s[h,:] + b_s[h]) in fp64 on the f64 MFMA.  fc: A = X (fp32 [N, ldx] as in the forward), W = W1;
+ * fc2: A = hid1 of rbnn_fc_forward_f64 (fc: not read), W = Wm.  1 launch. */
+int rbnn_fc_hidden_dp(const rbnn_posterior *net, const float *X, int32_t ldx, const int32_t *sample_idx, int32_t n_samples,
+                      int32_t n_points, const double *hid1, double *hidL, void *stream);
+
+/* The weight gradients of n_points points, ADDED to the six outputs (see above).  dZ of the head; dact1 (and dact2) as
+ * rbnn_fc_input_grad_f64 left them; hid1 of the forward and hidL of rbnn_fc_hidden_dp.  Reads no weight: there is no sample_idx.
+ * fc (hid1, dact2, dWm, dbm not read): 2 launches, fc2: 3. */
+int rbnn_fc_weight_grads_dp(const rbnn_posterior *net, const float *X, int32_t ldx, int32_t n_samples, int32_t n_points,
+                            const double *dZ, const double *dact1, const double *hid1, const double *dact2, const double *hidL,
+                            double *dW1, double *db1, double *dWm, double *dbm, double *dW2, double *db2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,9 @@ assert len(CONV_FP64_WS_KEYS) == CONV_FP64_WS_BUFFERS
 CONV_WGRAD_DP_WS_KEYS = ("ce", "dO2", "dO1")                       # rbnn_conv_wgrad_dp_workspace_query's order: the weight-gradient checker's own buffers
 assert len(CONV_WGRAD_DP_WS_KEYS) == CONV_WGRAD_DP_WS_BUFFERS
 CONV_WGRAD_DP_OUT_KEYS = ("dK1w", "dK1b", "dK2w", "dK2b", "dFw", "dFb")     # rbnn_conv_weight_grads_dp's six outputs, in its order
+FC_WGRAD_DP_WS_KEYS = ("ce", "hidL")                              # rbnn_fc_wgrad_dp_workspace_query's order: the fc / fc2 weight-gradient checker's own buffers
+assert len(FC_WGRAD_DP_WS_KEYS) == FC_WGRAD_DP_WS_BUFFERS
+FC_WGRAD_DP_OUT_KEYS = ("dW1", "db1", "dWm", "dbm", "dW2", "db2")  # rbnn_fc_weight_grads_dp's six outputs, in its order (dWm, dbm: fc2)
 
 _lib = None
 
@@ -361,6 +364,27 @@ class HipKernels:
         check(self.lib.rbnn_conv_weight_grads_dp(C.byref(net.descriptor()), ptr(X), X.stride(0), ptr(sidx), S, X.shape[0], ptr(ws["dZ"]),
                                                  ptr(ws["P1"]), ptr(ws["arg1"]), ptr(ws["Q2"]), ptr(ws["arg2"]), ptr(ws["dO2"]), ptr(ws["dO1"]),
                                                  *(ptr(out[k]) for k in CONV_WGRAD_DP_OUT_KEYS), stream_of(X)), "rbnn_conv_weight_grads_dp")
+
+    # -- ... and of the fc / fc2 weight gradients (rbnn_fc_wgrad_dp.inc): behind fc_forward_f64 with logits out, conv_head_ce_dp and
+    #    fc_input_grad_f64 -----------------------------------------------------------------------------------------------------------------
+    def fc_wgrad_dp_workspace_sizes(self, net, N, S):
+        out = (C.c_size_t * FC_WGRAD_DP_WS_BUFFERS)()
+        check(self.lib.rbnn_fc_wgrad_dp_workspace_query(C.byref(net.descriptor(lazy_ok=True)), N, S, out), "rbnn_fc_wgrad_dp_workspace_query")
+        return dict(zip(FC_WGRAD_DP_WS_KEYS, out))
+
+    def fc_hidden_dp(self, net, X, sidx, S, ws):
+        """ws: the forward's workspace (hid1: fc2) and hidL, which is written: the activations of the last hidden layer."""
+        require_gpu(X, "X")
+        check(self.lib.rbnn_fc_hidden_dp(C.byref(net.descriptor()), ptr(X), X.stride(0), ptr(sidx), S, X.shape[0], ptr(ws.get("hid1")),
+                                         ptr(ws["hidL"]), stream_of(X)), "rbnn_fc_hidden_dp")
+
+    def fc_weight_grads_dp(self, net, X, S, ws, out):
+        """ws: the forward's workspace after fc_input_grad_f64 (dZ, dact1, hid1, dact2) and hidL in one dict; out: float64 tensors keyed like
+        FC_WGRAD_DP_OUT_KEYS (dWm, dbm: fc2 only), which the call ADDS to."""
+        require_gpu(X, "X")
+        check(self.lib.rbnn_fc_weight_grads_dp(C.byref(net.descriptor()), ptr(X), X.stride(0), S, X.shape[0], ptr(ws["dZ"]), ptr(ws["dact1"]),
+                                               ptr(ws.get("hid1")), ptr(ws.get("dact2")), ptr(ws["hidL"]),
+                                               *(ptr(out.get(k)) for k in FC_WGRAD_DP_OUT_KEYS), stream_of(X)), "rbnn_fc_weight_grads_dp")
 
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):

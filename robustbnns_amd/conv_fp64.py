@@ -15,7 +15,7 @@ import torch
 from . import _hip
 from ._hip import LOSS_MEAN_PROB, LOSS_PER_SAMPLE, OUT_LOGITS, OUT_PROBS
 from .engine import AttackEngine, to_labels
-from .fp64_core import Fp64Core
+from .fp64_core import Fp64Core, wgrad_arguments
 
 
 def kink_margin(post, x, n_samples, block=512):
@@ -128,18 +128,8 @@ class ConvFp64Engine:
         `ce` is the per-point CE, unscaled in both.  The points run in blocks under RBNN_FP64_WS_GB and every gradient element is one
         accumulation chain over the points in ascending order, carried from block to block: the result is bit-identical between runs and
         between point-block budgets."""
-        if reduction not in ("sum", "mean"):
-            raise _hip.HipError(f"the fp64 conv checker's weight gradients take reduction 'sum' or 'mean', not {reduction!r}")
-        x, yl = torch.as_tensor(x), torch.as_tensor(y)
-        N, p = int(x.shape[0]), self.post
-        if N < 1:
-            raise _hip.HipError("the fp64 conv checker's weight gradients need at least one point")
-        if yl.dim() >= 2:
-            yl = yl.argmax(-1)
-        if yl.numel() != N:
-            raise ValueError(f"{yl.numel()} labels for {N} points")
-        if int(yl.min()) < 0 or int(yl.max()) >= p.C:
-            raise _hip.HipError(f"the fp64 conv checker's weight gradients take labels in [0, {p.C}): got {int(yl.min())} .. {int(yl.max())}")
+        p = self.post
+        x, yl, N = wgrad_arguments("the fp64 conv checker", x, y, p.C, reduction)
         X = self._inputs(x)
         labels = to_labels(yl, self.device)
         sidx, S = self._samples(n_samples, seeds)

@@ -970,3 +970,5 @@ int rbnn_svi_materialize(const float* loc, const float* scale_raw, const float* 
 
 // the fp64 precision mode (fc / fc2 forward and expected input gradient on the f64 MFMA): kernels and C-ABI
 #include "rbnn_fp64.inc"
+// ... and of the fc / fc2 weight gradients (the hidden activations and the contractions over the points): kernels and C-ABI
+#include "rbnn_fc_wgrad_dp.inc"

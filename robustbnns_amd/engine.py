@@ -25,7 +25,8 @@ in the HIP kernels behind `kernels` (robustbnns_amd._hip.HipKernels — there is
 this package; tests inject a CPU fake to exercise the multi-process orchestration under gloo).
 "fp64" (opt-in, never picked by auto / fast): fc / fc2 on one GPU with the fp32 data widened on load and every operation in fp64, the
 contractions on the f64 MFMA (rbnn_fc_forward_f64 / rbnn_fc_input_grad_f64, rbnn_fp64.inc): forward, the three label-loss gradients and their
-norms come back as float64, fgsm / pgd images stay fp32 (only the gradient's sign is read).  The device-side checker of the other modes.
+norms come back as float64, fgsm / pgd images stay fp32 (only the gradient's sign is read).  The device-side checker of the other modes —
+and, through weight_gradients (rbnn_fc_wgrad_dp.inc), of the fc / fc2 trainers' and samplers' weight gradients.
 """
 import os
 
@@ -33,7 +34,8 @@ import torch
 
 from . import _hip
 from ._hip import (LOSS_MEAN_LOGIT, LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_UPSTREAM, LOSS_UPSTREAM_LOGIT, OUT_LOGITS, OUT_PROBS)
-from .fp64_core import Fp64Core
+from .fp64_core import Fp64Core, wgrad_arguments
+from .posterior import LAYER_KEYS
 
 _WS_DTYPE = {"mask1": torch.int32, "mask2": torch.int32}
 
@@ -122,7 +124,9 @@ class AttackEngine:
         self._ws_cache = {}
         self.precision = self._resolve_precision(precision)
         if self.precision == "fp64":            # blocks of whole 16-point tiles under the workspace budget; the gradient is [N, D_pad]
-            self.fp64 = Fp64Core(self.k, posterior, self.device, [self.k.f64_workspace_sizes], self.k.fc_forward_f64, self.k.fc_input_grad_f64, 16,
+            # (the second size query is weight_gradients': ce, hidL)
+            self.fp64 = Fp64Core(self.k, posterior, self.device, [self.k.f64_workspace_sizes, self.k.fc_wgrad_dp_workspace_sizes],
+                                 self.k.fc_forward_f64, self.k.fc_input_grad_f64, 16,
                                  posterior.Dp, "precision='fp64' differentiates the three label losses; the autograd hook's upstream gradient "
                                  "is not built in fp64")
         self._scales = None                     # device-resident operand scales of an attack's iterates (split mode), set by the attack loops
@@ -529,6 +533,51 @@ class AttackEngine:
         xin = self._flat(x) if self.precision == "lowdim" else self.pad_inputs(x)
         G = self.gradient(xin, to_labels(y, self.device), sidx, S, LOSS_PER_SAMPLE, norms=nb)
         return (self.unpad(G, x), nb[0], nb[1]) if norms else self.unpad(G, x)
+
+    # ------------------------------------------------------------------ weight gradients in fp64 (csrc/rbnn_fc_wgrad_dp.inc)
+    def weight_gradients(self, x, y, n_samples, seeds=None, reduction="sum"):
+        """The weight gradients of the fc / fc2 trainers' loss in fp64, per sample (precision='fp64' only): ({state_dict key: float64
+        [S, *state_dict shape]}, ce float64 [S, N]), as ConvFp64Engine.weight_gradients returns them.  Row s is d/dW_s of
+        sum_n CE(W_s; x_n, y_n) ('sum': the data term of the SVI / HMC step) or of the mean over the N points ('mean': NnTrainer's loss, the
+        1/N inside dZ as in its head); CE = logsumexp(z) - z_y on the LOGITS, and `ce` is the per-point CE, unscaled in both.  The points run
+        in blocks of whole 16-point tiles under RBNN_FP64_WS_GB (the input gradient's scratch, a by-product, comes on top) and every
+        gradient element is one accumulation chain over the points in ascending order, carried from block to block: the result is
+        bit-identical between runs and between point-block budgets."""
+        if self.precision != "fp64":
+            raise _hip.HipError(f"weight_gradients is the fp64 checker of the fc / fc2 trainers' gradients and runs under precision='fp64' "
+                                f"only: this engine computes in {self.precision!r}, and an fp32 answer under this name would be a lie")
+        p = self.post
+        x, yl, N = wgrad_arguments("the fp64 fc checker", x, y, p.C, reduction)
+        if x.requires_grad:
+            raise _hip.HipError("the fp64 fc checker's weight gradients take no input with requires_grad: the autograd hook is not built in fp64")
+        X = self.pad_inputs(x)
+        labels = to_labels(yl, self.device)
+        sidx, S = self.sample_index(n_samples, seeds)
+        fc2 = p.arch == "fc2"
+        shapes = {"dW1": (p.Hp, p.D), "db1": (p.Hp,), "dWm": (p.Hp, p.Hp), "dbm": (p.Hp,), "dW2": (p.C, p.Hp), "db2": (p.C,)}
+        out = {}
+        for k, shp in shapes.items():               # the kernels add to these: zero before the first block
+            if fc2 or k not in ("dWm", "dbm"):
+                n = S * int(torch.Size(shp).numel())
+                out[k] = self.fp64.buffer(-(-n // 2) * 16)[:n].view((S,) + shp).zero_()
+        ce = self.fp64.buffer(-(-S * N // 2) * 16)[:S * N].view(S, N)
+        blocks = self.fp64.point_blocks(N, S, 2)
+        G = self.fp64.buffer((blocks[0][1] - blocks[0][0]) * p.Dp * 8).view(-1, p.Dp)       # the input gradient: a by-product, discarded
+        for lo, hi in blocks:
+            n = hi - lo
+            ws = {**self.fp64.workspace(n, S), **self.fp64.workspace(n, S, 1)}
+            self.k.fc_forward_f64(p, X[lo:hi], sidx, S, OUT_LOGITS, ws)
+            self.k.conv_head_ce_dp(ws["P"], labels[lo:hi], S, n, p.C, 1.0 / N if reduction == "mean" else 1.0, ws["dZ"], ws["ce"])
+            self.k.fc_hidden_dp(p, X[lo:hi], sidx, S, ws)
+            self.k.fc_input_grad_f64(p, sidx, S, n, ws, 1.0, G[:n])          # dact1 (dact2) <- dL/d(pre-activation)
+            self.k.fc_weight_grads_dp(p, X[lo:hi], S, ws, out)
+            ce[:, lo:hi] = ws["ce"].view(S, n)
+        if p.Hp != p.H:                             # a padded hidden unit has act(0) != 0 under the sigmoid: its columns are not zero, and not the net's
+            real = {"dW1": (p.H, p.D), "db1": (p.H,), "dWm": (p.H, p.H), "dbm": (p.H,), "dW2": (p.C, p.H), "db2": (p.C,)}
+            out = {k: v[(slice(None),) + tuple(slice(0, d) for d in real[k])].contiguous() for k, v in out.items()}
+        names = [k for k in _hip.FC_WGRAD_DP_OUT_KEYS if k in out]
+        keys = [layer + sfx for layer in LAYER_KEYS[p.arch] for sfx in (".weight", ".bias")]
+        return dict(zip(keys, (out[k] for k in names))), ce
 
     # ------------------------------------------------------------------ attacks
     def _step(self, X, X0, labels, sidx, S, mode, alpha, alpha_scalar, eps, project):

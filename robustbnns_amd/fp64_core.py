@@ -1,7 +1,8 @@
-"""What the fp64 checkers share on the host: AttackEngine's precision='fp64' (fc / fc2, rbnn_fp64.inc) and conv_fp64.ConvFp64Engine with its
-weight gradients (rbnn_conv_fp64.inc, rbnn_conv_wgrad_dp.inc).  The workspace budget, the point blocks cut from it, the cached workspaces and
-the sequence forward -> sum over samples -> loss -> input gradient per block are written here once; a user gives the pair of kernel wrappers,
-its workspace-size queries, the block unit and the gradient's width.
+"""What the fp64 checkers share on the host: AttackEngine's precision='fp64' (fc / fc2, rbnn_fp64.inc, rbnn_fc_wgrad_dp.inc) and
+conv_fp64.ConvFp64Engine (rbnn_conv_fp64.inc, rbnn_conv_wgrad_dp.inc), each with its weight gradients.  The workspace budget, the point blocks
+cut from it, the cached workspaces, the sequence forward -> sum over samples -> loss -> input gradient per block and what both
+weight_gradients refuse are written here once; a user gives the pair of kernel wrappers, its workspace-size queries, the block unit and the
+gradient's width.
 
 Every result element is one accumulation chain that does not know its block, so blocking changes no bits."""
 import os
@@ -17,6 +18,24 @@ _U8 = ("arg1", "arg2")                      # the conv forward's argmax images: 
 def ws_budget():
     """Bytes the fp64 workspaces of one point block may take: RBNN_FP64_WS_GB (default 4)."""
     return float(os.environ.get("RBNN_FP64_WS_GB", "4")) * 2 ** 30
+
+
+def wgrad_arguments(who, x, y, n_classes, reduction):
+    """What both checkers' weight_gradients refuse before anything is launched (`who` names the checker in the message): a reduction other
+    than 'sum' / 'mean', no point, labels outside [0, n_classes).  -> (x as a tensor, integer labels [N], N)"""
+    if reduction not in ("sum", "mean"):
+        raise _hip.HipError(f"{who}'s weight gradients take reduction 'sum' or 'mean', not {reduction!r}")
+    x, yl = torch.as_tensor(x), torch.as_tensor(y)
+    N = int(x.shape[0])
+    if N < 1:
+        raise _hip.HipError(f"{who}'s weight gradients need at least one point")
+    if yl.dim() >= 2:
+        yl = yl.argmax(-1)
+    if yl.numel() != N:
+        raise ValueError(f"{yl.numel()} labels for {N} points")
+    if int(yl.min()) < 0 or int(yl.max()) >= n_classes:
+        raise _hip.HipError(f"{who}'s weight gradients take labels in [0, {n_classes}): got {int(yl.min())} .. {int(yl.max())}")
+    return x, yl, N
 
 
 class Fp64Core:
