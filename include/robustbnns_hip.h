@@ -1296,6 +1296,48 @@ int rbnn_fc_weight_grads_dp(const rbnn_posterior *net, const float *X, int32_t l
                             const double *dZ, const double *dact1, const double *hid1, const double *dact2, const double *hidL,
                             double *dW1, double *db1, double *dWm, double *dbm, double *dW2, double *db2, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Weight-space PCA of posterior samples (csrc/rbnn_wpca.inc): the numerical half of the reference's test_multimodal.py, which
+ * projects the flattened samples of HMC posteriors and 1000 draws of the N(0, I) prior onto two principal components with
+ * sklearn's PCA on the host.  With n rows of P weights, n << P, PCA is the n x n Gram matrix of the centred rows, contracted
+ * over P, and an n x n eigenproblem (the host's).  Rows are fp32 with their own row strides (in elements, >= the columns of the
+ * call) and need 4-byte alignment only; every product and sum is double precision, the Gram contraction on
+ * v_mfma_f64_16x16x4_f64, and the mean is subtracted in double precision BEFORE the product.  The caller sweeps P in column
+ * slabs whose borders are multiples of RBNN_WPCA_CHUNK and passes pointers offset to the slab: every call below sees columns
+ * [0, P) of its own pointers.  No atomics; two runs are bit-identical; the bits of C[i,j] are a function of row i of Y, row j of
+ * X, mu and the total column count alone — not of m, n, the other rows, the workspace or the slabs.  Every argument is checked on
+ * the host before any launch: a null pointer RBNN_ERR_NULL; a count below 1, a stride below the columns, e0 not a multiple of 4,
+ * more than RBNN_WPCA_MAX_COMPONENTS components, a workspace below the minimum, a size whose product overflows RBNN_ERR_SHAPE.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_WPCA_CHUNK 2048          /* columns of one partial sum of the Gram contraction */
+#define RBNN_WPCA_TENSOR 0x57504341   /* the Philox counter word of the prior's rows ("WPCA") */
+#define RBNN_WPCA_MAX_COMPONENTS 16
+
+/* The workspace of rbnn_wpca_cross_gram for Y [m, P] against X [n, P]: one chunk's partials of every 16 x 16 tile,
+ * min = ceil(m/16) ceil(n/16) 256 doubles, which the call needs at least; full = ceil(P / RBNN_WPCA_CHUNK) of them, with which it
+ * runs one round.  [host] */
+int rbnn_wpca_workspace_query(int32_t m, int32_t n, int64_t P, size_t *min_bytes, size_t *full_bytes);
+
+/* out[r - r0, e - e0] (fp32, row stride ld >= w) for rows r0 .. r0 + n and columns e0 .. e0 + w of the prior's matrix: the standard
+ * normal of Philox4x32-10 counter (e / 4, RBNN_WPCA_TENSOR, r, 0) under the 64-bit key, component e % 4, through the SVI draw's
+ * Box-Muller.  A value depends on (key, r, e) only.  n <= 65535 per call, e0 + w <= 2^34.  1 launch. */
+int rbnn_wpca_normal_rows(uint64_t key, int32_t r0, int32_t n, int64_t e0, int64_t w, float *out, int64_t ld, void *stream);
+
+/* mu[e] = (sum_r X[r, e]) / n in double precision, r ascending, e < P.  1 launch. */
+int rbnn_wpca_col_mean(const float *X, int64_t ldx, int32_t n, int64_t P, double *mu, void *stream);
+
+/* C[i, j] += sum_{e < P} (Y[i, e] - mu[e]) (X[j, e] - mu[e]) for Y [m, P], X [n, P], C [m, ldc >= n] doubles: the caller zeroes C
+ * before the first slab.  One wave per 16 x 16 tile and chunk starts from zero and sums its chunk in a fixed column order; a round
+ * is as many chunks as ws (ws_bytes, at least the query's minimum) holds; a second launch per round adds the round's partials to C
+ * in chunk order.  2 launches per round. */
+int rbnn_wpca_cross_gram(const float *Y, int64_t ldy, int32_t m, const float *X, int64_t ldx, int32_t n, const double *mu, int64_t P,
+                         double *C, int64_t ldc, double *ws, size_t ws_bytes, void *stream);
+
+/* V[c, e] = sum_i A[c, i] (X[i, e] - mu[e]) for A [k, n] doubles, k <= RBNN_WPCA_MAX_COMPONENTS, i ascending, V [k, ldv >= P]
+ * doubles: the principal axes when A = (u / sqrt(lambda))^T.  1 launch. */
+int rbnn_wpca_components(const double *A, int32_t k, const float *X, int64_t ldx, int32_t n, const double *mu, int64_t P, double *V,
+                         int64_t ldv, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
