@@ -1338,6 +1338,38 @@ int rbnn_wpca_cross_gram(const float *Y, int64_t ldy, int32_t m, const float *X,
 int rbnn_wpca_components(const double *A, int32_t k, const float *X, int64_t ldx, int32_t n, const double *mu, int64_t P, double *V,
                          int64_t ldv, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-weight convergence diagnostics of HMC chains (csrc/rbnn_chain_diag.inc): split R-hat and effective sample size per
+ * element, what pyro's mcmc.diagnostics() gives per element of every sample site (pyro's ops.stats formulas).  X is the pooled
+ * stack of a run of C chains of N draws as fp32 [C * N, ldx >= P], row c * N + t = draw t of chain c, 4-byte alignment; every
+ * column is one independent problem, computed by one lane in double precision with plain FMAs:
+ *    m_c = (sum_t x[c,t]) / N,  d[c,t] = x[c,t] - m_c             (subtracted before any product)
+ *    S[c,k] = sum_{t < N-k} d[c,t] d[c,t+k],  gamma[c,k] = S[c,k] / (N - k)
+ *    W = mean_c(gamma[c,0]) N / (N - 1),  V = W (N - 1) / N  (+ the unbiased variance over c of m_c when C > 1)
+ *    r_hat = sqrt(V / W);  split_r_hat: the same on the 2C sequences of length h = N / 2, the first h and the last h draws of
+ *    each chain (the middle draw of an odd N is dropped): hmc.split_r_hat's value for a [C, N] input
+ *    rho_0 = 1,  rho_k = 1 - (W - mean_c gamma[c,k]) / V,  Rho_p = rho_2p + rho_2p+1 for p < N / 2
+ *    Rho'_p = min_{q <= p} max(Rho_q, 0)  (Geyer's initial monotone positive sequence)
+ *    tau = -1 + 2 sum_p Rho'_p,  n_eff = C N / tau,  n_pairs = the first p with Rho_p <= 0, or N / 2
+ *    mean, std: over all C N draws, std unbiased
+ * A constant column (W == 0): r_hat and split_r_hat are 1 when V == 0 too and inf otherwise, tau and n_eff NaN, n_pairs 0.
+ * Nothing else is clamped: a tau <= 0 of short chains gives the n_eff the formula gives.  Every sum runs in ascending t, then
+ * ascending c; no atomics; two runs are bit-identical, and the bits of a column's results are a function of its C N values alone —
+ * not of P, the other columns, ldx, the alignment of X or the column slabs of the caller.  Every input element is read from
+ * global memory once.  Checked on the host before any launch: X null RBNN_ERR_NULL; C < 1, N < 4,
+ * N > RBNN_CHAIN_DIAG_MAX_DRAWS, P < 1, C N >= 2^31, ldx < P or a size whose product overflows RBNN_ERR_SHAPE.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_CHAIN_DIAG_MAX_DRAWS 768   /* draws per chain: 12 N bytes of LDS per column, 16 columns per block at this N */
+
+/* max_draws = RBNN_CHAIN_DIAG_MAX_DRAWS (written whatever the shape); lds_bytes = what a block of rbnn_chain_diag takes at this
+ * n_draws: 12 n_draws T with T = 64 (n_draws <= 53), 32 (<= 106) or 16 columns.  Either pointer may be null.  [host] */
+int rbnn_chain_diag_query(int32_t n_chains, int32_t n_draws, int64_t P, int32_t *max_draws, size_t *lds_bytes);
+
+/* The seven results per column, doubles [P] (n_pairs: int32 [P]); an output that is null is not written.  1 launch. */
+int rbnn_chain_diag(const float *X, int64_t ldx, int32_t n_chains, int32_t n_draws, int64_t P,
+                    double *mean, double *std, double *r_hat, double *split_r_hat,
+                    double *tau, double *n_eff, int32_t *n_pairs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

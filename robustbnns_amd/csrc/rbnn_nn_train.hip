@@ -67,3 +67,5 @@ int rbnn_nn_train_finalize(const rbnn_nn_train_net* net, const rbnn_nn_train_ws*
 
 // the weight-space PCA of posterior samples: entry points of its own, nothing of the trainers' (see the file's header for why it sits here)
 #include "rbnn_wpca.inc"
+// ... and the per-weight diagnostics of HMC chains, for the same reason
+#include "rbnn_chain_diag.inc"
