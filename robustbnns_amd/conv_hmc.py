@@ -18,8 +18,9 @@ block once per transition, sampling makes no device->host synchronisation.  Two 
 ConvLockstepHmc runs K such chains of one net shape with every launch covering all of them (BNN.train_hmc_conv(num_chains=K)): it is
 hmc.LockstepHmc's host side (hmc._LockstepChains) on the rbnn_conv_hmc_chains_* entry points.  The chains are the members of the conv
 ensemble's forward and weight gradients (4 + 7 launches whatever K is), so the positions, gradients and every per-parameter chain buffer are
-TENSOR-MAJOR — six blocks [K, size of tensor] — and four element-wise kernels of csrc/rbnn_hmc.hip run the single chain's bodies on that
-layout; the partial sums, state blocks, logs and sample stacks stay chain-major.  Chain k is bit-identical to ConvHmcSampler running it
+TENSOR-MAJOR — six blocks [K, size of tensor] — and the four element-wise lockstep kernels of csrc/rbnn_hmc.hip, the ones hmc.LockstepHmc
+launches, run the single chain's bodies on that layout through their tensor-major view; the partial sums, state blocks, logs and sample
+stacks stay chain-major.  Chain k is bit-identical to ConvHmcSampler running it
 alone; hmc.split_r_hat is the convergence figure that goes with several chains.  conv_hmc_chains_group says how many chains' workspaces fit
 the conv workspace budget.
 

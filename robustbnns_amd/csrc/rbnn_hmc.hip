@@ -32,9 +32,11 @@
 // rbnn_conv_svi_train_net whose W is the trajectory's position and whose grad receives dCE/dW.  No device code of its own.
 //
 // K chains over conv nets of one shape (rbnn_conv_hmc_chains_*): the chain is grid dimension y, the per-parameter buffers are tensor-major (the
-// stacks the conv forward and weight gradients of K nets work on: rbnn_conv_hmc_chains_stage / _gradient in rbnn_conv_train.hip).  Four kernels
-// of their own (conv_chains_momentum / _update / _commit / _window_end_kernel) call the bodies below on a shifted view of chain k with the single
-// chain's flat index; the decision is lockstep_decide_kernel.  Chain k is bit-identical to the single conv chain.
+// stacks the conv forward and weight gradients of K nets work on: rbnn_conv_hmc_chains_stage / _gradient in rbnn_conv_train.hip).  Chain k is bit-identical to the single conv chain.
+//
+// Both lockstep forms are ONE set of kernels and one host body per operation: lockstep_momentum / _update / _commit / _window_end_kernel<View>
+// call the bodies below with the single chain's flat index on chain k's buffers, and the view (ChainMajor, TensorMajor) says where those lie
+// and how its entry points' checks differ; the decision, which touches no per-parameter buffer, is lockstep_decide_kernel for both.
 #define RBNN_TRAIN_LOCKSTEP
 #include "rbnn_train_gemm.hpp"
 #include "rbnn_conv_layout.hpp"
@@ -233,9 +235,10 @@ __global__ void __launch_bounds__(ELT_THREADS) hmc_window_end_kernel(long long n
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K chains in lockstep: the chain is grid dimension y of every launch.  Chain k's buffers are the shared ones at k times their stride; its
-// key is keys[k]; with active != NULL a chain whose entry is 0 is neither read nor written (its blocks return at once, before any barrier).
-// No sum crosses chains and a chain's block plan does not depend on K: chain k is bit-identical to that chain alone.
+// K chains behind every launch: the chain is grid dimension y.  Chain k's key is keys[k]; with active != NULL a chain whose entry is 0 is
+// neither read nor written (its blocks return at once, before any barrier).  No sum crosses chains and a chain's block plan does not depend
+// on K: chain k is bit-identical to that chain alone.  The partial sums, state, log and samples of chain k lie at k times their stride; where
+// its per-parameter buffers (and its part of W / grad) lie is the VIEW's answer, the one thing the two layouts differ in.
 // ---------------------------------------------------------------------------------------------------
 struct Chains {
     rbnn_hmc_lockstep s;
@@ -246,10 +249,12 @@ struct Chains {
 
 __device__ __forceinline__ bool chain_active(const Chains& a) { return !a.s.active || a.s.active[blockIdx.y] != 0; }
 
-__device__ __forceinline__ rbnn_hmc_chain chain_of(const Chains& a) {
-    const long long k = blockIdx.y, at = k * a.s.chain_stride;
+// chain blockIdx.y's view, its per-parameter buffers shifted by `shift` (not read by the decision)
+__device__ __forceinline__ rbnn_hmc_chain chain_of(const Chains& a, long long shift) {
+    const long long k = blockIdx.y;
     rbnn_hmc_chain c;
-    c.q_cur = a.s.q_cur + at; c.g_cur = a.s.g_cur + at; c.r = a.s.r + at; c.m_inv = a.s.m_inv + at; c.w_mean = a.s.w_mean + at; c.w_m2 = a.s.w_m2 + at;
+    c.q_cur = a.s.q_cur + shift; c.g_cur = a.s.g_cur + shift; c.r = a.s.r + shift; c.m_inv = a.s.m_inv + shift;
+    c.w_mean = a.s.w_mean + shift; c.w_m2 = a.s.w_m2 + shift;
     c.k0_part = a.s.k0_part + k * a.s.qpart_stride;
     c.k1_part = a.s.k1_part + k * a.s.epart_stride; c.p_part = a.s.p_part + k * a.s.epart_stride;
     c.state = a.s.state + k * RBNN_HMC_STATE;
@@ -259,19 +264,70 @@ __device__ __forceinline__ rbnn_hmc_chain chain_of(const Chains& a) {
     return c;
 }
 
+__device__ __forceinline__ int seg_of_element(const Layout& L, long long i) {
+    int s = 0;
+#pragma unroll
+    for (int j = 1; j < 6; ++j) if (j < L.n && i >= L.s[j].off) s = j;
+    return s;
+}
+
+// A view: shift(a, L, i, quad) is what to add to the single chain's flat index i (a quad of the momentum draw, else an element) to reach
+// chain blockIdx.y's value in a per-parameter buffer, W or grad; the host members say how the entry points of that layout differ.
+//
+// CHAIN-MAJOR (rbnn_hmc_lockstep_*): [K, chain_stride], the net an rbnn_nn_train_net whose P / grad are the trajectory buffers.
+struct ChainMajor {
+    using Net = rbnn_nn_train_net;
+    static constexpr bool nulls_before_shapes = false;           // a missing W / grad / further pointer is refused behind the block's shapes
+    static __device__ __forceinline__ long long shift(const Chains& a, const Layout&, long long, bool) {
+        return (long long)blockIdx.y * a.s.chain_stride;
+    }
+    static int net(const Net* n, Layout* L, Chains* a, int* K) {
+        const int rc = check_members(n);
+        if (rc) return rc;
+        *L = layout_of(*n); a->W = n->P; a->grad = n->grad; *K = n->n_members;
+        return RBNN_OK;
+    }
+    static bool stride_ok(const Net* n, const Layout& L, long long stride) { return stride >= L.n_params && n->member_stride == stride; }
+    static int points(const Net*, int n_points) { return n_points < 1 ? RBNN_ERR_SHAPE : RBNN_OK; }
+};
+
+// TENSOR-MAJOR (rbnn_conv_hmc_chains_*): six blocks [K, size of tensor], block t at K times the single chain's offset of tensor t, as the conv
+// forward and weight gradients of K nets need them (rbnn_conv_hmc_chains_stage / _gradient in rbnn_conv_train.hip).  A thread finds the
+// segment of its quad / element in the single chain's layout and shifts by  K off_t + k size_t - off_t : a block covers the quads / elements
+// of the single kernel's block of that index (a block that straddles two tensors has threads with different shifts) and writes the same
+// partial sum.  There is no room between chains, and the point count has the conv workspace's limits.
+struct TensorMajor {
+    using Net = rbnn_conv_hmc_chains_net;
+    static constexpr bool nulls_before_shapes = true;
+    static __device__ __forceinline__ long long shift(const Chains&, const Layout& L, long long i, bool quad) {
+        const Seg& sg = L.s[quad ? seg_of(L, i) : seg_of_element(L, i)];
+        return ((long long)gridDim.y - 1) * sg.off + (long long)blockIdx.y * sg.cols;
+    }
+    static int net(const Net* n, Layout* L, Chains* a, int* K) {
+        const int rc = check_conv_chains_net(n);
+        if (rc) return rc;
+        *L = conv_svi_layout(n->hidden, n->n_classes); a->W = n->W; a->grad = n->grad; *K = n->n_chains;
+        return RBNN_OK;
+    }
+    static bool stride_ok(const Net*, const Layout& L, long long stride) { return stride == L.n_params; }
+    static int points(const Net* n, int n_points) { return check_conv_chains_points(n, n_points); }
+};
+
+template <class View>
 __global__ void __launch_bounds__(ELT_THREADS) lockstep_momentum_kernel(const Layout L, const Chains a, unsigned long long key_xor, uint32_t draw_id,
                                                                         const uint32_t* __restrict__ draw_ids) {
     __shared__ float red[ELT_THREADS];
     if (!chain_active(a)) return;
-    const rbnn_hmc_chain c = chain_of(a);
-    const float k = momentum_quad(L, c, (long long)blockIdx.x * ELT_THREADS + threadIdx.x, a.s.keys[blockIdx.y] ^ key_xor,
-                                  draw_ids ? draw_ids[blockIdx.y] : draw_id);
+    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    const rbnn_hmc_chain c = chain_of(a, View::shift(a, L, q, true));
+    const float k = momentum_quad(L, c, q, a.s.keys[blockIdx.y] ^ key_xor, draw_ids ? draw_ids[blockIdx.y] : draw_id);
     block_sum_to(k, red, c.k0_part);
 }
 
 // step < 0: `phase` for every active chain.  step >= 0: leapfrog step `step` of chains with their own lengths steps[k]: MID while
 // step + 1 < steps[k], CLOSE at step + 1 == steps[k], nothing behind it.
-__global__ void __launch_bounds__(ELT_THREADS) lockstep_update_kernel(const Chains a, int phase, int step) {
+template <class View>
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_update_kernel(const Layout L, const Chains a, int phase, int step) {
     __shared__ float red[ELT_THREADS];
     if (!chain_active(a)) return;
     if (step >= 0) {
@@ -279,10 +335,10 @@ __global__ void __launch_bounds__(ELT_THREADS) lockstep_update_kernel(const Chai
         if (step >= Lk) return;
         phase = step + 1 < Lk ? RBNN_HMC_MID : RBNN_HMC_CLOSE;
     }
-    const rbnn_hmc_chain c = chain_of(a);
-    const long long at = (long long)blockIdx.y * a.s.chain_stride;
+    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x, shift = View::shift(a, L, i, false);
+    const rbnn_hmc_chain c = chain_of(a, shift);
     float kin = 0.f, pot = 0.f;
-    update_element((long long)blockIdx.x * ELT_THREADS + threadIdx.x, a.n_params, a.W + at, a.grad + at, c, phase, kin, pot);
+    update_element(i, a.n_params, a.W + shift, a.grad + shift, c, phase, kin, pot);
     if (phase == RBNN_HMC_CLOSE || phase == RBNN_HMC_ENERGY) {
         block_sum_to(kin, red, c.k1_part);
         block_sum_to(pot, red, c.p_part);
@@ -297,12 +353,13 @@ struct LockstepDecide {
     int mode, adapt, window_end;
 };
 
+// the decision touches no per-parameter buffer: one kernel for both layouts
 __global__ void __launch_bounds__(256) lockstep_decide_kernel(const LockstepDecide d) {
     __shared__ double red[256];
     if (!chain_active(d.a)) return;
     const long long k = blockIdx.y;
     DecideArgs a;
-    a.c = chain_of(d.a);
+    a.c = chain_of(d.a, 0);
     a.ce = d.ce + k * d.n_points;
     a.n_points = d.counts ? min((long long)max(d.counts[k], 0), d.n_points) : d.n_points;
     a.n_qpart = d.n_qpart; a.n_epart = d.n_epart; a.transition = d.transition; a.key = d.a.s.keys[k];
@@ -310,126 +367,53 @@ __global__ void __launch_bounds__(256) lockstep_decide_kernel(const LockstepDeci
     decide_chain(a, red);
 }
 
-__global__ void __launch_bounds__(ELT_THREADS) lockstep_commit_kernel(const Chains a, int force, float welford_n, long long sample_row) {
+template <class View>
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_commit_kernel(const Layout L, const Chains a, int force, float welford_n, long long sample_row) {
     const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
     if (i >= a.n_params || !chain_active(a)) return;
-    const rbnn_hmc_chain c = chain_of(a);
-    const long long at = (long long)blockIdx.y * a.s.chain_stride;
-    commit_element(i, a.W + at, a.grad + at, c, force, welford_n, sample_row >= 0 ? c.samples + sample_row * a.n_params : nullptr);
-}
-
-__global__ void __launch_bounds__(ELT_THREADS) lockstep_window_end_kernel(const Chains a, float scale, float shift) {
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (i >= a.n_params || !chain_active(a)) return;
-    window_end_element(i, chain_of(a), scale, shift);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// K chains over CONV nets in one set of launches (rbnn_conv_hmc_chains_*): the chain is grid dimension y as above, but the per-parameter buffers
-// (and W / grad) are TENSOR-MAJOR — six blocks [K, size of tensor], block t at K times the single chain's offset of tensor t — as the conv forward
-// and weight gradients of K nets need them.  A thread finds the segment of its quad / element in the single chain's layout, shifts every
-// per-parameter pointer of chain k by  K off_t + k size_t - off_t  and calls the bodies above with the single chain's flat index: a block covers
-// the quads / elements of the single kernel's block of that index (a block that straddles two tensors has threads with different shifts) and
-// writes the same partial sum, so chain k is bit-identical to the single chain.  Partial sums, state, log and samples stay chain-major.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int seg_of_element(const Layout& L, long long i) {
-    int s = 0;
-#pragma unroll
-    for (int j = 1; j < 6; ++j) if (j < L.n && i >= L.s[j].off) s = j;
-    return s;
-}
-
-// chain blockIdx.y's view for flat indices inside segment sg (one row of sg.cols columns); shift: the same for W / grad
-__device__ __forceinline__ rbnn_hmc_chain conv_chain_of(const Chains& a, const Seg& sg, long long& shift) {
-    rbnn_hmc_chain c = chain_of(a);                                                  // the chain-major part: partial sums, state, log, samples
-    shift = ((long long)gridDim.y - 1) * sg.off + (long long)blockIdx.y * sg.cols;
-    c.q_cur = a.s.q_cur + shift; c.g_cur = a.s.g_cur + shift; c.r = a.s.r + shift; c.m_inv = a.s.m_inv + shift;
-    c.w_mean = a.s.w_mean + shift; c.w_m2 = a.s.w_m2 + shift;
-    return c;
-}
-
-__global__ void __launch_bounds__(ELT_THREADS) conv_chains_momentum_kernel(const Layout L, const Chains a, unsigned long long key_xor, uint32_t draw_id,
-                                                                           const uint32_t* __restrict__ draw_ids) {
-    __shared__ float red[ELT_THREADS];
-    if (!chain_active(a)) return;
-    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    long long shift;
-    const rbnn_hmc_chain c = conv_chain_of(a, L.s[seg_of(L, q)], shift);
-    const float k = momentum_quad(L, c, q, a.s.keys[blockIdx.y] ^ key_xor, draw_ids ? draw_ids[blockIdx.y] : draw_id);
-    block_sum_to(k, red, c.k0_part);
-}
-
-__global__ void __launch_bounds__(ELT_THREADS) conv_chains_update_kernel(const Layout L, const Chains a, int phase, int step) {
-    __shared__ float red[ELT_THREADS];
-    if (!chain_active(a)) return;
-    if (step >= 0) {
-        const int Lk = a.s.steps[blockIdx.y];
-        if (step >= Lk) return;
-        phase = step + 1 < Lk ? RBNN_HMC_MID : RBNN_HMC_CLOSE;
-    }
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    long long shift;
-    const rbnn_hmc_chain c = conv_chain_of(a, L.s[seg_of_element(L, i)], shift);
-    float kin = 0.f, pot = 0.f;
-    update_element(i, a.n_params, a.W + shift, a.grad + shift, c, phase, kin, pot);
-    if (phase == RBNN_HMC_CLOSE || phase == RBNN_HMC_ENERGY) {
-        block_sum_to(kin, red, c.k1_part);
-        block_sum_to(pot, red, c.p_part);
-    }
-}
-
-__global__ void __launch_bounds__(ELT_THREADS) conv_chains_commit_kernel(const Layout L, const Chains a, int force, float welford_n, long long sample_row) {
-    const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (i >= a.n_params || !chain_active(a)) return;
-    long long shift;
-    const rbnn_hmc_chain c = conv_chain_of(a, L.s[seg_of_element(L, i)], shift);
+    const long long shift = View::shift(a, L, i, false);
+    const rbnn_hmc_chain c = chain_of(a, shift);
     commit_element(i, a.W + shift, a.grad + shift, c, force, welford_n, sample_row >= 0 ? c.samples + sample_row * a.n_params : nullptr);
 }
 
-__global__ void __launch_bounds__(ELT_THREADS) conv_chains_window_end_kernel(const Layout L, const Chains a, float scale, float shift_m) {
+template <class View>
+__global__ void __launch_bounds__(ELT_THREADS) lockstep_window_end_kernel(const Layout L, const Chains a, float scale, float shift_m) {
     const long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
     if (i >= a.n_params || !chain_active(a)) return;
-    long long shift;
-    window_end_element(i, conv_chain_of(a, L.s[seg_of_element(L, i)], shift), scale, shift_m);
+    window_end_element(i, chain_of(a, View::shift(a, L, i, false)), scale, shift_m);
 }
 
-int check_chain(const rbnn_hmc_chain* c) {
-    if (!c) return RBNN_ERR_NULL;
-    if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state)
-        return RBNN_ERR_NULL;
-    return RBNN_OK;
+// ---------------------------------------------------------------------------------------------------
+// The range tests and the window-end scalars of every form, each stated once.
+// ---------------------------------------------------------------------------------------------------
+// the buffers every chain block needs; rbnn_hmc_chain and rbnn_hmc_lockstep name them alike
+template <class Block> bool chain_block_null(const Block& c) {
+    return !c.q_cur || !c.g_cur || !c.r || !c.m_inv || !c.w_mean || !c.w_m2 || !c.k0_part || !c.k1_part || !c.p_part || !c.state;
 }
 
-// the chains of a lockstep call and the net whose P / grad are their trajectory buffers -> the kernels' argument
-int check_chains(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* c, Chains* out) {
-    int rc = check_members(net);
-    if (rc) return rc;
-    if (!c) return RBNN_ERR_NULL;
-    if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state || !c->keys)
-        return RBNN_ERR_NULL;
-    const Layout L = layout_of(*net);
-    if (c->chain_stride < L.n_params || net->member_stride != c->chain_stride) return RBNN_ERR_SHAPE;
-    if (c->qpart_stride < (long long)blocks_for(L.n_quads) || c->epart_stride < (long long)blocks_for(L.n_params)) return RBNN_ERR_SHAPE;
-    if (c->log_rows < 0 || c->sample_rows < 0) return RBNN_ERR_SHAPE;
-    out->s = *c; out->W = net->P; out->grad = net->grad; out->n_params = L.n_params;
-    return RBNN_OK;
+int check_chain(const rbnn_hmc_chain* c) { return (!c || chain_block_null(*c)) ? RBNN_ERR_NULL : RBNN_OK; }
+
+int check_phase(int phase) { return (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY) ? RBNN_ERR_UNSUPPORTED : RBNN_OK; }
+
+int check_decision(long long transition, int mode) {
+    if (transition < 0) return RBNN_ERR_SHAPE;
+    return (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) ? RBNN_ERR_UNSUPPORTED : RBNN_OK;
 }
 
-// the chains of a conv call, in the order of the header's section: net NULL, the descriptor, NULL pointers (trajectory: the call reads net->W /
-// net->grad; more: one further pointer of the call, checked when `need_more`), then the shapes of the chain block
-int check_conv_chains(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* c, bool trajectory, bool need_more, const void* more, Layout* L,
-                      Chains* out) {
-    const int rc = check_conv_chains_net(net);
-    if (rc) return rc;
-    if (!c) return RBNN_ERR_NULL;
-    if (!c->q_cur || !c->g_cur || !c->r || !c->m_inv || !c->w_mean || !c->w_m2 || !c->k0_part || !c->k1_part || !c->p_part || !c->state || !c->keys)
-        return RBNN_ERR_NULL;
-    if ((trajectory && (!net->W || !net->grad)) || (need_more && !more)) return RBNN_ERR_NULL;
-    *L = conv_svi_layout(net->hidden, net->n_classes);
-    if (c->chain_stride != L->n_params) return RBNN_ERR_SHAPE;                         // tensor-major: there is no room between chains
-    if (c->qpart_stride < (long long)blocks_for(L->n_quads) || c->epart_stride < (long long)blocks_for(L->n_params)) return RBNN_ERR_SHAPE;
-    if (c->log_rows < 0 || c->sample_rows < 0) return RBNN_ERR_SHAPE;
-    out->s = *c; out->W = net->W; out->grad = net->grad; out->n_params = L->n_params;
+int check_commit(const float* samples, long long sample_rows, long long sample_row, int welford_n) {
+    if (sample_row >= 0) {
+        if (!samples) return RBNN_ERR_NULL;
+        if (sample_row >= sample_rows) return RBNN_ERR_SHAPE;
+    }
+    return welford_n < 0 ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+
+// m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5): the two scalars are formed in double and rounded to fp32 once
+struct WindowEnd { float scale, shift; };
+int window_end_scalars(int n_window, WindowEnd* out) {
+    if (n_window < 2) return RBNN_ERR_SHAPE;
+    const double w = (double)n_window;
+    *out = {(float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0))};
     return RBNN_OK;
 }
 
@@ -473,7 +457,7 @@ template <class Net> int chain_update(const Net* net, const rbnn_hmc_chain* chai
     int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (!net->W || !net->grad) return RBNN_ERR_NULL;
-    if (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY) return RBNN_ERR_UNSUPPORTED;
+    if ((rc = check_phase(phase))) return rc;
     const long long n = L.n_params;
     hipLaunchKernelGGL(hmc_update_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, net->W, net->grad, *chain, (int)phase);
     return launch_status();
@@ -485,8 +469,8 @@ template <class Net> int chain_decide(const Net* net, const rbnn_hmc_chain* chai
     int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (!ce) return RBNN_ERR_NULL;
-    if (n_points < 1 || transition < 0) return RBNN_ERR_SHAPE;
-    if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
+    if (n_points < 1) return RBNN_ERR_SHAPE;
+    if ((rc = check_decision(transition, mode))) return rc;
     DecideArgs a = {};
     a.c = *chain; a.ce = ce; a.n_points = n_points; a.n_qpart = blocks_for(L.n_quads); a.n_epart = blocks_for(L.n_params);
     a.transition = transition; a.key = key; a.mode = mode; a.adapt = adapt; a.window_end = window_end;
@@ -500,31 +484,105 @@ template <class Net> int chain_commit(const Net* net, const rbnn_hmc_chain* chai
     int rc = chain_layout(net, &L);
     if (rc || (rc = check_chain(chain))) return rc;
     if (!net->W || !net->grad) return RBNN_ERR_NULL;
+    if ((rc = check_commit(chain->samples, chain->sample_rows, sample_row, welford_n))) return rc;
     const long long n = L.n_params;
-    float* row = nullptr;
-    if (sample_row >= 0) {
-        if (!chain->samples) return RBNN_ERR_NULL;
-        if (sample_row >= chain->sample_rows) return RBNN_ERR_SHAPE;
-        row = chain->samples + sample_row * n;
-    }
-    if (welford_n < 0) return RBNN_ERR_SHAPE;
     hipLaunchKernelGGL(hmc_commit_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, net->W, net->grad, *chain, (int)force,
-                       (float)welford_n, row);
+                       (float)welford_n, sample_row >= 0 ? chain->samples + sample_row * n : nullptr);
     return launch_status();
 }
 
 template <class Net> int chain_window_end(const Net* net, const rbnn_hmc_chain* chain, int32_t n_window, void* stream) {
     Layout L;
     int rc = chain_layout(net, &L);
-    if (rc || (rc = check_chain(chain))) return rc;
-    if (n_window < 2) return RBNN_ERR_SHAPE;
+    WindowEnd w;
+    if (rc || (rc = check_chain(chain)) || (rc = window_end_scalars(n_window, &w))) return rc;
     const long long n = L.n_params;
-    // m_inv = (n / (n + 5)) M2 / (n - 1) + 1e-3 * 5 / (n + 5): the two scalars are formed in double and rounded to fp32 once
-    const double w = (double)n_window;
-    hipLaunchKernelGGL(hmc_window_end_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, *chain,
-                       (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
+    hipLaunchKernelGGL(hmc_window_end_kernel, dim3(blocks_for(n)), dim3(ELT_THREADS), 0, (hipStream_t)stream, n, *chain, w.scale, w.shift);
     return launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------------
+// K chains: what the chain-major entry points (rbnn_hmc_lockstep_*) and the tensor-major ones (rbnn_conv_hmc_chains_*) do once the view has
+// turned their net into a Layout, the trajectory's buffers and K.  Each keeps the order of its header section's refusals.
+// ---------------------------------------------------------------------------------------------------
+struct Lockstep { Layout L; Chains a; int K; };
+
+// net NULL and the descriptor, the chain block's NULL pointers, its shapes.  trajectory: the call reads the net's W / grad; more: one further
+// pointer of the call, needed when `need_more`: refused where the view's section says, in front of the shapes or behind them.
+template <class View>
+int lockstep_args(const typename View::Net* net, const rbnn_hmc_lockstep* c, bool trajectory, bool need_more, const void* more, Lockstep* out) {
+    const int rc = View::net(net, &out->L, &out->a, &out->K);
+    if (rc) return rc;
+    if (!c || chain_block_null(*c) || !c->keys) return RBNN_ERR_NULL;
+    const bool missing = (trajectory && (!out->a.W || !out->a.grad)) || (need_more && !more);
+    if (View::nulls_before_shapes && missing) return RBNN_ERR_NULL;
+    const Layout& L = out->L;
+    if (!View::stride_ok(net, L, c->chain_stride)) return RBNN_ERR_SHAPE;
+    if (c->qpart_stride < (long long)blocks_for(L.n_quads) || c->epart_stride < (long long)blocks_for(L.n_params)) return RBNN_ERR_SHAPE;
+    if (c->log_rows < 0 || c->sample_rows < 0) return RBNN_ERR_SHAPE;
+    if (missing) return RBNN_ERR_NULL;
+    out->a.s = *c; out->a.n_params = L.n_params;
+    return RBNN_OK;
+}
+
+template <class View>
+int lockstep_momentum(const typename View::Net* net, const rbnn_hmc_lockstep* chains, uint64_t key_xor, uint32_t draw_id, const uint32_t* draw_ids,
+                      void* stream) {
+    Lockstep l = {};
+    const int rc = lockstep_args<View>(net, chains, false, false, nullptr, &l);
+    if (rc) return rc;
+    hipLaunchKernelGGL(lockstep_momentum_kernel<View>, dim3(blocks_for(l.L.n_quads), l.K), dim3(ELT_THREADS), 0, (hipStream_t)stream, l.L, l.a,
+                       (unsigned long long)key_xor, draw_id, draw_ids);
+    return launch_status();
+}
+
+template <class View>
+int lockstep_update(const typename View::Net* net, const rbnn_hmc_lockstep* chains, int32_t phase, int32_t step, void* stream) {
+    Lockstep l = {};
+    int rc = lockstep_args<View>(net, chains, true, false, nullptr, &l);
+    if (rc) return rc;
+    if (step >= 0 && !chains->steps) return RBNN_ERR_NULL;
+    if (step < 0 && (rc = check_phase(phase))) return rc;
+    hipLaunchKernelGGL(lockstep_update_kernel<View>, dim3(blocks_for(l.a.n_params), l.K), dim3(ELT_THREADS), 0, (hipStream_t)stream, l.L, l.a,
+                       (int)phase, (int)step);
+    return launch_status();
+}
+
+// counts: NULL for every chain on all n_points points (the tensor-major form has no counts)
+template <class View>
+int lockstep_decide(const typename View::Net* net, const rbnn_hmc_lockstep* chains, const float* ce, const int32_t* counts, int32_t n_points,
+                    int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
+    Lockstep l = {};
+    int rc = lockstep_args<View>(net, chains, false, true, ce, &l);
+    if (rc || (rc = View::points(net, n_points)) || (rc = check_decision(transition, mode))) return rc;
+    LockstepDecide d = {};
+    d.a = l.a; d.ce = ce; d.counts = counts; d.n_points = n_points; d.n_qpart = blocks_for(l.L.n_quads); d.n_epart = blocks_for(l.L.n_params);
+    d.transition = transition; d.mode = mode; d.adapt = adapt; d.window_end = window_end;
+    hipLaunchKernelGGL(lockstep_decide_kernel, dim3(1, l.K), dim3(256), 0, (hipStream_t)stream, d);
+    return launch_status();
+}
+
+template <class View>
+int lockstep_commit(const typename View::Net* net, const rbnn_hmc_lockstep* chains, int32_t force, int32_t welford_n, int64_t sample_row,
+                    void* stream) {
+    Lockstep l = {};
+    int rc = lockstep_args<View>(net, chains, true, sample_row >= 0, chains ? chains->samples : nullptr, &l);
+    if (rc || (rc = check_commit(chains->samples, chains->sample_rows, sample_row, welford_n))) return rc;
+    hipLaunchKernelGGL(lockstep_commit_kernel<View>, dim3(blocks_for(l.a.n_params), l.K), dim3(ELT_THREADS), 0, (hipStream_t)stream, l.L, l.a,
+                       (int)force, (float)welford_n, (long long)sample_row);
+    return launch_status();
+}
+
+template <class View> int lockstep_window_end(const typename View::Net* net, const rbnn_hmc_lockstep* chains, int32_t n_window, void* stream) {
+    Lockstep l = {};
+    WindowEnd w;
+    int rc = lockstep_args<View>(net, chains, false, false, nullptr, &l);
+    if (rc || (rc = window_end_scalars(n_window, &w))) return rc;
+    hipLaunchKernelGGL(lockstep_window_end_kernel<View>, dim3(blocks_for(l.a.n_params), l.K), dim3(ELT_THREADS), 0, (hipStream_t)stream, l.L, l.a,
+                       w.scale, w.shift);
+    return launch_status();
+}
+
 
 }  // namespace
 
@@ -584,130 +642,41 @@ int rbnn_hmc_lockstep_gradient(const rbnn_nn_train_net* net, const float* X, int
 
 int rbnn_hmc_lockstep_momentum(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, uint64_t key_xor, uint32_t draw_id,
                                const uint32_t* draw_ids, void* stream) {
-    Chains a = {};
-    const int rc = check_chains(net, chains, &a);
-    if (rc) return rc;
-    const Layout L = layout_of(*net);
-    hipLaunchKernelGGL(lockstep_momentum_kernel, dim3(blocks_for(L.n_quads), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
-                       (unsigned long long)key_xor, draw_id, draw_ids);
-    return launch_status();
+    return lockstep_momentum<ChainMajor>(net, chains, key_xor, draw_id, draw_ids, stream);
 }
-
 int rbnn_hmc_lockstep_update(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, int32_t phase, int32_t step, void* stream) {
-    Chains a = {};
-    const int rc = check_chains(net, chains, &a);
-    if (rc) return rc;
-    if (!net->P || !net->grad) return RBNN_ERR_NULL;
-    if (step >= 0 && !chains->steps) return RBNN_ERR_NULL;
-    if (step < 0 && (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY)) return RBNN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(lockstep_update_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a, (int)phase,
-                       (int)step);
-    return launch_status();
+    return lockstep_update<ChainMajor>(net, chains, phase, step, stream);
 }
-
 int rbnn_hmc_lockstep_decide(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, const float* ce, const int32_t* counts,
                              int32_t n_points, int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
-    LockstepDecide d = {};
-    const int rc = check_chains(net, chains, &d.a);
-    if (rc) return rc;
-    if (!ce) return RBNN_ERR_NULL;
-    if (n_points < 1 || transition < 0) return RBNN_ERR_SHAPE;
-    if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
-    const Layout L = layout_of(*net);
-    d.ce = ce; d.counts = counts; d.n_points = n_points; d.n_qpart = blocks_for(L.n_quads); d.n_epart = blocks_for(L.n_params);
-    d.transition = transition; d.mode = mode; d.adapt = adapt; d.window_end = window_end;
-    hipLaunchKernelGGL(lockstep_decide_kernel, dim3(1, net->n_members), dim3(256), 0, (hipStream_t)stream, d);
-    return launch_status();
+    return lockstep_decide<ChainMajor>(net, chains, ce, counts, n_points, transition, mode, adapt, window_end, stream);
 }
-
 int rbnn_hmc_lockstep_commit(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, int32_t force, int32_t welford_n, int64_t sample_row,
                              void* stream) {
-    Chains a = {};
-    const int rc = check_chains(net, chains, &a);
-    if (rc) return rc;
-    if (!net->P || !net->grad) return RBNN_ERR_NULL;
-    if (sample_row >= 0) {
-        if (!chains->samples) return RBNN_ERR_NULL;
-        if (sample_row >= chains->sample_rows) return RBNN_ERR_SHAPE;
-    }
-    if (welford_n < 0) return RBNN_ERR_SHAPE;
-    hipLaunchKernelGGL(lockstep_commit_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a, (int)force,
-                       (float)welford_n, (long long)sample_row);
-    return launch_status();
+    return lockstep_commit<ChainMajor>(net, chains, force, welford_n, sample_row, stream);
 }
-
 int rbnn_hmc_lockstep_window_end(const rbnn_nn_train_net* net, const rbnn_hmc_lockstep* chains, int32_t n_window, void* stream) {
-    Chains a = {};
-    const int rc = check_chains(net, chains, &a);
-    if (rc) return rc;
-    if (n_window < 2) return RBNN_ERR_SHAPE;
-    const double w = (double)n_window;                                               // the two scalars as rbnn_hmc_window_end forms them
-    hipLaunchKernelGGL(lockstep_window_end_kernel, dim3(blocks_for(a.n_params), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a,
-                       (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
-    return launch_status();
+    return lockstep_window_end<ChainMajor>(net, chains, n_window, stream);
 }
 
 // ---- K chains over conv nets: tensor-major buffers (staging and gradient: rbnn_conv_train.hip) ----
 int rbnn_conv_hmc_chains_momentum(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, uint64_t key_xor, uint32_t draw_id,
                                   const uint32_t* draw_ids, void* stream) {
-    Layout L;
-    Chains a = {};
-    const int rc = check_conv_chains(net, chains, false, false, nullptr, &L, &a);
-    if (rc) return rc;
-    hipLaunchKernelGGL(conv_chains_momentum_kernel, dim3(blocks_for(L.n_quads), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
-                       (unsigned long long)key_xor, draw_id, draw_ids);
-    return launch_status();
+    return lockstep_momentum<TensorMajor>(net, chains, key_xor, draw_id, draw_ids, stream);
 }
-
 int rbnn_conv_hmc_chains_update(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, int32_t phase, int32_t step, void* stream) {
-    Layout L;
-    Chains a = {};
-    const int rc = check_conv_chains(net, chains, true, false, nullptr, &L, &a);
-    if (rc) return rc;
-    if (step < 0 && (phase < RBNN_HMC_OPEN || phase > RBNN_HMC_ENERGY)) return RBNN_ERR_UNSUPPORTED;
-    if (step >= 0 && !chains->steps) return RBNN_ERR_NULL;
-    hipLaunchKernelGGL(conv_chains_update_kernel, dim3(blocks_for(a.n_params), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
-                       (int)phase, (int)step);
-    return launch_status();
+    return lockstep_update<TensorMajor>(net, chains, phase, step, stream);
 }
-
 int rbnn_conv_hmc_chains_decide(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, const float* ce, int32_t n_points,
                                 int64_t transition, int32_t mode, int32_t adapt, int32_t window_end, void* stream) {
-    Layout L;
-    LockstepDecide d = {};
-    int rc = check_conv_chains(net, chains, false, true, ce, &L, &d.a);
-    if (rc || (rc = check_conv_chains_points(net, n_points))) return rc;
-    if (transition < 0) return RBNN_ERR_SHAPE;
-    if (mode < RBNN_HMC_DECIDE_INIT || mode > RBNN_HMC_DECIDE_TRANSITION) return RBNN_ERR_UNSUPPORTED;
-    // the decision touches no per-parameter buffer: the chain-major kernel, every chain on all n_points points
-    d.ce = ce; d.counts = nullptr; d.n_points = n_points; d.n_qpart = blocks_for(L.n_quads); d.n_epart = blocks_for(L.n_params);
-    d.transition = transition; d.mode = mode; d.adapt = adapt; d.window_end = window_end;
-    hipLaunchKernelGGL(lockstep_decide_kernel, dim3(1, net->n_chains), dim3(256), 0, (hipStream_t)stream, d);
-    return launch_status();
+    return lockstep_decide<TensorMajor>(net, chains, ce, nullptr, n_points, transition, mode, adapt, window_end, stream);
 }
-
 int rbnn_conv_hmc_chains_commit(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, int32_t force, int32_t welford_n,
                                 int64_t sample_row, void* stream) {
-    Layout L;
-    Chains a = {};
-    const int rc = check_conv_chains(net, chains, true, sample_row >= 0, chains ? chains->samples : nullptr, &L, &a);
-    if (rc) return rc;
-    if (welford_n < 0 || sample_row >= chains->sample_rows) return RBNN_ERR_SHAPE;
-    hipLaunchKernelGGL(conv_chains_commit_kernel, dim3(blocks_for(a.n_params), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
-                       (int)force, (float)welford_n, (long long)sample_row);
-    return launch_status();
+    return lockstep_commit<TensorMajor>(net, chains, force, welford_n, sample_row, stream);
 }
-
 int rbnn_conv_hmc_chains_window_end(const rbnn_conv_hmc_chains_net* net, const rbnn_hmc_lockstep* chains, int32_t n_window, void* stream) {
-    Layout L;
-    Chains a = {};
-    const int rc = check_conv_chains(net, chains, false, false, nullptr, &L, &a);
-    if (rc) return rc;
-    if (n_window < 2) return RBNN_ERR_SHAPE;
-    const double w = (double)n_window;                                               // the two scalars as rbnn_hmc_window_end forms them
-    hipLaunchKernelGGL(conv_chains_window_end_kernel, dim3(blocks_for(a.n_params), net->n_chains), dim3(ELT_THREADS), 0, (hipStream_t)stream, L, a,
-                       (float)(w / ((w + 5.0) * (w - 1.0))), (float)(1e-3 * 5.0 / (w + 5.0)));
-    return launch_status();
+    return lockstep_window_end<TensorMajor>(net, chains, n_window, stream);
 }
 
 }  // extern "C"

@@ -93,20 +93,31 @@ def read_param_store(path):
     return out
 
 
-def lockstep_history(sampler, k, idx=None):
-    """Chain k's logs of a hmc.LockstepHmc run, in the layout of BNN.hmc_history."""
-    h = {"eps": sampler.eps_log[k], "L": sampler.L_log[k], "dH": sampler.dH_log[k], "accept_prob": sampler.accept_prob_log[k],
-         "accepted": sampler.accepted_log[k], "m_inv": sampler.m_inv[k].cpu(), "key": sampler.chain_keys[k]}
+def lockstep_history(sampler, k=None, idx=None):
+    """One chain's logs in the layout of BNN.hmc_history: chain k of a lockstep sampler (hmc.LockstepHmc, conv_hmc.ConvLockstepHmc: its logs
+    are lists with one entry per chain), or with k None the chain of a single sampler (its logs are the attributes themselves)."""
+    of = (lambda v: v) if k is None else (lambda v: v[k])
+    h = {"eps": of(sampler.eps_log), "L": of(sampler.L_log), "dH": of(sampler.dH_log), "accept_prob": of(sampler.accept_prob_log),
+         "accepted": of(sampler.accepted_log), "m_inv": of(sampler.m_inv).cpu(), "key": sampler.key if k is None else sampler.chain_keys[k]}
     if idx is not None:
         h["resampled"] = idx.cpu()
     return h
 
 
-def lockstep_r_hat(sampler, warmup):
-    """Split-R-hat of the chains' potential (the logged U_new) over the sampling phase; nan with fewer than 4 samples or one chain."""
+def lockstep_r_hat(log, warmup):
+    """Split-R-hat of the chains' potential (the logged U_new of log [K, transitions, columns]) over the sampling phase; nan with fewer than
+    4 samples or one chain."""
     from .hmc import LOG_COLUMNS, split_r_hat
-    U = sampler.log[:, warmup:, LOG_COLUMNS.index("U_new")]
+    U = log[:, warmup:, LOG_COLUMNS.index("U_new")]
     return split_r_hat(U) if U.shape[1] >= 4 else float("nan")
+
+
+def require_one_shape(nets):
+    """The lockstep SVI drivers' refusal of nets that differ in shape from the first."""
+    shape_of = lambda b: (b.architecture, b.activation, tuple(b.input_shape), int(b.output_size), int(b.hidden_size))
+    for net in nets[1:]:
+        if shape_of(net.basenet) != shape_of(nets[0].basenet):
+            raise ValueError(f"lockstep SVI nets share one net shape: {shape_of(net.basenet)} is not {shape_of(nets[0].basenet)}")
 
 
 def svi_lockstep_prologue(net):
@@ -171,11 +182,8 @@ def train_svi_lockstep(nets, x_train, y_train, n_inputs, device, rel_path=TESTS,
         require_gpu_fc("SVI training", net.basenet.architecture)
     require_gpu_fc("SVI training", device=device)
     b0 = nets[0].basenet
-    shape_of = lambda b: (b.architecture, b.activation, tuple(b.input_shape), int(b.output_size), int(b.hidden_size))
-    for net in nets[1:]:
-        if shape_of(net.basenet) != shape_of(b0):
-            raise ValueError(f"lockstep SVI nets share one net shape: {shape_of(net.basenet)} is not {shape_of(b0)}")
-    n_inputs = [min(int(n), int(x_train.shape[0])) for n in n_inputs]
+    require_one_shape(nets)
+    n_inputs =[min(int(n), int(x_train.shape[0])) for n in n_inputs]
     if min(n_inputs) < 1:
         raise ValueError("every member needs at least one training point")
     from .svi_train import LockstepSvi
@@ -211,11 +219,8 @@ def train_conv_svi_lockstep(nets, x_train, y_train, device, rel_path=TESTS, batc
     for net in nets:
         check_conv_trainable(net.basenet.input_shape, device)
     b0 = nets[0].basenet
-    shape_of = lambda b: (b.architecture, b.activation, tuple(b.input_shape), int(b.output_size), int(b.hidden_size))
-    for net in nets[1:]:
-        if shape_of(net.basenet) != shape_of(b0):
-            raise ValueError(f"lockstep SVI nets share one net shape: {shape_of(net.basenet)} is not {shape_of(b0)}")
-    names = [net.name for net in nets]
+    require_one_shape(nets)
+    names =[net.name for net in nets]
     for name in names:
         if names.count(name) > 1:
             raise ValueError(f"two nets are named {name!r}: their saved files would overwrite each other (give them different epochs or lr, or "
@@ -581,32 +586,11 @@ class BNN(nn.Module):
         require_gpu_fc("HMC", self.basenet.architecture)
         require_gpu_fc("HMC", device=device)
         from .hmc import HmcSampler, LockstepHmc
-        x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
         b, K = self.basenet, int(num_chains)
-        if K == 1:
-            sampler = HmcSampler(b.architecture, b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, key,
-                                 batch_size=int(x_batch.shape[0]))
-            stack = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
-            idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
-            self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
-                                "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
-        else:
-            from .hmc import initial_position
-            from .svi_train import draw_key
-            q0s, keys = [q0], [key]
-            for _ in range(1, K):
-                q0s.append(initial_position(state_shapes(b)))
-                keys.append(draw_key())
-            sampler = LockstepHmc(b.architecture, b.activation, b.input_shape, b.output_size, q0s, self.step_size, self.num_steps, device, keys,
-                                  batch_size=int(x_batch.shape[0]))
-            stacks = sampler.run(x_batch.to(device), y_batch.to(device).argmax(-1), batch_samples, self.warmup)
-            stack = {k: torch.cat([s[k] for s in stacks], 0) for k in stacks[0]}          # chain-major [K * batch_samples, ...]
-            idx = torch.randint(0, K * batch_samples, (self.n_samples,)).to(device)
-            self.hmc_history = lockstep_history(sampler, 0, idx)
-            self.hmc_history.update({"stack": stack, "chains": [lockstep_history(sampler, k) for k in range(K)],
-                                     "r_hat_U": lockstep_r_hat(sampler, self.warmup)})
-        self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
-        self.save(rel_path=rel_path, filename=filename)
+        net = (b.architecture, b.activation, b.input_shape, b.output_size)
+        self._sample_hmc(train_loader, device, rel_path, filename, K, lambda B: K,
+                         lambda q0, key, B: HmcSampler(*net, q0, self.step_size, self.num_steps, device, key, batch_size=B),
+                         lambda q0s, keys, B: LockstepHmc(*net, q0s, self.step_size, self.num_steps, device, keys, batch_size=B))
 
     def train_hmc_conv(self, train_loader, device, rel_path=TESTS, filename=None, num_chains=1, group=None):
         """train_hmc for the conv architecture of the 1x28x28 geometry (conv_hmc.ConvHmcSampler: the chain's kernels of csrc/rbnn_hmc.hip
@@ -634,36 +618,43 @@ class BNN(nn.Module):
         from .conv_train import check_conv_trainable
         check_conv_trainable(self.basenet.input_shape, device)
         from .conv_hmc import ConvHmcSampler, ConvLockstepHmc, conv_hmc_chains_group
-        x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
         b = self.basenet
+        net = (b.activation, b.input_shape, b.output_size)
+        self._sample_hmc(train_loader, device, rel_path, filename, K,
+                         lambda B: conv_hmc_chains_group(b.activation, b.hidden_size, b.output_size, K, B) if group is None else int(group),
+                         lambda q0, key, B: ConvHmcSampler(*net, q0, self.step_size, self.num_steps, device, key, batch_size=B),
+                         lambda q0s, keys, B: ConvLockstepHmc(*net, q0s, self.step_size, self.num_steps, device, keys, batch_size=B))
+
+    def _sample_hmc(self, train_loader, device, rel_path, filename, K, group_of, one_chain, lockstep_chains):
+        """train_hmc and train_hmc_conv behind their guards: the prologue, the draws of chains 1..K-1 (every host draw before the first chain
+        runs), the chains on the last batch — one_chain(q0, key, B) for K = 1, else lockstep_chains(q0s, keys, B) for consecutive groups of
+        group_of(B) chains (fc / fc2: one group of K) —, the chain-major stack, the resampling, hmc_history, set_posterior_samples and save()."""
+        x_batch, y_batch, batch_samples, q0, key = self._hmc_prologue(train_loader, device)
         x, labels, B = x_batch.to(device), y_batch.to(device).argmax(-1), int(x_batch.shape[0])
         if K == 1:
-            sampler = ConvHmcSampler(b.activation, b.input_shape, b.output_size, q0, self.step_size, self.num_steps, device, key, batch_size=B)
+            sampler = one_chain(q0, key, B)
             stack = sampler.run(x, labels, batch_samples, self.warmup)
-            idx = torch.randint(0, batch_samples, (self.n_samples,)).to(device)
-            self.hmc_history = {"eps": sampler.eps_log, "L": sampler.L_log, "dH": sampler.dH_log, "accept_prob": sampler.accept_prob_log,
-                                "accepted": sampler.accepted_log, "m_inv": sampler.m_inv.cpu(), "key": sampler.key, "resampled": idx.cpu()}
+            chains = [lockstep_history(sampler)]
         else:
-            from types import SimpleNamespace
             from .hmc import initial_position
             from .svi_train import draw_key
             q0s, keys = [q0], [key]
             for _ in range(1, K):
-                q0s.append(initial_position(state_shapes(b)))
+                q0s.append(initial_position(state_shapes(self.basenet)))
                 keys.append(draw_key())
-            group = conv_hmc_chains_group(b.activation, b.hidden_size, b.output_size, K, B) if group is None else int(group)
+            group = group_of(B)
             stacks, chains, logs = [], [], []
             for a in range(0, K, group):
-                sampler = ConvLockstepHmc(b.activation, b.input_shape, b.output_size, q0s[a:a + group], self.step_size, self.num_steps, device,
-                                          keys[a:a + group], batch_size=B)
+                sampler = lockstep_chains(q0s[a:a + group], keys[a:a + group], B)
                 stacks += [{k: v.clone() for k, v in s.items()} for s in sampler.run(x, labels, batch_samples, self.warmup)]
                 chains += [lockstep_history(sampler, k) for k in range(sampler.K)]
                 logs.append(sampler.log)
                 del sampler                                                               # the next group's workspaces take its place
             stack = {k: torch.cat([s[k] for s in stacks], 0) for k in stacks[0]}          # chain-major [K * batch_samples, ...]
-            idx = torch.randint(0, K * batch_samples, (self.n_samples,)).to(device)
-            self.hmc_history = {**chains[0], "resampled": idx.cpu(), "stack": stack, "chains": chains,
-                                "r_hat_U": lockstep_r_hat(SimpleNamespace(log=torch.cat(logs, 0)), self.warmup)}
+        idx = torch.randint(0, K * batch_samples, (self.n_samples,)).to(device)
+        self.hmc_history = {**chains[0], "resampled": idx.cpu()}
+        if K > 1:
+            self.hmc_history.update({"stack": stack, "chains": chains, "r_hat_U": lockstep_r_hat(torch.cat(logs, 0), self.warmup)})
         self.set_posterior_samples({k: v.index_select(0, idx).contiguous() for k, v in stack.items()}, device)
         self.save(rel_path=rel_path, filename=filename)
 

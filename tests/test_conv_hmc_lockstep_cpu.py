@@ -308,11 +308,15 @@ def test_chain_group_follows_the_budget(monkeypatch):
 
 
 def test_the_four_new_kernels_use_no_scratch():
+    """The tensor-major instances of the four lockstep kernel templates of csrc/rbnn_hmc.hip (what the conv chains launch), and the chain-major
+    instances beside them: exactly four each, no scratch, no spilled VGPRs."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import kernel_resources as KR
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
-    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::conv_chains_\w+_kernel\(", n)}
-    assert sorted(re.search(r"conv_chains_(\w+)_kernel", n).group(1) for n in res) == ["commit", "momentum", "update", "window_end"], sorted(res)
-    bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}
-    assert not bad, bad
+    for view in ("TensorMajor", "ChainMajor"):
+        name = r"::lockstep_(\w+)_kernel<\(anonymous namespace\)::" + view + r">\("
+        res = {n: r for n, r in KR.kernel_resources().items() if re.search(name, n)}
+        assert sorted(re.search(name, n).group(1) for n in res) == ["commit", "momentum", "update", "window_end"], sorted(res)
+        bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}
+        assert not bad, bad
