@@ -1370,6 +1370,64 @@ int rbnn_chain_diag(const float *X, int64_t ldx, int32_t n_chains, int32_t n_dra
                     double *mean, double *std, double *r_hat, double *split_r_hat,
                     double *tau, double *n_eff, int32_t *n_pairs, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Posterior-predictive uncertainty and calibration (csrc/rbnn_predictive.inc): what the per-sample probabilities P [S][N][ldp] that
+ * every forward leaves in its workspace say beyond their mean.  P is fp32 (the exact, triple, split and conv forwards) or double
+ * precision (the two checkers): elem_type names which, RBNN_PREDICTIVE_FLOAT or RBNN_PREDICTIVE_DOUBLE.  Element (s, n, c) lies at
+ * P + s * sample_stride + n * ldp + c (strides in elements, ldp >= C, sample_stride >= N * ldp); columns c >= C are never read.
+ * For one point, with p_s[c] the probabilities of sample s, widened to double precision on load — everything from the first sum on
+ * is double precision —, natural logarithms and 0 ln 0 = 0:
+ *    pbar[c] = (sum_s p_s[c]) / S                                  s ascending
+ *    entropy             H = -sum_c pbar[c] ln pbar[c]             c ascending         (total uncertainty)
+ *    expected_entropy    E = -(sum_c (sum_s p_s[c] ln p_s[c])) / S s, then c ascending (aleatoric part)
+ *    mutual_information  H - E, as that difference; nothing is clamped                 (epistemic part)
+ *    prediction          the first maximum of pbar over c < C (torch's argmax rule), int32
+ *    confidence          pbar[prediction]
+ *    agreement           (double)(number of s whose own first-maximum class == prediction) / (double)S
+ *    variance            the population variance over s of p_s[prediction]: Welford's update per class in ascending s
+ *                        (d = p - mean; mean += d / (s + 1); M2 += d (p - mean)), M2[prediction] / S — never E[x^2] - m^2
+ *    with labels y:      nll = -ln pbar[y] (+inf when pbar[y] == 0), brier = sum_c (pbar[c] - [c == y])^2, c ascending,
+ *                        correct = (prediction == y), int32.  A label outside [0, C) names no class: pbar[y] counts as 0.
+ * Prefixes: a call takes 1 .. RBNN_PREDICTIVE_MAX_PREFIXES strictly ascending lengths 1 <= S_1 < ... < S_J <= S (a host array) and
+ * writes row j of every output, at out + j * out_stride (out_stride >= N, in elements), for the first S_j samples — in ONE pass
+ * over P; the bits of row j are those of a call with the single prefix S_j.  Samples past S_J are not read.
+ * Calibration bins the points by confidence into n_bins intervals (lo, hi]:
+ *    b = min(n_bins - 1, max(0, (int)ceil(confidence * n_bins) - 1))          in double precision, exactly as written
+ * and gives per bin the count, the sum of confidence and the number correct, and over all points the sum of nll, the sum of brier
+ * and the number correct: RBNN_PREDICTIVE_BLOCK points at a time in ascending order, then the blocks in ascending order.
+ * No atomics; two runs are bit-identical; the bits of a point's figures are a function of its own S x C values and the prefix list
+ * alone — not of N, the other points, the strides or the alignment of P.  Checked on the host before any launch: a null pointer
+ * RBNN_ERR_NULL (outputs excepted: one that is null is not written; nll, brier and correct need labels); n_classes outside
+ * 2 .. RBNN_CPAD, a count below 1, ldp < C, sample_stride < N * ldp, out_stride < N, more than RBNN_PREDICTIVE_MAX_PREFIXES
+ * prefixes or prefixes not strictly ascending in 1 .. S, n_bins outside 1 .. RBNN_PREDICTIVE_MAX_BINS, a workspace below the
+ * query's, an unknown elem_type or a size whose product overflows RBNN_ERR_SHAPE; P or an output off its element's alignment
+ * RBNN_ERR_ALIGN.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define RBNN_PREDICTIVE_FLOAT 0
+#define RBNN_PREDICTIVE_DOUBLE 1
+#define RBNN_PREDICTIVE_MAX_PREFIXES 8
+#define RBNN_PREDICTIVE_MAX_BINS 64
+#define RBNN_PREDICTIVE_BLOCK 256     /* points of one partial sum of the calibration */
+
+/* Row j < n_prefixes of every output (doubles; prediction and correct int32) <- the figures of the first prefixes[j] samples.
+ * labels: int32 [N] on the device, or null.  prefixes: host array.  1 launch. */
+int rbnn_predictive_stats(const void *P, int32_t elem_type, int64_t sample_stride, int32_t ldp, int32_t n_samples, int32_t n_points,
+                          int32_t n_classes, const int32_t *labels, const int32_t *prefixes, int32_t n_prefixes, int64_t out_stride,
+                          double *entropy, double *expected_entropy, double *mutual_information, double *confidence,
+                          double *agreement, double *variance, double *nll, double *brier, int32_t *prediction, int32_t *correct,
+                          void *stream);
+
+/* bytes <- the workspace of rbnn_predictive_calibration: ceil(N / RBNN_PREDICTIVE_BLOCK) blocks of 3 n_bins + 3 partial sums of 8
+ * bytes.  [host] */
+int rbnn_predictive_calibration_query(int32_t n_points, int32_t n_bins, size_t *bytes);
+
+/* confidence (doubles) and correct (int32) of N points, nll and brier (doubles) or null -> bin_count, bin_correct (int64 [n_bins]),
+ * bin_confidence (doubles [n_bins]), totals (doubles [2]: the sums of nll and brier, 0 where the input is null) and n_correct
+ * (int64 [1]).  ws: 8-byte aligned device memory of at least the query's size.  2 launches. */
+int rbnn_predictive_calibration(const double *confidence, const int32_t *correct, const double *nll, const double *brier,
+                                int32_t n_points, int32_t n_bins, int64_t *bin_count, double *bin_confidence, int64_t *bin_correct,
+                                double *totals, int64_t *n_correct, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

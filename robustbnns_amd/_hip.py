@@ -386,6 +386,24 @@ class HipKernels:
                                                ptr(ws.get("hid1")), ptr(ws.get("dact2")), ptr(ws["hidL"]),
                                                *(ptr(out.get(k)) for k in FC_WGRAD_DP_OUT_KEYS), stream_of(X)), "rbnn_fc_weight_grads_dp")
 
+    # -- posterior-predictive uncertainty (rbnn_predictive.inc): reads the P of any forward above --------------------------------------------
+    PREDICTIVE_OUTPUTS = ("entropy", "expected_entropy", "mutual_information", "confidence", "agreement", "variance", "nll", "brier",
+                          "prediction", "correct")                        # rbnn_predictive_stats' ten outputs, in its order
+
+    def predictive_stats(self, P, Cn, labels, prefixes, out, lo=0):
+        """P: [S, n, ld] float32 or float64 with stride(2) == 1 (a forward's workspace as it stands).  out: name -> [J, N] tensor (float64;
+        prediction, correct int32; a name left out is not computed), of which columns lo .. lo + n are written: row j the figures of the
+        first prefixes[j] samples."""
+        if P.dtype not in (torch.float32, torch.float64) or P.dim() != 3 or (P.shape[2] > 1 and P.stride(2) != 1) or P.device.type != "cuda":
+            raise HipError(f"predictive_stats takes a float32 / float64 [S, n, ld] tensor on the GPU with stride(2) == 1, not {P.dtype} "
+                           f"{tuple(P.shape)} on {P.device}")
+        some = next(iter(out.values()))
+        pre = (C.c_int32 * len(prefixes))(*prefixes)
+        outs = [None if out.get(k) is None else C.c_void_p(out[k].data_ptr() + lo * out[k].element_size()) for k in self.PREDICTIVE_OUTPUTS]
+        check(self.lib.rbnn_predictive_stats(ptr(P), PREDICTIVE_DOUBLE if P.dtype == torch.float64 else PREDICTIVE_FLOAT, P.stride(0), P.stride(1),
+                                             P.shape[0], P.shape[1], Cn, ptr(labels), pre, len(prefixes), some.stride(0), *outs, stream_of(P)),
+              "rbnn_predictive_stats")
+
     # -- conv architecture ---------------------------------------------------------------------------
     def conv_workspace_sizes(self, net, N, S):
         out = ConvWorkspaceSizes()

@@ -395,6 +395,22 @@ class ConvEngine(AttackEngine):
             return super().forward(x, n_samples, seeds, logits)
         return self._blocked(lambda xb: AttackEngine.forward(self, xb, n_samples, seeds, logits), x, n_samples=n_samples)
 
+    def sample_outputs(self, x, n_samples, seeds=None):
+        from .uncertainty import check_engine
+        check_engine(self, "sample_outputs()")                                  # (before the group's plan is asked for)
+        parts = self._blocked(lambda xb: AttackEngine.sample_outputs(self, xb, n_samples, seeds), x, n_samples=n_samples, cat=False)
+        return parts if torch.is_tensor(parts) else torch.cat(parts, 1)
+
+    def uncertainty(self, x, n_samples, y=None, seeds=None, n_samples_list=None):
+        """Point block by point block, the records concatenated: a point's figures do not know its block."""
+        from . import uncertainty as U
+        U.check_prefixes(n_samples, n_samples_list)
+        y = U.check_labels(y, int(x.shape[0]))
+        U.check_engine(self, "uncertainty()")
+        run = lambda xb, yb=None: AttackEngine.uncertainty(self, xb, n_samples, yb, seeds, n_samples_list)
+        parts = self._blocked(run, x, *(() if y is None else (y,)), n_samples=n_samples, cat=False)
+        return parts if isinstance(parts, U.PredictiveUncertainty) else U.concat(parts)
+
     def loss_gradients(self, x, y, n_samples, seeds=None, norms=False):
         y = torch.as_tensor(y)
         parts = self._blocked(lambda xb, yb: AttackEngine.loss_gradients(self, xb, yb, n_samples, seeds, norms), x, y,

@@ -102,6 +102,20 @@ class ConvFp64Engine:
         sidx, S = self._samples(n_samples, seeds)
         return self.fp64.forward(X, sidx, S, OUT_LOGITS if logits else OUT_PROBS)[:, :self.post.C].clone()
 
+    # ------------------------------------------------------------------ per-sample outputs and predictive uncertainty (csrc/rbnn_predictive.inc)
+    def _sample_blocks(self, x, sidx, S):
+        return self.fp64.sample_blocks(self._inputs(x), sidx, S)
+
+    def sample_outputs(self, x, n_samples, seeds=None):
+        """[S, N, C] float64: the probabilities of every sample; forward() is their mean.  A copy."""
+        from .uncertainty import engine_sample_outputs
+        return engine_sample_outputs(self, x, n_samples, seeds)
+
+    def uncertainty(self, x, n_samples, y=None, seeds=None, n_samples_list=None):
+        """AttackEngine.uncertainty from the fp64 P of this checker: the same kernel, its double-precision instantiation."""
+        from .uncertainty import engine_uncertainty
+        return engine_uncertainty(self, x, n_samples, y, seeds, n_samples_list)
+
     def loss_gradients(self, x, y, n_samples, seeds=None, norms=False):
         """lossGradients.loss_gradient for every row of x (lossGradients.py:20-40): float64 in x's shape; norms=True: also the per-point
         Linf and L2 norms of those gradients (float64 [N] each)."""

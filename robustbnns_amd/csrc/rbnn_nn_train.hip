@@ -69,3 +69,5 @@ int rbnn_nn_train_finalize(const rbnn_nn_train_net* net, const rbnn_nn_train_ws*
 #include "rbnn_wpca.inc"
 // ... and the per-weight diagnostics of HMC chains, for the same reason
 #include "rbnn_chain_diag.inc"
+// ... and the posterior-predictive uncertainty and calibration kernels
+#include "rbnn_predictive.inc"

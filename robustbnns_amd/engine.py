@@ -33,6 +33,7 @@ import os
 import torch
 
 from . import _hip
+from . import uncertainty as _uncertainty
 from ._hip import (LOSS_MEAN_LOGIT, LOSS_MEAN_PROB, LOSS_PER_SAMPLE, LOSS_UPSTREAM, LOSS_UPSTREAM_LOGIT, OUT_LOGITS, OUT_PROBS)
 from .fp64_core import Fp64Core, wgrad_arguments
 from .posterior import LAYER_KEYS
@@ -436,6 +437,34 @@ class AttackEngine:
         xin = self._flat(x) if self.precision == "lowdim" else self.pad_inputs(x)
         out = self.forward_padded(xin, sidx, S, OUT_LOGITS if logits else OUT_PROBS)
         return out[:, :self.post.C]
+
+    # ------------------------------------------------------------------ per-sample outputs and predictive uncertainty (csrc/rbnn_predictive.inc)
+    def _sample_blocks(self, x, sidx, S):
+        """Runs the probabilities forward point block by point block and yields (lo, hi, P [S, hi - lo, 16]): the workspace's per-sample
+        probabilities of points lo .. hi as the forward kernels wrote them (a view, valid until the next launch on this engine).  A lowdim
+        engine stores no P (one launch sums the samples): its call runs the generic fp32 forward, rbnn_fc_forward, on the same posterior."""
+        if self.precision == "fp64":
+            yield from self.fp64.sample_blocks(self.pad_inputs(x), sidx, S)
+            return
+        Xp = self.pad_inputs(x)
+        N = Xp.shape[0]
+        ws = self.workspace(N, S)
+        if self.precision == "lowdim":
+            self.k.fc_forward(self.post, Xp, sidx, S, OUT_PROBS, ws)
+        else:
+            self._forward_kernels(Xp, sidx, S, OUT_PROBS, ws)
+        yield 0, N, ws["P"][:S * N * _hip.CPAD].view(S, N, _hip.CPAD)
+
+    def sample_outputs(self, x, n_samples, seeds=None):
+        """[S, N, C]: the probabilities of every sample, as the forward kernels wrote them — forward() is their mean.  A copy; float32, or
+        float64 under precision='fp64'."""
+        return _uncertainty.engine_sample_outputs(self, x, n_samples, seeds)
+
+    def uncertainty(self, x, n_samples, y=None, seeds=None, n_samples_list=None):
+        """uncertainty.PredictiveUncertainty of every row of x from the P of ONE forward: entropy, expected_entropy, mutual_information,
+        confidence, agreement, variance (float64), prediction (int32) and, with labels y, nll, brier (float64) and correct (int32) — [N] each,
+        or [J, N] with n_samples_list (up to 8 strictly ascending prefix lengths of the call's samples, one pass over P)."""
+        return _uncertainty.engine_uncertainty(self, x, n_samples, y, seeds, n_samples_list)
 
     def vjp(self, x, grad_out, sidx, S, logits):
         """d<grad_out, forward(x)>/dx for forward = mean over samples of probabilities (or logits)."""

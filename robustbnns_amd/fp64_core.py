@@ -89,6 +89,14 @@ class Fp64Core:
             self.k.reduce_samples_f64(ws["P"], S, hi - lo, self.post.C, 1.0 / S, out[lo:hi])
         return out
 
+    def sample_blocks(self, X, sidx, S):
+        """The probabilities forward per point block -> (lo, hi, P float64 [S, hi - lo, 16]): every sample's own output, before the mean (a
+        view of the cached workspace, valid until the next launch)."""
+        for lo, hi in self.point_blocks(X.shape[0], S):
+            ws = self.workspace(hi - lo, S)
+            self._forward(self.post, X[lo:hi], sidx, S, OUT_PROBS, ws)
+            yield lo, hi, ws["P"][:S * (hi - lo) * _hip.CPAD].view(S, hi - lo, _hip.CPAD)
+
     def gradient(self, X, labels, sidx, S, mode, norms=None):
         """The summed expected input gradient, float64 [N, width] (a fresh tensor): forward + sum over samples + loss + backward per point
         block.  The 1/S of every loss is inside dZ, as in the fp64 oracle.  norms = (linf [N], l2 [N]) float64 buffers: filled too."""
