@@ -15,7 +15,7 @@ svi_train.SviTrainer makes for fc / fc2 (its docstring has the formulas), around
 
 14 launches a step without the accuracy forward, 19 with it (csrc/rbnn_conv_train.hip), plus the two torch copies that stage the batch; one
 stream, no atomics, no device->host synchronisation: two runs are bit-identical.  ConvSviTrainer stands on flat_params.FlatNets with conv's key
-list and offers SviTrainer's surface (gradients, step, begin_epoch, epoch_totals, params); the epoch loop is BNN's, shared with BNN.train.
+list, through svi_train.SingleGuide (step, begin_epoch, epoch_totals, params: shared with SviTrainer); the epoch loop is BNN's, shared with BNN.train.
 
 Several guides of ONE conv net shape train in LOCKSTEP: `ConvLockstepSvi.step(rows)` is that step for K guides, each with its own
 parameters, Philox key, learning rate and rows of a resident data set, in one set of launches whose count does not depend on K (the
@@ -38,8 +38,8 @@ import torch.nn.functional as F
 from . import _hip
 from .conv import ConvStackedPosterior, ConvSviGuide
 from .conv_train import CONV_KEYS, check_conv_trainable, conv_group, conv_net, conv_workspace, tensor_major, views
-from .flat_params import FlatNets, flatten
-from .svi_train import ACC_KEY, ACC_SAMPLES, ADAM_EPS, BETAS, LockstepGuides, LockstepSvi
+from .flat_params import flatten
+from .svi_train import ACC_KEY, ACC_SAMPLES, ADAM_EPS, BETAS, LockstepGuides, LockstepSvi, SingleGuide
 
 
 class _LiveConvGuide:
@@ -52,10 +52,12 @@ class _LiveConvGuide:
         self.loc, self.sigma, self.device = loc, sigma, torch.device(device)
 
 
-class ConvSviTrainer(FlatNets):
+class ConvSviTrainer(SingleGuide):
     """Device-resident SVI state of one conv guide: flat loc / raw / sigma / Adam moments, the one-sample weight buffer and its gradient
     [n_params] in state_dict order, the workspaces for up to Bmax points, the resident S = 10 stack of the accuracy forward and a device-side
-    accumulator stats [3] = [step loss, sum of step losses, correct predictions]."""
+    accumulator stats [3] = [step loss, sum of step losses, correct predictions].  step(x, labels, accuracy=True) is SingleGuide's, on x
+    [B, 1, 28, 28] or [B, 784]."""
+    ADAM_ENTRY = "rbnn_conv_svi_adam_step"
 
     def __init__(self, activation, input_shape, n_classes, loc, raw, lr, device, key, batch_size=128):
         check_conv_trainable(input_shape, device)
@@ -105,34 +107,8 @@ class ConvSviTrainer(FlatNets):
         _hip.check(lib.rbnn_conv_svi_weight_grads(net, _hip.ptr(self.X), self.Dp, B, ws, st), "rbnn_conv_svi_weight_grads")
         return B
 
-    def step(self, x, labels, accuracy=True):
-        """One SVI step on the device batch (x [B, 1, 28, 28] or [B, 784], labels int [B]); accuracy: the 10-sample forward of the updated
-        guide is scored too.  No device->host synchronisation."""
-        B = self.gradients(x, labels)
-        lib, st = self.k.lib, _hip.stream_of(self.X)
-        _hip.check(lib.rbnn_conv_svi_adam_step(C.byref(self.net), C.c_uint64(self.key), C.c_uint32(self.t & 0xFFFFFFFF), self.t + 1, self.lr,
-                                               BETAS[0], BETAS[1], ADAM_EPS, _hip.ptr(self.kl_part), st), "rbnn_conv_svi_adam_step")
-        psum = None
-        if accuracy:
-            self.acc_post.redraw(self.key ^ ACC_KEY, self.t)
-            self.k.conv_forward(self.acc_post, self.X[:B], None, ACC_SAMPLES, _hip.OUT_PROBS, self.acc_ws)
-            self.k.reduce_samples(self.acc_ws["P"], ACC_SAMPLES, B, self.C, 1.0, self.Psum)
-            psum = self.Psum
-        _hip.check(lib.rbnn_svi_train_finalize(_hip.ptr(self.kl_part), self.n_partials, _hip.ptr(self.ws_t["ce"]), B, _hip.ptr(psum), _hip.CPAD,
-                                               _hip.ptr(self.labels), self.C, _hip.ptr(self.stats), st), "rbnn_svi_train_finalize")
-        self.t += 1
-
-    def begin_epoch(self):
-        self.stats[1:].zero_()
-
-    def epoch_totals(self):
-        """(sum of the step losses, correct predictions) since begin_epoch(): the one device->host sync of an epoch."""
-        s = self.stats.tolist()
-        return s[1], s[2]
-
-    def params(self):
-        """(loc, raw scale) as dicts state_dict key -> fresh device tensor."""
-        return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
+    def accuracy_forward(self, B):
+        self.k.conv_forward(self.acc_post, self.X[:B], None, ACC_SAMPLES, _hip.OUT_PROBS, self.acc_ws)
 
 
 FLAT_BUFFERS = ("loc", "raw", "sigma", "m_loc", "v_loc", "m_raw", "v_raw", "W", "grad")

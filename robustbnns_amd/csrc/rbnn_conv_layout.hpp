@@ -43,7 +43,7 @@ inline int check_conv_dims(int activation, int in_channels, int in_width, int hi
     return RBNN_OK;
 }
 
-// the descriptor of K SVI guides in lockstep (rbnn_conv_train.hip; rbnn_svi.hip: their Adam + KL step): the K * RBNN_SVI_MULTI_ACC_SAMPLES nets of
+// the descriptor of K SVI guides in lockstep (rbnn_conv_train.hip; rbnn_svi.hip: the launch of their Adam + KL step): the K * RBNN_SVI_MULTI_ACC_SAMPLES nets of
 // the accuracy forward are a grid dimension, so every entry point takes at most 65535 / RBNN_SVI_MULTI_ACC_SAMPLES guides
 constexpr int CONV_SVI_MAX_GUIDES = 65535 / RBNN_SVI_MULTI_ACC_SAMPLES;
 inline int check_conv_svils_net(const rbnn_conv_svi_guides_net* n) {
@@ -51,6 +51,10 @@ inline int check_conv_svils_net(const rbnn_conv_svi_guides_net* n) {
     const int rc = check_conv_dims(n->activation, n->in_channels, n->in_width, n->hidden, n->n_classes);
     if (rc) return rc;
     return (n->n_guides < 1 || n->n_guides > CONV_SVI_MAX_GUIDES) ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+// the guides' own buffers as the record the host helpers of rbnn_svi_step.hpp take
+inline rbnn_svi_multi conv_svils_guides(const rbnn_conv_svi_guides_net* n) {
+    return {n->loc, n->raw, n->sigma, n->m_loc, n->v_loc, n->m_raw, n->v_raw, n->kl_part, n->stats, n->keys, n->part_stride};
 }
 
 // the descriptor and the point count of K HMC chains in one set of launches (rbnn_conv_train.hip: staging and gradient; rbnn_hmc.hip: the chain's

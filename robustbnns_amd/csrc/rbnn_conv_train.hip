@@ -18,7 +18,7 @@
 //      rbnn_conv_svi_train_draw     W = loc + sigma * eps for the six tensors: rbnn_svi_draw_flat on views of the flat buffers, 1 launch
 //      rbnn_conv_svi_train_forward  the training forward above on W with the SUMMED cross-entropy (dZ = softmax - e_y, no 1 / B): 3 + 1 launches
 //      rbnn_conv_svi_weight_grads   the weight gradients above, reading W and writing grad = dCE/dW: 7 launches, the same kernels
-//      rbnn_conv_svi_adam_step      rbnn_svi_step.hpp's adam_kernel<false> over the six conv tensors, each one row of n_elem columns (the
+//      rbnn_conv_svi_adam_step      rbnn_svi_step.hpp's adam_kernel<Single> over the six conv tensors, each one row of n_elem columns (the
 //                                   regenerated eps quad is e / 4, rbnn_svi_draw_flat's counter): loc, raw, sigma, moments, KL partials.  1 launch
 //      the step's sums are rbnn_svi_train_finalize (rbnn_train.hip: 1 launch); the accuracy forward is the host's (rbnn_svi_draw_flat of 10
 //      weight sets into a resident stack, rbnn_conv_forward on the exact path, rbnn_reduce_samples: 1 + 3 + 1 launches).
@@ -41,18 +41,19 @@
 //
 // and SVI training of K conv guides of one shape in LOCKSTEP (the SVI step above for every guide in one set of launches; the flat buffers are
 // tensor-major as the ensemble's, so the guides are the members of the staging, the forward and the weight gradients):
-//      rbnn_conv_svi_guides_draw      W[k] = loc[k] + sigma[k] * eps(keys[k], draw id): conv_svils_draw_kernel, the flat draw's bits.  1 launch
+//      rbnn_conv_svi_guides_draw      W[k] = loc[k] + sigma[k] * eps(keys[k], draw id): svils_draw_kernel<TensorMajor>, the flat draw's bits.  1 launch
 //      rbnn_conv_svi_guides_gradient  rbnn_conv_ens_stage, the members' forward with the SUMMED cross-entropy (dZ scale 1), the members' 7
 //                                    weight-gradient launches on the view (P = W, grad = grad): 1 + 4 + 7 launches
-//      rbnn_conv_svi_guides_adam_step conv_svils_adam_kernel: rbnn_svi_adam_kernel.inc's text on tensor-major offsets, per-guide key and lr.  1 launch.
-//                                    Kernel and entry point stand in rbnn_svi.hip, not here: a second Adam kernel in THIS unit changes the
-//                                    code its adam_kernel<false> compiles to (profiles/conv_svi_lockstep/README.txt)
-//      rbnn_conv_svi_guides_accuracy  conv_svils_draw_kernel of the K * 10 weight sets under keys[k] ^ key_xor, the exact forward of those nets on
+//      rbnn_conv_svi_guides_adam_step adam_kernel<TensorMajor>: the single guide's Adam + KL text on tensor-major offsets, per-guide key and lr.  1 launch.
+//                                    Instantiated and launched in rbnn_svi.hip, not here: a second instance of adam_kernel in THIS unit changes
+//                                    the code its adam_kernel<Single> compiles to (profiles/svi_one_family/README.txt)
+//      rbnn_conv_svi_guides_accuracy  svils_draw_kernel<TensorMajor> of the K * 10 weight sets under keys[k] ^ key_xor, the exact forward of those nets on
 //                                    the K staged batches (conv1_pool_grouped_kernel: set k * 10 + s reads guide k's rows; conv2_pool_kernel and
 //                                    conv_fc_kernel as they are), conv_svils_acc_sum_kernel: 1 + 3 + 1 launches
-//      rbnn_conv_svi_guides_finalize  conv_svils_finalize_kernel, one block per guide: the step's sums and the epoch's end on the device.  1 launch
+//      rbnn_conv_svi_guides_finalize  svils_finalize_kernel<false>, one block per guide: the step's sums and the epoch's end on the device.  1 launch
 //      One lockstep SVI step = 1 + 12 + 1 + 1 = 15 launches without the accuracy forward, 20 with it, whatever K is.  A guide that has finished
-//      (active[k] == 0) is skipped by the four conv_svils_* kernels: nothing of its state is written again.
+//      (active[k] == 0) is skipped by the four kernels: nothing of its state is written again.  The draw, Adam + KL and finalize kernels are
+//      rbnn_svi_step.hpp's templates, the ones the fc guides of rbnn_svi_lockstep.hip run guide-major.
 //
 // and the gradient of K HMC chains over conv nets of one shape (the chain's element-wise kernels: rbnn_hmc.hip), the chains as the members:
 //      rbnn_conv_hmc_chains_stage     rbnn_conv_ens_stage on the view: 1 launch, once per batch
@@ -321,41 +322,11 @@ inline int check_conv_ens_points(const rbnn_conv_ens_net* n, int B) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K SVI guides in lockstep: the kernels that join the members' forward and weight gradients above to the SVI step.  Tensor-major buffers: guide
-// k's segment sg of a [K n_params] buffer starts at K sg.off + k sg.cols (every conv segment is one row of sg.cols columns).  Each returns at
-// once, the whole block, for a guide with active[k] == 0.  (conv_svils_adam_kernel, the fourth of them, stands in rbnn_svi.hip.)
+// K SVI guides in lockstep: what joins the members' forward and weight gradients above to the SVI step.  Tensor-major buffers: guide k's segment
+// sg of a [K n_params] buffer starts at K sg.off + k sg.cols (svi::TensorMajor; every conv segment is one row of sg.cols columns), and the draw,
+// Adam + KL (launched from rbnn_svi.hip) and finalize kernels are rbnn_svi_step.hpp's on that view.  Each returns at once, the whole block, for a guide with active[k] == 0.
 // ---------------------------------------------------------------------------------------------------
 constexpr int ACC_S = RBNN_SVI_MULTI_ACC_SAMPLES;
-
-// One thread per quad of weight set blockIdx.y = guide * per + sample of n_sets = K * per sets (per = 1: the training draw at sample 0; per =
-// ACC_S: the accuracy stack): draw_quad, i.e. rbnn_svi_draw_flat's fmaf(sigma, eps, loc) with the counter (e / 4, tensor id, sample, draw id).
-struct ConvSvilsDrawArgs {
-    Layout L;
-    const float *loc, *sigma;
-    float* W;
-    const unsigned long long* keys;
-    const int32_t* active;
-    unsigned long long key_xor;
-    uint32_t draw_id;
-    int per, n_guides;
-};
-
-__global__ void __launch_bounds__(ELT_THREADS) conv_svils_draw_kernel(const ConvSvilsDrawArgs a) {
-    const int k = blockIdx.y / a.per, s = blockIdx.y % a.per;
-    if (a.active[k] == 0) return;
-    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (q >= a.L.n_quads) return;
-    const Seg sg = a.L.s[seg_of(a.L, q)];
-    const int c4 = (int)(q - sg.first_quad);
-    const unsigned long long key = a.keys[k] ^ a.key_xor;
-    const Rng rng = {(uint32_t)key, (uint32_t)(key >> 32), (uint32_t)s, a.draw_id};
-    const long long go = a.n_guides * sg.off + (long long)k * sg.cols;
-    float w[4];
-    draw_quad(rng, sg.tensor_id, a.loc + go, a.sigma + go, 0, c4, sg.cols, w);
-    float* const out = a.W + (long long)a.n_guides * a.per * sg.off + (long long)blockIdx.y * sg.cols + 4 * c4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (4 * c4 + j < sg.cols) out[j] = w[j];
-}
 
 // Psum[k, b, :] = sum_s P[k ACC_S + s, b, :], one thread per (point, 4-class quad) of guide blockIdx.y, s = 0, 1, ... in that order: the sum
 // reduce_samples_kernel (rbnn_kernels.hip) makes with scale 1.
@@ -369,40 +340,6 @@ __global__ void __launch_bounds__(ELT_THREADS) conv_svils_acc_sum_kernel(const C
     for (int s = 0; s < ACC_S; ++s) sum += *(const f32x4*)(a.P + (((long long)k * ACC_S + s) * a.B + b) * RBNN_CPAD + 4 * q);
 #pragma unroll
     for (int r = 0; r < 4; ++r) if (4 * q + r < a.C) a.Psum[((long long)k * a.B + b) * RBNN_CPAD + 4 * q + r] = sum[r];
-}
-
-// One block per guide: finalize_kernel's sums (rbnn_train.hip; svi_step_sums) over the guide's B staged points, then the epoch's end as
-// svils_finalize_kernel (rbnn_svi_lockstep.hip) writes it: epoch_slot[k] in [0, log_rows) -> epoch_log[k, slot] = (sum of the step losses,
-// correct predictions) of the epoch that ends with this step, and both accumulators are zeroed.
-struct ConvSvilsFinalArgs {
-    const float *kl_part, *ce, *Psum;
-    const int32_t *labels, *active, *epoch_slot;
-    double *stats, *epoch_log;
-    long long part_stride;
-    int n_part, B, C, log_rows;
-};
-
-__global__ void __launch_bounds__(256) conv_svils_finalize_kernel(const ConvSvilsFinalArgs a) {
-    __shared__ double red[256];
-    __shared__ double cnt[256];
-    const int k = blockIdx.x;
-    if (a.active[k] == 0) return;
-    const long long pt = (long long)k * a.B;
-    svi::svi_step_sums<false>(a.kl_part + k * a.part_stride, a.n_part, a.ce + pt, a.B, a.Psum ? a.Psum + pt * RBNN_CPAD : nullptr, RBNN_CPAD, a.C,
-                              a.labels + pt, nullptr, 0, red, cnt);
-    if (threadIdx.x == 0) {
-        double* const st = a.stats + 3LL * k;
-        st[0] = red[0];
-        const double loss = st[1] + red[0], correct = st[2] + cnt[0];
-        const int slot = a.epoch_slot ? a.epoch_slot[k] : -1;
-        if (slot >= 0 && slot < a.log_rows) {
-            double* const row = a.epoch_log + ((long long)k * a.log_rows + slot) * 2;
-            row[0] = loss; row[1] = correct;
-            st[1] = 0.0; st[2] = 0.0;
-        } else {
-            st[1] = loss; st[2] = correct;
-        }
-    }
 }
 
 inline int check_conv_svils_points(const rbnn_conv_svi_guides_net* n, int B) {
@@ -759,14 +696,13 @@ int rbnn_conv_svi_adam_step(const rbnn_conv_svi_train_net* net, uint64_t key, ui
     a.loc = net->loc; a.raw = net->raw; a.sigma = net->sigma; a.m_loc = net->m_loc; a.v_loc = net->v_loc; a.m_raw = net->m_raw; a.v_raw = net->v_raw;
     a.grad = net->grad; a.kl_part = kl_partials; a.key = key; a.draw_id = draw_id;
     a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(svi::adam_kernel<false>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(svi::adam_kernel<svi::Single>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------
 // The SVI step of K conv guides in lockstep: the members' stage / forward / weight gradients above on the view (P = W, grad = grad) with the
-// summed cross-entropy, around the kernels of the guides (the Adam + KL step: rbnn_svi.hip).  Every refusal comes before the first launch of an
-// entry point.
+// summed cross-entropy, around the kernels of the guides (rbnn_conv_svi_guides_adam_step: rbnn_svi.hip).  Every refusal comes before the first launch of an entry point.
 // ---------------------------------------------------------------------------------------------------
 int rbnn_conv_svi_guides_sizes(const rbnn_conv_svi_guides_net* net, int32_t n_points, rbnn_conv_svi_guides_bytes* out) {
     int rc = check_conv_svils_net(net);
@@ -797,12 +733,8 @@ int rbnn_conv_svi_guides_draw(const rbnn_conv_svi_guides_net* net, const int32_t
     const int rc = check_conv_svils_net(net);
     if (rc) return rc;
     if (!active || !net->loc || !net->sigma || !net->W || !net->keys) return RBNN_ERR_NULL;
-    ConvSvilsDrawArgs a = {};
-    a.L = conv_svi_layout(net->hidden, net->n_classes);
-    a.loc = net->loc; a.sigma = net->sigma; a.W = net->W; a.keys = (const unsigned long long*)net->keys; a.active = active;
-    a.key_xor = 0; a.draw_id = draw_id; a.per = 1; a.n_guides = net->n_guides;
-    hipLaunchKernelGGL(conv_svils_draw_kernel, dim3(blocks_for(a.L.n_quads), net->n_guides), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return svi::guides_draw<svi::TensorMajor>(conv_svi_layout(net->hidden, net->n_classes), conv_svils_guides(net), net->W, active, net->n_guides, 1, 0,
+                                              0, draw_id, (hipStream_t)stream);
 }
 
 int rbnn_conv_svi_guides_gradient(const rbnn_conv_svi_guides_net* net, const float* X, int32_t ldx, int32_t n_rows, const int32_t* labels,
@@ -848,12 +780,9 @@ int rbnn_conv_svi_guides_accuracy(const rbnn_conv_svi_guides_net* net, const int
     w.P = ws->acc_P; w.P1 = ws->acc_P1; w.st1 = ws->acc_st1; w.Q2 = ws->acc_Q2; w.st2 = ws->acc_st2;
     ConvArgs c = {};
     if ((rc = conv_forward_args(&p, p.K2w, true, ws->Xs, DIN, n_points, nullptr, KS, RBNN_OUT_PROBS, &w, c))) return rc;
-    ConvSvilsDrawArgs d = {};
-    d.L = conv_svi_layout(net->hidden, net->n_classes);
-    d.loc = net->loc; d.sigma = net->sigma; d.W = W; d.keys = (const unsigned long long*)net->keys; d.active = active;
-    d.key_xor = key_xor; d.draw_id = draw_id; d.per = ACC_S; d.n_guides = K;
-    hipLaunchKernelGGL(conv_svils_draw_kernel, dim3(blocks_for(d.L.n_quads), KS), dim3(ELT_THREADS), 0, st, d);
-    if ((rc = launch_status())) return rc;
+    if ((rc = svi::guides_draw<svi::TensorMajor>(conv_svi_layout(net->hidden, net->n_classes), conv_svils_guides(net), W, active, K, ACC_S, 0, key_xor,
+                                                 draw_id, st)))
+        return rc;
     if ((rc = launch_conv_forward_grouped(net->activation, c, st))) return rc;
     const ConvSvilsAccSumArgs r = {ws->acc_P, active, ws->Psum, n_points, net->n_classes};
     hipLaunchKernelGGL(conv_svils_acc_sum_kernel, dim3(blocks_for(4LL * n_points), K), dim3(ELT_THREADS), 0, st, r);
@@ -867,13 +796,13 @@ int rbnn_conv_svi_guides_finalize(const rbnn_conv_svi_guides_net* net, const int
     if (!active || !ws || !ws->ce || !ws->labels || (with_accuracy && !ws->Psum) || !net->kl_part || !net->stats || (epoch_slot && !epoch_log))
         return RBNN_ERR_NULL;
     if ((rc = check_conv_svils_points(net, n_points))) return rc;
-    ConvSvilsFinalArgs a = {};
+    svi::GuidesFinalArgs a = {};
     a.n_part = (int)blocks_for(conv_svi_layout(net->hidden, net->n_classes).n_quads);
     if (net->part_stride < a.n_part || log_rows < 0) return RBNN_ERR_SHAPE;
-    a.kl_part = net->kl_part; a.ce = ws->ce; a.Psum = with_accuracy ? ws->Psum : nullptr; a.labels = ws->labels; a.active = active;
+    a.kl_part = net->kl_part; a.ce = ws->ce; a.Psum = with_accuracy ? ws->Psum : nullptr; a.labels = ws->labels; a.live = active;
     a.epoch_slot = epoch_slot; a.stats = net->stats; a.epoch_log = epoch_log; a.part_stride = net->part_stride;
     a.B = n_points; a.C = net->n_classes; a.log_rows = log_rows;
-    hipLaunchKernelGGL(conv_svils_finalize_kernel, dim3(net->n_guides), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(svi::svils_finalize_kernel<false>, dim3(net->n_guides), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

@@ -17,8 +17,8 @@
 // The images' power-of-two scales are host integers fixed per guide from the a-priori bound |w| <= |loc| + 6.77 softplus(scale)
 // (Box-Muller on a 32-bit uniform cannot exceed sqrt(-2 ln 2^-33) = 6.764): no abs-max pass, no device->host sync per draw.
 //
-// At the end of the file, a tenant: the Adam + KL step of the conv SVI guides in lockstep (conv_svils_adam_kernel), which regenerates its eps
-// with this generator; why it stands here is said there.
+// At the end of the file: rbnn_conv_svi_guides_adam_step, which launches rbnn_svi_step.hpp's adam_kernel<TensorMajor> (its eps is this generator's);
+// why the instance is made here is said there.
 #include "rbnn_common.hpp"
 #include <algorithm>
 
@@ -306,27 +306,13 @@ int rbnn_svi_draw_images(const rbnn_posterior* net, const rbnn_triple_images* tp
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------
-// The Adam + KL step of K conv SVI guides in LOCKSTEP (rbnn_conv_svi_guides_adam_step; the step's other entry points and its description are
-// rbnn_conv_train.hip's).  conv_svils_adam_kernel is rbnn_svi_adam_kernel.inc's text, the text of adam_kernel<true>, on TENSOR-MAJOR buffers:
-// guide blockIdx.y's segment of a [K n_params] buffer lies at K * (the segment's offset) + k * (its size).  eps is regenerated from the guide's
-// key with this unit's generator, the step size is formed per guide from lr[k], the KL partials are [K, part_stride], and a guide with
-// active[k] == 0 is neither read nor written.  It stands HERE, behind the draw kernels, because a unit that already holds an instance of
-// adam_kernel compiles that instance to other code once this kernel joins it (rbnn_conv_train.hip: adam_kernel<false>; rbnn_svi_lockstep.hip:
-// adam_kernel<true>; two LDS reads of the last reduction step, profiles/conv_svi_lockstep/README.txt); this unit holds none, and its own
-// kernels keep their code.
+// The Adam + KL step of K conv SVI guides in LOCKSTEP: adam_kernel<TensorMajor> of rbnn_svi_step.hpp (the step's other entry points and its
+// description are rbnn_conv_train.hip's).  The instance is made HERE because a unit that already holds an instance of adam_kernel compiles that
+// one to other code once a second joins it (rbnn_conv_train.hip's adam_kernel<Single>: two LDS reads of the last reduction step,
+// profiles/svi_one_family/README.txt); this unit holds no other, and its own kernels keep their code.
 // ---------------------------------------------------------------------------------------------------
 #include "rbnn_svi_step.hpp"
 #include "rbnn_conv_layout.hpp"
-
-namespace {
-
-#define RBNN_SVI_ADAM_KERNEL conv_svils_adam_kernel
-#define RBNN_SVI_ADAM_TENSOR_MAJOR 1
-#include "rbnn_svi_adam_kernel.inc"
-#undef RBNN_SVI_ADAM_KERNEL
-#undef RBNN_SVI_ADAM_TENSOR_MAJOR
-
-}  // namespace
 
 extern "C" {
 
@@ -337,17 +323,10 @@ int rbnn_conv_svi_guides_adam_step(const rbnn_conv_svi_guides_net* net, const in
     if (!active || !lr || !net->loc || !net->raw || !net->sigma || !net->m_loc || !net->v_loc || !net->m_raw || !net->v_raw || !net->grad ||
         !net->kl_part || !net->keys)
         return RBNN_ERR_NULL;
-    AdamArgs a = {};
-    a.L = conv_svi_layout(net->hidden, net->n_classes);
-    if (step < 1 || net->part_stride < (long long)blocks_for(a.L.n_quads)) return RBNN_ERR_SHAPE;
-    a.loc = net->loc; a.raw = net->raw; a.sigma = net->sigma; a.m_loc = net->m_loc; a.v_loc = net->v_loc; a.m_raw = net->m_raw; a.v_raw = net->v_raw;
-    a.grad = net->grad; a.kl_part = net->kl_part; a.draw_id = draw_id;
-    a.s = adam_scalars(step, 1.0, beta1, beta2, adam_eps);            // step_size is formed per guide in the kernel from lr[k] and bc1
-    a.keys = (const unsigned long long*)net->keys; a.counts = active; a.lr = lr; a.bc1 = 1.0 - pow(beta1, (double)step);
-    a.part_stride = net->part_stride;
-    hipLaunchKernelGGL(conv_svils_adam_kernel, dim3(blocks_for(a.L.n_quads), net->n_guides), dim3(ELT_THREADS), 0, (hipStream_t)stream, a,
-                       (int)net->n_guides);
-    return launch_status();
+    const Layout L = conv_svi_layout(net->hidden, net->n_classes);
+    if (step < 1 || net->part_stride < (long long)blocks_for(L.n_quads)) return RBNN_ERR_SHAPE;
+    return guides_adam_step<TensorMajor>(L, conv_svils_guides(net), net->grad, active, net->n_guides, 0, draw_id, step, lr, beta1, beta2,
+                                         adam_eps, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -2,11 +2,13 @@
 // the guide is grid dimension y, as the member is in rbnn_nn_train.hip and the chain in rbnn_hmc.hip):
 //
 //      rbnn_svi_multi_draw       W[k] = loc[k] + sigma[k] * eps(keys[k], draw_id)           what rbnn_svi_train_draw writes for that key
+//                                   (svils_draw_kernel<GuideMajor>, rbnn_svi_step.hpp)
 //      rbnn_svi_multi_gradient   lockstep_forward(inv_S = 1) + lockstep_weight_grads on the net whose P is W (rbnn_train_gemm.hpp, SKIP form)
-//      rbnn_svi_multi_adam_step  adam_kernel<true> (rbnn_svi_step.hpp): per-guide key and learning rate, KL partials [K, part_stride]
+//      rbnn_svi_multi_adam_step  adam_kernel<GuideMajor> (rbnn_svi_step.hpp): per-guide key and learning rate, KL partials [K, part_stride]
 //      rbnn_svi_multi_accuracy   10 weight sets per guide from the live loc / sigma (rbnn_svi_draw's generator at sample s), the hidden layers of
 //                                   the K * 10 nets through the GEMM kernel, then softmax and the sum over the samples per (guide, point)
-//      rbnn_svi_multi_finalize   one block per guide: the step's loss, the running sums, and the epoch's end on the device
+//      rbnn_svi_multi_finalize   svils_finalize_kernel<true> (rbnn_svi_step.hpp), one block per guide: the step's loss over its counts[k] points,
+//                                   the running sums, and the epoch's end on the device
 //
 // A guide with counts[k] == 0 has finished its epochs: every kernel returns at once for it and nothing of its state is written.  No atomics, no sum
 // across guides, and a guide's blocks and tiles do not depend on K: guide k is bit-identical to rbnn_train.hip's entry points running it alone
@@ -18,38 +20,6 @@
 namespace {
 
 constexpr int ACC_S = RBNN_SVI_MULTI_ACC_SAMPLES;
-
-// One thread per quad of member blockIdx.y = guide * per + sample (per = 1: the training draw at sample 0).
-struct DrawArgs {
-    Layout L;
-    const float *loc, *sigma;
-    float* W;
-    const unsigned long long* keys;
-    const int32_t* counts;
-    unsigned long long key_xor;
-    uint32_t draw_id;
-    int per;
-    long long member_stride;
-};
-
-__global__ void __launch_bounds__(ELT_THREADS) svils_draw_kernel(const DrawArgs a) {
-    const int k = blockIdx.y / a.per, s = blockIdx.y % a.per;
-    if (a.counts[k] == 0) return;
-    const long long q = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
-    if (q >= a.L.n_quads) return;
-    const Seg sg = a.L.s[seg_of(a.L, q)];
-    const int Q = (sg.cols + 3) >> 2;
-    const long long ql = q - sg.first_quad;
-    const int r = (int)(ql / Q), c4 = (int)(ql % Q);
-    const unsigned long long key = a.keys[k] ^ a.key_xor;
-    const Rng rng = {(uint32_t)key, (uint32_t)(key >> 32), (uint32_t)s, a.draw_id};
-    const long long go = (long long)k * a.member_stride + sg.off;
-    float w[4];
-    draw_quad(rng, sg.tensor_id, a.loc + go, a.sigma + go, r, c4, sg.cols, w);
-    float* const out = a.W + (long long)blockIdx.y * a.member_stride + sg.off + (long long)r * sg.cols + 4 * c4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (4 * c4 + j < sg.cols) out[j] = w[j];
-}
 
 // ---------------------------------------------------------------------------------------------------
 // The accuracy forward's output layer: one wave per (guide, point).  For each of the guide's ACC_S nets z = H W2^T + b2, p = softmax(z);
@@ -103,41 +73,6 @@ __global__ void __launch_bounds__(256) svils_acc_head_kernel(const AccHeadArgs a
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// One block per guide: finalize_kernel's sums (svi_step_sums) over the guide's counts[k] points, then the epoch's end: epoch_slot[k] >= 0 ->
-// epoch_log[k, slot] = (sum of the step losses, correct predictions) of the epoch that ends with this step, and both accumulators are zeroed.
-// ---------------------------------------------------------------------------------------------------
-struct FinalArgs {
-    const float *kl_part, *ce, *Psum;
-    const int32_t *labels, *rows, *counts, *epoch_slot;
-    double *stats, *epoch_log;
-    long long part_stride;
-    int n_part, B, C, idx_max, log_rows;
-};
-
-__global__ void __launch_bounds__(256) svils_finalize_kernel(const FinalArgs a) {
-    __shared__ double red[256];
-    __shared__ double cnt[256];
-    const int k = blockIdx.x, n = a.counts[k];
-    if (n == 0) return;
-    const long long pt = (long long)k * a.B;
-    svi_step_sums<true>(a.kl_part + k * a.part_stride, a.n_part, a.ce + pt, n, a.Psum ? a.Psum + pt * RBNN_CPAD : nullptr, RBNN_CPAD, a.C, a.labels,
-                        a.rows + pt, a.idx_max, red, cnt);
-    if (threadIdx.x == 0) {
-        double* const st = a.stats + 3LL * k;
-        st[0] = red[0];
-        const double loss = st[1] + red[0], correct = st[2] + cnt[0];
-        const int slot = a.epoch_slot ? a.epoch_slot[k] : -1;
-        if (slot >= 0 && slot < a.log_rows) {
-            double* const row = a.epoch_log + ((long long)k * a.log_rows + slot) * 2;
-            row[0] = loss; row[1] = correct;
-            st[1] = 0.0; st[2] = 0.0;
-        } else {
-            st[1] = loss; st[2] = correct;
-        }
-    }
-}
-
 int check_guides(const rbnn_nn_train_net* net, const rbnn_svi_multi* g, const Layout& L) {
     if (!g) return RBNN_ERR_NULL;
     if (net->member_stride < L.n_params || g->part_stride < (long long)blocks_for(L.n_quads)) return RBNN_ERR_SHAPE;
@@ -159,13 +94,9 @@ int rbnn_svi_multi_draw(const rbnn_nn_train_net* net, const rbnn_svi_multi* guid
     int rc = check_svils(net);
     if (rc) return rc;
     if (!guides || !counts || !net->P || !guides->loc || !guides->sigma || !guides->keys) return RBNN_ERR_NULL;
-    DrawArgs a = {};
-    a.L = layout_of(*net);
-    if ((rc = check_guides(net, guides, a.L))) return rc;
-    a.loc = guides->loc; a.sigma = guides->sigma; a.W = net->P; a.keys = (const unsigned long long*)guides->keys; a.counts = counts;
-    a.key_xor = 0; a.draw_id = draw_id; a.per = 1; a.member_stride = net->member_stride;
-    hipLaunchKernelGGL(svils_draw_kernel, dim3(blocks_for(a.L.n_quads), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
-    return launch_status();
+    const Layout L = layout_of(*net);
+    if ((rc = check_guides(net, guides, L))) return rc;
+    return guides_draw<GuideMajor>(L, *guides, net->P, counts, net->n_members, 1, net->member_stride, 0, draw_id, (hipStream_t)stream);
 }
 
 int rbnn_svi_multi_gradient(const rbnn_nn_train_net* net, const float* X, int32_t ldx, int32_t n_rows, const int32_t* labels,
@@ -186,16 +117,10 @@ int rbnn_svi_multi_adam_step(const rbnn_nn_train_net* net, const rbnn_svi_multi*
     const rbnn_svi_multi& g = *guides;
     if (!g.loc || !g.raw || !g.sigma || !g.m_loc || !g.v_loc || !g.m_raw || !g.v_raw || !g.kl_part || !g.keys) return RBNN_ERR_NULL;
     if (step < 1) return RBNN_ERR_SHAPE;
-    AdamArgs a = {};
-    a.L = layout_of(*net);
-    if ((rc = check_guides(net, guides, a.L))) return rc;
-    a.loc = g.loc; a.raw = g.raw; a.sigma = g.sigma; a.m_loc = g.m_loc; a.v_loc = g.v_loc; a.m_raw = g.m_raw; a.v_raw = g.v_raw;
-    a.grad = net->grad; a.kl_part = g.kl_part; a.draw_id = draw_id;
-    a.s = adam_scalars(step, 1.0, beta1, beta2, adam_eps);            // step_size is formed per guide in the kernel from lr[k] and bc1
-    a.keys = (const unsigned long long*)g.keys; a.counts = counts; a.lr = lr; a.bc1 = 1.0 - pow(beta1, (double)step);
-    a.member_stride = net->member_stride; a.part_stride = g.part_stride;
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks_for(a.L.n_quads), net->n_members), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
-    return launch_status();
+    const Layout L = layout_of(*net);
+    if ((rc = check_guides(net, guides, L))) return rc;
+    return guides_adam_step<GuideMajor>(L, g, net->grad, counts, net->n_members, net->member_stride, draw_id, step, lr, beta1, beta2, adam_eps,
+                                        (hipStream_t)stream);
 }
 
 int rbnn_svi_multi_accuracy(const rbnn_nn_train_net* net, const rbnn_svi_multi* guides, const float* X, int32_t ldx, int32_t n_rows,
@@ -213,11 +138,7 @@ int rbnn_svi_multi_accuracy(const rbnn_nn_train_net* net, const rbnn_svi_multi* 
     if (B < 1 || n_rows < 1 || ldx < D || (long long)K * ACC_S * B * H > (1LL << 40)) return RBNN_ERR_SHAPE;
     const long long ps = net->member_stride, bh = (long long)B * H;
     hipStream_t st = (hipStream_t)stream;
-    DrawArgs d = {};
-    d.L = L; d.loc = guides->loc; d.sigma = guides->sigma; d.W = acc->W; d.keys = (const unsigned long long*)guides->keys; d.counts = counts;
-    d.key_xor = key_xor; d.draw_id = draw_id; d.per = ACC_S; d.member_stride = ps;
-    hipLaunchKernelGGL(svils_draw_kernel, dim3(blocks_for(L.n_quads), K * ACC_S), dim3(ELT_THREADS), 0, st, d);
-    if ((rc = launch_status())) return rc;
+    if ((rc = guides_draw<GuideMajor>(L, *guides, acc->W, counts, K, ACC_S, ps, key_xor, draw_id, st))) return rc;
     const float* W = acc->W;
     GemmArgs g = {};
     g.n_prob = 1; g.counts = counts; g.per = ACC_S;
@@ -244,11 +165,11 @@ int rbnn_svi_multi_finalize(const rbnn_nn_train_net* net, const rbnn_svi_multi* 
     const Layout L = layout_of(*net);
     if ((rc = check_guides(net, guides, L))) return rc;
     if (n_points < 1 || n_rows < 1 || log_rows < 0) return RBNN_ERR_SHAPE;
-    FinalArgs a = {};
-    a.kl_part = guides->kl_part; a.ce = ce; a.Psum = Psum; a.labels = labels; a.rows = rows; a.counts = counts; a.epoch_slot = epoch_slot;
+    GuidesFinalArgs a = {};
+    a.kl_part = guides->kl_part; a.ce = ce; a.Psum = Psum; a.labels = labels; a.rows = rows; a.live = counts; a.epoch_slot = epoch_slot;
     a.stats = guides->stats; a.epoch_log = epoch_log; a.part_stride = guides->part_stride; a.n_part = (int)blocks_for(L.n_quads);
     a.B = n_points; a.C = net->n_classes; a.idx_max = n_rows - 1; a.log_rows = log_rows;
-    hipLaunchKernelGGL(svils_finalize_kernel, dim3(net->n_members), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(svils_finalize_kernel<true>, dim3(net->n_members), dim3(256), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

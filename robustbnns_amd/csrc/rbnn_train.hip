@@ -12,7 +12,7 @@
 // sample 0, draw id)), so the update regenerates it instead of storing it, and the weights equal what rbnn_svi_draw writes for the same
 // (key, draw id) at sample 0.  No atomics anywhere: every sum has one fixed order, two runs are bit-identical.
 // The parameter layout, the activations, Adam and the block reductions are rbnn_train_core.hpp; the Adam + KL kernel and the
-// step's sums are rbnn_svi_step.hpp (shared with the guides in lockstep, rbnn_svi_lockstep.hip); the forward / backward GEMM and head kernels
+// step's sums are rbnn_svi_step.hpp (shared with the guides in lockstep; here the Single view); the forward / backward GEMM and head kernels
 // are rbnn_train_gemm.hpp, instantiated here for a single net (LOCKSTEP = false; inv_S = 1: the CE is summed).
 #include "rbnn_train_gemm.hpp"
 #include "rbnn_svi_step.hpp"
@@ -148,7 +148,7 @@ int rbnn_svi_adam_step(const rbnn_svi_train_net* net, uint64_t key, uint32_t dra
     a.loc = net->loc; a.raw = net->raw; a.sigma = net->sigma; a.m_loc = net->m_loc; a.v_loc = net->v_loc; a.m_raw = net->m_raw; a.v_raw = net->v_raw;
     a.grad = net->grad; a.kl_part = kl_partials; a.key = key; a.draw_id = draw_id;
     a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(adam_kernel<Single>, dim3(blocks_for(a.L.n_quads)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
     return launch_status();
 }
 

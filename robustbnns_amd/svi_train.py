@@ -67,9 +67,45 @@ class _LiveGuide:
         self._desc = None
 
 
-class SviTrainer(FlatNets):
+class SingleGuide(FlatNets):
+    """The host surface SviTrainer and conv_svi_train.ConvSviTrainer share: one SVI step around a class's own gradients(), the epoch counters
+    and the parameters.  A class names its Adam + KL entry point (ADAM_ENTRY: both take the same arguments) and runs its accuracy forward
+    (accuracy_forward(B): the ACC_SAMPLES nets of acc_post on self.X[:B] into acc_ws["P"])."""
+
+    def step(self, x, labels, accuracy=True):
+        """One SVI step on the device batch (x [B, ...], labels int [B]); accuracy: the 10-sample forward of the updated guide is scored too.
+        No device->host synchronisation."""
+        B = self.gradients(x, labels)
+        lib, st = self.k.lib, _hip.stream_of(self.X)
+        _hip.check(getattr(lib, self.ADAM_ENTRY)(C.byref(self.net), C.c_uint64(self.key), C.c_uint32(self.t & 0xFFFFFFFF), self.t + 1, self.lr,
+                                                 BETAS[0], BETAS[1], ADAM_EPS, _hip.ptr(self.kl_part), st), self.ADAM_ENTRY)
+        psum = None
+        if accuracy:
+            self.acc_post.redraw(self.key ^ ACC_KEY, self.t)
+            self.accuracy_forward(B)
+            self.k.reduce_samples(self.acc_ws["P"], ACC_SAMPLES, B, self.C, 1.0, self.Psum)
+            psum = self.Psum
+        _hip.check(lib.rbnn_svi_train_finalize(_hip.ptr(self.kl_part), self.n_partials, _hip.ptr(self.ws_t["ce"]), B, _hip.ptr(psum), _hip.CPAD,
+                                               _hip.ptr(self.labels), self.C, _hip.ptr(self.stats), st), "rbnn_svi_train_finalize")
+        self.t += 1
+
+    def begin_epoch(self):
+        self.stats[1:].zero_()
+
+    def epoch_totals(self):
+        """(sum of the step losses, correct predictions) since begin_epoch(): the one device->host sync of an epoch."""
+        s = self.stats.tolist()
+        return s[1], s[2]
+
+    def params(self):
+        """(loc, raw scale) as dicts state_dict key -> fresh device tensor."""
+        return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
+
+
+class SviTrainer(SingleGuide):
     """Device-resident SVI state of one fc / fc2 guide: flat loc / raw / sigma / Adam moments, the one-sample weight buffer, the workspaces,
     the resident S = 10 stack of the accuracy forward and a device-side accumulator [step loss, sum of losses, correct predictions]."""
+    ADAM_ENTRY = "rbnn_svi_adam_step"
 
     def __init__(self, arch, activation, input_shape, n_classes, loc, raw, lr, device, key, batch_size=128):
         require_gpu_fc("SVI training", arch, device)
@@ -132,31 +168,10 @@ class SviTrainer(FlatNets):
         No device->host synchronisation."""
         if accuracy and not self.accuracy_supported:          # before anything is launched: no half-applied step
             raise NotImplementedError(f"hidden {self.H}: outside what rbnn_fc_forward covers (32, 64 or a multiple of 128): no accuracy forward")
-        B = self.gradients(x, labels)
-        lib, st = self.k.lib, _hip.stream_of(self.X)
-        _hip.check(lib.rbnn_svi_adam_step(C.byref(self.net), C.c_uint64(self.key), C.c_uint32(self.t & 0xFFFFFFFF), self.t + 1, self.lr,
-                                          BETAS[0], BETAS[1], ADAM_EPS, _hip.ptr(self.kl_part), st), "rbnn_svi_adam_step")
-        psum = None
-        if accuracy:
-            self.acc_post.redraw(self.key ^ ACC_KEY, self.t)
-            self.k.fc_forward(self.acc_post, self.X[:B], None, ACC_SAMPLES, _hip.OUT_PROBS, self.acc_ws)
-            self.k.reduce_samples(self.acc_ws["P"], ACC_SAMPLES, B, self.C, 1.0, self.Psum)
-            psum = self.Psum
-        _hip.check(lib.rbnn_svi_train_finalize(_hip.ptr(self.kl_part), self.n_partials, _hip.ptr(self.ws_t["ce"]), B, _hip.ptr(psum), _hip.CPAD,
-                                               _hip.ptr(self.labels), self.C, _hip.ptr(self.stats), st), "rbnn_svi_train_finalize")
-        self.t += 1
+        super().step(x, labels, accuracy)
 
-    def begin_epoch(self):
-        self.stats[1:].zero_()
-
-    def epoch_totals(self):
-        """(sum of the step losses, correct predictions) since begin_epoch(): the one device->host sync of an epoch."""
-        s = self.stats.tolist()
-        return s[1], s[2]
-
-    def params(self):
-        """(loc, raw scale) as dicts state_dict key -> fresh device tensor."""
-        return ({k: v.clone() for k, v in self.unflat(self.loc).items()}, {k: v.clone() for k, v in self.unflat(self.raw).items()})
+    def accuracy_forward(self, B):
+        self.k.fc_forward(self.acc_post, self.X[:B], None, ACC_SAMPLES, _hip.OUT_PROBS, self.acc_ws)
 
 
 class LockstepGuides(FlatNets):
