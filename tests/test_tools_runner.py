@@ -174,3 +174,136 @@ def test_recipes():
     assert [f'{e["RBNN_FC2_GROUP_FWD"]} {e["RBNN_FC2_GROUP_BWD"]}' for _, e, _, _ in ab.RECIPES["fc2_groups"]] == groups
     assert all(t is False and a == ["--workload", "fc2", "--steps", "10", "--warmup", "2", "--posterior", "stored"] and len(e) == 2 for _, e, t, a in ab.RECIPES["fc2_groups"])
     assert ab.env_configs("collectives", [], []) is ab.RECIPES["collectives"]
+
+
+# ---------------------------------------------------------------------------------------------- the nine tools/*_timing.py programs
+import importlib                                              # noqa: E402
+import statistics                                             # noqa: E402
+
+import torch                                                  # noqa: E402
+
+import timing                                                 # noqa: E402
+import torch_baselines as TB                                  # noqa: E402
+
+ANSWERS = [(134, ""), (139, ""), (124, ""), (137, ""), (-6, ""), (-11, ""), (-9, ""), (0, FAULT), (1, "")]
+NINE = ["hmc_timing", "nn_train_timing", "svi_train_timing", "conv_hmc_timing", "conv_svi_train_timing", "conv_train_timing", "chain_diag_timing",
+        "uncertainty_timing", "weight_pca_timing"]
+# (tool, options, kind, tag, the arguments that tell each case's child from the others)
+PARENTS = [
+    ("hmc_timing", [], "hmc_timing", "hmc_timing", [["--shape", s] for s in ("2,32,2,1024", "2,128,2,1024", "2,512,2,1024", "784,512,10,5000")]),
+    ("hmc_timing", ["--chains", "8"], "hmc_timing", "hmc_timing", [["--shape", s, "--chains", "8"] for s in ("2,32,2,1024", "2,512,2,1024")]),
+    ("nn_train_timing", [], "nn_train_timing", "nn_train_timing", [["--nets", H, "--members", "1,10,100", "--steps", "100"] for H in ("512", "1024")]),
+    ("svi_train_timing", [], "svi_train_timing", "svi_train_timing", [["--nets", H, "--steps-per-epoch", "0", "--warmup", "20"] for H in ("512", "1024")]),
+    ("svi_train_timing", ["--members", "1,8,32"], "svi_train_timing", "svi_train_timing",
+     [["--nets", H, "--members", K, "--steps", "40"] for H in ("32", "512") for K in ("1", "8", "32")]),
+    ("conv_hmc_timing", [], "timing", "conv_hmc_timing", [["--nets", H, "--torch", "1", "--n", "2", "--batch", "5000"] for H in ("512", "1024")]),
+    ("conv_hmc_timing", ["--chains", "1,8"], "timing", "conv_hmc_timing", [["--nets", H, "--chains", K, "--n", "2"] for H in ("512", "1024") for K in ("1", "8")]),
+    ("conv_svi_train_timing", [], "timing", "conv_svi_timing", [["--nets", H, "--steps", "40"] for H in ("512", "1024")]),
+    ("conv_svi_train_timing", ["--members", "1,8,32"], "timing", "conv_svi_lockstep_timing",
+     [["--nets", H, "--members", K, "--accuracy", acc, "--steps", "40"] for H in ("512", "1024") for K in ("1", "8", "32") for acc in ("1", "0")]),
+    ("conv_train_timing", [], "timing", "conv_train_timing", [["--nets", H, "--steps", "40"] for H in ("512", "1024")]),
+    ("conv_train_timing", ["--members", "1,8,32"], "timing", "conv_ensemble_timing",
+     [["--nets", H, "--members", M, "--steps", "40"] for H in ("512", "1024") for M in ("1", "8", "32")]),
+    ("chain_diag_timing", [], "timing", "chain_diag_timing", [["--cases", c, "--reps", "7", "--torch-reps", "3"] for c in ("8x50", "8x250")]),
+    ("uncertainty_timing", [], "timing", "uncertainty_timing", [["--cases", c, "--reps", "7"] for c in ("fc512", "conv512", "parity_fc", "parity_conv")]),
+    ("weight_pca_timing", [], "timing", "weight_pca_timing", [["--cases", c, "--reps", "7", "--host-reps", "3"] for c in ("posterior50", "same150", "prior1000")]),
+]
+
+
+@pytest.fixture
+def fake_out(monkeypatch, tmp_path):
+    f = Fake()
+    monkeypatch.setattr(steps, "start", f)
+    monkeypatch.setattr(steps, "OUT", str(tmp_path))
+    f.root = str(tmp_path)
+    return f
+
+
+def holds(cmd, words):
+    return any(cmd[i:i + len(words)] == words for i in range(len(cmd)))
+
+
+@pytest.mark.parametrize("tool, options, kind, tag, cases", PARENTS, ids=[p[0] + "".join(p[1][:1]) for p in PARENTS])
+def test_timing_tool_starts_one_checked_child_per_case(fake_out, capsys, tool, options, kind, tag, cases):
+    assert sorted({p[0] for p in PARENTS}) == sorted(NINE)
+    importlib.import_module(tool).main(options)
+    assert len(fake_out.gpu) == len(cases)
+    script = os.path.join(ROOT, "tools", tool + ".py")
+    for (cmd, _), words in zip(fake_out.gpu, cases):
+        assert cmd[:7] == ["timeout", "-k", "10", str(steps.LIMITS[kind]), steps.PY, script, "--child"]
+        assert holds(cmd, words[:2]) and all(holds(cmd, words[i:i + 2]) for i in range(0, len(words), 2))
+    assert len([f for f in os.listdir(os.path.join(fake_out.root, tag)) if f.endswith(".log")]) == len(cases)       # one log per case under <OUT>/<tag>/
+    assert capsys.readouterr().out.count('"metric"') == len(cases)               # each child's last JSON line is printed (here: the fake's bench line)
+
+
+@pytest.mark.parametrize("answer", ANSWERS)
+@pytest.mark.parametrize("tool", NINE)
+def test_timing_tool_starts_nothing_after_a_failed_case(fake_out, tool, answer):
+    fake_out.answers = {2: answer}
+    with pytest.raises(steps.Stop):
+        importlib.import_module(tool).main([])
+    assert len(fake_out.gpu) == 2 and fake_out.gpu[0][0] != fake_out.gpu[1][0]          # the third case never started, none started twice
+
+
+@pytest.mark.parametrize("n", [1, 2, 7, 8])
+def test_timing_summary(n):
+    ms = sorted(3.0 + ((5 * i) % 7) * 0.25 for i in range(n))
+    s = timing.summary(ms)
+    assert s["median"] == statistics.median(ms) and s["spread"] == (ms[-1] - ms[0]) / statistics.median(ms)
+    assert (s["min"], s["max"], s["blocks"]) == (ms[0], ms[-1], n)
+    assert timing.summary(ms, 4)["median"] == statistics.median(ms) / 4 and timing.summary(ms, 4)["spread"] == s["spread"]
+    assert timing.stats(ms) == {"median_ms": s["median"], "min_ms": ms[0], "max_ms": ms[-1], "runs": n}
+
+
+def test_timing_tools_fill_their_figures_from_the_summary():
+    ms, tool = [1.0, 2.0, 4.0, 5.0, 9.0], importlib.import_module
+    assert timing.summary(ms)["blocks"] == 5 and timing.stats(ms)["runs"] == 5 and "runs" not in timing.stats(ms, runs=False)
+    assert tool("conv_hmc_timing").figures(ms, 2) == {"ms_per_transition": 2.0, "ms_per_leapfrog_step": 0.2, "chain_transitions_per_s": 500.0, "spread": 2.0}
+    assert tool("conv_svi_train_timing").figure(ms, 4, 2) == {"ms_per_step": 1.0, "spread": 2.0, "guide_steps_per_s": 2000.0}
+    assert tool("conv_train_timing").figure(ms, 4) == {"ms_per_step": 1.0, "spread": 2.0}
+    assert tool("nn_train_timing").figure(ms, 8, "a", "a_spread") == {"a": 0.5, "a_spread": 2.0}
+    wall = timing.wall(lambda: None, 5, sync=lambda: None)                       # the host clock gives as many times as it was asked for, sorted
+    assert len(wall) == 5 and wall == sorted(wall) and timing.stats(wall)["runs"] == 5
+
+
+def small_nets():
+    """(arch, the package's base net, inputs, labels) at fc2 D = 2, H = 32, C = 2, N = 4 and conv 1x28x28, hidden 16, C = 10, N = 2."""
+    from robustbnns_amd.model_nn import NN
+    torch.manual_seed(3)
+    return [("fc2", NN("half_moons", (1, 2, 1), 2, 32, "leaky", "fc2", 0.01, 1), torch.rand(4, 1, 2, 1), torch.tensor([0, 1, 1, 0])),
+            ("conv", NN("mnist", (1, 28, 28), 10, 16, "leaky", "conv", 0.01, 1), torch.rand(2, 1, 28, 28), torch.tensor([3, 7]))]
+
+
+def test_baseline_logits_are_the_base_nets_forward():
+    for arch, net, x, _ in small_nets():
+        W = dict(net.state_dict())
+        assert list(W) == TB.KEYS[arch] and [tuple(v.shape) for v in W.values()] == [s for _, s in (TB.fc2_shapes(2, 32, 2) if arch == "fc2" else TB.conv_shapes(16, 10))]
+        with torch.no_grad():
+            assert torch.allclose(TB.logits(arch, W, x), net.model(x))
+
+
+def test_baseline_hmc_transition():
+    for arch, net, x, y in small_nets():
+        q0, grad = {k: v.clone() for k, v in net.state_dict().items()}, TB.potential_grad(arch, x, y)
+        q, u, g, dH = TB.hmc_transition(grad, (q0, None), torch.Generator().manual_seed(5), 3, 0.0)
+        assert all(torch.equal(q[k], q0[k]) for k in q0) and float(dH) == 0.0              # a step of size 0 goes nowhere, bit for bit
+        assert torch.equal(u, grad(q0)[0]) and all(torch.equal(g[k], grad(q0)[1][k]) for k in q0)
+        runs = [TB.hmc_transition(grad, TB.hmc_transition(grad, (q0, None), gen, 3, 1e-3), gen, 3, 1e-3) for gen in
+                (torch.Generator().manual_seed(5), torch.Generator().manual_seed(5))]
+        assert all(torch.equal(runs[0][0][k], runs[1][0][k]) for k in q0) and torch.equal(runs[0][3], runs[1][3])
+        assert any(not torch.equal(runs[0][0][k], q0[k]) for k in q0) or float(runs[0][3]) > 0    # it moved, or the move was refused
+
+
+def test_baseline_svi_and_adam_steps_move_every_parameter():
+    for arch, net, x, y in small_nets():
+        forward = lambda W, x: TB.logits(arch, W, x)
+        loc0 = {k: v.clone() for k, v in net.state_dict().items()}
+        raw0 = {k: torch.full_like(v, -3.0) for k, v in loc0.items()}
+        loc, raw, opt = TB.svi_parameters(loc0, raw0, 0.01, "cpu")
+        hits = TB.svi_step(forward, loc, raw, opt, x, y, accuracy=True)
+        assert 0 <= int(hits) <= len(y) and TB.svi_step(forward, loc, raw, opt, x, y) is None
+        for new, old in ((loc, loc0), (raw, raw0)):
+            assert all(bool(torch.isfinite(new[k]).all()) and not torch.equal(new[k].detach(), old[k]) for k in old)
+        W = {k: v.clone().requires_grad_(True) for k, v in loc0.items()}
+        TB.adam_member_step(forward, W, torch.optim.Adam(list(W.values()), lr=0.01), x, y)
+        assert all(bool(torch.isfinite(W[k]).all()) and not torch.equal(W[k].detach(), loc0[k]) for k in loc0)

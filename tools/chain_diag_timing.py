@@ -6,45 +6,20 @@ fc2-512 net — P = 669 706 weights — for the pooled stacks of 8 chains of 50 
 Each figure: median and min..max of wall-clock times around whole calls, the device synchronised before and after.  Beside diagnose():
 a device copy of the same bytes (the floor of one read of the input) and a torch float64 restatement of the same definitions on the same
 GPU, swept in column slabs so that its temporaries stay bounded.  The draws are synthetic: one point far from the origin plus an AR(1)-like
-walk per chain, as the samples of HMC chains lie.  Every case is measured in a child process of its own, started through steps.Runner (one
-time limit each; a fault, an abort or a time limit ends the tool); one JSON line per case.  --child: the measuring program itself."""
+walk per chain, as the samples of HMC chains lie.  Every case is measured in a child process of its own through timing.cases; one JSON line
+per case.  --child: the measuring program itself."""
 import argparse
-import json
-import os
-import statistics
-import sys
-import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import __graft_entry__ as G                                    # noqa: E402
-import steps as S                                  # noqa: E402
+import timing as T
 
 P = 784 * 512 + 512 + 512 * 512 + 512 + 512 * 10 + 10            # 669 706
 DEV = "cuda:0"
 TORCH_SLAB = 32768
 
 
-def wall(fn, reps):
-    """ms of `reps` calls after one warm-up call, sorted."""
-    fn()
-    out = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(1e3 * (time.perf_counter() - t0))
-    return sorted(out)
-
-
-def stats(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": ms[0], "max_ms": ms[-1], "runs": len(ms)}
-
-
-def chain_rows(K, draws, seed):
+def chain_rows(K, draws, seed, P=P):
     g = torch.Generator(device=DEV).manual_seed(seed)
     X = torch.empty(K * draws, P, device=DEV)
     centre = torch.randn(1, P, device=DEV, generator=g)
@@ -67,7 +42,7 @@ def _r_hat(x):
 
 def torch_restatement(X, K):
     """The definitions of include/robustbnns_hip.h in torch float64, vectorised over a slab of columns -> (split_r_hat, tau, n_eff) [P]."""
-    draws = X.shape[0] // K
+    draws, P = X.shape[0] // K, X.shape[1]
     h = draws // 2
     out = [torch.empty(P, dtype=torch.float64, device=X.device) for _ in range(3)]
     for e0 in range(0, P, TORCH_SLAB):
@@ -89,37 +64,31 @@ def torch_restatement(X, K):
     return out
 
 
-def child(a):
+def measure(K, draws, reps, torch_reps, P=P):
     from robustbnns_amd.chain_diagnostics import diagnose
-    G.build()
-    K, draws = (int(v) for v in a.cases.split("x"))
-    X = chain_rows(K, draws, 1)
-    res = {"case": a.cases, "P": P, "chains": K, "draws": draws, "input_bytes": X.numel() * 4}
-    res["diagnose"] = stats(wall(lambda: diagnose(X, K), a.reps))
+    X = chain_rows(K, draws, 1, P)
+    res = {"case": f"{K}x{draws}", "P": P, "chains": K, "draws": draws, "input_bytes": X.numel() * 4}
+    res["diagnose"] = T.stats(T.wall(lambda: diagnose(X, K), reps))
     dst = torch.empty_like(X)
-    res["device_copy"] = stats(wall(lambda: dst.copy_(X), a.reps))
+    res["device_copy"] = T.stats(T.wall(lambda: dst.copy_(X), reps))
     del dst
-    res["torch_float64"] = stats(wall(lambda: torch_restatement(X, K), a.torch_reps))
+    res["torch_float64"] = T.stats(T.wall(lambda: torch_restatement(X, K), torch_reps))
     d, t = diagnose(X, K), torch_restatement(X, K)
     res["max_rel_diff_tau_vs_torch"] = float(((d.tau - t[1]).abs() / t[1].abs().clamp_min(1e-300)).max())
     res["n_eff_median"] = float(d.n_eff.median())
-    print(json.dumps(res), flush=True)
+    return res
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=T.BLOCKS)
     ap.add_argument("--torch-reps", type=int, default=3)
     ap.add_argument("--cases", default="8x50,8x250")
-    ap.add_argument("--child", action="store_true", help="measure in this process (what the runner starts, one case at a time)")
-    a = ap.parse_args()
+    ap.add_argument("--child", action="store_true", help="measure ONE case in this process (what the runner starts)")
+    a = ap.parse_args(argv)
     if a.child:
-        return child(a)
-    runner = S.Runner("chain_diag_timing")
-    for case in a.cases.split(","):
-        text = runner.gpu("timing", case, [S.PY, os.path.abspath(__file__), "--child", "--cases", case, "--reps", str(a.reps), "--torch-reps",
-                                           str(a.torch_reps)])
-        print(json.dumps(S.last_json(text)), flush=True)
+        return T.child(lambda: measure(*(int(v) for v in a.cases.split("x")), a.reps, a.torch_reps))
+    T.cases("chain_diag_timing", __file__, [(case, ["--cases", case] + T.opts(a, "reps", "torch_reps")) for case in a.cases.split(",")])
 
 
 if __name__ == "__main__":

@@ -22,7 +22,10 @@ OUT = os.path.abspath(os.environ.get("RBNN_TOOLS_OUT") or os.path.join(ROOT, "to
 # bench_other (a lean run of another workload or under torch.distributed.run): NOT MEASURED; under seven minutes, so that no step but the test
 # tier, whose output streams into its log, can keep a visit silent for longer than that.  timing (one net of conv_svi_train_timing.py, its
 # torch-autograd side included): 3 x the measured wall time (12.0 s for conv-512, 10.1 s for conv-1024) + 90 s.
-LIMITS = {"tests": 1100, "smoke": 300, "harness": 120, "bench": 102, "pmc": 102, "bench_full": 400, "bench_other": 400, "timing": 126}
+# hmc_timing, nn_train_timing, svi_train_timing (one shape or net of those tools): NOT MEASURED per case; the provisional 400 s of unmeasured kinds
+# until profiles/timing_tools/README.txt has the wall times.
+LIMITS = {"tests": 1100, "smoke": 300, "harness": 120, "bench": 102, "pmc": 102, "bench_full": 400, "bench_other": 400, "timing": 126,
+          "hmc_timing": 400, "nn_train_timing": 400, "svi_train_timing": 400}
 STOP_STATUSES = (134, 139, 124, 137, -6, -11, -9)            # abort, segmentation fault, time limit, kill: as a shell and as a Python parent see them
 FAULT_TEXT = "an illegal memory access was encountered"
 

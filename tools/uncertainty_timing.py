@@ -10,41 +10,15 @@ S = 16, N = 2048.  Each figure: median and min..max of wall-clock times around w
 parity_fc / parity_conv: the largest difference of every figure between each fp32 mode (exact, triple, split) and the fp64 checker on the
 same posterior and inputs, at fc-512, S = 100, N = 1000 and conv-64, S = 8, N = 256 (reported, not asserted: a different prediction at a
 near-tie moves confidence, agreement and variance by what the two classes differ in).
-Every case is measured in a child process of its own, started through steps.Runner (one time limit each; a fault, an abort or a time limit
-ends the tool); one JSON line per case.  --child: the measuring program itself."""
+Every case is measured in a child process of its own through timing.cases; one JSON line per case.  --child: the measuring program itself."""
 import argparse
-import json
-import os
-import statistics
-import sys
-import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import __graft_entry__ as G                                    # noqa: E402
-import steps as S                                  # noqa: E402
+import timing as T
 
 DEV = "cuda:0"
 FLOATS = ("entropy", "expected_entropy", "mutual_information", "confidence", "agreement", "variance", "nll", "brier")
-
-
-def wall(fn, reps):
-    """ms of `reps` calls after one warm-up call, sorted."""
-    fn()
-    out = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(1e3 * (time.perf_counter() - t0))
-    return sorted(out)
-
-
-def stats(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": ms[0], "max_ms": ms[-1], "runs": len(ms)}
 
 
 def engines(kind, hidden, n_samples, precisions):
@@ -82,9 +56,9 @@ def time_case(kind, hidden, n_samples, N, reps):
     x, y = O.synthetic_inputs(N, (1, 28, 28), 10, seed=1)
     x, y = x.to(DEV), y.argmax(-1).to(DEV)
     res = {"arch": kind, "hidden": hidden, "S": n_samples, "N": N, "C": 10, "precision": eng.precision}
-    res["forward"] = stats(wall(lambda: eng.forward(x, n_samples), reps))
-    res["uncertainty"] = stats(wall(lambda: eng.uncertainty(x, n_samples, y=y), reps))
-    res["uncertainty_8_prefixes"] = stats(wall(lambda: eng.uncertainty(x, n_samples, y=y, n_samples_list=[1, 2, 3, 5, 8, 10, 12, n_samples]), reps))
+    res["forward"] = T.stats(T.wall(lambda: eng.forward(x, n_samples), reps))
+    res["uncertainty"] = T.stats(T.wall(lambda: eng.uncertainty(x, n_samples, y=y), reps))
+    res["uncertainty_8_prefixes"] = T.stats(T.wall(lambda: eng.uncertainty(x, n_samples, y=y, n_samples_list=[1, 2, 3, 5, 8, 10, 12, n_samples]), reps))
     P = eng.sample_outputs(x, n_samples)
     P16 = torch.zeros(n_samples, N, _hip.CPAD, device=DEV)
     P16[:, :, :10] = P                                            # the layout the forward leaves: rows padded to 16
@@ -92,10 +66,10 @@ def time_case(kind, hidden, n_samples, N, reps):
     out = {f: torch.empty(1, N, dtype=torch.int32 if f in ("prediction", "correct") else torch.float64, device=DEV)
            for f in _hip.HipKernels.PREDICTIVE_OUTPUTS}
     k, labels = _hip.HipKernels(), y.int()
-    res["stats_kernel"] = stats(wall(lambda: k.predictive_stats(P16, 10, labels, [n_samples], out), reps))
+    res["stats_kernel"] = T.stats(T.wall(lambda: k.predictive_stats(P16, 10, labels, [n_samples], out), reps))
     dst = torch.empty_like(P16)
-    res["device_copy"] = stats(wall(lambda: dst.copy_(P16), reps))
-    res["torch_float64"] = stats(wall(lambda: torch_restatement(P16, 10, y), reps))
+    res["device_copy"] = T.stats(T.wall(lambda: dst.copy_(P16), reps))
+    res["torch_float64"] = T.stats(T.wall(lambda: torch_restatement(P16, 10, y), reps))
     t = torch_restatement(P16, 10, y)
     res["max_diff_vs_torch"] = {f: float((out[f][0] - t[f]).abs().max()) for f in FLOATS}
     res["prediction_mismatches_vs_torch"] = int((out["prediction"][0] != t["prediction"]).sum())
@@ -117,29 +91,19 @@ def parity_case(kind, hidden, n_samples, N):
     return res
 
 
-CASES = {"fc512": lambda a: time_case("fc", 512, 100, 10000, a.reps), "conv512": lambda a: time_case("conv", 512, 16, 2048, a.reps),
-         "parity_fc": lambda a: parity_case("fc", 512, 100, 1000), "parity_conv": lambda a: parity_case("conv", 64, 8, 256)}
+CASES = {"fc512": lambda reps: time_case("fc", 512, 100, 10000, reps), "conv512": lambda reps: time_case("conv", 512, 16, 2048, reps),
+         "parity_fc": lambda reps: parity_case("fc", 512, 100, 1000), "parity_conv": lambda reps: parity_case("conv", 64, 8, 256)}
 
 
-def child(a):
-    G.build()
-    res = CASES[a.cases](a)
-    res["case"] = a.cases
-    print(json.dumps(res), flush=True)
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=T.BLOCKS)
     ap.add_argument("--cases", default=",".join(CASES))
-    ap.add_argument("--child", action="store_true", help="measure in this process (what the runner starts, one case at a time)")
-    a = ap.parse_args()
+    ap.add_argument("--child", action="store_true", help="measure ONE case in this process (what the runner starts)")
+    a = ap.parse_args(argv)
     if a.child:
-        return child(a)
-    runner = S.Runner("uncertainty_timing")
-    for case in a.cases.split(","):
-        text = runner.gpu("timing", case, [S.PY, os.path.abspath(__file__), "--child", "--cases", case, "--reps", str(a.reps)])
-        print(json.dumps(S.last_json(text)), flush=True)
+        return T.child(lambda: {**CASES[a.cases](a.reps), "case": a.cases})
+    T.cases("uncertainty_timing", __file__, [(case, ["--cases", case] + T.opts(a, "reps")) for case in a.cases.split(",")])
 
 
 if __name__ == "__main__":
