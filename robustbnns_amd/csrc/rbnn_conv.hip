@@ -30,26 +30,99 @@ namespace {
 // Two threads per pooled position (16 channels each): 144 / 196 positions alone left 44 % / 23 % of a 256-thread block's lanes idle in
 // the FMA loop (0.52 -> see profiles/r03a/conv_small_kernels.txt).  Each output is still produced by one thread in the same order.
 // (3x32x32: 196 positions fill a 256-thread block well enough, and the two-halves form measured slower there: 2.45 -> 2.66 ms at c5)
-// The kernel's text is rbnn_conv1_pool_kernel.inc, included once per form: conv1_pool_kernel (X [N, ldx], every sample reads point n's row), and
-// conv1_pool_packed_kernel for the lockstep conv trainer (X [S * N, ldx], the block reads its own row s * N + n: every member has its own batch),
-// and conv1_pool_grouped_kernel for the accuracy forward of conv SVI guides in lockstep (the samples of a group of RBNN_SVI_MULTI_ACC_SAMPLES
-// share their guide's batch: sample s reads row (s / that many) * N + n).
+// ROWS says which row of X the block reads.  0: X is [N, ldx] and every sample reads point n's row (the attack path).  1, packed: X is
+// [S * N, ldx] and the block reads its own row s * N + n (every member has its own batch: the lockstep conv trainer).  2, grouped: X is
+// [S / RBNN_SVI_MULTI_ACC_SAMPLES * N, ldx] and sample s reads row (s / that many) * N + n (the samples of a group share their guide's batch:
+// the accuracy forward of the conv SVI guides in lockstep).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#define RBNN_CONV1_KERNEL conv1_pool_kernel
-#define RBNN_CONV1_PACKED 0
-#include "rbnn_conv1_pool_kernel.inc"
-#undef RBNN_CONV1_KERNEL
-#undef RBNN_CONV1_PACKED
-#define RBNN_CONV1_KERNEL conv1_pool_packed_kernel
-#define RBNN_CONV1_PACKED 1
-#include "rbnn_conv1_pool_kernel.inc"
-#undef RBNN_CONV1_KERNEL
-#undef RBNN_CONV1_PACKED
-#define RBNN_CONV1_KERNEL conv1_pool_grouped_kernel
-#define RBNN_CONV1_PACKED 2
-#include "rbnn_conv1_pool_kernel.inc"
-#undef RBNN_CONV1_KERNEL
-#undef RBNN_CONV1_PACKED
+template <int ACT, class G, int ROWS>
+__global__ void __launch_bounds__(conv1_threads<G>(), 1) conv1_pool_kernel(const ConvArgs a) {
+    constexpr int NPP = G::P1W * G::P1W, IW = G::IW, NTH = conv1_threads<G>();
+    // Weights in LDS as CHANNEL PAIRS: [c / 2][ci][tap][2] (52 floats per (pair, ci): thirteen aligned float4).  The FMA loop then runs on
+    // v_pk_fma_f32 — one instruction = the same tap of two output channels against one broadcast patch value — i.e. at the packed fp32 rate
+    // (round 4; the un-packed loop ran at 0.73 of the plain FMA rate: 2.09 ms per C5 pass).  Every output is still one fp32 FMA chain in
+    // the same (input channel, ky, kx) order: results are bit-identical.
+    constexpr int WROW = 52;
+    __shared__ __attribute__((aligned(16))) float wsh[(C1 / 2) * G::CIN * WROW];
+    __shared__ __attribute__((aligned(8))) float xsh[G::DIN];
+    static_assert(IW % 2 == 0, "patch pairs are 8-byte aligned");
+    const long long sn = blockIdx.x;
+    const int n = (int)(sn % a.N), s = (int)(sn / a.N), tid = threadIdx.x;
+    const int sw = a.sidx ? a.sidx[s] : s;
+    for (int e = tid; e < C1 * G::K1; e += NTH) {                        // e = (c, ci, tap) as nn.Conv2d stores it
+        const int c = e / G::K1, k = e - c * G::K1;
+        wsh[((c >> 1) * G::CIN + k / 25) * WROW + 2 * (k % 25) + (c & 1)] = a.K1w[(long long)sw * C1 * G::K1 + e];
+    }
+    long long row = n;
+    if constexpr (ROWS == 1) row = sn;
+    else if constexpr (ROWS == 2) row = (long long)(s / RBNN_SVI_MULTI_ACC_SAMPLES) * a.N + n;
+    for (int e = tid; e < G::DIN; e += NTH) xsh[e] = a.X[row * a.ldx + e];
+    __syncthreads();
+    constexpr int NH = conv1_halves<G>(), CPT = C1 / NH;                  // channels per thread
+    if (tid >= NH * NPP) return;
+    const int pos = tid % NPP, c0 = (tid / NPP) * CPT;
+    const int py = pos / G::P1W, px = pos % G::P1W;
+    // the 6 x 6 patch as 18 aligned PAIRS per input channel: v_pk_fma_f32 broadcasts either half of a pair to both lanes (op_sel), so a patch
+    // value costs half a register pair — spelled as a scalar broadcast the compiler kept every value twice (216 registers, two waves per SIMD)
+    f32x2 patch[G::CIN][6][3];
+#pragma unroll
+    for (int ci = 0; ci < G::CIN; ++ci)
+#pragma unroll
+        for (int y = 0; y < 6; ++y)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) patch[ci][y][j] = *(const f32x2*)(xsh + ci * (IW * IW) + (2 * py + y) * IW + 2 * px + 2 * j);
+    float* const p1 = a.P1 + sn * G::P1SZ + pos;                         // dense [S][N][32][P1W][P1W]
+    uint8_t* const st = a.st1 + sn * G::P1SZ + pos;
+#pragma unroll 1
+    for (int cp = c0 / 2; cp < (c0 + CPT) / 2; ++cp) {
+        f32x2 v4[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v4[q] = (f32x2){0.f, 0.f};
+#pragma unroll
+        for (int ci = 0; ci < G::CIN; ++ci) {                             // channel-major accumulation, taps in (ky, kx) order
+            asm volatile("" ::: "memory");                               // keep the three input channels' weight reads from being hoisted together (156 registers)
+            const float* const wrow = wsh + (cp * G::CIN + ci) * WROW;
+#pragma unroll
+            for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 5; ++kx) {
+                    const int tap = ky * 5 + kx;
+                    // one 16-byte read per tap pair (it keeps 52 more registers live than 8-byte reads: 252 VGPRs, hence one wave per SIMD in the launch bounds)
+                    const f32x4 w4 = *(const f32x4*)(wrow + 4 * (tap >> 1));
+                    const f32x2 wv = (tap & 1) ? (f32x2){w4[2], w4[3]} : (f32x2){w4[0], w4[1]};
+#pragma unroll
+                    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                        for (int dx = 0; dx < 2; ++dx) {
+                            // acc.{lo,hi} += w.{lo,hi} * pair.{half}: the broadcast is the instruction's op_sel (written as a vector splat,
+                            // the compiler hoisted 108 materialised (p, p) pairs out of the channel loop: 252 registers)
+                            const f32x2 pp = patch[ci][dy + ky][(dx + kx) >> 1];
+                            // The BROADCAST operand (the patch pair, one half of it for both result lanes) is src0: op_sel / op_sel_hi bit 0.  Rounds 3-5 had it as
+                            // src1 (op_sel:[0,1,0]) — a form hipcc itself never emits (it canonicalises a packed-fp32 broadcast onto src0) and that is NOT reliable
+                            // on gfx950 when waves of another kernel share the SIMD: with two processes on one GPU the low result lane intermittently took the
+                            // other half of the pair (46 of 320 forward calls differed from their own reference; 0 of 320 in this form; profiles/r05w).  The
+                            // product is commutative: results are bit-identical to the old form's (one process).
+                            if ((dx + kx) & 1) asm("v_pk_fma_f32 %0, %2, %1, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(v4[dy * 2 + dx]) : "v"(wv), "v"(pp));
+                            else               asm("v_pk_fma_f32 %0, %2, %1, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(v4[dy * 2 + dx]) : "v"(wv), "v"(pp));
+                        }
+                }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int c = 2 * cp + h;
+            const float b = a.K1b[(long long)sw * C1 + c];
+            float best = 0.f, best_pre = 0.f;
+            int arg = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float pre = v4[q][h] + b, v = smooth_act<ACT>() ? act_fwd<ACT>(pre) : pre;
+                if (q == 0 || v > best) { best = v; best_pre = pre; arg = q; }   // first maximum wins (torch max_pool2d)
+            }
+            p1[c * NPP] = smooth_act<ACT>() ? best : act_fwd<ACT>(best);
+            st[c * NPP] = (uint8_t)(arg | (best_pre > 0.f ? 4 : 0));
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------
 // conv2: one block = one (sample, point); 4 waves, each 64 output channels x the point's NPOS output positions
@@ -411,12 +484,10 @@ __global__ void __launch_bounds__(512, 2) conv2_pool_split_kernel(const ConvArgs
     }
 }
 
-// ROWS: which row of X a (sample, point) block reads — 0: n, 1: s N + n (packed), 2: (s / RBNN_SVI_MULTI_ACC_SAMPLES) N + n (grouped)
+// ROWS: which row of X a (sample, point) block reads (conv1_pool_kernel)
 template <int ACT, class G, int ROWS = 0>
 int launch_conv_forward(const ConvArgs& a, hipStream_t st) {
-    if constexpr (ROWS == 2) hipLaunchKernelGGL((conv1_pool_grouped_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
-    else if constexpr (ROWS == 1) hipLaunchKernelGGL((conv1_pool_packed_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
-    else hipLaunchKernelGGL((conv1_pool_kernel<ACT, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
+    hipLaunchKernelGGL((conv1_pool_kernel<ACT, G, ROWS>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
     int rc = launch_status();
     if (rc) return rc;
     constexpr int LDSB = conv2_lds_floats<G>() * 4;
@@ -1132,7 +1203,7 @@ int launch_conv1_pool(int act, int in_channels, const ConvArgs& a, hipStream_t s
     auto go = [&](auto g) {
         using G = decltype(g);
         return for_activation(act, [&](auto actc) {
-            hipLaunchKernelGGL((conv1_pool_kernel<decltype(actc)::value, G>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
+            hipLaunchKernelGGL((conv1_pool_kernel<decltype(actc)::value, G, 0>), dim3((unsigned)((long long)a.S * a.N)), dim3(conv1_threads<G>()), 0, st, a);
             return launch_status();
         });
     };

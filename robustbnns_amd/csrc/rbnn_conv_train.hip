@@ -10,6 +10,7 @@
 //                                 dK2 | dK2b     = sum over (point, position) of dO2 x [P1 patch | 1], per batch slice  (GEMM, mode G_DK2)
 //                                 dK1 | dK1b     = sum over (point, position) of dO1 x [x patch | 1], per batch slice   (GEMM, mode G_DK1)
 //                                 the slices' partial sums added in one fixed order, fp64                               (conv_reduce_kernel)
+//                                 conv_weight_grads<ENS> is these seven launches for both forms; the kernels are templates on ENS
 //      rbnn_conv_adam_step        torch.optim.Adam's single-tensor formula on the flat buffer: 1 launch                  (nn_adam_kernel<false>)
 //      rbnn_conv_train_finalize   the fp32-rounded mean CE of the step, its running sum, the correct predictions: 1 launch (nn_finalize_kernel<false>)
 //                                 both kernels are rbnn_nn_step.hpp's, shared with the fc members of rbnn_nn_train.hip, the member index compiled out
@@ -28,16 +29,15 @@
 // shapes, so every launch of the single net's step takes the member as a grid dimension and the launch count does not grow with M):
 //      rbnn_conv_ens_stage          member m's B rows of the resident data (rows [M, B], clamped) -> Xs [M B, 784], labels [M B]: 1 launch
 //                                   (conv_ens_stage_kernel); no kernel after it sees rows, every heavy kernel works on a packed batch
-//      rbnn_conv_ens_forward        the exact forward with S = M samples on the packed batch (conv1_pool_packed_kernel reads row s N + n;
+//      rbnn_conv_ens_forward        the exact forward with S = M samples on the packed batch (conv1_pool_kernel<.., 1> reads row s N + n;
 //                                   conv2_pool_kernel and conv_fc_kernel as they are) and conv_head_kernel over M B points: 3 + 1 launches
-//      rbnn_conv_ens_weight_grads   the 7 launches above, member = blockIdx.y (train_gemm_kernel<true>, conv_ens_do2 / _route1 / _reduce_kernel)
-//                                   or blockIdx.z (conv_ens_wgrad_gemm_kernel: y is the K slice); partial sums [M][slices][...].  The slice
-//                                   counts stay functions of B and Hc alone: member m's sums are added in the single net's order
+//      rbnn_conv_ens_weight_grads   the 7 launches above with ENS = true: member = blockIdx.y (train_gemm_kernel<true, false>, conv_do2 /
+//                                   _route1_kernel, conv_ens_reduce_kernel) or blockIdx.z (conv_wgrad_gemm_kernel: y is the K slice); partial sums
+//                                   [M][slices][...].  The slice counts stay functions of B and Hc alone: member m's sums in the single net's order
 //      rbnn_conv_ens_adam_step      nn_adam_kernel<false> over all M n_params elements (element-wise: the members share t and lr): 1 launch
 //      rbnn_conv_ens_finalize       nn_finalize_kernel<true>, one block per member: 1 launch
 //      One lockstep step = 1 + 4 + 7 + 1 + 1 = 14 launches whatever M is.  The flat buffers are TENSOR-MAJOR (six blocks [M, size of tensor]
-//      in state_dict order: rbnn_conv_posterior's stacks, so the forward addresses member m as sample m).  conv_ens_do2 / _wgrad_gemm /
-//      _route1_kernel are the single net's text (rbnn_conv_wgrad_kernels.inc, included twice) on member views; the single net's kernels keep their code.
+//      in state_dict order: rbnn_conv_posterior's stacks, so the forward addresses member m as sample m).
 //
 // and SVI training of K conv guides of one shape in LOCKSTEP (the SVI step above for every guide in one set of launches; the flat buffers are
 // tensor-major as the ensemble's, so the guides are the members of the staging, the forward and the weight gradients):
@@ -48,7 +48,7 @@
 //                                    Instantiated and launched in rbnn_svi.hip, not here: a second instance of adam_kernel in THIS unit changes
 //                                    the code its adam_kernel<Single> compiles to (profiles/svi_one_family/README.txt)
 //      rbnn_conv_svi_guides_accuracy  svils_draw_kernel<TensorMajor> of the K * 10 weight sets under keys[k] ^ key_xor, the exact forward of those nets on
-//                                    the K staged batches (conv1_pool_grouped_kernel: set k * 10 + s reads guide k's rows; conv2_pool_kernel and
+//                                    the K staged batches (conv1_pool_kernel<.., 2>: set k * 10 + s reads guide k's rows; conv2_pool_kernel and
 //                                    conv_fc_kernel as they are), conv_svils_acc_sum_kernel: 1 + 3 + 1 launches
 //      rbnn_conv_svi_guides_finalize  svils_finalize_kernel<false>, one block per guide: the step's sums and the epoch's end on the device.  1 launch
 //      One lockstep SVI step = 1 + 12 + 1 + 1 = 15 launches without the accuracy forward, 20 with it, whatever K is.  A guide that has finished
@@ -144,7 +144,48 @@ __global__ void __launch_bounds__(64) conv_head_kernel(const ConvHeadArgs a) {
 // form: pool 2 has stride 1, so a position lies in up to 4 windows; it adds those that selected it in the fixed order (y-1, x-1), (y-1, x),
 // (y, x-1), (y, x).
 // ---------------------------------------------------------------------------------------------------
+// ENS (this kernel, the conv GEMMs and conv_route1_kernel): the lockstep form.  The kernel first moves its argument record to the views of ITS
+// member (blockIdx.y; the GEMM: blockIdx.z, y being the K slice) of arrays packed [M, B, .], then runs the single net's text.  The single net's
+// instances read none of the arguments behind the record.
 struct ConvDo2Args { const float *dZ, *Fw, *Q2; const uint8_t* st2; float* dO2; int Hc, C; };
+
+template <int ACT, bool ENS> __global__ void __launch_bounds__(256) conv_do2_kernel(ConvDo2Args a, const int B) {
+    if constexpr (ENS) {                                                   // member blockIdx.y of [M, B, .] and of Fw [M, C, 49 Hc]
+        const long long mem = blockIdx.y, pt = mem * B, F = (long long)a.Hc * NP2;
+        a.dZ += pt * RBNN_CPAD; a.Fw += mem * a.C * F; a.Q2 += pt * F; a.st2 += pt * F; a.dO2 += pt * a.Hc * NPOS;
+    }
+    __shared__ float gs[4][NP2];
+    __shared__ int as[4][NP2];
+    const int t = threadIdx.x, groups = a.Hc >> 2;
+    const int b = blockIdx.x / groups, hc0 = 4 * (blockIdx.x % groups);
+    const int F = a.Hc * NP2;
+    if (t < 4 * NP2) {
+        const int hl = t / NP2, p = t % NP2;
+        const long long f = (long long)(hc0 + hl) * NP2 + p;
+        float dq = 0.f;
+        for (int c = 0; c < a.C; ++c) dq = fmaf(a.dZ[(long long)b * RBNN_CPAD + c], a.Fw[(long long)c * F + f], dq);
+        const int st = a.st2[(long long)b * F + f];
+        float d;
+        if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.Q2[(long long)b * F + f]);
+        else d = (st & 4) ? 1.f : act_neg_slope<ACT>();
+        gs[hl][p] = dq * d;
+        as[hl][p] = st & 3;
+    }
+    __syncthreads();
+    const int hl = t >> 6, pos = t & 63, y = pos >> 3, x = pos & 7;
+    float s = 0.f;
+#pragma unroll
+    for (int dy = 1; dy >= 0; --dy)
+#pragma unroll
+        for (int dx = 1; dx >= 0; --dx) {
+            const int wy = y - dy, wx = x - dx;                            // the window whose cell (dy, dx) this position is
+            if (wy >= 0 && wy < P2W && wx >= 0 && wx < P2W) {
+                const int p = wy * P2W + wx;
+                if (as[hl][p] == dy * 2 + dx) s += gs[hl][p];
+            }
+        }
+    a.dO2[((long long)b * a.Hc + hc0 + hl) * NPOS + pos] = s;
+}
 
 // ---------------------------------------------------------------------------------------------------
 // The conv GEMMs  C(m, n) = sum_k A(m, k) B(n, k)  on v_mfma_f32_16x16x4_f32, operands gathered (zero outside [M, N, K]):
@@ -183,6 +224,70 @@ template <int MODE> __device__ __forceinline__ float wg_load_b(const WgArgs& g, 
     return g.Bsrc[(long long)hc * K2 + n * 25 + (k - hc * 25)];
 }
 
+template <int MODE, bool ENS>
+__global__ void __launch_bounds__(256) conv_wgrad_gemm_kernel(WgArgs g, const long long a_mem, const long long b_mem, const long long o_mem) {
+    if constexpr (ENS) {                                                   // member blockIdx.z: its operands and its slices [slices][M, N]
+        const long long mem = blockIdx.z;
+        g.A += mem * a_mem; g.Bsrc += mem * b_mem; g.out += mem * o_mem;
+    }
+    constexpr int NTN = MODE == G_DP1 ? 2 : 4, TN = 16 * NTN;
+    __shared__ float As[GK][GLD], Bs[GK][TN + 4];
+    const int tiles_n = (g.N + TN - 1) / TN;
+    const int m0 = GT * (blockIdx.x / tiles_n), n0 = TN * (blockIdx.x % tiles_n);
+    const int k_begin = blockIdx.y * g.kc, k_end = min(k_begin + g.kc, g.K);
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 15, lg = lane >> 4;
+    f32x4 acc[NTN], tot[NTN];
+#pragma unroll
+    for (int nt = 0; nt < NTN; ++nt) acc[nt] = tot[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int kk = t & 15, r0 = t >> 4;
+    float ra[4], rb[NTN];
+    auto fetch = [&](int k0) {
+        const int k = k0 + kk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = m0 + r0 + 16 * i;
+            ra[i] = (m < g.M && k < k_end) ? wg_load_a<MODE>(g, m, k) : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < NTN; ++i) {
+            const int n = n0 + r0 + 16 * i;
+            rb[i] = (n < g.N && k < k_end) ? wg_load_b<MODE>(g, n, k) : 0.f;
+        }
+    };
+    int stage = 0;
+    fetch(k_begin);
+    for (int k0 = k_begin; k0 < k_end; k0 += GK, ++stage) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) As[kk][r0 + 16 * i] = ra[i];
+#pragma unroll
+        for (int i = 0; i < NTN; ++i) Bs[kk][r0 + 16 * i] = rb[i];
+        __syncthreads();
+        if (k0 + GK < k_end) fetch(k0 + GK);
+#pragma unroll
+        for (int ks = 0; ks < GK / 4; ++ks) {
+            const float a = As[4 * ks + lg][16 * wave + li];
+#pragma unroll
+            for (int nt = 0; nt < NTN; ++nt) acc[nt] = MFMA16(a, Bs[4 * ks + lg][16 * nt + li], acc[nt]);
+        }
+        __syncthreads();
+        if ((stage & 31) == 31) {
+#pragma unroll
+            for (int nt = 0; nt < NTN; ++nt) { tot[nt] += acc[nt]; acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
+    }
+    // lane holds C(m0 + 16 wave + 4 lg + r, n0 + 16 nt + li)
+#pragma unroll
+    for (int nt = 0; nt < NTN; ++nt) {
+        tot[nt] += acc[nt];
+        const int n = n0 + 16 * nt + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + 16 * wave + 4 * lg + r;
+            if (m < g.M && n < g.N) g.out[((long long)blockIdx.y * g.M + m) * g.N + n] = tot[nt][r];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // dO1[b, ci, 24 x 24]: one thread per (b, pooled position, ci).  dP1 = the slices of partP in increasing order (fp64), times act' (relu /
 // leaky: the pool-1 stash's sign bit; sigmoid / tanh: from the value in P1), goes to the cell of its 2 x 2 window that the stash names and
@@ -190,26 +295,28 @@ template <int MODE> __device__ __forceinline__ float wg_load_b(const WgArgs& g, 
 // ---------------------------------------------------------------------------------------------------
 struct ConvRouteArgs { const float *part, *P1; const uint8_t* st1; float* dO1; long long n; int splits; };
 
-// The text of conv_do2_kernel, conv_wgrad_gemm_kernel and conv_route1_kernel is rbnn_conv_wgrad_kernels.inc, included once per form: the single
-// net's kernels, and conv_ens_do2_kernel / conv_ens_wgrad_gemm_kernel / conv_ens_route1_kernel, which run it on the views of one member.
-#define RBNN_DO2_KERNEL conv_do2_kernel
-#define RBNN_WGEMM_KERNEL conv_wgrad_gemm_kernel
-#define RBNN_ROUTE1_KERNEL conv_route1_kernel
-#define RBNN_CONV_WG_ENS 0
-#include "rbnn_conv_wgrad_kernels.inc"
-#undef RBNN_DO2_KERNEL
-#undef RBNN_WGEMM_KERNEL
-#undef RBNN_ROUTE1_KERNEL
-#undef RBNN_CONV_WG_ENS
-#define RBNN_DO2_KERNEL conv_ens_do2_kernel
-#define RBNN_WGEMM_KERNEL conv_ens_wgrad_gemm_kernel
-#define RBNN_ROUTE1_KERNEL conv_ens_route1_kernel
-#define RBNN_CONV_WG_ENS 1
-#include "rbnn_conv_wgrad_kernels.inc"
-#undef RBNN_DO2_KERNEL
-#undef RBNN_WGEMM_KERNEL
-#undef RBNN_ROUTE1_KERNEL
-#undef RBNN_CONV_WG_ENS
+template <int ACT, bool ENS> __global__ void __launch_bounds__(ELT_THREADS) conv_route1_kernel(ConvRouteArgs a, const int B) {
+    if constexpr (ENS) {                       // member blockIdx.y of part [M][splits][n], P1 / st1 / dO1 [M, B, .]; a.n: ONE member's elements
+        const long long mem = blockIdx.y, pt = mem * B;
+        a.part += mem * a.splits * a.n; a.P1 += pt * P1SZ; a.st1 += pt * P1SZ; a.dO1 += pt * C1 * NO1;
+    }
+    const long long e = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    if (e >= a.n) return;
+    double s = 0.0;
+    for (int sp = 0; sp < a.splits; ++sp) s += (double)a.part[(long long)sp * a.n + e];
+    const int ci = (int)(e & (C1 - 1));
+    const long long m = e >> 5;
+    const int b = (int)(m / PP1), pp = (int)(m - (long long)b * PP1);
+    const long long at = (long long)b * P1SZ + ci * PP1 + pp;
+    const int st = a.st1[at];
+    float d;
+    if (smooth_act<ACT>()) d = act_grad_from_value<ACT>(a.P1[at]);
+    else d = (st & 4) ? 1.f : act_neg_slope<ACT>();
+    const float v = (float)s * d;
+    float* const o = a.dO1 + ((long long)b * C1 + ci) * NO1 + (2 * (pp / P1W)) * O1W + 2 * (pp % P1W);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[(q >> 1) * O1W + (q & 1)] = (st & 3) == q ? v : 0.f;
+}
 
 // ---------------------------------------------------------------------------------------------------
 // The slices' partial sums -> grad: one thread per element of dK2 | dK2b and of dK1 | dK1b, slices in increasing order, fp64.
@@ -282,17 +389,12 @@ inline int check_conv_batch(const float* X, int ldx, int B) {
     return aligned16(X) ? RBNN_OK : RBNN_ERR_ALIGN;
 }
 
-template <int MODE> int wg_launch(const WgArgs& g, int splits, hipStream_t st) {
-    constexpr int TN = MODE == G_DP1 ? 32 : 64;
-    const int tiles = ((g.M + GT - 1) / GT) * ((g.N + TN - 1) / TN);
-    hipLaunchKernelGGL(conv_wgrad_gemm_kernel<MODE>, dim3(tiles, splits), dim3(256), 0, st, g);
-    return launch_status();
-}
 // the same tiles and slices for every member (grid dimension z): member m's operands at A + m a_mem, Bsrc + m b_mem, its slices at out + m o_mem
-template <int MODE> int wg_ens_launch(const WgArgs& g, int splits, int members, long long a_mem, long long b_mem, long long o_mem, hipStream_t st) {
+template <int MODE, bool ENS>
+int wg_launch(const WgArgs& g, int splits, int members, long long a_mem, long long b_mem, long long o_mem, hipStream_t st) {
     constexpr int TN = MODE == G_DP1 ? 32 : 64;
     const int tiles = ((g.M + GT - 1) / GT) * ((g.N + TN - 1) / TN);
-    hipLaunchKernelGGL(conv_ens_wgrad_gemm_kernel<MODE>, dim3(tiles, splits, members), dim3(256), 0, st, g, a_mem, b_mem, o_mem);
+    hipLaunchKernelGGL((conv_wgrad_gemm_kernel<MODE, ENS>), dim3(tiles, splits, members), dim3(256), 0, st, g, a_mem, b_mem, o_mem);
     return launch_status();
 }
 
@@ -319,6 +421,103 @@ inline int check_conv_ens_net(const rbnn_conv_ens_net* n) {
 
 inline int check_conv_ens_points(const rbnn_conv_ens_net* n, int B) {
     return (B < 1 || B > MAX_POINTS || (long long)n->n_members * B > MAX_ENS_POINTS) ? RBNN_ERR_SHAPE : RBNN_OK;
+}
+
+// the five shape fields every conv net descriptor starts with
+template <class To, class From> inline void copy_conv_shape(To& to, const From& from) {
+    to.activation = from.activation; to.in_channels = from.in_channels; to.in_width = from.in_width; to.hidden = from.hidden;
+    to.n_classes = from.n_classes;
+}
+
+// the n_stored nets of a flat buffer (L: conv_layout for one, conv_ens_layout for a tensor-major stack) as the forward's posterior
+template <class Net> inline rbnn_conv_posterior conv_posterior_of(const Net& shape, const float* base, const ConvLayout& L, int n_stored) {
+    rbnn_conv_posterior p = {};
+    copy_conv_shape(p, shape);
+    p.n_stored = n_stored;
+    p.K1w = base + L.K1w; p.K1b = base + L.K1b; p.K2w = base + L.K2w; p.K2b = base + L.K2b; p.Fw = base + L.Fw; p.Fb = base + L.Fb;
+    return p;
+}
+
+// the head over the n points of ws->logits (a workspace of either form): the training forwards' last launch
+template <class Ws> inline int launch_conv_head(const Ws* ws, const int32_t* labels, int n, int C, float dz_scale, void* stream) {
+    const ConvHeadArgs h = {ws->logits, labels, ws->dZ, ws->ce, ws->correct, n, C, dz_scale};
+    hipLaunchKernelGGL(conv_head_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
+    return launch_status();
+}
+
+// what the weight gradients read and write of a workspace, of either form
+template <class Ws> inline bool wg_buffers(const Ws* ws) {
+    return ws && ws->P1 && ws->st1 && ws->Q2 && ws->st2 && ws->dZ && ws->dO2 && ws->dO1 && ws->part2 && ws->part1 && ws->partP;
+}
+
+// The seven launches of the weight gradients, after the entry point's checks.  ENS = false is the single net: M = 1, L = conv_layout, X the
+// caller's batch.  ENS = true is M members in lockstep: L = conv_ens_layout, X = ws->Xs with ldx = 784, every array packed [M, B, .], the
+// member a grid dimension (y; the conv GEMMs: z) and the partial sums [M][slices][...].  The single net's kernels read no member stride.
+template <bool ENS, class Net, class Ws>
+int conv_weight_grads(const Net* net, int M, const ConvLayout& L, const float* X, int ldx, int B, const Ws* ws, hipStream_t st) {
+    const int Hc = net->hidden, C = net->n_classes;
+    const long long F = (long long)Hc * NP2;
+    float* const G = net->grad;
+    // dFw | dFb: the strided GEMM, its member form with the member as grid dimension y
+    GemmArgs ga = {};
+    ga.n_prob = 1;
+    ga.p[0] = wgrad_prob(ws->dZ, RBNN_CPAD, ws->Q2, F, (long long)B * F, C, (int)F, B, G + L.Fw, G + L.Fb, 0);
+    ga.p[0].c_mem = (long long)C * F;
+    ga.p[0].bias_mem = C;
+    int rc = gemm_launch<ENS>(ga, M, st);
+    if (rc) return rc;
+    // dO2
+    const ConvDo2Args d = {ws->dZ, net->P + L.Fw, ws->Q2, ws->st2, ws->dO2, Hc, C};
+    rc = for_activation(net->activation, [&](auto a) {
+        hipLaunchKernelGGL((conv_do2_kernel<decltype(a)::value, ENS>), dim3((unsigned)B * (Hc / 4), M), dim3(256), 0, st, d, B);
+        return launch_status();
+    });
+    if (rc) return rc;
+    // dP1 = conv2^T(dO2) per slice of the channels, then dO1 through pool 1
+    int perP, sP;
+    dp1_slices(B, Hc, perP, sP);
+    const long long nP = (long long)B * PP1 * C1, dO2_mem = (long long)B * Hc * NPOS;
+    WgArgs g = {};
+    g.Hc = Hc; g.ldx = ldx;
+    g.A = ws->dO2; g.Bsrc = net->P + L.K2w; g.out = ws->partP;
+    g.M = B * PP1; g.N = C1; g.K = Hc * 25; g.kc = perP * 400;
+    if ((rc = wg_launch<G_DP1, ENS>(g, sP, M, dO2_mem, (long long)Hc * K2, sP * nP, st))) return rc;
+    const ConvRouteArgs ro = {ws->partP, ws->P1, ws->st1, ws->dO1, nP, sP};
+    rc = for_activation(net->activation, [&](auto a) {
+        hipLaunchKernelGGL((conv_route1_kernel<decltype(a)::value, ENS>), dim3(blocks_for(ro.n), M), dim3(ELT_THREADS), 0, st, ro, B);
+        return launch_status();
+    });
+    if (rc) return rc;
+    // the two split contractions and their reduction
+    int per2, s2, per1, s1;
+    slices(B, MAX_SPLITS2, per2, s2);
+    slices(B, MAX_SPLITS1, per1, s1);
+    g.A = ws->dO2; g.Bsrc = ws->P1; g.out = ws->part2; g.M = Hc; g.N = N2; g.K = B * NPOS; g.kc = per2 * NPOS;
+    if ((rc = wg_launch<G_DK2, ENS>(g, s2, M, dO2_mem, (long long)B * P1SZ, (long long)s2 * Hc * N2, st))) return rc;
+    g.A = ws->dO1; g.Bsrc = X; g.out = ws->part1; g.M = C1; g.N = N1; g.K = B * NO1; g.kc = per1 * NO1;
+    if ((rc = wg_launch<G_DK1, ENS>(g, s1, M, (long long)B * C1 * NO1, (long long)B * ldx, (long long)s1 * C1 * N1, st))) return rc;
+    const dim3 red(blocks_for((long long)Hc * N2 + C1 * N1), M);
+    if constexpr (ENS) {
+        const ConvEnsRedArgs r = {ws->part2, ws->part1, G, Hc, s2, s1, L.K1b, L.K2w, L.K2b};
+        hipLaunchKernelGGL(conv_ens_reduce_kernel, red, dim3(ELT_THREADS), 0, st, r);
+    } else {                                                               // a kernel of its own: folded into one template, its code changed
+        const ConvRedArgs r = {ws->part2, ws->part1, G, Hc, s2, s1, L.K2w, L.K2b};
+        hipLaunchKernelGGL(conv_reduce_kernel, red, dim3(ELT_THREADS), 0, st, r);
+    }
+    return launch_status();
+}
+
+// torch.optim.Adam on a whole flat buffer of n_params elements (element-wise: the members of a lockstep buffer share t and lr): 1 launch
+template <class Net> int conv_adam_step(const Net* net, long long n_params, int64_t step, double lr, double beta1, double beta2, double adam_eps,
+                                        void* stream) {
+    if (!net->P || !net->m || !net->v || !net->grad) return RBNN_ERR_NULL;
+    if (step < 1) return RBNN_ERR_SHAPE;
+    AdamArgs a = {};
+    a.n_params = n_params;
+    a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad;
+    a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
+    hipLaunchKernelGGL(nn_adam_kernel<false>, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
+    return launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -349,7 +548,7 @@ inline int check_conv_svils_points(const rbnn_conv_svi_guides_net* n, int B) {
 // the guides as the members of rbnn_conv_ens_*: P = the drawn W, grad = dCE/dW, the first fifteen workspaces
 inline rbnn_conv_ens_net conv_svils_members(const rbnn_conv_svi_guides_net* n) {
     rbnn_conv_ens_net e = {};
-    e.activation = n->activation; e.in_channels = n->in_channels; e.in_width = n->in_width; e.hidden = n->hidden; e.n_classes = n->n_classes;
+    copy_conv_shape(e, *n);
     e.n_members = n->n_guides; e.P = n->W; e.grad = n->grad;
     return e;
 }
@@ -397,17 +596,11 @@ static int train_forward(const rbnn_conv_train_net* net, const float* X, int32_t
     if (!net->P || !labels || !ws || !ws->logits || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->ce || !ws->correct) return RBNN_ERR_NULL;
     if ((rc = check_conv_batch(X, ldx, n_points))) return rc;
     if (!aligned16(net->P)) return RBNN_ERR_ALIGN;
-    const ConvLayout L = conv_layout(net->hidden, net->n_classes);
-    rbnn_conv_posterior p = {};
-    p.activation = net->activation; p.hidden = net->hidden; p.n_classes = net->n_classes; p.n_stored = 1;
-    p.in_channels = net->in_channels; p.in_width = net->in_width;
-    p.K1w = net->P + L.K1w; p.K1b = net->P + L.K1b; p.K2w = net->P + L.K2w; p.K2b = net->P + L.K2b; p.Fw = net->P + L.Fw; p.Fb = net->P + L.Fb;
+    const rbnn_conv_posterior p = conv_posterior_of(*net, net->P, conv_layout(net->hidden, net->n_classes), 1);
     rbnn_conv_workspace w = {};
     w.P = ws->logits; w.P1 = ws->P1; w.st1 = ws->st1; w.Q2 = ws->Q2; w.st2 = ws->st2;
     if ((rc = rbnn_conv_forward(&p, X, ldx, n_points, nullptr, 1, RBNN_OUT_LOGITS, &w, stream))) return rc;
-    const ConvHeadArgs h = {ws->logits, labels, ws->dZ, ws->ce, ws->correct, n_points, net->n_classes, dz_scale};
-    hipLaunchKernelGGL(conv_head_kernel, dim3((n_points + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
-    return launch_status();
+    return launch_conv_head(ws, labels, n_points, net->n_classes, dz_scale, stream);
 }
 
 int rbnn_conv_train_forward(const rbnn_conv_train_net* net, const float* X, int32_t ldx, const int32_t* labels, int32_t n_points,
@@ -419,64 +612,15 @@ int rbnn_conv_weight_grads(const rbnn_conv_train_net* net, const float* X, int32
                            void* stream) {
     int rc = check_conv_net(net);
     if (rc) return rc;
-    if (!net->P || !net->grad || !ws || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->dO2 || !ws->dO1 || !ws->part2 || !ws->part1 ||
-        !ws->partP)
-        return RBNN_ERR_NULL;
+    if (!net->P || !net->grad || !wg_buffers(ws)) return RBNN_ERR_NULL;
     if ((rc = check_conv_batch(X, ldx, n_points))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int Hc = net->hidden, C = net->n_classes, B = n_points, F = Hc * NP2;
-    const ConvLayout L = conv_layout(Hc, C);
-    float* const G = net->grad;
-    // dFw | dFb
-    GemmArgs ga = {};
-    ga.n_prob = 1;
-    ga.p[0] = wgrad_prob(ws->dZ, RBNN_CPAD, ws->Q2, F, 0, C, F, B, G + L.Fw, G + L.Fb, 0);
-    if ((rc = gemm_launch<false>(ga, 1, st))) return rc;
-    // dO2
-    const ConvDo2Args d = {ws->dZ, net->P + L.Fw, ws->Q2, ws->st2, ws->dO2, Hc, C};
-    rc = for_activation(net->activation, [&](auto act) {
-        hipLaunchKernelGGL(conv_do2_kernel<decltype(act)::value>, dim3((unsigned)B * (Hc / 4)), dim3(256), 0, st, d);
-        return launch_status();
-    });
-    if (rc) return rc;
-    // dP1 = conv2^T(dO2) per slice of the channels, then dO1 through pool 1
-    int perP, sP;
-    dp1_slices(B, Hc, perP, sP);
-    WgArgs g = {};
-    g.Hc = Hc; g.ldx = ldx;
-    g.A = ws->dO2; g.Bsrc = net->P + L.K2w; g.out = ws->partP;
-    g.M = B * PP1; g.N = C1; g.K = Hc * 25; g.kc = perP * 400;
-    if ((rc = wg_launch<G_DP1>(g, sP, st))) return rc;
-    const ConvRouteArgs ro = {ws->partP, ws->P1, ws->st1, ws->dO1, (long long)B * PP1 * C1, sP};
-    rc = for_activation(net->activation, [&](auto act) {
-        hipLaunchKernelGGL(conv_route1_kernel<decltype(act)::value>, dim3(blocks_for(ro.n)), dim3(ELT_THREADS), 0, st, ro);
-        return launch_status();
-    });
-    if (rc) return rc;
-    // the two split contractions and their reduction
-    int per2, s2, per1, s1;
-    slices(B, MAX_SPLITS2, per2, s2);
-    slices(B, MAX_SPLITS1, per1, s1);
-    g.A = ws->dO2; g.Bsrc = ws->P1; g.out = ws->part2; g.M = Hc; g.N = N2; g.K = B * NPOS; g.kc = per2 * NPOS;
-    if ((rc = wg_launch<G_DK2>(g, s2, st))) return rc;
-    g.A = ws->dO1; g.Bsrc = X; g.out = ws->part1; g.M = C1; g.N = N1; g.K = B * NO1; g.kc = per1 * NO1;
-    if ((rc = wg_launch<G_DK1>(g, s1, st))) return rc;
-    const ConvRedArgs r = {ws->part2, ws->part1, G, Hc, s2, s1, L.K2w, L.K2b};
-    hipLaunchKernelGGL(conv_reduce_kernel, dim3(blocks_for((long long)Hc * N2 + C1 * N1)), dim3(ELT_THREADS), 0, st, r);
-    return launch_status();
+    return conv_weight_grads<false>(net, 1, conv_layout(net->hidden, net->n_classes), X, ldx, n_points, ws, (hipStream_t)stream);
 }
 
 int rbnn_conv_adam_step(const rbnn_conv_train_net* net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void* stream) {
     const int rc = check_conv_net(net);
     if (rc) return rc;
-    if (!net->P || !net->m || !net->v || !net->grad) return RBNN_ERR_NULL;
-    if (step < 1) return RBNN_ERR_SHAPE;
-    AdamArgs a = {};
-    a.n_params = conv_layout(net->hidden, net->n_classes).n_params;
-    a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad;
-    a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(nn_adam_kernel<false>, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return conv_adam_step(net, conv_layout(net->hidden, net->n_classes).n_params, step, lr, beta1, beta2, adam_eps, stream);
 }
 
 int rbnn_conv_train_finalize(const rbnn_conv_train_ws* ws, int32_t n_points, double* stats, void* stream) {
@@ -497,8 +641,7 @@ int rbnn_conv_ens_sizes(const rbnn_conv_ens_net* net, int32_t n_points, rbnn_con
     if (!out) return RBNN_ERR_NULL;
     if ((rc = check_conv_ens_points(net, n_points))) return rc;
     rbnn_conv_train_net one = {};
-    one.activation = net->activation; one.in_channels = net->in_channels; one.in_width = net->in_width; one.hidden = net->hidden;
-    one.n_classes = net->n_classes;
+    copy_conv_shape(one, *net);
     rbnn_conv_train_bytes s;
     if ((rc = rbnn_conv_train_sizes(&one, n_points, &s))) return rc;
     const size_t M = (size_t)net->n_members;
@@ -535,21 +678,14 @@ static int ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const rbn
     if ((rc = check_conv_ens_points(net, n_points))) return rc;
     if (!aligned16(net->P)) return RBNN_ERR_ALIGN;
     const int M = net->n_members;
-    const ConvLayout L = conv_ens_layout(net->hidden, net->n_classes, M);
-    rbnn_conv_posterior p = {};
-    p.activation = net->activation; p.hidden = net->hidden; p.n_classes = net->n_classes; p.n_stored = M;
-    p.in_channels = net->in_channels; p.in_width = net->in_width;
-    p.K1w = net->P + L.K1w; p.K1b = net->P + L.K1b; p.K2w = net->P + L.K2w; p.K2b = net->P + L.K2b; p.Fw = net->P + L.Fw; p.Fb = net->P + L.Fb;
+    const rbnn_conv_posterior p = conv_posterior_of(*net, net->P, conv_ens_layout(net->hidden, net->n_classes, M), M);
     if ((rc = validate_conv(&p))) return rc;
     rbnn_conv_workspace w = {};
     w.P = ws->logits; w.P1 = ws->P1; w.st1 = ws->st1; w.Q2 = ws->Q2; w.st2 = ws->st2;
     ConvArgs a = {};
     if ((rc = conv_forward_args(&p, p.K2w, true, ws->Xs, DIN, n_points, nullptr, M, RBNN_OUT_LOGITS, &w, a))) return rc;
     if ((rc = launch_conv_forward_packed(net->activation, a, (hipStream_t)stream))) return rc;
-    const int n = M * n_points;
-    const ConvHeadArgs h = {ws->logits, ws->labels, ws->dZ, ws->ce, ws->correct, n, net->n_classes, summed ? 1.f : 1.f / (float)n_points};
-    hipLaunchKernelGGL(conv_head_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, h);
-    return launch_status();
+    return launch_conv_head(ws, ws->labels, M * n_points, net->n_classes, summed ? 1.f : 1.f / (float)n_points, stream);
 }
 
 int rbnn_conv_ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
@@ -559,68 +695,16 @@ int rbnn_conv_ens_forward(const rbnn_conv_ens_net* net, int32_t n_points, const 
 int rbnn_conv_ens_weight_grads(const rbnn_conv_ens_net* net, int32_t n_points, const rbnn_conv_ens_ws* ws, void* stream) {
     int rc = check_conv_ens_net(net);
     if (rc) return rc;
-    if (!net->P || !net->grad || !ws || !ws->Xs || !ws->P1 || !ws->st1 || !ws->Q2 || !ws->st2 || !ws->dZ || !ws->dO2 || !ws->dO1 || !ws->part2 ||
-        !ws->part1 || !ws->partP)
-        return RBNN_ERR_NULL;
+    if (!net->P || !net->grad || !wg_buffers(ws) || !ws->Xs) return RBNN_ERR_NULL;
     if ((rc = check_conv_ens_points(net, n_points))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int Hc = net->hidden, C = net->n_classes, B = n_points, M = net->n_members;
-    const long long F = (long long)Hc * NP2;
-    const ConvLayout L = conv_ens_layout(Hc, C, M);
-    float* const G = net->grad;
-    // dFw | dFb of every member: the member form of the strided GEMM (grid dimension y)
-    GemmArgs ga = {};
-    ga.n_prob = 1;
-    ga.p[0] = wgrad_prob(ws->dZ, RBNN_CPAD, ws->Q2, F, (long long)B * F, C, (int)F, B, G + L.Fw, G + L.Fb, 0);
-    ga.p[0].c_mem = (long long)C * F;
-    ga.p[0].bias_mem = C;
-    if ((rc = gemm_launch<true>(ga, M, st))) return rc;
-    // dO2
-    const ConvDo2Args d = {ws->dZ, net->P + L.Fw, ws->Q2, ws->st2, ws->dO2, Hc, C};
-    rc = for_activation(net->activation, [&](auto act) {
-        hipLaunchKernelGGL(conv_ens_do2_kernel<decltype(act)::value>, dim3((unsigned)B * (Hc / 4), M), dim3(256), 0, st, d, B);
-        return launch_status();
-    });
-    if (rc) return rc;
-    // dP1 per slice of the channels, then dO1 through pool 1
-    int perP, sP;
-    dp1_slices(B, Hc, perP, sP);
-    const long long nP = (long long)B * PP1 * C1, dO2_mem = (long long)B * Hc * NPOS;
-    WgArgs g = {};
-    g.Hc = Hc; g.ldx = DIN;
-    g.A = ws->dO2; g.Bsrc = net->P + L.K2w; g.out = ws->partP;
-    g.M = B * PP1; g.N = C1; g.K = Hc * 25; g.kc = perP * 400;
-    if ((rc = wg_ens_launch<G_DP1>(g, sP, M, dO2_mem, (long long)Hc * K2, sP * nP, st))) return rc;
-    const ConvRouteArgs ro = {ws->partP, ws->P1, ws->st1, ws->dO1, nP, sP};
-    rc = for_activation(net->activation, [&](auto act) {
-        hipLaunchKernelGGL(conv_ens_route1_kernel<decltype(act)::value>, dim3(blocks_for(ro.n), M), dim3(ELT_THREADS), 0, st, ro, B);
-        return launch_status();
-    });
-    if (rc) return rc;
-    // the two split contractions and their reduction
-    int per2, s2, per1, s1;
-    slices(B, MAX_SPLITS2, per2, s2);
-    slices(B, MAX_SPLITS1, per1, s1);
-    g.A = ws->dO2; g.Bsrc = ws->P1; g.out = ws->part2; g.M = Hc; g.N = N2; g.K = B * NPOS; g.kc = per2 * NPOS;
-    if ((rc = wg_ens_launch<G_DK2>(g, s2, M, dO2_mem, (long long)B * P1SZ, (long long)s2 * Hc * N2, st))) return rc;
-    g.A = ws->dO1; g.Bsrc = ws->Xs; g.out = ws->part1; g.M = C1; g.N = N1; g.K = B * NO1; g.kc = per1 * NO1;
-    if ((rc = wg_ens_launch<G_DK1>(g, s1, M, (long long)B * C1 * NO1, (long long)B * DIN, (long long)s1 * C1 * N1, st))) return rc;
-    const ConvEnsRedArgs r = {ws->part2, ws->part1, G, Hc, s2, s1, L.K1b, L.K2w, L.K2b};
-    hipLaunchKernelGGL(conv_ens_reduce_kernel, dim3(blocks_for((long long)Hc * N2 + C1 * N1), M), dim3(ELT_THREADS), 0, st, r);
-    return launch_status();
+    const int M = net->n_members;
+    return conv_weight_grads<true>(net, M, conv_ens_layout(net->hidden, net->n_classes, M), ws->Xs, DIN, n_points, ws, (hipStream_t)stream);
 }
 
 int rbnn_conv_ens_adam_step(const rbnn_conv_ens_net* net, int64_t step, double lr, double beta1, double beta2, double adam_eps, void* stream) {
     const int rc = check_conv_ens_net(net);
     if (rc) return rc;
-    if (!net->P || !net->m || !net->v || !net->grad) return RBNN_ERR_NULL;
-    if (step < 1) return RBNN_ERR_SHAPE;
-    AdamArgs a = {};
-    a.n_params = conv_ens_layout(net->hidden, net->n_classes, net->n_members).n_params;      // element-wise: the whole buffer is one launch
-    a.P = net->P; a.m = net->m; a.v = net->v; a.grad = net->grad;
-    a.s = adam_scalars(step, lr, beta1, beta2, adam_eps);
-    hipLaunchKernelGGL(nn_adam_kernel<false>, dim3(blocks_for(a.n_params)), dim3(ELT_THREADS), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return conv_adam_step(net, conv_ens_layout(net->hidden, net->n_classes, net->n_members).n_params, step, lr, beta1, beta2, adam_eps, stream);
 }
 
 int rbnn_conv_ens_finalize(const rbnn_conv_ens_net* net, const rbnn_conv_ens_ws* ws, int32_t n_points, double* stats, void* stream) {
@@ -640,7 +724,7 @@ int rbnn_conv_ens_finalize(const rbnn_conv_ens_net* net, const rbnn_conv_ens_ws*
 static int conv_svi_view(const rbnn_conv_svi_train_net* g, rbnn_conv_train_net* v) {
     if (!g) return RBNN_ERR_NULL;
     *v = {};
-    v->activation = g->activation; v->in_channels = g->in_channels; v->in_width = g->in_width; v->hidden = g->hidden; v->n_classes = g->n_classes;
+    copy_conv_shape(*v, *g);
     v->P = g->W; v->grad = g->grad;
     return check_conv_net(v);
 }
@@ -769,12 +853,8 @@ int rbnn_conv_svi_guides_accuracy(const rbnn_conv_svi_guides_net* net, const int
     hipStream_t st = (hipStream_t)stream;
     const int K = net->n_guides, KS = K * ACC_S;
     // the stack of the K S nets: tensor-major over the sets, so set k S + s is sample k S + s of an rbnn_conv_posterior
-    const ConvLayout L = conv_ens_layout(net->hidden, net->n_classes, KS);
-    rbnn_conv_posterior p = {};
-    p.activation = net->activation; p.hidden = net->hidden; p.n_classes = net->n_classes; p.n_stored = KS;
-    p.in_channels = net->in_channels; p.in_width = net->in_width;
     float* const W = ws->acc_W;
-    p.K1w = W + L.K1w; p.K1b = W + L.K1b; p.K2w = W + L.K2w; p.K2b = W + L.K2b; p.Fw = W + L.Fw; p.Fb = W + L.Fb;
+    const rbnn_conv_posterior p = conv_posterior_of(*net, W, conv_ens_layout(net->hidden, net->n_classes, KS), KS);
     if ((rc = validate_conv(&p))) return rc;
     rbnn_conv_workspace w = {};
     w.P = ws->acc_P; w.P1 = ws->acc_P1; w.st1 = ws->acc_st1; w.Q2 = ws->acc_Q2; w.st2 = ws->acc_st2;
@@ -816,7 +896,7 @@ static_assert(MAX_MEMBERS == CONV_MAX_CHAINS && MAX_POINTS == CONV_CHAINS_MAX_PO
 
 static rbnn_conv_ens_net conv_chains_members(const rbnn_conv_hmc_chains_net* n) {
     rbnn_conv_ens_net e = {};
-    e.activation = n->activation; e.in_channels = n->in_channels; e.in_width = n->in_width; e.hidden = n->hidden; e.n_classes = n->n_classes;
+    copy_conv_shape(e, *n);
     e.n_members = n->n_chains; e.P = n->W; e.grad = n->grad;
     return e;
 }

@@ -457,11 +457,11 @@ __global__ void __launch_bounds__(256, 2) conv1_pool_x3_kernel(const ConvArgs a,
                         b2.w[q] = *(const unsigned*)(src + 2 * T::PLB);
                     }
                     // six exact product terms, smallest first; the four accumulators of a (dy) are independent chains
-#define RBNN_C1X3_TERM(AP, BP) \
+#define C1X3_TERM(AP, BP) \
                     _Pragma("unroll") for (int dx = 0; dx < 2; ++dx) \
                         _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) acc[dy][dx][mt] = MFMA_H(AP[dx][mt][t].v, BP.v, acc[dy][dx][mt]);
-                    RBNN_C1X3_TERM(A0, b2) RBNN_C1X3_TERM(A2, b0) RBNN_C1X3_TERM(A1, b1) RBNN_C1X3_TERM(A1, b0) RBNN_C1X3_TERM(A0, b1) RBNN_C1X3_TERM(A0, b0)
-#undef RBNN_C1X3_TERM
+                    C1X3_TERM(A0, b2) C1X3_TERM(A2, b0) C1X3_TERM(A1, b1) C1X3_TERM(A1, b0) C1X3_TERM(A0, b1) C1X3_TERM(A0, b0)
+#undef C1X3_TERM
                     __builtin_amdgcn_sched_barrier(0);                   // one fragment set in flight: hoisted, the reads of all six steps spilled beside the 144 weight registers
                 }
             // ---- bias, 2x2 max-pool over (dy, dx) with the first maximum winning (torch max_pool2d; candidates in conv1_pool_kernel's order

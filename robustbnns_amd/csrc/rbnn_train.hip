@@ -103,7 +103,7 @@ int rbnn_svi_train_forward(const rbnn_svi_train_net* net, const float* X, int32_
     h.Hl = fc2 ? ws->hid2 : ws->hid1; h.Dl = fc2 ? ws->dact2 : ws->dact1;
     h.W2 = W + L.s[L.n - 2].off; h.b2 = W + L.s[L.n - 1].off; h.labels = labels;
     h.dZ = ws->dZ; h.ce = ws->ce; h.dA = fc2 ? ws->dA2 : ws->dA1; h.B = B; h.H = H; h.C = C; h.inv_S = 1.f;
-    hipLaunchKernelGGL(train_head_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, st, h);
+    hipLaunchKernelGGL((train_head_kernel<false, false>), dim3((B + 3) / 4), dim3(256), 0, st, h);
     if ((rc = launch_status())) return rc;
     if (fc2) {
         // dA1[b, i] = (sum_o dA2[b, o] Wm[o, i]) act'1[b, i]

@@ -1,7 +1,7 @@
 // rbnn_train_gemm.hpp — the forward / backward of an fc / fc2 net on the fp32 MFMA, shared by the units that launch it (rbnn_train.hip,
 // rbnn_nn_train.hip, rbnn_hmc.hip, rbnn_svi_lockstep.hip): one strided GEMM kernel and one output-layer + loss kernel, for M independent members in lockstep (grid
 // dimension y), and the host side of the lockstep forward / weight gradients.
-// Both bodies are templates on LOCKSTEP.  false is a single net: member 0, no index arrays — the member strides, a_idx / b_idx / rows and the
+// Both kernels are templates on LOCKSTEP and SKIP.  LOCKSTEP = false is a single net: member 0, no index arrays — the member strides, a_idx / b_idx / rows and the
 // clamp are compiled out (measured: with them the SVI step was 5 % and an HMC transition 5 - 7 % slower than the kernels it had before).
 #pragma once
 #include "rbnn_train_core.hpp"
@@ -47,8 +47,82 @@ template <bool LOCKSTEP> __device__ __forceinline__ int gathered(const int32_t* 
     return (LOCKSTEP && idx) ? min(max(idx[at + i], 0), idx_max) : i;
 }
 
-// The kernels' text is rbnn_train_kernels.inc, included below once per form: train_gemm_kernel / train_head_kernel, and train_gemm_skip_kernel /
-// train_head_skip_kernel, which leave out a finished member (templates: only the unit that launches them, rbnn_svi_lockstep.hip, has them).
+// SKIP (LOCKSTEP with counts only, launched by rbnn_svi_lockstep.hip alone): a member, or a group of `per` members, with counts == 0 has
+// finished; its blocks return at once and its workspaces keep what they held.
+template <bool LOCKSTEP, bool SKIP> __global__ void __launch_bounds__(256) train_gemm_kernel(const GemmArgs g) {
+    static_assert(LOCKSTEP || !SKIP, "only a lockstep launch has members to skip");
+    __shared__ float As[GK][GLD], Bs[GK][GLD];
+    long long idx_row = LOCKSTEP ? blockIdx.y : 0;
+    if constexpr (SKIP) {
+        idx_row = blockIdx.y / g.per;
+        if (g.counts[idx_row] == 0) return;
+    }
+    int pi = 0;
+#pragma unroll
+    for (int j = 1; j < 3; ++j) if (j < g.n_prob && (int)blockIdx.x >= g.p[j].first_tile) pi = j;
+    const GemmProb& p = g.p[pi];
+    const long long mem = LOCKSTEP ? blockIdx.y : 0;
+    const int tile = blockIdx.x - p.first_tile, m0 = GT * (tile / p.tiles_n), n0 = GT * (tile % p.tiles_n);
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, li = lane & 15, lg = lane >> 4;
+    const int n_real = p.ones_n >= 0 ? p.ones_n : p.N;
+    const float* const A = p.A + mem * p.a_mem;
+    const float* const Bm = p.B + mem * p.b_mem;
+    const long long idx_at = idx_row * p.idx_mem;
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < p.K; k0 += GK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = t + 256 * i;
+            int mm, kk;
+            if (p.a_k == 1) { mm = idx >> 4; kk = idx & 15; } else { mm = idx & 63; kk = idx >> 6; }     // coalesced along the unit stride
+            const int m = m0 + mm, k = k0 + kk;
+            float av = 0.f;
+            if (m < p.M && k < p.K) av = A[(long long)gathered<LOCKSTEP>(p.a_idx, idx_at, m, p.idx_max) * p.a_m + k * p.a_k];
+            As[kk][mm] = av;
+            int nn, kb;
+            if (p.b_k == 1) { nn = idx >> 4; kb = idx & 15; } else { nn = idx & 63; kb = idx >> 6; }
+            const int n = n0 + nn, kq = k0 + kb;
+            float bv = 0.f;
+            if (kq < p.K) {
+                if (n < n_real) bv = Bm[n * p.b_n + (long long)gathered<LOCKSTEP>(p.b_idx, idx_at, kq, p.idx_max) * p.b_k];
+                else if (n == p.ones_n) bv = 1.f;
+            }
+            Bs[kb][nn] = bv;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < GK / 4; ++ks) {
+            const float a = As[4 * ks + lg][16 * wave + li];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = MFMA16(a, Bs[4 * ks + lg][16 * nt + li], acc[nt]);
+        }
+        __syncthreads();
+    }
+    // lane holds C(m0 + 16 wave + 4 lg + r, n0 + 16 nt + li)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        const int n = n0 + 16 * nt + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + 16 * wave + 4 * lg + r;
+            if (m >= p.M || n >= p.N) continue;
+            const float v = acc[nt][r];
+            if (n == p.ones_n) { p.bias_out[mem * p.bias_mem + m] = v; continue; }
+            const long long o = mem * p.c_mem + (long long)m * p.ldc + n;
+            if (p.epi == EPI_FWD) {
+                const float pre = v + p.bias[mem * p.bias_mem + n], h = act_value(p.act, pre);
+                p.Cout[o] = h;
+                p.Dout[o] = act_deriv(p.act, pre, h);
+            } else if (p.epi == EPI_MUL) {
+                p.Cout[o] = v * p.Dmul[o];
+            } else {
+                p.Cout[o] = v;
+            }
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Output layer + loss: one wave per (member, point).  z = H W2^T + b2, CE = logsumexp(z) - z_y (Categorical(logits=log_softmax(z)) /
@@ -67,22 +141,68 @@ struct HeadArgs {
     float inv_S;
 };
 
-#define RBNN_GEMM_KERNEL train_gemm_kernel
-#define RBNN_HEAD_KERNEL train_head_kernel
-#define RBNN_KERNELS_SKIP false
-#include "rbnn_train_kernels.inc"
-#undef RBNN_GEMM_KERNEL
-#undef RBNN_HEAD_KERNEL
-#undef RBNN_KERNELS_SKIP
-// SKIP (LOCKSTEP with counts only): a member, or a group of `per` members, with counts == 0 has finished; its blocks return at once and its
-// workspaces keep what they held
-#define RBNN_GEMM_KERNEL train_gemm_skip_kernel
-#define RBNN_HEAD_KERNEL train_head_skip_kernel
-#define RBNN_KERNELS_SKIP true
-#include "rbnn_train_kernels.inc"
-#undef RBNN_GEMM_KERNEL
-#undef RBNN_HEAD_KERNEL
-#undef RBNN_KERNELS_SKIP
+template <bool LOCKSTEP, bool SKIP> __global__ void __launch_bounds__(256) train_head_kernel(const HeadArgs a) {
+    static_assert(LOCKSTEP || !SKIP, "only a lockstep launch has members to skip");
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= a.B) return;
+    const long long mem = LOCKSTEP ? blockIdx.y : 0, pt = mem * a.B + b;
+    if constexpr (SKIP) {
+        if (a.counts[mem] == 0) return;
+    }
+    if (LOCKSTEP && a.counts && b >= a.counts[mem]) {                  // not a point of this member: ce, dZ, dA and correct are zero
+        if (lane == 0) {
+            a.ce[pt] = 0.f;
+            if (a.correct) a.correct[pt] = 0;
+#pragma unroll
+            for (int c = 0; c < RBNN_CPAD; ++c) a.dZ[pt * RBNN_CPAD + c] = 0.f;
+        }
+        for (int h = lane; h < a.H; h += 64) a.dA[pt * a.H + h] = 0.f;
+        return;
+    }
+    const float* const W2 = a.W2 + mem * a.p_mem;
+    float z[RBNN_CPAD];
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c) z[c] = 0.f;
+    const float* hrow = a.Hl + pt * a.H;
+    for (int h = lane; h < a.H; h += 64) {
+        const float hv = hrow[h];
+#pragma unroll
+        for (int c = 0; c < RBNN_CPAD; ++c) if (c < a.C) z[c] = fmaf(hv, W2[(long long)c * a.H + h], z[c]);
+    }
+    const float* const b2 = a.b2 + mem * a.p_mem;
+#pragma unroll
+    for (int c = 0; c < RBNN_CPAD; ++c) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) z[c] += __shfl_xor(z[c], off, 64);
+        if (c < a.C) z[c] += b2[c];
+    }
+    const int y = a.labels[gathered<LOCKSTEP>(a.rows, mem * a.B, b, a.idx_max)];
+    float g[RBNN_CPAD];
+    ce_softmax_grad<RBNN_CPAD>(z, a.C, y, a.inv_S, g);
+    if (lane == 0) {
+        float m = -INFINITY, zy = 0.f;
+        int best = 0;
+        for (int c = 0; c < a.C; ++c) {
+            if (z[c] > m) { m = z[c]; best = c; }                     // strictly greater: the first maximum, as torch.argmax
+            if (c == y) zy = z[c];
+        }
+        float den = 0.f, rest = 0.f;
+        for (int c = 0; c < a.C; ++c) { const float e = expf(z[c] - m); den += e; if (c != y) rest += e; }
+        // label = argmax: CE = log(1 + sum_{c != y} e^(z_c - z_y)) without the cancellation of log(den) - 0
+        a.ce[pt] = (zy == m) ? log1pf(rest) : logf(den) - (zy - m);
+        if (a.correct) a.correct[pt] = best == y ? 1 : 0;
+#pragma unroll
+        for (int c = 0; c < RBNN_CPAD; ++c) a.dZ[pt * RBNN_CPAD + c] = g[c];
+    }
+    const float* drow = a.Dl + pt * a.H;
+    float* arow = a.dA + pt * a.H;
+    for (int h = lane; h < a.H; h += 64) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < RBNN_CPAD; ++c) if (c < a.C) s = fmaf(g[c], W2[(long long)c * a.H + h], s);
+        arow[h] = s * drow[h];
+    }
+}
 
 template <bool LOCKSTEP, bool SKIP = false> int gemm_launch(GemmArgs& g, int members, hipStream_t st) {
     if (SKIP && (!g.counts || g.per < 1)) return RBNN_ERR_NULL;
@@ -93,8 +213,7 @@ template <bool LOCKSTEP, bool SKIP = false> int gemm_launch(GemmArgs& g, int mem
         p.first_tile = tiles;
         tiles += p.tiles_n * ((p.M + GT - 1) / GT);
     }
-    if constexpr (SKIP) hipLaunchKernelGGL(train_gemm_skip_kernel<LOCKSTEP>, dim3(tiles, members), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(train_gemm_kernel<LOCKSTEP>, dim3(tiles, LOCKSTEP ? members : 1), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((train_gemm_kernel<LOCKSTEP, SKIP>), dim3(tiles, LOCKSTEP ? members : 1), dim3(256), 0, st, g);
     return launch_status();
 }
 
@@ -174,8 +293,7 @@ inline int lockstep_forward(const rbnn_nn_train_net* net, const LockstepBatch& b
     h.idx_max = b.n_rows - 1;
     h.dZ = ws->dZ; h.ce = ws->ce; h.correct = ws->correct; h.dA = fc2 ? ws->dA2 : ws->dA1; h.B = B; h.H = H; h.C = C;
     h.inv_S = inv_S;
-    if constexpr (SKIP) hipLaunchKernelGGL(train_head_skip_kernel<true>, dim3((B + 3) / 4, M), dim3(256), 0, st, h);
-    else hipLaunchKernelGGL(train_head_kernel<true>, dim3((B + 3) / 4, M), dim3(256), 0, st, h);
+    hipLaunchKernelGGL((train_head_kernel<true, SKIP>), dim3((B + 3) / 4, M), dim3(256), 0, st, h);
     if ((rc = launch_status())) return rc;
     if (fc2) {
         // dA1[b, i] = (sum_o dA2[b, o] Wm[o, i]) act'1[b, i]

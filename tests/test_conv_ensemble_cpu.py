@@ -202,7 +202,8 @@ def test_conv_ensemble_kernels_use_no_scratch():
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
     res = {n: r for n, r in KR.kernel_resources().items()
-           if re.search(r"::(conv_ens_\w+_kernel|conv1_pool_packed_kernel|nn_finalize_kernel<true>|train_gemm_kernel<true>)", n)}
+           if re.search(r"::(conv_ens_(stage|reduce)_kernel|conv_(do2|route1|wgrad_gemm)_kernel<\d, true>|conv1_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28>, 1>|"
+                        r"nn_finalize_kernel<true>|train_gemm_kernel<true, false>)", n)}
     # stage, reduce, do2 and route1 x 4 activations, the GEMM in its 3 modes, the packed conv1 x 4 activations, the per-member statistics and strided GEMM
     assert len(res) == 2 + 8 + 3 + 4 + 2, sorted(res)
     bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}

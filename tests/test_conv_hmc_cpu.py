@@ -237,8 +237,8 @@ def test_kernels_of_a_conv_hmc_transition_use_no_scratch():
     import kernel_resources as KR
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
-    step = (r"conv[12]_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28> >|::conv_fc_kernel\(|::conv_(head|reduce)_kernel\(|"
-            r"::conv_(do2|wgrad_gemm|route1)_kernel<\d>|::train_gemm_kernel<false>|::hmc_(momentum|update|decide|commit|window_end)_kernel\(")
+    step = (r"conv1_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28>, 0>|conv2_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28> >|::conv_fc_kernel\(|::conv_(head|reduce)_kernel\(|"
+            r"::conv_(do2|wgrad_gemm|route1)_kernel<\d, false>|::train_gemm_kernel<false, false>|::hmc_(momentum|update|decide|commit|window_end)_kernel\(")
     res = {n: r for n, r in KR.kernel_resources().items() if re.search(step, n)}
     # conv1 / conv2 x 4 activations, the Linear, the head, the strided GEMM (dFw), do2 and route1 x 4, the conv GEMM in 3 modes, the partial
     # sums' reduction, and the chain's five kernels

@@ -296,7 +296,7 @@ def test_conv_svi_lockstep_kernels_use_no_scratch():
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
     res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(conv_svils_\w+_kernel|svils_draw_kernel<.*TensorMajor>|svils_finalize_kernel<false>|adam_kernel<.*TensorMajor>|"
-                                                                             r"conv1_pool_grouped_kernel)", n)}
+                                                                             r"conv1_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28>, 2>)", n)}
     # draw, Adam + KL, the sum over the accuracy samples, finalize; the grouped conv1 x 4 activations
     assert len(res) == 4 + 4, sorted(res)
     bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}

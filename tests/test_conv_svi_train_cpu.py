@@ -210,8 +210,8 @@ def test_kernels_of_a_conv_svi_step_use_no_scratch():
     import kernel_resources as KR
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
-    step = (r"svi_draw_flat_kernel\(|conv[12]_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28> >|::conv_fc_kernel\(|::conv_(head|reduce)_kernel\(|"
-            r"::conv_(do2|wgrad_gemm|route1)_kernel<\d>|::train_gemm_kernel<false>|svi::\(anonymous namespace\)::adam_kernel<svi::\(anonymous namespace\)::Single>|"
+    step = (r"svi_draw_flat_kernel\(|conv1_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28>, 0>|conv2_pool_kernel<\d, rbnn_conv_shared::Geo<1, 28> >|::conv_fc_kernel\(|::conv_(head|reduce)_kernel\(|"
+            r"::conv_(do2|wgrad_gemm|route1)_kernel<\d, false>|::train_gemm_kernel<false, false>|svi::\(anonymous namespace\)::adam_kernel<svi::\(anonymous namespace\)::Single>|"
             r"\)::reduce_samples_kernel\(|\(anonymous namespace\)::finalize_kernel\(")
     res = {n: r for n, r in KR.kernel_resources().items() if re.search(step, n)}
     # the draw, conv1 / conv2 x 4 activations, the Linear, the head, the strided GEMM (dFw), do2 and route1 x 4, the conv GEMM in 3 modes, the

@@ -227,7 +227,8 @@ def test_conv_training_kernels_use_no_scratch():
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
     res = {n: r for n, r in KR.kernel_resources().items()
-           if re.search(r"::(conv_(head|do2|wgrad_gemm|route1|reduce)_kernel|nn_(adam|finalize)_kernel<false>|train_gemm_kernel<false>)", n)}
+           if re.search(r"::(conv_(head|reduce)_kernel\(|conv_(do2|wgrad_gemm|route1)_kernel<\d, false>|nn_(adam|finalize)_kernel<false>|"
+                        r"train_gemm_kernel<false, false>)", n)}
     # head, reduce, adam, finalize (rbnn_nn_step.hpp's, for one net), do2 and route1 x 4 activations, the GEMM in its 3 modes, and the strided GEMM (dFw)
     assert len(res) == 4 + 8 + 3 + 1, sorted(res)
     bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}

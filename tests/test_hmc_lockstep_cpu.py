@@ -138,7 +138,7 @@ def test_lockstep_kernels_use_no_scratch():
     import kernel_resources as KR
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
-    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(lockstep_\w+_kernel|train_gemm_kernel<true>|train_head_kernel<true>)", n)}
+    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(lockstep_\w+_kernel|train_(gemm|head)_kernel<true, false>)", n)}
     assert len(res) == 11, sorted(res)     # four element-wise templates in two views, the decision, the GEMM and the head
     bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}
     assert not bad, bad

@@ -55,6 +55,23 @@ def test_ablation_switches_are_fenced(tmp_path):
     assert subprocess.run([str(tmp_path / "probe")]).returncode == 7          # the marker is planted: rbnn_build_flags() would say 1
 
 
+def test_no_kernel_text_is_included_once_per_form():
+    """A kernel that comes in several forms is a template, not a text included several times between #define / #undef blocks that rename it:
+    no file under csrc/ includes the same file twice, and none carries an `#undef RBNN_` line.  The one exception is
+    rbnn_triple_fwd_epilogue.inc, text inside one kernel body of rbnn_triple.hip (a lambda changed that kernel)."""
+    import __graft_entry__ as ge
+    twice, undefs = [], []
+    for name in sorted(os.listdir(ge.CSRC)):
+        if not name.endswith((".hip", ".hpp", ".inc")):
+            continue
+        text = open(os.path.join(ge.CSRC, name)).read()
+        included = re.findall(r'(?m)^\s*#\s*include\s*"([^"]+)"', text)
+        twice += [(name, inc) for inc in sorted(set(included)) if included.count(inc) > 1]
+        undefs += [(name, line.strip()) for line in text.split("\n") if re.match(r"\s*#\s*undef\s+RBNN_", line)]
+    assert twice == [("rbnn_triple.hip", "rbnn_triple_fwd_epilogue.inc")], twice
+    assert not undefs, undefs
+
+
 def test_load_refuses_a_library_built_with_ablation_switches(monkeypatch):
     class Fake:
         def __getattr__(self, name):

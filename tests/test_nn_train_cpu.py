@@ -170,7 +170,7 @@ def test_training_kernels_use_no_scratch():
     import kernel_resources as KR
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
-    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(train_gemm_kernel<true>|train_head_kernel<true>|nn_adam_kernel<true>|nn_finalize_kernel<true>)", n)}
+    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(train_(gemm|head)_kernel<true, false>|nn_adam_kernel<true>|nn_finalize_kernel<true>)", n)}
     assert len(res) == 4, sorted(res)
     bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}
     assert not bad, bad

@@ -242,7 +242,7 @@ def test_the_new_kernels_use_no_scratch():
     import kernel_resources as KR
     if not os.path.exists(KR.READELF):
         pytest.skip("llvm-readelf not in this image")
-    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(svils_\w+_kernel|adam_kernel<\(anonymous namespace\)::GuideMajor>|train_(gemm|head)_skip_kernel<true>)", n)}
+    res = {n: r for n, r in KR.kernel_resources().items() if re.search(r"::(svils_\w+_kernel|adam_kernel<\(anonymous namespace\)::GuideMajor>|train_(gemm|head)_kernel<true, true>)", n)}
     # the accuracy head, the draw and the finalize in both of their instances (guide-major here, tensor-major for the conv guides), Adam + KL, GEMM, head
     assert len(res) == 1 + 2 + 2 + 1 + 1 + 1, sorted(res)
     bad = {n: (r["scratch"], r["spill_vgpr"]) for n, r in res.items() if r["scratch"] or r["spill_vgpr"]}
